@@ -13,11 +13,15 @@ batch of 150-bp reads that is already resident in HBM.  After the K steps the
 sample is closed inside the timed region: ucount from the seen-bitmap and, for
 N > 1, the RCCL merge (bitmap slices all_to_all + one all_reduce).
 
-Rank 0 prints ONE JSON line (metric, roofline, cpu_baseline).
+Rank 0 prints ONE JSON line (metric, roofline; with --full also cpu_baseline and the other legs).
 
-Defaults: 200 timed steps after 50 warm-up steps (1 M pairs each); the full-size cross-check against the reference's
-cell placement, the random-line probe, the host-buffer leg, the nk10 FASTQ.gz leg and the CPU baseline all run AFTER the
-timed region.  Development aids (never part of the metric): KID_BENCH_RANDOM_READS=1 (reads without a database k-mer),
+Defaults: 200 timed steps after 50 warm-up steps (1 M pairs each).  A plain run sets up, warms up, times the steps and
+prints the line, nothing else.  --full adds, AFTER the timed region, the full-size cross-check against the reference's
+cell placement, the random-line probe, the host-buffer leg, the nk10 FASTQ.gz leg, the CPU baseline and (N > 1) the
+merged counters against one table; each of them can also be switched on or off by its own option.
+--dump-outputs DIR writes what the last timed step handed back (per-read final targets; gcount / ucount of the closed
+sample) as DIR/<name>.npy in float64; the inputs are seeded, so two builds can be compared output for output.
+Development aids (never part of the metric): KID_BENCH_RANDOM_READS=1 (reads without a database k-mer),
 KID_BENCH_ABLATION=1 (accept builds whose counters are wrong on purpose: tools/ab_bench.py with -DKID_ABLATE_* libraries).
 """
 import argparse
@@ -46,7 +50,10 @@ READ_LEN = 150
 #  translation caches settle -- so the default warms up for 50 steps and times 200: profiles/r02/ab_warmup.txt)
 CONFIGS = {"1m": {"pairs": 1_000_000, "steps": 200, "warmup": 50, "batches": 4},
            "roofline100m": {"pairs": 100_000_000, "steps": 4, "warmup": 2, "batches": 1}}
+# what --full switches on (a plain run: all 0); each can still be set on its own
+FULL_DEFAULTS = {"cpu_reads": 300_000, "host_leg": 1, "e2e_leg": 1, "verify_ranks": 1, "gather": 1, "xcheck": 1}
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s
+DUMP_MAX_READS = 4_000_000  # --dump-outputs: more per-read results than this are written as a seeded sample (32 MB)
 
 
 def log(*a):
@@ -287,6 +294,25 @@ def traffic_from_profile(args, info):
     return None, why
 
 
+def dump_outputs(out_dir, out_final, g, u):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- the per-read final targets of
+    that step's batch and the closed sample's gcount / ucount -- as float64 .npy files (exact: integers below 2^53).
+    Beyond DUMP_MAX_READS reads the final targets are a fixed, seeded sample, written with its read indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    n = out_final.numel()
+    arrays = {}
+    if n > DUMP_MAX_READS:
+        idx = np.unique(np.random.default_rng(20240229).integers(0, n, DUMP_MAX_READS // 2))
+        arrays["final_targets"] = out_final[torch.from_numpy(idx).to(out_final.device)].cpu().numpy()
+        arrays["final_targets_read_index"] = idx
+    else:
+        arrays["final_targets"] = out_final.cpu().numpy()
+    arrays["gcount"], arrays["ucount"] = g, u
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a).astype(np.float64))
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -297,31 +323,41 @@ def main():
     ap.add_argument("--pairs", type=int, default=None, help="read pairs per rank per step (default: the config's)")
     ap.add_argument("--scale", type=float, default=1.0, help="DB scale (1.0 = 108.6 M k-mers)")
     ap.add_argument("--log2-slots", type=int, default=30)
-    ap.add_argument("--cpu-reads", type=int, default=300_000, help="reads of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run, after the timed region, everything beyond the headline figure: the reference-geometry "
+                         "cross-check, the random-line probe, the host-buffer and nk10 legs, the CPU baseline, the multi-rank check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (final targets, gcount, ucount) as DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-reads", type=int, default=None, help="reads of the CPU baseline sample (0 = skip; --full: 300000)")
     ap.add_argument("--batches", type=int, default=None, help="distinct resident read batches cycled over the steps")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-cores CPU baseline leg (0 = every core of this host)")
     ap.add_argument("--overlap-pack", type=int, default=0,
                     help="KID_OPT_INPUTS_READY: pack + prepare of the next resident batch run beside the classify kernels of this one "
                          "(measured: same pairs/s, the classify kernel is 5-8 %% slower while pack shares the chip: profiles/r02/ab_overlap_pack.txt)")
-    ap.add_argument("--host-leg", type=int, default=1, help="N = 1: also time the host-buffer (PCIe-inclusive) path")
-    ap.add_argument("--e2e-leg", type=int, default=1, help="N = 1: also time the nk10 command line on FASTQ.gz files")
-    ap.add_argument("--verify-ranks", type=int, default=1,
+    ap.add_argument("--host-leg", type=int, default=None, help="N = 1: also time the host-buffer (PCIe-inclusive) path (--full: 1)")
+    ap.add_argument("--e2e-leg", type=int, default=None, help="N = 1: also time the nk10 command line on FASTQ.gz files (--full: 1)")
+    ap.add_argument("--verify-ranks", type=int, default=None,
                     help="N > 1: rank 0 re-classifies every rank's reads on its own table after the timed region and compares "
-                         "the merged counters with that single-table result")
-    ap.add_argument("--gather", type=int, default=1, help="also measure the random 16-byte gather ceiling")
+                         "the merged counters with that single-table result (--full: 1)")
+    ap.add_argument("--gather", type=int, default=None, help="also measure the random 16-byte gather ceiling (--full: 1)")
     ap.add_argument("--step-events", type=int, default=0, help="1: events around every step as well as around every classify kernel")
     ap.add_argument("--read-len", type=int, default=150, help="read length (configs[1]: 150; configs[4]: 250)")
     ap.add_argument("--geometry", choices=["minloc", "ref"], default="minloc",
                     help="table placement: minimizer-localised (default) or the reference's fmix64/triangular one")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to rehearse "
                                                       "several ranks on one GPU: the merge then goes through host memory)")
-    ap.add_argument("--xcheck", type=int, default=1,
+    ap.add_argument("--xcheck", type=int, default=None,
                     help="classify the first batch on a second table built with the reference's geometry too: "
-                         "full-size parity of the two placements + the reference-geometry probe count")
+                         "full-size parity of the two placements + the reference-geometry probe count (--full: 1)")
     args = ap.parse_args()
     for k_, v_ in CONFIGS[args.config].items():
         if getattr(args, k_) is None:
             setattr(args, k_, v_)
+    for k_, v_ in FULL_DEFAULTS.items():
+        if getattr(args, k_) is None:
+            setattr(args, k_, v_ if args.full else 0)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     global READ_LEN
     READ_LEN = args.read_len
 
@@ -409,6 +445,8 @@ def main():
         tt = torch.tensor([elapsed], dtype=torch.float64, device=device if args.backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    # (before the cross-check below, which classifies into out_final again)
+    dumped = dump_outputs(args.dump_outputs, out_final, g, u) if args.dump_outputs and rank == 0 else None
 
     classify_ms, classify_launches = sample.kernel_time()  # the dominant kernel (HIP events around every launch of it, on the launch stream)
     kernel_ms = [a.elapsed_time(b) for a, b in ev] if ev else [classify_ms]
@@ -546,7 +584,7 @@ def main():
             "config": {"workload": "bact10-synth DB (%d 30-mers on the real bact10 taxonomy, 2^%d-cell table resident in HBM), "
                                    "%d synthetic %d bp read pairs per GPU per step, reads resident in HBM" % (
                                        info.n_entries, args.log2_slots, args.pairs, READ_LEN),
-                       "name": args.config, "inputs_ready_option": bool(args.overlap_pack), "db_scale": args.scale, "pairs_per_gpu_per_step": args.pairs, "read_len": READ_LEN, "k": K,
+                       "name": args.config, "full": args.full, "dumped_outputs": dumped, "inputs_ready_option": bool(args.overlap_pack), "db_scale": args.scale, "pairs_per_gpu_per_step": args.pairs, "read_len": READ_LEN, "k": K,
                        "merged_counters_equal_single_table": ranks_verified, "per_rank": per_rank,
                        "slowest_rank": None if per_rank is None else max(per_rank, key=lambda r_: r_["closed_after_s"])["rank"],
                        "sharding": "reads sharded over %d rank(s), DB replicated" % world},
@@ -563,6 +601,8 @@ def main():
                          "kernel_source_sha256_16": kernel_source_sha(),
                          "lookups_per_launch": st["lookups"] / args.steps, "probes_per_launch": probes_per_launch,
                          "cells_read_per_launch": cells_read_per_launch, "geometry": args.geometry,
+                         "probes_per_launch_source": "reference-geometry table (--xcheck)" if ref_probes_per_lookup is not None
+                                                     else "this table's own cells (no --xcheck)",
                          "fullsize_parity_vs_reference_geometry": xcheck,
                          "lookups_per_s": st["lookups"] / (classify_ms / 1e3), "kernel_only_pairs_per_s": args.pairs / avg_kernel_s,
                          **extra},

@@ -26,7 +26,7 @@ if lib:
     env["KMER_ID_AMD_LIB"] = lib
 for rd in range(rounds):
     for v in args:
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-reads", "0"] + common + v.split()
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-reads", "0"] + common + v.split()
         p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
         out = p.stdout.decode().strip().splitlines()
         try:

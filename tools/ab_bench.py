@@ -14,7 +14,7 @@ if "--" in args:
     args, extra = args[:i], args[i + 1:]
 for lib in args:
     env = dict(os.environ, KMER_ID_AMD_LIB=os.path.abspath(lib))
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-reads", "0", "--gather", "0"] + extra,
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-reads", "0", "--gather", "0"] + extra,
                          env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode().strip().splitlines()
     try:
         d = json.loads(out[-1]); r = d["roofline"]
