@@ -232,6 +232,49 @@ int kid_sample_gcount(kid_sample *s, int64_t *gcount);
  * 8 * kid_sample_seen_bytes (byte ranges of the bitmap helpers above are multiples of 16) */
 int kid_sample_ucount_range(kid_sample *s, uint64_t bit_begin, uint64_t bit_end, int64_t *ucount);
 
+/* ---- probe-database builder ------------------------------------------------------------------------------------
+ * Replaces the table of kmer_build_vf6.cpp (Hashtable, :132-215) and its three passes (process_seq, process_seq3,
+ * process_seq2: :353-457, :553-640): 2^log2_cells uint32 cells, direct mapped by fmix64 of the canonical 30-mer, no key
+ * stored; cell = target << 11 | count (0 = empty, 1 = spoiled).  Text is ACGTN, one byte per base (anything but A, C, G,
+ * T breaks a k-mer); a call takes a whole sequence and streams it through the device in chunks of batch_bases.
+ *   parent[ntar]   Tree1::parent after the add_edge calls (:81-97); entries in [0, ntar), else KID_ERR_TREE
+ *   ntar           at most 2^21 (KID_ERR_ARG beyond: target << 11 overflows a cell)
+ *   log2_cells     10..40; 35 is the reference's MAXHASH (128 GiB)
+ *   batch_bases    k-mer positions per chunk (0 = 2^24)                                                            */
+typedef struct kid_builder kid_builder;
+typedef struct kid_build_cand {
+    uint64_t key;      /* canonical 30-mer */
+    int64_t gpos;      /* gpos_base + index of its last base in the text */
+    int32_t target;    /* cell target (> 1) */
+    uint16_t count;    /* cell count (>= minct[target]) */
+    uint8_t strand_r;  /* 1: keyF >= keyR ('R'), 0: 'F' */
+    uint8_t flags;     /* bit 0: check_entropy passes; bit 1: the k-mer is "bad" (printed, :546-548) */
+} kid_build_cand;
+/* free / total bytes of `device`'s memory (a 2^35-cell table needs 128 GiB) */
+int kid_device_mem_info(int device, uint64_t *free_bytes, uint64_t *total_bytes);
+int kid_builder_create(int device, int log2_cells, const int32_t *parent, int32_t ntar, uint64_t batch_bases, kid_builder **out);
+void kid_builder_destroy(kid_builder *b);
+/* phase 1, HashAdd (:168-193) for every 30-mer of text; target in [2, ntar) */
+int kid_builder_add(kid_builder *b, const uint8_t *text, uint64_t len, int32_t target);
+/* phase 2, HashRemove (:195-204) for every 30-mer of text */
+int kid_builder_remove(kid_builder *b, const uint8_t *text, uint64_t len);
+/* minct per target (:611-618), needed by kid_builder_claim; n = ntar */
+int kid_builder_set_minct(kid_builder *b, const int32_t *minct, int32_t n);
+/* phase 3, getHash (:206-213) over the text in order: every 30-mer reads its cell and sets it to 1.  out receives, in gpos
+ * order, the occurrences that were the first to read a cell with target > 1 and count >= minct[target]; the caller applies
+ * "gpos > minpos" and the MAXPROBES cap.  text[0] is at gpos_base; cap >= len - 29.  Sequences (orgs) must be claimed in
+ * the reference's order.                                                                                           */
+int kid_builder_claim(kid_builder *b, const uint8_t *text, uint64_t len, int64_t gpos_base, kid_build_cand *out, uint64_t cap,
+                      uint64_t *n_out);
+/* number of cells phase 1 filled (the reference's ht->size) */
+int kid_builder_size(kid_builder *b, uint64_t *n_filled);
+/* cells [first_cell, first_cell + n) of the table, for tests */
+int kid_builder_export(kid_builder *b, uint64_t first_cell, uint64_t n, uint32_t *out);
+/* the device's check_entropy flags (kid_build_cand.flags) for n keys, for tests */
+int kid_builder_entropy(kid_builder *b, const uint64_t *keys, uint64_t n, uint8_t *flags);
+/* device time (HIP events around the kernels) and bases handed over, per phase (add, remove, claim) */
+int kid_builder_stats(kid_builder *b, double device_ms[3], uint64_t bases[3]);
+
 /* (The synthetic workload generators, the random-gather probe and the device memory helpers that bench.py and the
  *  tests use live in kmer_id_amd_bench.h: they are not part of the boundary.)                                        */
 #ifdef __cplusplus

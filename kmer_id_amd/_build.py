@@ -15,7 +15,8 @@ LIB = os.path.join(HERE, "libkmer_id_amd.so")
 BIN_DIR = os.path.join(HERE, "bin")
 NK10 = os.path.join(BIN_DIR, "nk10")
 # front-end -> its main file; everything else under host/ is shared
-FRONT_ENDS = {"nk10": "nk10_main.cpp", "kmer_read_vf6": "vf6_main.cpp", "kmer_read_m3": "m3_main.cpp"}
+FRONT_ENDS = {"nk10": "nk10_main.cpp", "kmer_read_vf6": "vf6_main.cpp", "kmer_read_m3": "m3_main.cpp",
+              "kmer_build_vf6": "build_main.cpp"}
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-value", "-Wno-unused-result"]
 
@@ -35,7 +36,7 @@ def _newer(target, sources):
 
 
 def lib_sources():
-    return [os.path.join(CSRC, f) for f in ("kid_api.hip", "kid_kernels.hip.h", "kid_common.h")] + [
+    return [os.path.join(CSRC, f) for f in ("kid_api.hip", "kid_kernels.hip.h", "kid_build.hip.h", "kid_common.h")] + [
         os.path.join(ROOT, "include", "kmer_id_amd.h"), os.path.join(ROOT, "include", "kmer_id_amd_bench.h")]
 
 

@@ -83,6 +83,17 @@ PROTOTYPES = {
     "kid_dev_upload": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]),
     "kid_dev_download": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64]),
     "kid_dev_sync": (C.c_int, [C.c_int]),
+    "kid_device_mem_info": (C.c_int, [C.c_int, c_u64p, c_u64p]),
+    "kid_builder_create": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int32, C.c_uint64, c_void_pp]),
+    "kid_builder_destroy": (None, [C.c_void_p]),
+    "kid_builder_add": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int32]),
+    "kid_builder_remove": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64]),
+    "kid_builder_set_minct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "kid_builder_claim": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int64, C.c_void_p, C.c_uint64, c_u64p]),
+    "kid_builder_size": (C.c_int, [C.c_void_p, c_u64p]),
+    "kid_builder_export": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "kid_builder_entropy": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "kid_builder_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 KID_OPT_INPUTS_READY = 1
