@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "kid_driver.h"
 #include "kid_textio.h"
 #include "kmer_id_amd.h"
 
@@ -154,7 +155,7 @@ void check(int rc, const char *what)
     if (rc != 0) {
         std::cout.flush();
         std::cerr << "kmer_build_vf6: " << what << ": " << kid_strerror(rc) << " (" << kid_last_error() << ")\n";
-        exit(3);
+        leave_now(3); // (a genome reader may still be running: nothing is unwound under it)
     }
 }
 

@@ -26,8 +26,9 @@ void die_kid(int rc)
 {
     std::cerr << "kmer_id_amd: " << kid_strerror(rc) << ": " << kid_last_error() << "\n";
     // (a quality line shorter than its sequence, found by the GPU's process_qual: the reference dies in std::string::at,
-    //  abort -> 134; "out of memory in table" is exit 1, newkmer_10nx.cpp:256-260)
-    exit(rc == KID_ERR_TABLE_FULL ? 1 : rc == KID_ERR_FORMAT ? 134 : 3);
+    //  abort -> 134; "out of memory in table" is exit 1, newkmer_10nx.cpp:256-260).  Other threads may still be reading
+    //  files or using the GPU: nothing is unwound, no destructor runs under them.
+    leave_now(rc == KID_ERR_TABLE_FULL ? 1 : rc == KID_ERR_FORMAT ? 134 : 3);
 }
 
 static double seconds_since(const std::chrono::steady_clock::time_point &t0)
@@ -88,8 +89,9 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
     return e;
 }
 
-std::vector<int> parse_devices(const std::string &list)
+std::vector<int> parse_devices(int device, const std::string &list)
 {
+    if (list.empty()) return std::vector<int>(1, device);
     std::vector<int> out;
     size_t pos = 0;
     while (pos <= list.size()) {
@@ -111,29 +113,25 @@ void engine_reset(Engine &e)
 }
 
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
-                 unsigned flags, int device)
+                 unsigned flags, const std::vector<int> &devices)
 {
+    if (devices.empty()) { std::cerr << "kmer_id_amd: no device given\n"; leave_now(2); }
     e.ntar = (int)parent.size();
     e.k = k;
     int rc = kid_db_build(ps.keys.data(), ps.targets.data(), ps.keys.size(), parent.data(), e.ntar, k, log2_slots, max_probes,
-                          flags, device, &e.db);
-    if (rc == KID_ERR_TABLE_FULL) return false;
+                          flags, devices[0], &e.db);
+    if (rc == KID_ERR_TABLE_FULL) {
+        std::cout << "out of memory in table " << std::endl;
+        return false;
+    }
     if (rc != KID_OK) die_kid(rc);
     rc = kid_sample_begin(e.db, &e.sample);
     if (rc != KID_OK) die_kid(rc);
     e.dbs.assign(1, e.db);
     e.samples.assign(1, e.sample);
-    return true;
-}
-
-bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
-                 unsigned flags, const std::vector<int> &devices)
-{
-    if (devices.empty()) { std::cerr << "kmer_id_amd: no device given\n"; exit(2); }
-    if (!engine_open(e, ps, parent, k, log2_slots, max_probes, flags, devices[0])) return false;
     for (size_t i = 1; i < devices.size(); i++) { // the reference, pinned into every GPU's HBM: device-to-device copies of the one built table
         kid_db *r = nullptr;
-        int rc = kid_db_replicate(e.db, devices[i], &r);
+        rc = kid_db_replicate(e.db, devices[i], &r);
         if (rc != KID_OK) die_kid(rc);
         e.dbs.push_back(r);
         kid_sample *s = nullptr;
@@ -229,23 +227,6 @@ SourceStats Prefetcher::file_stats(size_t index)
 
 double Prefetcher::seconds_waited() const { return impl_->waited_s; }
 
-std::unique_ptr<ReadBatch> Prefetcher::next(size_t index)
-{
-    Impl::Slot &s = impl_->slots[index];
-    std::unique_lock<std::mutex> lk(impl_->m);
-    const auto t0 = std::chrono::steady_clock::now();
-    impl_->cv.wait(lk, [&] { return !s.q.empty() || s.done; });
-    impl_->waited_s += seconds_since(t0);
-    if (!s.q.empty()) {
-        std::unique_ptr<ReadBatch> b = std::move(s.q.front());
-        s.q.pop_front();
-        impl_->cv.notify_all();
-        return b;
-    }
-    if (s.failed) throw s.failure; // what was read before the failure has been handed out, as in the reference
-    return nullptr;
-}
-
 std::unique_ptr<ReadBatch> Prefetcher::next_any(size_t lo, size_t hi, size_t &which)
 {
     std::unique_lock<std::mutex> lk(impl_->m);
@@ -299,9 +280,13 @@ static void collect_fastq_block(ReadBatch &b, const HostBuf &io, std::vector<uin
     b.stop.assign(stop, stop + nr);
 }
 
-void run_files_together(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, std::vector<long long> &handed,
-                        const std::function<void(size_t)> &done)
+long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file,
+                    const std::function<void(size_t, long long)> &done)
 {
+    // Two batches in flight per device: while the GPU classifies batch b, batch b + 1 is uploaded and the results of
+    // batch b - 1 go through the read saver -- in file order, which is what decides the "first 12 reads of a target"
+    // (newkmer_10nx.cpp:608-612).  FASTQ files arrive as text blocks with a line index (FastqStream): those are trimmed
+    // and classified on the GPU (kid_classify_fastq_async); everything else as reads with their range.
     struct InFlight {
         std::unique_ptr<ReadBatch> batch;
         std::vector<uint32_t> final_targ;
@@ -309,21 +294,10 @@ void run_files_together(Engine &e, Prefetcher &pf, size_t first, size_t count, R
         uint64_t ticket = 0;
         kid_sample *sample = nullptr;
         size_t file = 0;
-        bool last_of_file = false;
     };
     std::deque<InFlight> q;
-    handed.assign(count, 0);
+    std::vector<long long> handed(count, 0);
     const size_t max_in_flight = 2 * e.samples.size();
-    std::vector<char> ended(count, 0);   // no more batches will come from the file
-    std::vector<size_t> pending(count, 0); // batches of the file still in flight
-    size_t next_done = 0;
-    auto announce = [&]() { // files that are through, in file order
-        while (next_done < count && ended[next_done] && pending[next_done] == 0) {
-            saver.file_done(next_done);
-            done(next_done);
-            next_done++;
-        }
-    };
     auto retire = [&]() {
         InFlight &f = q.front();
         const auto t0 = std::chrono::steady_clock::now();
@@ -331,10 +305,8 @@ void run_files_together(Engine &e, Prefetcher &pf, size_t first, size_t count, R
         e.gpu_wait_s += seconds_since(t0);
         if (rc != KID_OK) die_kid(rc);
         if (f.batch->fq) collect_fastq_block(*f.batch, f.io, f.final_targ);
-        handed[f.file] += saver.add_batch_of(f.file, *f.batch, f.final_targ, e.k);
-        pending[f.file]--;
+        handed[f.file] += saver.add_batch_of(saver_file + f.file, *f.batch, f.final_targ, e.k);
         q.pop_front();
-        announce();
     };
     try {
         for (;;) {
@@ -345,7 +317,6 @@ void run_files_together(Engine &e, Prefetcher &pf, size_t first, size_t count, R
             InFlight &f = q.back();
             f.batch = std::move(b);
             f.file = which - first;
-            pending[f.file]++;
             const size_t nr = f.batch->size();
             f.sample = e.samples[e.next_sample]; // batches are dealt round-robin over the devices
             e.next_sample = (e.next_sample + 1) % e.samples.size();
@@ -369,68 +340,53 @@ void run_files_together(Engine &e, Prefetcher &pf, size_t first, size_t count, R
         throw;
     }
     while (!q.empty()) retire();
-    for (size_t f = 0; f < count; f++) ended[f] = 1;
-    announce();
-}
-
-long long run_file(Engine &e, Prefetcher &pf, size_t index, ReadSaver &saver)
-{
-    // Two batches in flight per device: while the GPU classifies batch b, batch b + 1 is uploaded and the results of
-    // batch b - 1 go through the read saver -- in file order, which is what decides the "first 12 reads of a target"
-    // (newkmer_10nx.cpp:608-612).  FASTQ files arrive as text blocks with a line index (FastqStream): those are trimmed
-    // and classified on the GPU (kid_classify_fastq_async); everything else as reads with their range.
-    struct InFlight {
-        std::unique_ptr<ReadBatch> batch;
-        std::vector<uint32_t> final_targ;
-        HostBuf io;
-        uint64_t ticket = 0;
-        kid_sample *sample = nullptr;
-    };
-    std::deque<InFlight> q;
     long long n = 0;
-    const size_t max_in_flight = 2 * e.samples.size();
-    auto retire = [&]() {
-        InFlight &f = q.front();
-        const auto t0 = std::chrono::steady_clock::now();
-        int rc = kid_classify_wait(f.sample, f.ticket);
-        e.gpu_wait_s += seconds_since(t0);
-        if (rc != KID_OK) die_kid(rc);
-        if (f.batch->fq) collect_fastq_block(*f.batch, f.io, f.final_targ);
-        n += saver.add_batch(*f.batch, f.final_targ, e.k);
-        q.pop_front();
-    };
-    try {
-        while (std::unique_ptr<ReadBatch> b = pf.next(index)) {
-            q.emplace_back();
-            InFlight &f = q.back();
-            f.batch = std::move(b);
-            const size_t nr = f.batch->size();
-            f.sample = e.samples[e.next_sample]; // batches are dealt round-robin over the devices
-            e.next_sample = (e.next_sample + 1) % e.samples.size();
-            int rc;
-            const auto t_sub = std::chrono::steady_clock::now();
-            if (f.batch->fq) {
-                rc = submit_fastq_block(f.sample, *f.batch, f.io, &f.ticket);
-            } else {
-                f.final_targ.resize(nr);
-                rc = kid_classify_batch_async(f.sample, f.batch->bases.data(), f.batch->offsets.data(), f.batch->start.data(),
-                                              f.batch->stop.data(), nr, f.final_targ.data(), &f.ticket);
-            }
-            e.submit_s += seconds_since(t_sub);
-            if (rc != KID_OK) die_kid(rc);
-            while (q.size() > max_in_flight) retire();
-        }
-    } catch (const Fatal &) {
-        // the file failed behind the batches handed out so far: those are the library's until waited for, and the
-        // reference had processed them before it met the failure
-        while (!q.empty()) retire();
-        throw;
+    for (size_t f = 0; f < count; f++) {
+        saver.file_done(saver_file + f);
+        if (done) done(f, handed[f]);
+        n += handed[f];
     }
-    while (!q.empty()) retire();
     return n;
 }
 
-void dry_dump_db(FILE *f, const std::vector<int32_t> &parent, const ProbeSet &ps)
+std::vector<SourceOpener> make_openers(const std::vector<std::string> &paths, int k, std::vector<char> &missing,
+                                       std::unique_ptr<ReadSource> (*open)(const std::string &, int, bool *))
+{
+    missing.assign(paths.size(), 0);
+    std::vector<SourceOpener> files;
+    for (size_t f = 0; f < paths.size(); f++) {
+        const std::string path = paths[f];
+        char *flag = &missing[f];
+        files.push_back([path, k, flag, open]() {
+            bool m = false;
+            std::unique_ptr<ReadSource> src = open(path, k, &m);
+            *flag = m ? 1 : 0;
+            return src;
+        });
+    }
+    return files;
+}
+
+ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
+{
+    ReaderOptions o;
+    o.threads = default_threads;
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        const char *v = (i + 1 < argc) ? argv[i + 1] : "";
+        if (a == "--k") o.k = atoi(v);
+        if (a == "--log2-slots") o.log2_slots = atoi(v);
+        if (a == "--device") o.device = atoi(v);
+        if (a == "--devices") o.device_list = v;
+        if (a == "--batch-reads") o.batch_reads = (size_t)atoll(v);
+        if (a == "--dry-run") o.dry_run = v;
+        if (a == "--threads") o.threads = atoi(v);
+        if (a == "--db-cache") o.db_cache = v;
+    }
+    return o;
+}
+
+static void dry_dump_db(FILE *f, const std::vector<int32_t> &parent, const ProbeSet &ps)
 {
     fprintf(f, "PARENT %zu\n", parent.size());
     for (size_t i = 0; i < parent.size(); i++)
@@ -439,7 +395,7 @@ void dry_dump_db(FILE *f, const std::vector<int32_t> &parent, const ProbeSet &ps
     for (size_t i = 0; i < ps.keys.size(); i++) fprintf(f, "%llu %u\n", (unsigned long long)ps.keys[i], ps.targets[i]);
 }
 
-void dry_dump_source(FILE *f, const std::string &label, ReadSource &src, size_t batch_reads, int k)
+static void dry_dump_source(FILE *f, const std::string &label, ReadSource &src, size_t batch_reads, int k)
 {
     ReadBatch b;
     fprintf(f, "FILE %s\n", label.c_str());
@@ -463,6 +419,20 @@ void dry_dump_source(FILE *f, const std::string &label, ReadSource &src, size_t 
         }
     }
     src.close();
+}
+
+int write_dry_run(const std::string &path, const char *prog, const std::vector<int32_t> &parent, const ProbeSet &ps,
+                  const std::vector<std::string> &labels, const std::vector<SourceOpener> &files, size_t batch_reads, int k)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) { perror(prog); return 2; }
+    dry_dump_db(f, parent, ps);
+    for (size_t i = 0; i < files.size(); i++) {
+        std::unique_ptr<ReadSource> src = files[i]();
+        if (src) dry_dump_source(f, labels[i], *src, batch_reads, k);
+    }
+    fclose(f);
+    return 0;
 }
 
 void finish_sample(Engine &e, const std::string &result_path)

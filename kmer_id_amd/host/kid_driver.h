@@ -1,5 +1,5 @@
 // kid_driver.h -- what the three front-ends (nk10, kmer_read_vf6, kmer_read_m3) share: the database
-// on the GPU, the reader-thread / GPU-thread pipeline over one input file, closing a sample.
+// on the GPU, the reader-thread / GPU-thread pipeline over the input files, closing a sample.
 #pragma once
 #include <functional>
 #include <memory>
@@ -32,6 +32,7 @@ struct Engine {
 // sample at the same time (nk10 --samples-in-flight).  The owner must outlive it.
 std::unique_ptr<Engine> engine_worker(const Engine &owner);
 
+// The library's error, then leave_now() with the reference's exit code: 1 for a full table, 134 for a malformed record, else 3
 [[noreturn]] void die_kid(int rc);
 // The end of a front-end that has written everything: flush the standard streams and leave without unwinding -- giving
 // page-locked buffers, device memory and the HIP runtime back one by one takes 0.15 s that the operating system does at once.
@@ -45,14 +46,13 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
                    std::vector<int32_t> &parent, ProbeSet &ps, bool *from_cache = nullptr, int threads = 0,
                    StartupTiming *timing = nullptr, std::thread *cache_writer = nullptr);
 
-// Hashtable + Tree1 onto the GPU.  Returns false where the reference prints "out of memory in table"
-// and exits with 1 (newkmer_10nx.cpp:256-260).
-bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
-                 unsigned flags, int device);
-// the same on several devices ("0,1,2,3"; a device may be named twice): the table is built once and replicated
+// Hashtable + Tree1 onto the GPU(s) of parse_devices(): the table is built on the first device and replicated into the
+// others.  Returns false after printing the reference's "out of memory in table " (newkmer_10nx.cpp:256-260: the caller
+// exits with 1).
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
-std::vector<int> parse_devices(const std::string &list);
+// --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
+std::vector<int> parse_devices(int device, const std::string &list);
 // newkmer_10nx.cpp:1017-1019 on every replica
 void engine_reset(Engine &e);
 
@@ -67,31 +67,47 @@ class Prefetcher {
 public:
     Prefetcher(std::vector<SourceOpener> files, int threads, size_t batch_reads, size_t batch_bases, size_t depth = 3);
     ~Prefetcher();
-    // next batch of file `index` (indices must be visited in increasing order); nullptr at its end
-    std::unique_ptr<ReadBatch> next(size_t index);
     // next batch of ANY of the files [lo, hi) -- whichever has one ready; `which` says whose.  nullptr when all of them
     // are at their end.  A file that failed throws its Fatal only once the files before it in the range are through
     // (the reference would have read those completely before it met the failure).
     std::unique_ptr<ReadBatch> next_any(size_t lo, size_t hi, size_t &which);
     SourceStats file_stats(size_t index); // of a file that is through
-    double seconds_waited() const;        // the consumer, inside next() / next_any(): the host stages were the slower side
+    double seconds_waited() const;        // the consumer, inside next_any(): the host stages were the slower side
 private:
     struct Impl;
     std::unique_ptr<Impl> impl_;
 };
 
-// classify every batch of file `index`; returns the number of reads handed to process_read
-long long run_file(Engine &e, Prefetcher &pf, size_t index, ReadSaver &saver);
-// the same for the files [first, first + count) of ONE sample, read and classified at the same time (the two mates of
-// nk10: two inflate threads instead of one after the other); the counters do not care about the order, the read saver
-// restores it.  handed[f]: reads of file first + f handed to process_read; done(f) is called when file first + f is
-// through, in file order.
-void run_files_together(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, std::vector<long long> &handed,
-                        const std::function<void(size_t)> &done);
+// Classify the files [first, first + count) of ONE sample, read at the same time (the two mates of nk10: two inflate
+// threads instead of one after the other); the counters do not care about the order, the read saver restores it.
+// `saver_file` is the saver's index of file `first` (a saver may span several calls: the files of a kmer_read_vf6 job,
+// -f1 and -f2 of kmer_read_m3).  done(f, handed), if given, is called for every file first + f in file order once all of
+// them are through, with the number of its reads handed to process_read.  Returns the reads handed of all the files.
+long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file = 0,
+                    const std::function<void(size_t, long long)> &done = nullptr);
 
-// --dry-run support (host stages only, no GPU): what WOULD be handed to the GPU, as text
-void dry_dump_db(FILE *f, const std::vector<int32_t> &parent, const ProbeSet &ps);
-void dry_dump_source(FILE *f, const std::string &label, ReadSource &src, size_t batch_reads, int k);
+// One opener per path, each by `open`, which sets its bool when the file is a plain FASTA that is not there (the
+// reference's "nark <name>"): missing[f] holds it for file f once that file is through.  `missing` must not move
+// while the files are read.
+std::vector<SourceOpener> make_openers(const std::vector<std::string> &paths, int k, std::vector<char> &missing,
+                                       std::unique_ptr<ReadSource> (*open)(const std::string &, int, bool *) = open_by_suffix);
+
+// The options kmer_read_vf6 and kmer_read_m3 share, read the way the reference reads its own: a flag takes the next word
+// as its value (and that word is looked at as a flag too), a word that is no option is ignored.
+struct ReaderOptions {
+    int k = 30, log2_slots = 30, device = 0, threads = 0;
+    std::string device_list; // --devices: replicas of the table, batches dealt round-robin, counters merged
+    size_t batch_reads = 1 << 18;
+    std::string dry_run;     // --dry-run FILE: host stages only (no GPU), for the CPU test-suite
+    std::string db_cache;    // --db-cache FILE: binary cache of the parsed database
+};
+ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
+
+// --dry-run FILE (host stages only, no GPU): the database and the reads of `files` as they WOULD be handed to the GPU, as
+// text, each file under its label (a file without a reader is left out).  Returns the exit code: 0, or 2 when FILE cannot
+// be written (perror(prog)).
+int write_dry_run(const std::string &path, const char *prog, const std::vector<int32_t> &parent, const ProbeSet &ps,
+                  const std::vector<std::string> &labels, const std::vector<SourceOpener> &files, size_t batch_reads, int k);
 
 // gcount / ucount of the sample -> "<i>,<g>,<u>" lines
 void finish_sample(Engine &e, const std::string &result_path);

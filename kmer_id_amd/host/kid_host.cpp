@@ -56,6 +56,26 @@ bool strain_list_present(const std::string &path)
     return (bool)fin;
 }
 
+bool count_strains(const std::string &path, int &strains, int &targets)
+{
+    std::ifstream fin(path);
+    if (!fin) return false;
+    std::string line, acc;
+    int targi = 0, largest = 0;
+    strains = 0;
+    while (std::getline(fin, line)) {
+        if (!line.empty() && line.back() == '\r') line.pop_back();
+        if (line.length() > 1) {
+            std::stringstream ls(line);
+            ls >> targi >> acc;
+            if (targi > largest) largest = targi;
+            strains++;
+        }
+    }
+    targets = largest + 1;
+    return true;
+}
+
 // ---------------------------------------------------------------- gz line reader
 GzLines::GzLines(const std::string &path) : gz_(new GzStream(path)) // (throws when the file cannot be opened: exit 255 like the reference's gzread(NULL))
 {
@@ -567,6 +587,24 @@ bool PlainTokenStream::fill(ReadBatch &out, size_t max_reads, size_t max_bases)
         }
     }
     return out.size() > 0;
+}
+
+bool ends_with(const std::string &s, const std::string &suffix)
+{
+    return s.size() >= suffix.size() && s.compare(s.size() - suffix.size(), suffix.size(), suffix) == 0;
+}
+
+std::unique_ptr<ReadSource> open_by_suffix(const std::string &name, int k, bool *missing_plain_fasta)
+{
+    if (ends_with(name, ".fastq.gz")) return std::unique_ptr<ReadSource>(new FastqStream(name, k));
+    if (ends_with(name, ".fasta.gz")) return std::unique_ptr<ReadSource>(new FastaGzStream(name, k));
+    if (ends_with(name, ".fasta")) {
+        std::unique_ptr<PlainTokenStream> p(new PlainTokenStream(name, k, false));
+        if (!p->present() && missing_plain_fasta) *missing_plain_fasta = true;
+        return std::unique_ptr<ReadSource>(std::move(p));
+    }
+    if (ends_with(name, ".fastq")) return std::unique_ptr<ReadSource>(new PlainTokenStream(name, k, true));
+    return nullptr;
 }
 
 // ---------------------------------------------------------------- outputs

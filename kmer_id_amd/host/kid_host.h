@@ -24,6 +24,9 @@ std::vector<int32_t> load_tree(const std::string &path, int ntar);
 
 // strain list (newkmer_10nx.cpp:951-971): only its presence is observable ("narin <name>")
 bool strain_list_present(const std::string &path);
+// strain list of kmer_read_vf6 / kmer_read_m3 (kmer_read_vf6.cpp:1059-1089): every line of more than one character is a
+// strain, its first field a target; `targets` is the largest of them + 1.  false: the file cannot be read.
+bool count_strains(const std::string &path, int &strains, int &targets);
 
 // A flat array whose final size is not known while it is being filled by several threads (the entries of a 5 GB
 // probes file): address space for the most it can ever hold is reserved once (anonymous, no-reserve mapping: only the
@@ -204,6 +207,12 @@ private:
     std::string lseq_, seq_, acc_;
 };
 
+bool ends_with(const std::string &s, const std::string &suffix);
+// suffix dispatch of kmer_read_vf6 / kmer_read_m3 (kmer_read_vf6.cpp:1133-1152, kmer_read_m3.cpp:1083-1100): .fastq.gz,
+// .fasta.gz, .fasta, .fastq (no name has two of these endings, so the order the two programs test them in does not matter);
+// nullptr for anything else.  *missing_plain_fasta (if given) is set when a .fasta file cannot be opened.
+std::unique_ptr<ReadSource> open_by_suffix(const std::string &name, int k, bool *missing_plain_fasta);
+
 // ---------------------------------------------------------------- job lists (kmer_read_vf6)
 // <jname>/<jname>.txt: a header line "<job> <n>" followed by n lines naming input files, repeated
 // (kmer_read_vf6.cpp:1021-1057).  Read with the reference's extraction rules: lines of at most one character
@@ -239,11 +248,11 @@ public:
     ReadSaver(const std::string &first12_path, int ntar, const std::string &target_path = "", uint32_t save_target = 0,
               bool first12_enabled = true);
     ~ReadSaver();
-    // returns the number of reads of the batch that the reference hands to process_read (all of them, except in a FASTQ
-    // block: there the records process_qual drops are still in the batch, with stop - start < k)
-    long long add_batch(const ReadBatch &b, const std::vector<uint32_t> &final_targ, int k) { return add_batch_of(0, b, final_targ, k); }
-    // Several files of one sample read at the same time (the two mates, nk10): the batches of file f arrive in file
-    // order, but files interleave.  What the reference writes depends on the order "all of file 0, then all of file 1":
+    // Returns the number of reads of the batch that the reference hands to process_read (all of them, except in a FASTQ
+    // block: there the records process_qual drops are still in the batch, with stop - start < k).
+    // The files of a saver are numbered from 0 in the reference's order, and file_done(f) is called once file f is
+    // through.  Several files of one sample may be read at the same time (the two mates, nk10): the batches of file f
+    // arrive in file order, but files interleave.  What the reference writes depends on the order "all of file 0, then all of file 1":
     // the reads of a later file that can still be among a target's first 12 (the first 12 of that target within their
     // own file) wait in memory until the files before it are through (file_done).
     long long add_batch_of(size_t file, const ReadBatch &b, const std::vector<uint32_t> &final_targ, int k);

@@ -17,9 +17,10 @@
 //   --samples-in-flight N (threads / 2)  samples read and classified at the same time, each with its own counters on the GPU
 //   --timing         one JSON line on stderr when the run ends: seconds of the start-up phases (probes inflate / parse,
 //                    cache read / write, upload + table build on the GPU, first batch classified) and of the read files
-//   --dry-run FILE   host stages only (no GPU): parse the DB text files and the FASTQ files,
-//                    write what WOULD be handed to the GPU to FILE (used by the CPU test-suite)
+//   --dry-run FILE   host stages only (no GPU): parse the DB text files and the files a run would read (FASTQ, or
+//                    FASTA with --fasta), write what WOULD be handed to the GPU to FILE (used by the CPU test-suite)
 #include <dirent.h>
+#include <errno.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -36,6 +37,15 @@
 
 using namespace kidhost;
 
+static std::unique_ptr<ReadSource> open_fastq(const std::string &path, int k, bool *) { return std::unique_ptr<ReadSource>(new FastqStream(path, k)); }
+// process_fa (:877-913): no '\r' is removed
+static std::unique_ptr<ReadSource> open_fasta(const std::string &path, int k, bool *missing)
+{
+    std::unique_ptr<PlainTokenStream> p(new PlainTokenStream(path, k, false, /*strip_cr=*/false));
+    *missing = !p->present();
+    return std::unique_ptr<ReadSource>(std::move(p));
+}
+
 int main(int argc, char **argv)
 {
     std::string dname, db_dir = "./bact10/", e1 = "_R1_tr.fastq.gz", e2 = "_R2_tr.fastq.gz";
@@ -45,7 +55,6 @@ int main(int argc, char **argv)
     size_t batch_reads = 1 << 18;
     std::string dry_run, db_cache, device_list;
     bool fasta_mode = false;
-    bool parse_only = false; // --parse-only: run the reader pool over the directory without a GPU and report its rate
     bool timing = false;
     int in_flight = 0; // --samples-in-flight N (0: half the reader threads)
     const auto t_start = std::chrono::steady_clock::now();
@@ -68,7 +77,6 @@ int main(int argc, char **argv)
         else if (a == "--r2") e2 = val("--r2");
         else if (a == "--dry-run") dry_run = val("--dry-run");
         else if (a == "--db-cache") db_cache = val("--db-cache");
-        else if (a == "--parse-only") parse_only = true;
         else if (a == "--fasta") fasta_mode = true;
         else if (a == "--timing") timing = true;
         else if (a == "--samples-in-flight") in_flight = atoi(val("--samples-in-flight"));
@@ -109,7 +117,7 @@ int main(int argc, char **argv)
         // the HIP runtime takes 0.1-0.15 s to come up: while the database is being read, not after
         std::thread gpu_warm;
         Joiner join_gpu_warm{gpu_warm};
-        if (dry_run.empty() && !parse_only) {
+        if (dry_run.empty()) {
             const int warm_device = device_list.empty() ? device : atoi(device_list.c_str());
             gpu_warm = std::thread([warm_device] {
                 void *p = nullptr;
@@ -138,62 +146,37 @@ int main(int argc, char **argv)
         std::cout << "tree loaded" << std::endl;
         std::cout << ps.lines_parsed << " kmers loaded" << std::endl;
 
-        if (!dry_run.empty()) { // host stages only
-            FILE *f = fopen(dry_run.c_str(), "w");
-            if (!f) { perror("nk10"); return 2; }
-            dry_dump_db(f, parent, ps);
-            DIR *dd = opendir(dname.c_str());
-            std::vector<std::string> names;
-            if (dd) {
-                while (struct dirent *ent = readdir(dd)) {
-                    std::string n1 = ent->d_name;
-                    size_t pos = n1.find(e1);
-                    if (pos != std::string::npos) names.push_back(n1.substr(0, pos));
-                }
-                closedir(dd);
+        // ---- find the samples (:992-1014): every directory entry whose name contains the R1 suffix
+        std::vector<std::string> fnames;
+        bool dir_read = false;
+        int dir_errno = 0;
+        if (DIR *dir = opendir(dname.c_str())) {
+            while (struct dirent *ent = readdir(dir)) {
+                std::string name1 = ent->d_name;
+                size_t pos = name1.find(e1);
+                if (pos != std::string::npos) fnames.push_back(name1.substr(0, pos));
             }
-            for (const std::string &prefix : names)
-                for (const std::string &suffix : {e1, e2}) {
-                    FastqStream fq(dname + prefix + suffix, k);
-                    dry_dump_source(f, prefix + suffix, fq, batch_reads, k);
-                }
-            fclose(f);
-            return 0;
+            closedir(dir);
+            dir_read = true;
+        } else {
+            dir_errno = errno;
         }
+        const size_t n_samples = fnames.size(), files_per_sample = fasta_mode ? 1 : 2;
+        std::vector<std::string> names, paths; // per file: its name in the directory, its path
+        for (const std::string &prefix : fnames) {
+            names.push_back(prefix + e1);
+            if (!fasta_mode) names.push_back(prefix + e2);
+        }
+        for (const std::string &name : names) paths.push_back(dname + name);
+        std::vector<char> missing;
+        std::vector<SourceOpener> files = make_openers(paths, k, missing, fasta_mode ? open_fasta : open_fastq);
+        if (!dry_run.empty()) return write_dry_run(dry_run, "nk10", parent, ps, names, files, batch_reads, k); // host stages only
 
-        if (parse_only) {
-            DIR *dd = opendir(dname.c_str());
-            std::vector<SourceOpener> files;
-            if (dd) {
-                while (struct dirent *ent = readdir(dd)) {
-                    std::string n1 = ent->d_name;
-                    size_t pos = n1.find(e1);
-                    if (pos == std::string::npos) continue;
-                    for (const std::string &suffix : {e1, e2}) {
-                        const std::string path = dname + n1.substr(0, pos) + suffix;
-                        files.push_back([path, k]() { return std::unique_ptr<ReadSource>(new FastqStream(path, k)); });
-                    }
-                }
-                closedir(dd);
-            }
-            const size_t nf = files.size();
-            Prefetcher pf(std::move(files), threads, batch_reads, (size_t)256 << 20);
-            long long n = 0, bases = 0;
-            for (size_t f = 0; f < nf; f++)
-                while (std::unique_ptr<ReadBatch> b = pf.next(f)) { n += (long long)b->size(); bases += (long long)b->bases.size(); }
-            std::cout << n << " reads, " << bases << " bases parsed" << std::endl;
-            if (cache_writer.joinable()) cache_writer.join();
-            print_timing();
-            return 0;
-        }
         Engine eng;
         eng.batch_reads = batch_reads;
-        const std::vector<int> devices = device_list.empty() ? std::vector<int>(1, device) : parse_devices(device_list);
+        const std::vector<int> devices = parse_devices(device, device_list);
         if (gpu_warm.joinable()) gpu_warm.join();
-        if (!engine_open(eng, ps, parent, k, log2_slots, 0, 0, devices)) { // :256-260
-            std::cout << "out of memory in table " << std::endl;
-            return 1;
-        }
+        if (!engine_open(eng, ps, parent, k, log2_slots, 0, 0, devices)) return 1; // :256-260
         // file text goes into page-locked memory from here on: uploads by DMA, not through a CPU copy
         static int pin_device = devices[0];
         set_text_allocator([](size_t n) -> void * { void *p = nullptr; return kid_host_alloc(pin_device, n, &p) == KID_OK ? p : nullptr; },
@@ -215,46 +198,17 @@ int main(int argc, char **argv)
         }).detach();
         ps = ProbeSet();
 
-        // ---- find the samples (:992-1014): every directory entry whose name contains the R1 suffix
         std::cout << dname << std::endl;
-        std::vector<std::string> fnames;
-        DIR *dir = opendir(dname.c_str());
-        if (!dir) {
+        if (!dir_read) {
             std::cout << "hosed" << std::endl;
+            errno = dir_errno;
             perror("");
             return EXIT_FAILURE;
         }
-        while (struct dirent *ent = readdir(dir)) {
-            std::string name1 = ent->d_name;
-            size_t pos = name1.find(e1);
-            if (pos != std::string::npos) fnames.push_back(name1.substr(0, pos));
-        }
-        closedir(dir);
-
-        std::vector<SourceOpener> files;
-        std::vector<char> missing(fnames.size(), 0);
-        for (size_t f = 0; f < fnames.size(); f++) {
-            const std::string prefix = fnames[f];
-            if (fasta_mode) {
-                const std::string path = dname + prefix + e1;
-                char *flag = &missing[f];
-                files.push_back([path, k, flag]() {
-                    std::unique_ptr<PlainTokenStream> p(new PlainTokenStream(path, k, false, /*strip_cr=*/false));
-                    *flag = p->present() ? 0 : 1;
-                    return std::unique_ptr<ReadSource>(std::move(p));
-                });
-                continue;
-            }
-            for (const std::string &suffix : {e1, e2}) {
-                const std::string path = dname + prefix + suffix;
-                files.push_back([path, k]() { return std::unique_ptr<ReadSource>(new FastqStream(path, k)); });
-            }
-        }
         {   // the threads are shared out over the files that are read at the same time (before the first file is opened)
-            const size_t fps = fasta_mode ? 1 : 2;
             size_t at_once = in_flight < 1 ? 1 : (size_t)in_flight;
             if (at_once > fnames.size()) at_once = fnames.empty() ? 1 : fnames.size();
-            const size_t per_file = (size_t)threads / (fps * at_once);
+            const size_t per_file = (size_t)threads / (files_per_sample * at_once);
             set_inflate_threads(per_file >= 3 ? (int)per_file : 1);
         }
         Prefetcher pf(std::move(files), threads, eng.batch_reads, eng.batch_bases);
@@ -263,7 +217,6 @@ int main(int argc, char **argv)
         // waits for, so a directory of samples is as fast as the cores it may use.  What a sample prints is kept and
         // printed in directory order; a sample that fails ends the run where the reference would have ended it (the
         // samples before it complete, what later ones wrote is removed).
-        const size_t n_samples = fnames.size(), files_per_sample = fasta_mode ? 1 : 2;
         size_t n_workers = in_flight < 1 ? 1 : (size_t)in_flight;
         if (n_workers > n_samples) n_workers = n_samples ? n_samples : 1;
         struct SampleOut {
@@ -289,15 +242,14 @@ int main(int argc, char **argv)
             {
                 ReadSaver saver(dname + prefix + "_reads.txt", ntar);
                 if (fasta_mode) {
-                    tct += run_file(e, pf, fi0, saver);
-                    if (missing[f]) out += "nark " + dname + prefix + e1 + "\n";
+                    tct += run_files(e, pf, fi0, 1, saver);
+                    if (missing[fi0]) out += "nark " + paths[fi0] + "\n";
                     out += std::to_string(tct) + " reads loaded\n";
                 } else {
                     // the two mates are inflated, indexed and classified at the same time; "<tct> reads loaded" (:1030,:1036)
                     // comes when a file is through, R1 first
-                    std::vector<long long> handed;
-                    run_files_together(e, pf, fi0, 2, saver, handed, [&](size_t mate) {
-                        tct += handed[mate];
+                    run_files(e, pf, fi0, 2, saver, 0, [&](size_t mate, long long handed) {
+                        tct += handed;
                         std::lock_guard<std::mutex> lk(om);
                         if (t_first_file < 0) t_first_file = since_start();
                         t_file_done[mate] = since_start();

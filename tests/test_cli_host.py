@@ -187,6 +187,64 @@ def test_fatal_inputs_exit_codes(nk10, tmp_path):
     assert subprocess.run([nk10], stdout=subprocess.PIPE, stderr=subprocess.PIPE).returncode == 2
 
 
+@pytest.mark.gpu
+def test_short_quality_exit_code_on_gpu(nk10, tmp_path):
+    """the 134 case of test_fatal_inputs_exit_codes without --dry-run: the GPU trims the block, the library reports the
+    record as malformed when the sample is closed, and the program ends with the reference's abort code"""
+    cwd = str(tmp_path)
+    make_db_dir(cwd, 2e-5)
+    fq = os.path.join(cwd, "fq"); os.makedirs(fq)
+    with gzip.open(os.path.join(fq, "L_R1_tr.fastq.gz"), "wb") as fh:
+        fh.write(b"@a\nACGTACGT\n+\nIIII\n")
+    with gzip.open(os.path.join(fq, "L_R2_tr.fastq.gz"), "wb") as fh:
+        fh.write(b"@b\nACGT\n+\nIIII\n")
+    r = subprocess.run([nk10, fq + "/", "--log2-slots", "16"], cwd=cwd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=300)
+    assert r.returncode == 134, (r.returncode, r.stderr[-500:])
+    assert b"quality line shorter than the sequence" in r.stderr
+
+
+def _process_fa(path, k):
+    """newkmer_10nx.cpp process_fa (:877-913): the first token of every line ('\\r' kept; a line without one repeats the
+    token before), records joined, a record is kept when it is longer than k -> [(accession, sequence)]"""
+    out, acc, seq, tok = [], None, "", ""
+    for line in open(path, encoding="latin-1").read().split("\n")[:-1]:
+        if line.split():
+            tok = line.split()[0]
+        if tok.startswith(">"):
+            if len(seq) > k:
+                out.append((acc, seq))
+            seq, acc = "", tok[1:]
+        else:
+            seq += tok
+    if len(seq) > k:
+        out.append((acc, seq))
+    return out
+
+
+def test_dry_run_fasta_mode(nk10, gold_dir, tmp_path):
+    """--dry-run --fasta dumps the plain FASTA files the real run reads (one per sample), every record of them that is
+    longer than k, whole; the counts are the reference's "<n> reads loaded" lines"""
+    src = os.path.join(gold_dir, "e2e_fasta")
+    cwd = str(tmp_path)
+    make_db_dir(cwd, 2e-5)
+    fa = os.path.join(cwd, "fa"); os.makedirs(fa)
+    for f in os.listdir(src):
+        if f.endswith(".fasta"):
+            shutil.copy(os.path.join(src, f), fa)
+    dump = os.path.join(cwd, "dry.txt")
+    subprocess.run([nk10, fa + "/", "--fasta", "--r1", "_R1.fasta", "--dry-run", dump], cwd=cwd, check=True, stdout=subprocess.PIPE)
+    files = {}
+    for line in open(dump, encoding="latin-1").read().split("FILE ")[1:]:
+        name, *recs = line.rstrip("\n").split("\n")
+        files[name] = [tuple(r.split("\t")) for r in recs]
+    assert sorted(files) == ["X_R1.fasta", "Y_R1.fasta"]
+    for name, recs in files.items():
+        exp = _process_fa(os.path.join(fa, name), K)
+        assert recs == [(acc, "0", str(len(seq) - 1), seq) for acc, seq in exp], name
+    stdout = open(os.path.join(src, "stdout.txt")).read().splitlines()
+    assert ["%d reads loaded" % len(files[p + "_R1.fasta"]) for p in ("X", "Y")] == [stdout[stdout.index(p) + 1] for p in ("X", "Y")]
+
+
 # ------------------------------------------------------------------ whole program on the GPU
 def _run_e2e_small(nk10, gold_dir, cwd, extra, runs=1):
     src = os.path.join(gold_dir, "e2e_small")
