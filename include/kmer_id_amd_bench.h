@@ -8,6 +8,7 @@
 extern "C" {
 #endif
 struct kid_db;
+struct kid_sample;
 /* ---- synthetic workload generators (bench + tests; deterministic, seeded) ------
  * DB key j = canonical(splitmix64(seed + j) mod 4^k); target of key j follows
  * cum[] (cum[t] <= j < cum[t+1]).  Reads: see DESIGN.md "synthetic workload".    */
@@ -32,6 +33,12 @@ int kid_synth_reads_device(uint64_t db_seed, uint64_t read_seed, int k, const ui
  * out at 39 G cells/s where the line probe reaches 49 G lines/s).
  * *ms_out = milliseconds per launch.                                               */
 int kid_bench_gather(struct kid_db *db, uint64_t n_loads, int inflight, int iters, float *ms_out, uint64_t *loads_out);
+
+/* which kid_classify_kernel instantiations the sample has launched since it began or was last reset: bit
+ * PAIRK*16 | ROWS<<3 | HIST<<2 | MINLOC<<1 | (KFIX == 30) per instantiation (PAIRK 1 pair loop, 2 duo loop, 0 general
+ * loops).  A launch is recorded whether or not the kernel finds work: a batch with device-side offsets launches all
+ * three loops of its configuration, and the two the batch is not for return at once.                                 */
+int kid_sample_kernel_variants(struct kid_sample *s, uint64_t *mask);
 
 /* device memory helpers so that a host language without a HIP binding can stage buffers */
 int kid_dev_alloc(int device, uint64_t nbytes, void **d_ptr);

@@ -284,6 +284,13 @@ class Sample:
         check(self._lib.kid_sample_kernel_time_device(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def kernel_variants(self):
+        """-> the kid_classify_kernel instantiations launched since the sample began or was last reset, as a set of
+        (ROWS, HIST, MINLOC, KFIX, PAIRK) tuples (kid_sample_kernel_variants)"""
+        m = C.c_uint64(0)
+        check(self._lib.kid_sample_kernel_variants(self._h, C.byref(m)))
+        return {(b >> 3 & 1, b >> 2 & 1, b >> 1 & 1, 30 if b & 1 else 0, b >> 4) for b in range(64) if m.value >> b & 1}
+
     def seen_bytes(self):
         n = C.c_uint64(0)
         check(self._lib.kid_sample_seen_bytes(self._h, C.byref(n)))

@@ -131,6 +131,7 @@ struct kid_sample {
     uint8_t *long_tiles = nullptr; // "this tile of 256 positions holds a hit"
     uint64_t long_tiles_cap = 0;
     uint64_t reads_submitted = 0; // since the last reset: checked against the device's count when results are read
+    uint64_t kernel_variants = 0; // since the last reset: one bit per kid_classify_kernel instantiation launched (kid_sample_kernel_variants)
     // the scratch below is one set per sample: batches on different streams are ordered behind each other
     hipStream_t last_stream = nullptr;
     bool has_last_stream = false;
@@ -649,6 +650,7 @@ extern "C" int kid_sample_reset(kid_sample *s)
     }
     s->dev_clock_batches = 0;
     s->reads_submitted = 0;
+    s->kernel_variants = 0;
     if (s->seen_log_tail) KID_HIP(hipMemset(s->seen_log_tail, 0, KID_LOG_SHARDS * 64));
     if (s->seen_log) { // (a pass may have taken the log out of the argument blocks: KidLogArgs)
         int rc = kid_seenlog_point(s, s->seen_log, nullptr);
@@ -953,10 +955,13 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
         hipLaunchKernelGGL(kid_rebase_kernel, dim3(1), dim3(64), 0, stream, rare, pk.desc, pk.out_final, 0ull, 0u, 0, 0ull);
     }
 #define KID_LAUNCH1(R, H, M, KF, PK)                                                                                            \
-    hipLaunchKernelGGL((kid_classify_kernel<2, R, H, M, KF, PK>), dim3(grid), dim3(block),                                     \
-                       (((H) ? ((PK) ? hist_words16 : hist_words) : 0u) +                                                       \
-                        (size_t)wpb * ((PK) ? KID_PAIR_LDS_WORDS : wave_words)) * 4 + 32, stream,                              \
-                       db->d, pk, sd, (H) ? ((PK) ? hist_words16 : hist_words) : 0u, pk.desc, rare)
+    do {                                                                                                                        \
+        s->kernel_variants |= 1ull << ((PK) * 16 | (R) << 3 | (H) << 2 | (M) << 1 | ((KF) == 30));                              \
+        hipLaunchKernelGGL((kid_classify_kernel<2, R, H, M, KF, PK>), dim3(grid), dim3(block),                                  \
+                           (((H) ? ((PK) ? hist_words16 : hist_words) : 0u) +                                                   \
+                            (size_t)wpb * ((PK) ? KID_PAIR_LDS_WORDS : wave_words)) * 4 + 32, stream,                           \
+                           db->d, pk, sd, (H) ? ((PK) ? hist_words16 : hist_words) : 0u, pk.desc, rare);                        \
+    } while (0)
 #define KID_LAUNCH(R, H, M)                                                                                                    \
     do {                                                                                                                       \
         if (db->info.k == 30) KID_LAUNCH1(R, H, M, 30, 0);                                                                     \
@@ -1046,6 +1051,13 @@ static int kid_prep_stream_for(kid_sample *s, hipStream_t stream, hipStream_t *o
     if (!s->inputs_ready) return KID_OK;
     if (!s->prep_stream) KID_HIP(hipStreamCreateWithFlags(&s->prep_stream, hipStreamNonBlocking));
     *out = s->prep_stream;
+    return KID_OK;
+}
+
+extern "C" int kid_sample_kernel_variants(kid_sample *s, uint64_t *mask)
+{
+    if (!s || !mask) return kid_fail(KID_ERR_ARG, "null argument");
+    *mask = s->kernel_variants;
     return KID_OK;
 }
 

@@ -39,6 +39,10 @@
 #define KID_EARLY_QN 32u // ... while fewer than this many lookups are queued (profiles/r02/clumped_ec.txt)
 #define KID_GEN_ML_LDS_WORDS (104 + 3 * KID_CQ_CAP + KID_CQ_CAP / 4 + 64) // general loops on the minimizer-localised table: strip, counters, queue, results
 #define KID_CLASSIFY_OCC 8 // waves per SIMD the register allocator must leave room for
+// ... except the duo loop with ancestor rows: at 64 VGPRs it spills, and a spill or copy of a register that an
+// asynchronous inline-assembly load (below) has not filled yet carries a stale value past the explicit s_waitcnt --
+// wrong hits, found by tests/test_gpu_kernel_variants.py.  Allowed 128 VGPRs it takes 80 (6 waves per SIMD), no spill.
+#define KID_CLASSIFY_OCC_DUO_ROWS 4
 
 typedef uint32_t kid_u4 __attribute__((ext_vector_type(4)));
 typedef uint32_t kid_u2 __attribute__((ext_vector_type(2)));
@@ -480,7 +484,7 @@ struct KidGroup {      // a group of U*64 windows between its two halves
 // batch is for when it knows the longest read, else all three: the others return at once.  Separate
 // kernels, because each loop wants all 64 vector registers of an 8-waves-per-SIMD kernel for itself.
 template <int U, bool ROWS, bool HIST, bool MINLOC, int KFIX, int PAIRK>
-__global__ __launch_bounds__(512, KID_CLASSIFY_OCC) void kid_classify_kernel(const KidDevDb db, const KidInput b, const KidSampleDev s,
+__global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_ROWS : KID_CLASSIFY_OCC) void kid_classify_kernel(const KidDevDb db, const KidInput b, const KidSampleDev s,
                                                             const uint32_t hist_words,
                                                             const KidReadDesc *__restrict__ const descs,
                                                             const KidRareArgs *__restrict__ const rare)
