@@ -193,6 +193,56 @@ int kid_classify_fixed_device(kid_sample *s, const void *d_bases, uint32_t read_
 int kid_trim_batch(kid_db *db, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads,
                    int32_t *start, int32_t *stop, uint8_t *keep);
 
+/* ---- every read's k-mer hits ------------------------------------------------------
+ * What process_read folds (newkmer_10nx.cpp:526-595), handed out instead of folded: for every read, in read-position
+ * order, the k-mer windows for which Hashtable::getHash returns a target > 0 (targets equal to 1 included).
+ *   pos     index of the k-mer's first base, counted from the first byte of the read (not from `start`)
+ *   target  what getHash returns
+ *   entry   ordinal, in the arrays handed to kid_db_build, of the first-inserted entry with that key: the numbering
+ *           of the seen-bitmap ("multi-GPU merge helpers" below), i.e. the line of the probes file
+ * The calls are pure: they read the database and the caller's text and touch no sample (no gcount, no seen bit, no
+ * stats).  Reads, ranges and trimming are decided by the kernels that decide them for kid_classify_*; the probe cap of
+ * kmer_read_m3 (max_probes) is honoured.  Records of any length work.  The output is byte-identical across runs, across
+ * any split of the reads into calls and across the table kinds (minimizer-localised, KID_FLAG_REF_GEOMETRY,
+ * KID_FLAG_HOST_BUILD).
+ *   hit_offsets[n_reads + 1]  CSR: the hits of read r are hits[hit_offsets[r] .. hit_offsets[r + 1]); always complete
+ *   n_kmers[n_reads]          nullable; windows looked up per read (the read's share of kid_sample_stats' lookups)
+ *   hits[cap], *n_hits        *n_hits = hit_offsets[n_reads], always; hits is filled only if *n_hits <= cap, otherwise
+ *                             nothing is written to it and the call still returns KID_OK: size a buffer and call again
+ *                             (hits = NULL, cap = 0 is the sizing call)
+ * Argument errors as for kid_classify_batch (offsets not monotone, start/stop outside the read, more than 2^31-1
+ * reads: KID_ERR_ARG; a quality line shorter than its sequence: KID_ERR_FORMAT).
+ * Scratch: grows with the largest batch seen (16 B per read + 8 B per read for the tile index + 16 B per 64 windows,
+ * plus, for the host-buffer forms, a device copy of the inputs and outputs), never with the database; it belongs to
+ * the kid_db and is released by kid_db_destroy.  There is ONE set of it per kid_db, so calls on one kid_db run one after
+ * the other: every call, the device form included, first blocks the calling thread until the kernels of the call before
+ * are through.                                                                                                    */
+typedef struct kid_hit {
+    uint32_t pos, target, entry;
+} kid_hit;
+/* host buffers; offsets/start/stop as for kid_classify_batch (start = stop = NULL: whole reads) */
+int kid_db_read_hits(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                     uint64_t n_reads, uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits);
+/* a FASTQ text block as for kid_classify_fastq_async: process_qual runs on the GPU; a record that fails
+ * stop - start >= k has n_kmers 0 and no hits */
+int kid_db_read_hits_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                           uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits);
+/* Everything resident in HBM; the call returns once its kernels are queued on `stream` (but see above: it first waits
+ * on the host for the call before it on this kid_db).  The alignment / lifetime rules of kid_classify_batch_device
+ * hold for d_bases, d_offsets, d_start, d_stop.  d_hit_offsets: uint64[n_reads + 1]; d_n_kmers: uint32[n_reads], nullable;
+ * d_hits: kid_hit[cap], nullable with cap = 0; d_n_hits: one uint64, written on the device.  What the host cannot
+ * check is checked on the device and reported as KID_ERR_ARG by the next kid_db_read_hits_time: a [start, stop]
+ * outside its read (clamped to the read), and a batch with more than bases_nbytes / 64 + n_reads tiles of 64 windows
+ * (reads that overlap in the text, or offsets beyond bases_nbytes), which gets no hits at all: all offsets 0.      */
+int kid_db_read_hits_device(kid_db *db, const void *d_bases, uint64_t bases_nbytes, const void *d_offsets, const void *d_start,
+                            const void *d_stop, uint64_t n_reads, void *d_hit_offsets, void *d_n_kmers, void *d_hits, uint64_t cap,
+                            void *d_n_hits, void *stream);
+/* Device time of the hits kernels since the last query, the calls and the reads they belong to: one HIP event in front
+ * of a call's first kernel (descriptors), one behind its last (fill).  For kid_db_read_hits_device that is the kernels
+ * alone; the host-buffer forms read the number of hits back between count and fill (and may allocate), and that
+ * round trip lies inside the interval.  Synchronises with the last call.                                           */
+int kid_db_read_hits_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
+
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).
  * Synchronises the sample's outstanding work first.                             */

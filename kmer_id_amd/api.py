@@ -55,6 +55,27 @@ class PinnedBuffer:
             pass
 
 
+class ReadHits:
+    """Every read's k-mer hits in read-position order (kid_db_read_hits*): CSR `offsets` (uint64[n + 1]) over the
+    parallel uint32 arrays `pos`, `target`, `entry`, and `n_kmers` (uint32[n]: windows looked up per read)."""
+
+    def __init__(self, offsets, n_kmers, hits):
+        self.offsets = offsets
+        self.n_kmers = n_kmers
+        hits = hits.reshape(-1, 3)
+        self.pos = np.ascontiguousarray(hits[:, 0])
+        self.target = np.ascontiguousarray(hits[:, 1])
+        self.entry = np.ascontiguousarray(hits[:, 2])
+
+    def __len__(self):
+        return self.offsets.size - 1
+
+    def of(self, r):
+        """-> (pos, target, entry) of read r"""
+        a, b = int(self.offsets[r]), int(self.offsets[r + 1])
+        return self.pos[a:b], self.target[a:b], self.entry[a:b]
+
+
 class KmerDB:
     """Replaces `new Hashtable()` + `new Tree1()` + the add_kmer/add_edge load loops."""
 
@@ -125,6 +146,52 @@ class KmerDB:
         keep = np.empty(n, np.uint8)
         check(self._lib.kid_trim_batch(self._h, _ptr(quals), _ptr(offsets), n, _ptr(start), _ptr(stop), _ptr(keep)))
         return start, stop, keep
+
+    def _read_hits(self, call, n):
+        """the sizing call, then the call that fills a buffer of exactly that size"""
+        offsets = np.empty(n + 1, np.uint64)
+        n_kmers = np.empty(n, np.uint32)
+        total = C.c_uint64(0)
+        check(call(_ptr(offsets), _ptr(n_kmers), None, 0, C.byref(total)))
+        hits = np.empty(total.value * 3, np.uint32)
+        if total.value:
+            check(call(_ptr(offsets), _ptr(n_kmers), _ptr(hits), total.value, C.byref(total)))
+        return ReadHits(offsets, n_kmers, hits)
+
+    def read_hits(self, bases, offsets, start=None, stop=None):
+        """The k-mer hits of every read of a batch held in host memory (what process_read folds, newkmer_10nx.cpp:526-595),
+        in read-position order -> ReadHits.  Pure: no sample is touched."""
+        bases = _as(bases, np.uint8)
+        offsets = _as(offsets, np.uint64)
+        start = _as(start, np.int32)
+        stop = _as(stop, np.int32)
+        n = offsets.size - 1
+        return self._read_hits(lambda o, nk, h, cap, tot: self._lib.kid_db_read_hits(
+            self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, o, nk, h, cap, tot), n)
+
+    def read_hits_fastq(self, text, recs):
+        """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): process_qual
+        runs on the GPU; a record that fails stop - start >= k has no window and no hit."""
+        text = _as(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8)
+        recs = _as(recs, np.uint32).reshape(-1, 4)
+        n = recs.shape[0]
+        return self._read_hits(lambda o, nk, h, cap, tot: self._lib.kid_db_read_hits_fastq(
+            self._h, _ptr(text), text.size, _ptr(recs), n, o, nk, h, cap, tot), n)
+
+    def read_hits_device(self, d_bases, bases_nbytes, d_offsets, n_reads, d_hit_offsets, d_n_hits, d_start=0, d_stop=0,
+                         d_n_kmers=0, d_hits=0, cap=0, stream=0):
+        """Asynchronous, everything resident in HBM (raw pointers): kid_db_read_hits_device."""
+        check(self._lib.kid_db_read_hits_device(self._h, C.c_void_p(d_bases), bases_nbytes, C.c_void_p(d_offsets),
+                                                C.c_void_p(d_start or None), C.c_void_p(d_stop or None), n_reads,
+                                                C.c_void_p(d_hit_offsets), C.c_void_p(d_n_kmers or None),
+                                                C.c_void_p(d_hits or None), cap, C.c_void_p(d_n_hits),
+                                                C.c_void_p(stream or None)))
+
+    def read_hits_time(self):
+        """-> (device ms, calls, reads) of the hits kernels since the last query (HIP events around every call)"""
+        ms, calls, reads = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        check(self._lib.kid_db_read_hits_time(self._h, C.byref(ms), C.byref(calls), C.byref(reads)))
+        return ms.value, calls.value, reads.value
 
     def gather_ceiling(self, n_loads=1 << 28, inflight=4, iters=3):
         """Random gather rate over this DB's table: (ms per launch, loads per launch).  inflight 101 / 108: random

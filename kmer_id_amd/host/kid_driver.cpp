@@ -280,8 +280,82 @@ static void collect_fastq_block(ReadBatch &b, const HostBuf &io, std::vector<uin
     b.stop.assign(stop, stop + nr);
 }
 
+bool hits_option(int argc, char **argv)
+{
+    for (int i = 1; i < argc; i++)
+        if (strcmp(argv[i], "--hits") == 0) return true;
+    return false;
+}
+
+std::string hits_path_for(const std::string &result_path)
+{
+    std::string p = result_path;
+    const size_t at = p.rfind("result");
+    if (at != std::string::npos) p.replace(at, 6, "hits");
+    return p;
+}
+
+HitsWriter::HitsWriter(const std::string &path) : path_(path)
+{
+    if (on()) remove(path_.c_str());
+}
+
+void HitsWriter::add(size_t file, const std::string &lines)
+{
+    if (parts_.size() <= file) parts_.resize(file + 1);
+    parts_[file] += lines;
+}
+
+void HitsWriter::close()
+{
+    if (!on()) return;
+    FILE *f = fopen(path_.c_str(), "w");
+    if (!f) throw Fatal{2, "cannot write " + path_};
+    for (const std::string &p : parts_) fwrite(p.data(), 1, p.size(), f);
+    fclose(f);
+    parts_.clear();
+}
+
+// The hit lines of one classified batch (its start / stop / final targets are known): kid_db_read_hits* on the batch's
+// device -- the sizing call, then the call that fills a buffer of that size.
+static void hit_lines_of(kid_db *db, const ReadBatch &b, const std::vector<uint32_t> &final_targ, int k, std::string &out)
+{
+    const size_t nr = b.size();
+    std::vector<uint64_t> off(nr + 1);
+    std::vector<uint32_t> nk(nr);
+    std::vector<kid_hit> hits;
+    uint64_t total = 0;
+    auto call = [&](kid_hit *h, uint64_t cap) {
+        int rc = b.fq ? kid_db_read_hits_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, off.data(),
+                                               nk.data(), h, cap, &total)
+                      : kid_db_read_hits(db, b.bases.data(), b.offsets.data(), b.start.data(), b.stop.data(), nr, off.data(), nk.data(),
+                                         h, cap, &total);
+        if (rc != KID_OK) die_kid(rc);
+    };
+    call(nullptr, 0);
+    if (total == 0) return;
+    hits.resize(total);
+    call(hits.data(), total);
+    char num[64];
+    for (size_t r = 0; r < nr; r++) {
+        if (off[r + 1] == off[r]) continue;
+        if (b.fq && !(b.stop[r] - b.start[r] >= k)) continue; // (dropped by process_qual: it has no hits anyway)
+        int n = snprintf(num, sizeof(num), "%u\t%d\t%u\t%llu\t", final_targ[r], b.stop[r] - b.start[r] + 1, nk[r],
+                         (unsigned long long)(off[r + 1] - off[r]));
+        out.append(num, (size_t)n);
+        for (uint64_t i = off[r]; i < off[r + 1]; i++) {
+            n = snprintf(num, sizeof(num), "%s%u:%u:%u", i > off[r] ? " " : "", hits[i].pos, hits[i].target, hits[i].entry);
+            out.append(num, (size_t)n);
+        }
+        out += '\t';
+        if (b.fq) out.append(b.fq->text.data() + b.fq->acc_off[r], b.fq->acc_len[r]);
+        else out += b.acc[r];
+        out += '\n';
+    }
+}
+
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file,
-                    const std::function<void(size_t, long long)> &done)
+                    const std::function<void(size_t, long long)> &done, HitsWriter *hits)
 {
     // Two batches in flight per device: while the GPU classifies batch b, batch b + 1 is uploaded and the results of
     // batch b - 1 go through the read saver -- in file order, which is what decides the "first 12 reads of a target"
@@ -293,8 +367,10 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         HostBuf io;
         uint64_t ticket = 0;
         kid_sample *sample = nullptr;
+        kid_db *db = nullptr;
         size_t file = 0;
     };
+    std::string lines;
     std::deque<InFlight> q;
     std::vector<long long> handed(count, 0);
     const size_t max_in_flight = 2 * e.samples.size();
@@ -306,6 +382,11 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         if (rc != KID_OK) die_kid(rc);
         if (f.batch->fq) collect_fastq_block(*f.batch, f.io, f.final_targ);
         handed[f.file] += saver.add_batch_of(saver_file + f.file, *f.batch, f.final_targ, e.k);
+        if (hits && hits->on()) {
+            lines.clear();
+            hit_lines_of(f.db, *f.batch, f.final_targ, e.k, lines);
+            hits->add(saver_file + f.file, lines);
+        }
         q.pop_front();
     };
     try {
@@ -319,6 +400,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             f.file = which - first;
             const size_t nr = f.batch->size();
             f.sample = e.samples[e.next_sample]; // batches are dealt round-robin over the devices
+            f.db = e.dbs[e.next_sample];
             e.next_sample = (e.next_sample + 1) % e.samples.size();
             int rc;
             const auto t_sub = std::chrono::steady_clock::now();
@@ -383,6 +465,7 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
         if (a == "--threads") o.threads = atoi(v);
         if (a == "--db-cache") o.db_cache = v;
     }
+    o.hits = hits_option(argc, argv);
     return o;
 }
 

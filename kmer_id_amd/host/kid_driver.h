@@ -78,13 +78,35 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
+// --hits (shared by the three front-ends): beside its result file a sample / job gets a hits file, named like it with
+// "result" replaced by "hits".  One line per read that was handed to process_read and has at least one k-mer hit, in
+// the reference's read order (all of file 0, then file 1, ...), tab-separated, the header line last:
+//   <final_targ> <trimmed length> <n_kmers> <n_hits> <pos>:<target>:<entry> ... <header line as in _reads.txt>
+// The batches of files read at the same time interleave: the lines are held in memory per file and written in file
+// order by close() -- what is held is the hits file itself (reads without a hit leave nothing), nothing else.  A
+// writer that is not closed (its sample failed) leaves no file; one made with an empty path does nothing.
+bool hits_option(int argc, char **argv);                 // is --hits among the arguments
+std::string hits_path_for(const std::string &result_path); // ".../x_result.txt" -> ".../x_hits.txt"
+class HitsWriter {
+public:
+    explicit HitsWriter(const std::string &path); // removes a file left there by an earlier run
+    bool on() const { return !path_.empty(); }
+    void add(size_t file, const std::string &lines);
+    void close();
+private:
+    std::string path_;
+    std::vector<std::string> parts_; // [file]
+};
+
 // Classify the files [first, first + count) of ONE sample, read at the same time (the two mates of nk10: two inflate
 // threads instead of one after the other); the counters do not care about the order, the read saver restores it.
 // `saver_file` is the saver's index of file `first` (a saver may span several calls: the files of a kmer_read_vf6 job,
 // -f1 and -f2 of kmer_read_m3).  done(f, handed), if given, is called for every file first + f in file order once all of
 // them are through, with the number of its reads handed to process_read.  Returns the reads handed of all the files.
+// `hits`, if given and on, receives the hit lines of every batch: the hit pass (kid_db_read_hits*) of a batch runs on the
+// device that classified it, once its final targets are back.
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file = 0,
-                    const std::function<void(size_t, long long)> &done = nullptr);
+                    const std::function<void(size_t, long long)> &done = nullptr, HitsWriter *hits = nullptr);
 
 // One opener per path, each by `open`, which sets its bool when the file is a plain FASTA that is not there (the
 // reference's "nark <name>"): missing[f] holds it for file f once that file is through.  `missing` must not move
@@ -100,6 +122,7 @@ struct ReaderOptions {
     size_t batch_reads = 1 << 18;
     std::string dry_run;     // --dry-run FILE: host stages only (no GPU), for the CPU test-suite
     std::string db_cache;    // --db-cache FILE: binary cache of the parsed database
+    bool hits = false;       // --hits: a hits file beside the result file (ignored with --dry-run)
 };
 ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 

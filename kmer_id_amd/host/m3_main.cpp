@@ -66,20 +66,22 @@ int main(int argc, char **argv)
         if (r1name.empty()) throw Fatal{134, "no -f1 given (std::out_of_range in the reference, :1080)"};
         std::cout << r1name.length() << " : " << r1name[r1name.length() - 1] << std::endl;
         Prefetcher pf(std::move(files), opt.threads, eng.batch_reads, eng.batch_bases);
+        HitsWriter hits(opt.hits ? hits_path_for(wdir + "result.txt") : "");
         ReadSaver saver("", num_targ); // the reads file is commented out in this program (:612-621)
         auto is_fagz = [](const std::string &n) { return ends_with(n, ".fasta.gz"); };
         if (is_fagz(r1name)) std::cout << "true" << std::endl; // process_fagz, :789
-        long long tct = run_files(eng, pf, 0, 1, saver, 0);
+        long long tct = run_files(eng, pf, 0, 1, saver, 0, nullptr, &hits);
         if (missing[0]) std::cout << "nark " << r1name << std::endl;
         std::cout << tct << " reads loaded" << std::endl;
         if (have2) {
             if (is_fagz(r2name)) std::cout << "true" << std::endl;
-            tct += run_files(eng, pf, 1, 1, saver, 1);
+            tct += run_files(eng, pf, 1, 1, saver, 1, nullptr, &hits);
             if (missing[1]) std::cout << "nark " << r2name << std::endl;
             if (ends_with(r2name, ".fastq.gz")) std::cout << tct << " reads loaded" << std::endl; // printed inside that branch too (:1107)
             std::cout << tct << " reads loaded" << std::endl;
         }
         finish_sample(eng, wdir + "result.txt");
+        hits.close();
         leave_now(0);
     } catch (const Fatal &f) {
         std::cerr << f.message << "\n";

@@ -15,6 +15,7 @@
 //                    <prefix><r1 suffix> per sample, read by process_fa (:877-913), no R2 file
 //   --db-cache FILE  binary cache of the parsed database: read if valid, (re)written otherwise
 //   --samples-in-flight N (threads / 2)  samples read and classified at the same time, each with its own counters on the GPU
+//   --hits               also write <prefix>_hits.txt: every read's k-mer hits (kid_driver.h)
 //   --timing         one JSON line on stderr when the run ends: seconds of the start-up phases (probes inflate / parse,
 //                    cache read / write, upload + table build on the GPU, first batch classified) and of the read files
 //   --dry-run FILE   host stages only (no GPU): parse the DB text files and the files a run would read (FASTQ, or
@@ -80,6 +81,7 @@ int main(int argc, char **argv)
         else if (a == "--fasta") fasta_mode = true;
         else if (a == "--timing") timing = true;
         else if (a == "--samples-in-flight") in_flight = atoi(val("--samples-in-flight"));
+        else if (a == "--hits") {} // (hits_option below: the one place that reads it, shared with the sibling programs)
         else if (dname.empty()) dname = a;
         else { std::cerr << "nk10: unexpected argument " << a << "\n"; return 2; }
     }
@@ -87,6 +89,7 @@ int main(int argc, char **argv)
         std::cerr << "usage: nk10 /path-to-fastq-files/ [--db-dir ./bact10/] [--ntar 5982] [--k 30] [--log2-slots 30] [--device 0]\n";
         return 2;
     }
+    const bool want_hits = hits_option(argc, argv); // <prefix>_hits.txt beside <prefix>_result.txt (ignored with --dry-run)
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
     if (batch_reads < 1) batch_reads = 1;
     if (threads < 1) threads = 1;
@@ -239,10 +242,12 @@ int main(int argc, char **argv)
             engine_reset(e);
             out += prefix + "\n";
             long long tct = 0;
+            const std::string result_path = dname + prefix + "_result.txt";
+            HitsWriter hits(want_hits ? hits_path_for(result_path) : "");
             {
                 ReadSaver saver(dname + prefix + "_reads.txt", ntar);
                 if (fasta_mode) {
-                    tct += run_files(e, pf, fi0, 1, saver);
+                    tct += run_files(e, pf, fi0, 1, saver, 0, nullptr, &hits);
                     if (missing[fi0]) out += "nark " + paths[fi0] + "\n";
                     out += std::to_string(tct) + " reads loaded\n";
                 } else {
@@ -254,11 +259,12 @@ int main(int argc, char **argv)
                         if (t_first_file < 0) t_first_file = since_start();
                         t_file_done[mate] = since_start();
                         out += std::to_string(tct) + " reads loaded\n";
-                    });
+                    }, &hits);
                 }
             }
             const double t_reads_written = since_start();
-            finish_sample(e, dname + prefix + "_result.txt");
+            finish_sample(e, result_path);
+            hits.close();
             if (timing) {
                 char buf[256];
                 snprintf(buf, sizeof(buf), "{\"sample\": %zu, \"begin_s\": %.3f, \"r1_through_s\": %.3f, \"r2_through_s\": %.3f, \"reads_txt_written_s\": %.3f, "
@@ -316,6 +322,7 @@ int main(int argc, char **argv)
                 if (behind && outs[f].done) {
                     remove((dname + fnames[f] + "_result.txt").c_str());
                     remove((dname + fnames[f] + "_reads.txt").c_str());
+                    remove((dname + fnames[f] + "_hits.txt").c_str());
                 }
                 if (outs[f].failed) behind = true;
             }

@@ -74,17 +74,19 @@ int main(int argc, char **argv)
             engine_reset(eng);
             const std::string base = "./" + jname + "/" + jstr;
             long long tct = 0;
+            HitsWriter hits(opt.hits ? hits_path_for(base + "_result.txt") : "");
             {
                 ReadSaver saver(base + "_reads.txt", num_targ, save_target > 0 ? base + "_target_reads.txt" : "",
                                 (uint32_t)(save_target > 0 ? save_target : 0), save_target == 0);
                 for (int i = 0; i < jobs.n_inputs(j); i++, fi++) {
                     std::cout << names[fi] << std::endl;
-                    tct += run_files(eng, pf, fi, 1, saver, (size_t)i);
+                    tct += run_files(eng, pf, fi, 1, saver, (size_t)i, nullptr, &hits);
                     if (missing[fi]) std::cout << "nark " << names[fi] << std::endl;
                 }
             }
             std::cout << tct << " reads loaded" << std::endl;
             finish_sample(eng, base + "_result.txt");
+            hits.close();
         }
         leave_now(0);
     } catch (const Fatal &f) {
