@@ -36,7 +36,9 @@ def _newer(target, sources):
 
 
 def lib_sources():
-    return [os.path.join(CSRC, f) for f in ("kid_api.hip", "kid_kernels.hip.h", "kid_build.hip.h", "kid_hits.hip.h", "kid_common.h")] + [
+    """every file the library is built from: all of csrc/ (one translation unit, kid_api.hip, includes the rest) and the
+    two public headers"""
+    return sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h"))) + [
         os.path.join(ROOT, "include", "kmer_id_amd.h"), os.path.join(ROOT, "include", "kmer_id_amd_bench.h")]
 
 

@@ -1,0 +1,313 @@
+// kid_api_hits.h -- every read's k-mer hits: the scratch of a database's hit passes and kid_db_read_hits*.
+#pragma once
+#include "kid_api_db.h"
+#include "kid_hits.hip.h"
+
+// ---------------------------------------------------------------- every read's k-mer hits (kid_hits.hip.h)
+// Scratch of the hit pass: grow-only device buffers sized by the largest batch seen, one set per database (calls on
+// one kid_db run one after the other: a call first waits for the kernels of the call before).  Per batch: 16 B per
+// read (descriptors) + 8 B per read (first tile) + 16 B per tile of 64 windows (mask, first hit) + 8 B per 1024 of
+// either (scan totals); the host-buffer forms add a device copy of their inputs and outputs.
+struct KidHitsState {
+    KidDevBuf desc, tile_off, rsum, tile_mask, tile_hit_off, tsum, trim_start, trim_stop;          // every form
+    KidDevBuf in_bases, in_offsets, in_start, in_stop, in_recs, out_offsets, out_nk, out_hits;      // host-buffer forms
+    // unsigned long long [0..31] the `stats` block the prepare kernels write ([4] ranges outside the read, [8] short
+    // quality lines), [32] tiles of the batch, [33] hits of the batch, [34] sink for the prepare kernel's gcount
+    // correction, [35] batches with more tiles than the scratch was sized for,
+    // then a KidRareArgs (the prepare kernels announce the batch's longest read there; nobody reads it)
+    KidDevBuf ctl_buf;
+    KidEvent ev0, ev1;
+    bool pending = false;
+    double ms = 0;
+    uint64_t calls = 0, reads = 0;
+    uint32_t seq = 0;
+    unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
+};
+#define KID_HITS_CTL_WORDS 36u
+
+kid_db::~kid_db() {}
+
+// a little slack: batches of a file differ slightly in size
+static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensure(nbytes, ((nbytes + nbytes / 8) + 255u) & ~255ull); }
+
+// the elapsed time of the call before (and with it: its kernels are through, the scratch is free)
+static int kid_hits_settle(KidHitsState *h)
+{
+    if (!h->pending) return KID_OK;
+    KID_HIP(hipEventSynchronize(h->ev1.e));
+    float ms = 0;
+    KID_HIP(hipEventElapsedTime(&ms, h->ev0.e, h->ev1.e));
+    h->ms += ms;
+    h->pending = false;
+    return KID_OK;
+}
+
+static int kid_hits_state(kid_db *db, KidHitsState **out)
+{
+    if (!db->hits) {
+        std::unique_ptr<KidHitsState> h(new KidHitsState());
+        const size_t nb = KID_HITS_CTL_WORDS * 8 + sizeof(KidRareArgs);
+        KID_HIP(h->ctl_buf.alloc(nb));
+        KID_HIP(hipMemset(h->ctl(), 0, nb));
+        KID_HIP(h->ev0.create());
+        KID_HIP(h->ev1.create());
+        db->hits = std::move(h);
+    }
+    *out = db->hits.get();
+    return kid_hits_settle(*out);
+}
+
+// The kernels of one batch on `stream`, everything on the device.  b: bases / offsets / start / stop (recs: a FASTQ
+// block instead, start and stop are then outputs of the prepare kernel).  max_tiles: see below.
+static int kid_hits_launch(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles,
+                           uint64_t *d_hit_offsets, uint32_t *d_n_kmers, KidHit *d_hits, uint64_t cap, uint64_t *d_n_hits,
+                           hipStream_t stream, bool fill)
+{
+    const uint64_t n = b.n;
+    // max_tiles: what the tile arrays are sized for.  A read of L bytes has at most L / 64 + 1 tiles: the host-buffer
+    // forms add that up over their reads; the device form knows the text's size alone and takes bytes / 64 + reads, which
+    // holds unless reads overlap.  A batch with more tiles is refused on the device (kid_hits_scan_top_kernel).
+    KID_HIP(kid_hits_ensure(h->desc, n * sizeof(KidReadDesc)));
+    KID_HIP(kid_hits_ensure(h->tile_off, (n + 1) * 8));
+    KID_HIP(kid_hits_ensure(h->rsum, (n / KID_HITS_SCAN_BLOCK + 2) * 8));
+    KID_HIP(kid_hits_ensure(h->tile_mask, (max_tiles + 1) * 8));
+    KID_HIP(kid_hits_ensure(h->tile_hit_off, (max_tiles + 1) * 8));
+    KID_HIP(kid_hits_ensure(h->tsum, (max_tiles / KID_HITS_SCAN_BLOCK + 2) * 8));
+    unsigned long long *stats = h->ctl();
+    uint64_t *n_tiles = reinterpret_cast<uint64_t *>(h->ctl() + 32), *n_hits = reinterpret_cast<uint64_t *>(h->ctl() + 33);
+    KidRareArgs *rare = reinterpret_cast<KidRareArgs *>(h->ctl() + KID_HITS_CTL_WORDS);
+    KidReadDesc *desc = h->desc.as<KidReadDesc>();
+    uint64_t *tile_off = h->tile_off.as<uint64_t>(), *tile_hit_off = h->tile_hit_off.as<uint64_t>();
+    const int cu = db->num_cu;
+    KID_HIP(hipEventRecord(h->ev0.e, stream));
+    if (recs)
+        hipLaunchKernelGGL(kid_prepare_fastq_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, b.bases, recs, n, db->info.k,
+                           desc, const_cast<int32_t *>(b.start), const_cast<int32_t *>(b.stop), (uint32_t *)nullptr, stats, h->ctl() + 34, rare,
+                           ++h->seq, 0);
+    else
+        hipLaunchKernelGGL(kid_prepare_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, b, db->info.k, desc, stats, rare,
+                           ++h->seq, 0u, (KidLongList *)nullptr, 0);
+    // tiles per read -> first tile of every read (n_kmers is cleared on the way)
+    hipLaunchKernelGGL(kid_hits_scan_local_kernel<0>, dim3(kid_grid_for(n, KID_HITS_SCAN_BLOCK, cu * 8)), dim3(256), 0, stream,
+                       (const void *)desc, (const uint64_t *)nullptr, n, tile_off, h->rsum.as<uint64_t>(), d_n_kmers);
+    hipLaunchKernelGGL(kid_hits_scan_top_kernel, dim3(1), dim3(1024), 0, stream, h->rsum.as<uint64_t>(), (const uint64_t *)nullptr, n, n_tiles,
+                       max_tiles, h->ctl() + 35);
+    hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, tile_off,
+                       (const uint64_t *)h->rsum.as<uint64_t>(), (const uint64_t *)nullptr, n, (const uint64_t *)n_tiles);
+    KidHitsTiles a{};
+    a.bases = b.bases;
+    a.desc = desc;
+    a.tile_off = tile_off;
+    a.n_reads = n;
+    a.tile_mask = h->tile_mask.as<unsigned long long>();
+    const int tile_grid = kid_grid_for(max_tiles, KID_HITS_WG_TILES, cu * 32);
+    hipLaunchKernelGGL(kid_hits_count_kernel, dim3(tile_grid), dim3(256), 0, stream, db->d, a, d_n_kmers);
+    // hits per tile -> first hit of every tile
+    hipLaunchKernelGGL(kid_hits_scan_local_kernel<1>, dim3(kid_grid_for(max_tiles, KID_HITS_SCAN_BLOCK, cu * 8)), dim3(256), 0, stream,
+                       (const void *)a.tile_mask, (const uint64_t *)n_tiles, 0ull, tile_hit_off, h->tsum.as<uint64_t>(), (uint32_t *)nullptr);
+    hipLaunchKernelGGL(kid_hits_scan_top_kernel, dim3(1), dim3(1024), 0, stream, h->tsum.as<uint64_t>(), (const uint64_t *)n_tiles, 0ull, n_hits,
+                       ~0ull, (unsigned long long *)nullptr);
+    hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(max_tiles, 256, cu * 8)), dim3(256), 0, stream, tile_hit_off,
+                       (const uint64_t *)h->tsum.as<uint64_t>(), (const uint64_t *)n_tiles, 0ull, (const uint64_t *)n_hits);
+    hipLaunchKernelGGL(kid_hits_offsets_kernel, dim3(kid_grid_for(n + 1, 256, cu * 8)), dim3(256), 0, stream, (const uint64_t *)tile_off,
+                       (const uint64_t *)tile_hit_off, n, d_hit_offsets, d_n_hits);
+    if (fill && d_hits && cap)
+        hipLaunchKernelGGL(kid_hits_fill_kernel, dim3(tile_grid), dim3(256), 0, stream, db->d, a, (const uint64_t *)tile_hit_off, b.offsets, recs,
+                           d_hits, cap);
+    KID_HIP(hipGetLastError());
+    return KID_OK;
+}
+
+// the fill pass on its own: the host-buffer forms learn the number of hits first and then size their device buffer
+static int kid_hits_launch_fill(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, KidHit *d_hits,
+                                uint64_t cap, hipStream_t stream)
+{
+    KidHitsTiles a{};
+    a.bases = b.bases;
+    a.desc = h->desc.as<KidReadDesc>();
+    a.tile_off = h->tile_off.as<uint64_t>();
+    a.n_reads = b.n;
+    a.tile_mask = h->tile_mask.as<unsigned long long>();
+    hipLaunchKernelGGL(kid_hits_fill_kernel, dim3(kid_grid_for(max_tiles, KID_HITS_WG_TILES, db->num_cu * 32)), dim3(256), 0, stream, db->d, a,
+                       (const uint64_t *)h->tile_hit_off.as<uint64_t>(), b.offsets, recs, d_hits, cap);
+    KID_HIP(hipGetLastError());
+    return KID_OK;
+}
+
+static int kid_hits_close(KidHitsState *h, uint64_t n_reads, hipStream_t stream)
+{
+    KID_HIP(hipEventRecord(h->ev1.e, stream));
+    h->pending = true;
+    h->calls++;
+    h->reads += n_reads;
+    return KID_OK;
+}
+
+// what the prepare kernels found wrong with the batch just run (host-buffer forms: after the kernels)
+static int kid_hits_check(KidHitsState *h)
+{
+    unsigned long long st[KID_HITS_CTL_WORDS];
+    KID_HIP(hipMemcpy(st, h->ctl(), sizeof(st), hipMemcpyDeviceToHost));
+    if (st[4] == 0 && st[8] == 0 && st[35] == 0) return KID_OK;
+    KID_HIP(hipMemset(h->ctl(), 0, KID_HITS_CTL_WORDS * 8));
+    if (st[35] != 0)
+        return kid_fail(KID_ERR_ARG, "%llu batches held more windows than their text has bytes (reads that overlap, or a text longer than "
+                                     "bases_nbytes): they were given no hits", st[35]);
+    if (st[4] != 0)
+        return kid_fail(KID_ERR_ARG, "%llu reads had [start,stop] outside the read (string::at would throw)", st[4]);
+    return kid_fail(KID_ERR_FORMAT, "%llu FASTQ records have a quality line shorter than the sequence (qual.at() throws in the reference)", st[8]);
+}
+
+// the host-buffer forms behind their uploads: kernels, the count, the fill if the caller's buffer holds it, downloads
+static int kid_hits_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, uint64_t *hit_offsets,
+                             uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
+{
+    static_assert(sizeof(kid_hit) == sizeof(KidHit), "kid_hit is the device record");
+    const uint64_t n = b.n;
+    int rc;
+    KID_HIP(kid_hits_ensure(h->out_offsets, (n + 1) * 8));
+    KID_HIP(kid_hits_ensure(h->out_nk, n * 4));
+    uint64_t *d_total = reinterpret_cast<uint64_t *>(h->ctl() + 33);
+    rc = kid_hits_launch(db, h, b, recs, max_tiles, h->out_offsets.as<uint64_t>(), h->out_nk.as<uint32_t>(), nullptr, 0, nullptr, 0, false);
+    if (rc != KID_OK) return rc;
+    uint64_t total = 0;
+    KID_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, 0));
+    KID_HIP(hipStreamSynchronize(0));
+    const bool fill = hits && total > 0 && total <= cap;
+    if (fill) {
+        KID_HIP(kid_hits_ensure(h->out_hits, total * sizeof(KidHit)));
+        if ((rc = kid_hits_launch_fill(db, h, b, recs, max_tiles, h->out_hits.as<KidHit>(), total, 0)) != KID_OK) return rc;
+    }
+    if ((rc = kid_hits_close(h, n, 0)) != KID_OK) return rc;
+    KID_HIP(hipMemcpy(hit_offsets, h->out_offsets.p, (n + 1) * 8, hipMemcpyDeviceToHost));
+    if (n_kmers) KID_HIP(hipMemcpy(n_kmers, h->out_nk.p, n * 4, hipMemcpyDeviceToHost));
+    if (fill) KID_HIP(hipMemcpy(hits, h->out_hits.p, total * sizeof(KidHit), hipMemcpyDeviceToHost));
+    if ((rc = kid_hits_check(h)) != KID_OK) return rc;
+    *n_hits = total;
+    return KID_OK;
+}
+
+static int kid_hits_upload_text(KidHitsState *h, const uint8_t *src, uint64_t nbytes)
+{
+    KID_HIP(kid_hits_ensure(h->in_bases, kid_text_bytes(nbytes)));
+    return kid_upload_text(h->in_bases, src, nbytes, 0);
+}
+
+extern "C" int kid_db_read_hits(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                                uint64_t n_reads, uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
+{
+    if (!db || !hit_offsets || !n_hits) return kid_fail(KID_ERR_ARG, "null argument");
+    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
+    if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
+    if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
+    if (!bases || !offsets) return kid_fail(KID_ERR_ARG, "null argument");
+    if ((start == nullptr) != (stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
+    int64_t max_kmers = 0;
+    uint64_t max_tiles = 0;
+    int rc = kid_check_offsets_batch(offsets, start, stop, n_reads, db->info.k, &max_kmers, KID_HITS_TILE, &max_tiles);
+    if (rc != KID_OK) return rc;
+    rc = kid_use_device(db->device);
+    if (rc != KID_OK) return rc;
+    std::lock_guard<std::mutex> lock(db->hits_mu);
+    KidHitsState *h = nullptr;
+    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
+    const uint64_t base0 = offsets[0], nbytes = offsets[n_reads] - base0;
+    if ((rc = kid_hits_upload_text(h, bases + base0, nbytes)) != KID_OK) return rc;
+    KID_HIP(kid_hits_ensure(h->in_offsets, (n_reads + 1) * 8));
+    std::vector<uint64_t> rel; // (a synchronous copy reads it)
+    const uint64_t *off_src = kid_rebased_offsets(offsets, n_reads, rel);
+    KID_HIP(hipMemcpy(h->in_offsets.p, off_src, (n_reads + 1) * 8, hipMemcpyHostToDevice));
+    if (start) {
+        KID_HIP(kid_hits_ensure(h->in_start, n_reads * 4));
+        KID_HIP(kid_hits_ensure(h->in_stop, n_reads * 4));
+        KID_HIP(hipMemcpy(h->in_start.p, start, n_reads * 4, hipMemcpyHostToDevice));
+        KID_HIP(hipMemcpy(h->in_stop.p, stop, n_reads * 4, hipMemcpyHostToDevice));
+    }
+    KidBatch b{};
+    b.bases = h->in_bases.as<uint8_t>();
+    b.offsets = h->in_offsets.as<uint64_t>();
+    b.start = start ? h->in_start.as<int32_t>() : nullptr;
+    b.stop = start ? h->in_stop.as<int32_t>() : nullptr;
+    b.n = n_reads;
+    return kid_hits_host_run(db, h, b, nullptr, max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
+}
+
+extern "C" int kid_db_read_hits_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                                      uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
+{
+    if (!db || !hit_offsets || !n_hits) return kid_fail(KID_ERR_ARG, "null argument");
+    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
+    if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
+    if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
+    if (!text || !recs) return kid_fail(KID_ERR_ARG, "null argument");
+    uint64_t max_tiles = 0;
+    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, KID_HITS_TILE, &max_tiles);
+    if (rc != KID_OK) return rc;
+    rc = kid_use_device(db->device);
+    if (rc != KID_OK) return rc;
+    std::lock_guard<std::mutex> lock(db->hits_mu);
+    KidHitsState *h = nullptr;
+    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
+    if ((rc = kid_hits_upload_text(h, text, text_nbytes)) != KID_OK) return rc;
+    KID_HIP(kid_hits_ensure(h->in_recs, n_reads * sizeof(KidFastqRec)));
+    KID_HIP(kid_hits_ensure(h->trim_start, n_reads * 4));
+    KID_HIP(kid_hits_ensure(h->trim_stop, n_reads * 4));
+    KID_HIP(hipMemcpy(h->in_recs.p, recs, n_reads * sizeof(KidFastqRec), hipMemcpyHostToDevice));
+    KidBatch b{};
+    b.bases = h->in_bases.as<uint8_t>();
+    b.start = h->trim_start.as<int32_t>(); // (outputs of the prepare kernel here)
+    b.stop = h->trim_stop.as<int32_t>();
+    b.n = n_reads;
+    return kid_hits_host_run(db, h, b, h->in_recs.as<KidFastqRec>(), max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
+}
+
+extern "C" int kid_db_read_hits_device(kid_db *db, const void *d_bases, uint64_t bases_nbytes, const void *d_offsets, const void *d_start,
+                                       const void *d_stop, uint64_t n_reads, void *d_hit_offsets, void *d_n_kmers, void *d_hits,
+                                       uint64_t cap, void *d_n_hits, void *stream)
+{
+    if (!db || !d_hit_offsets || !d_n_hits || (n_reads && (!d_bases || !d_offsets))) return kid_fail(KID_ERR_ARG, "null argument");
+    if (((uintptr_t)d_bases & 15u) != 0) return kid_fail(KID_ERR_ARG, "d_bases must be 16-byte aligned");
+    if ((d_start == nullptr) != (d_stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
+    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
+    if (cap && !d_hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
+    int rc = kid_use_device(db->device);
+    if (rc != KID_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_reads == 0) {
+        KID_HIP(hipMemsetAsync(d_hit_offsets, 0, 8, st));
+        KID_HIP(hipMemsetAsync(d_n_hits, 0, 8, st));
+        return KID_OK;
+    }
+    std::lock_guard<std::mutex> lock(db->hits_mu);
+    KidHitsState *h = nullptr;
+    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
+    KidBatch b{};
+    b.bases = (const uint8_t *)d_bases;
+    b.offsets = (const uint64_t *)d_offsets;
+    b.start = (const int32_t *)d_start;
+    b.stop = (const int32_t *)d_stop;
+    b.n = n_reads;
+    rc = kid_hits_launch(db, h, b, nullptr, bases_nbytes / KID_HITS_TILE + n_reads, (uint64_t *)d_hit_offsets, (uint32_t *)d_n_kmers, (KidHit *)d_hits, cap,
+                         (uint64_t *)d_n_hits, st, true);
+    if (rc != KID_OK) return rc;
+    return kid_hits_close(h, n_reads, st);
+}
+
+extern "C" int kid_db_read_hits_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads)
+{
+    if (!db) return kid_fail(KID_ERR_ARG, "null argument");
+    if (device_ms) *device_ms = 0;
+    if (calls) *calls = 0;
+    if (reads) *reads = 0;
+    std::lock_guard<std::mutex> lock(db->hits_mu);
+    KidHitsState *h = db->hits.get();
+    if (!h) return KID_OK;
+    int rc = kid_use_device(db->device);
+    if (rc != KID_OK) return rc;
+    if ((rc = kid_hits_settle(h)) != KID_OK) return rc;
+    if (device_ms) *device_ms = h->ms;
+    if (calls) *calls = h->calls;
+    if (reads) *reads = h->reads;
+    h->ms = 0; h->calls = 0; h->reads = 0;
+    return kid_hits_check(h);
+}

@@ -323,6 +323,9 @@ int main(int argc, char **argv)
                     remove((dname + fnames[f] + "_result.txt").c_str());
                     remove((dname + fnames[f] + "_reads.txt").c_str());
                     remove((dname + fnames[f] + "_hits.txt").c_str());
+                } else if (behind && want_hits) {
+                    // never started: a hits file an earlier run left would stand beside no result of this one
+                    remove((dname + fnames[f] + "_hits.txt").c_str());
                 }
                 if (outs[f].failed) behind = true;
             }
