@@ -243,6 +243,52 @@ int kid_db_read_hits_device(kid_db *db, const void *d_bases, uint64_t bases_nbyt
  * round trip lies inside the interval.  Synchronises with the last call.                                           */
 int kid_db_read_hits_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
 
+/* ---- calling reads by k-mer support -------------------------------------------------
+ * kid_classify_* gives a read the target its hits fold to: one database k-mer among 121 windows calls a read.  These
+ * calls ask for more evidence.  For one read let t_1 .. t_m be the targets of its hits in read-position order (exactly
+ * the hits kid_db_read_hits reports, targets equal to 1 included) and n its n_kmers, the windows looked up.
+ *   final      process_read's left fold of t_1 .. t_m with msca, 0 when m = 0: what kid_classify_* returns for the read
+ *   S(c)       the number of hits whose target is c or a descendant of c; S(1) = m
+ *   the rule   two integers, min_hits >= 0 and min_permille in 0..1000 (KID_ERR_ARG beyond)
+ *   c passes   when S(c) >= min_hits and 1000 * S(c) >= min_permille * n   (64-bit integers; no floating point anywhere)
+ *   confident  0 if final = 0; else the first node on the path final, parent(final), .., 1 that passes, 0 if none does.
+ *              Under the rule (0, 0) confident = final for every read.
+ * msca returns the deeper node of a lineage, so final need not be an ancestor of every hit: hits at targets [6, 8] with
+ * 6 -> 8 fold to 8, with S(8) = 1 and S(6) = 2 -- which is what makes the climb meaningful.
+ * One kernel turns the hits of a batch into one record per read; it is a pure function of the hits (no atomics): the
+ * records are byte-identical across runs, splits of the batch into calls and table kinds.                            */
+typedef struct kid_support {
+    uint32_t final, confident, n_kmers, n_hits /* m */, s_final /* S(final), 0 if final = 0 */,
+        s_confident /* S(confident), 0 if confident = 0 */;
+} kid_support;
+/* Host buffers, as kid_db_read_hits / kid_db_read_hits_fastq: the hit pass runs into scratch the kid_db owns (it grows
+ * with the largest batch and its number of hits), then the support kernel; 24 bytes per read come back.  Errors as for
+ * kid_db_read_hits*; the calls obey its one-call-at-a-time rule (one set of scratch per kid_db).
+ *   out[n_reads]  nullable
+ *   tally         nullable: a sample OF THIS kid_db (another's: KID_ERR_ARG) that is counted as if the batch had been
+ *                 classified under the rule: gcount[confident]++ for exactly the reads kid_classify_batch /
+ *                 kid_classify_fastq_async would count (a read shorter than k handed in with whole-read ranges under
+ *                 target 0; a FASTQ record that fails stop - start >= k nowhere), and, for reads with confident > 0, the
+ *                 seen bit of every hit with target > 1.  The tally kernel runs in the sample's stream, behind whatever
+ *                 the sample has queued.  Classifying and tallying into one sample may be mixed; kid_sample_end,
+ *                 kid_sample_end_merged, kid_sample_reset and the seen-bitmap helpers work on a tallied sample as on any
+ *                 other.  kid_sample_stats is NOT updated by a tally.  A tally after kid_sample_end / _end_merged
+ *                 without kid_sample_reset is KID_ERR_STATE.  A batch the hit pass refuses is not counted at all.     */
+int kid_db_read_support(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                        uint64_t n_reads, uint32_t min_hits, uint32_t min_permille, kid_support *out, kid_sample *tally);
+int kid_db_read_support_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                              uint32_t min_hits, uint32_t min_permille, kid_support *out, kid_sample *tally);
+/* The kernel alone, for a CSR that is in HBM already (kid_db_read_hits_device with a d_hits that held all the hits):
+ * d_hit_offsets uint64[n_reads + 1], d_hits kid_hit[] (may be NULL when there is no hit), d_n_kmers uint32[n_reads],
+ * d_out kid_support[n_reads].  Asynchronous on `stream`; the host need not know the number of hits; no tally.  Like
+ * every call on a kid_db it first waits on the host for the kernels of the call before it.  A target outside
+ * (0, ntar) in d_hits is read as the root.                                                                          */
+int kid_db_support_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
+                                    uint32_t min_hits, uint32_t min_permille, void *d_out, void *stream);
+/* Device time of the support kernel ALONE since the last query (HIP events around it), its calls and reads; the hit pass
+ * of the host forms is in kid_db_read_hits_time.  Synchronises with the last call.                                  */
+int kid_db_read_support_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
+
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).
  * Synchronises the sample's outstanding work first.                             */

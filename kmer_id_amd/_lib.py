@@ -65,6 +65,13 @@ PROTOTYPES = {
     "kid_db_read_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "kid_db_read_hits_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
+    "kid_db_read_support": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                      C.c_void_p, C.c_void_p]),
+    "kid_db_read_support_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                            C.c_void_p, C.c_void_p]),
+    "kid_db_support_from_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                  C.c_void_p, C.c_void_p]),
+    "kid_db_read_support_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
     "kid_sample_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kid_sample_end_merged": (C.c_int, [c_void_pp, C.c_int, C.c_void_p, C.c_void_p]),
     "kid_sample_stats": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -76,6 +76,11 @@ class ReadHits:
         return self.pos[a:b], self.target[a:b], self.entry[a:b]
 
 
+# kid_support: one record per read (kid_db_read_support*)
+SUPPORT_DTYPE = np.dtype([("final", np.uint32), ("confident", np.uint32), ("n_kmers", np.uint32), ("n_hits", np.uint32),
+                          ("s_final", np.uint32), ("s_confident", np.uint32)])
+
+
 class KmerDB:
     """Replaces `new Hashtable()` + `new Tree1()` + the add_kmer/add_edge load loops."""
 
@@ -191,6 +196,46 @@ class KmerDB:
         """-> (device ms, calls, reads) of the hits kernels since the last query (HIP events around every call)"""
         ms, calls, reads = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
         check(self._lib.kid_db_read_hits_time(self._h, C.byref(ms), C.byref(calls), C.byref(reads)))
+        return ms.value, calls.value, reads.value
+
+    def read_support(self, bases, offsets, start=None, stop=None, min_hits=0, min_permille=0, tally=None):
+        """Call the reads of a batch held in host memory by k-mer support (kid_db_read_support): -> a structured array
+        (SUPPORT_DTYPE: final, confident, n_kmers, n_hits, s_final, s_confident), one record per read.  `confident` is
+        the first node on final's root path whose clade holds at least min_hits hits and min_permille / 1000 of the
+        read's k-mers, 0 if none does.  tally: a Sample of this database that is counted as if the batch had been
+        classified under the rule (gcount[confident]++, seen bits of the hits of reads with confident > 0)."""
+        bases = _as(bases, np.uint8)
+        offsets = _as(offsets, np.uint64)
+        start = _as(start, np.int32)
+        stop = _as(stop, np.int32)
+        n = offsets.size - 1
+        out = np.zeros(n, SUPPORT_DTYPE)
+        check(self._lib.kid_db_read_support(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
+                                            _ptr(out), tally._h if tally is not None else None))
+        return out
+
+    def read_support_fastq(self, text, recs, min_hits=0, min_permille=0, tally=None):
+        """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
+        fails stop - start >= k has no window and no hit, and a tally counts it nowhere."""
+        text = _as(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8)
+        recs = _as(recs, np.uint32).reshape(-1, 4)
+        n = recs.shape[0]
+        out = np.zeros(n, SUPPORT_DTYPE)
+        check(self._lib.kid_db_read_support_fastq(self._h, _ptr(text), text.size, _ptr(recs), n, min_hits, min_permille, _ptr(out),
+                                                  tally._h if tally is not None else None))
+        return out
+
+    def support_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
+        """The support kernel alone on a CSR resident in HBM (raw pointers, as kid_db_read_hits_device left it);
+        asynchronous on `stream`: kid_db_support_from_hits_device.  d_out: kid_support[n_reads] (SUPPORT_DTYPE)."""
+        check(self._lib.kid_db_support_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
+                                                        C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
+                                                        C.c_void_p(stream or None)))
+
+    def read_support_time(self):
+        """-> (device ms, calls, reads) of the support kernel alone since the last query"""
+        ms, calls, reads = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        check(self._lib.kid_db_read_support_time(self._h, C.byref(ms), C.byref(calls), C.byref(reads)))
         return ms.value, calls.value, reads.value
 
     def gather_ceiling(self, n_loads=1 << 28, inflight=4, iters=3):

@@ -1,6 +1,7 @@
 // kid_api.hip -- C ABI (include/kmer_id_amd.h) over the gfx950 kernels: the one translation unit of the library.
 // Here: the sample handle, the pacing of the hit log, kid_launch_classify and the classify entry points -- the launch
-// path a counter profile depends on.  The other areas are the kid_api_*.h files included below.  Host side only:
+// path a counter profile depends on.  The other areas are the kid_api_*.h files included below (kid_api_support.h
+// at the end: it counts into a sample).  Host side only:
 // handle bookkeeping and launches; no classification work is done on the CPU.
 #include <hip/hip_runtime.h>
 #include <memory>
@@ -14,6 +15,7 @@
 #include "kid_kernels.hip.h"
 #include "kid_build.hip.h"
 #include "kid_hits.hip.h"
+#include "kid_support.hip.h"
 #include "kid_api_core.h"
 #include "kid_api_db.h"
 #include "kid_api_hits.h"
@@ -75,6 +77,7 @@ struct kid_sample {
     // very long records: one word per k-mer position for the hits, one byte per tile of 256 positions ("holds a hit").
     // They grow together: long_tiles holds 16 bytes more than the tiles it is said to have.
     KidDevBuf long_hits, long_tiles;
+    bool ended = false; // kid_sample_end* has read the counters and no reset has followed: a tally is refused (kid_api_support.h)
     uint64_t reads_submitted = 0; // since the last reset: checked against the device's count when results are read
     uint64_t kernel_variants = 0; // since the last reset: one bit per kid_classify_kernel instantiation launched (kid_sample_kernel_variants)
     // the scratch below is one set per sample: batches on different streams are ordered behind each other
@@ -127,6 +130,7 @@ extern "C" int kid_sample_reset(kid_sample *s)
     }
     s->dev_clock_batches = 0;
     s->reads_submitted = 0;
+    s->ended = false;
     s->kernel_variants = 0;
     if (s->seen_log_tail.p) KID_HIP(hipMemset(s->seen_log_tail.p, 0, KID_LOG_SHARDS * 64));
     if (s->seen_log.p) { // (a pass may have taken the log out of the argument blocks: KidLogArgs)
@@ -833,7 +837,9 @@ extern "C" int kid_sample_end(kid_sample *s, int64_t *gcount, int64_t *ucount)
     if (!s || !gcount || !ucount) return kid_fail(KID_ERR_ARG, "null argument");
     int rc = kid_sample_gcount(s, gcount);
     if (rc != KID_OK) return rc;
-    return kid_sample_ucount_range(s, 0, s->seen_words * 32, ucount);
+    rc = kid_sample_ucount_range(s, 0, s->seen_words * 32, ucount);
+    if (rc == KID_OK) s->ended = true;
+    return rc;
 }
 
 // The counters of ONE sample of the input whose batches were dealt out over n kid_sample objects -- one per GPU, each
@@ -881,7 +887,10 @@ extern "C" int kid_sample_end_merged(kid_sample **samples, int n, int64_t *gcoun
             if (rc != KID_OK) return rc;
         }
     }
-    return kid_sample_ucount_range(s0, 0, s0->seen_words * 32, ucount);
+    rc = kid_sample_ucount_range(s0, 0, s0->seen_words * 32, ucount);
+    if (rc == KID_OK)
+        for (int i = 0; i < n; i++) samples[i]->ended = true;
+    return rc;
 }
 
 extern "C" int kid_sample_stats(kid_sample *s, uint64_t out[4])
@@ -937,3 +946,5 @@ extern "C" int kid_sample_seen_or(kid_sample *s, uint64_t byte_off, uint64_t nby
     KID_HIP(hipDeviceSynchronize());
     return KID_OK;
 }
+
+#include "kid_api_support.h"

@@ -21,6 +21,12 @@ struct KidHitsState {
     double ms = 0;
     uint64_t calls = 0, reads = 0;
     uint32_t seq = 0;
+    // kid_db_read_support* (kid_api_support.h): the host forms' records, and the events around the support kernel alone
+    KidDevBuf out_support;
+    KidEvent sup_ev0, sup_ev1;
+    bool sup_pending = false;
+    double sup_ms = 0;
+    uint64_t sup_calls = 0, sup_reads = 0;
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
 #define KID_HITS_CTL_WORDS 36u

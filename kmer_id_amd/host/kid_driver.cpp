@@ -65,6 +65,7 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 Engine::~Engine()
 {
     for (kid_sample *s : samples) kid_sample_destroy(s);
+    for (kid_sample *s : confident) kid_sample_destroy(s);
     if (owns_dbs)
         for (kid_db *d : dbs) kid_db_destroy(d);
 }
@@ -86,7 +87,20 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
         e->samples.push_back(s);
     }
     e->sample = e->samples[0];
+    engine_support(*e, owner.support);
     return e;
+}
+
+void engine_support(Engine &e, const SupportRule &rule)
+{
+    e.support = rule;
+    if (!rule.on) return;
+    for (kid_db *d : e.dbs) {
+        kid_sample *s = nullptr;
+        int rc = kid_sample_begin(d, &s);
+        if (rc != KID_OK) die_kid(rc);
+        e.confident.push_back(s);
+    }
 }
 
 std::vector<int> parse_devices(int device, const std::string &list)
@@ -106,6 +120,10 @@ std::vector<int> parse_devices(int device, const std::string &list)
 void engine_reset(Engine &e)
 {
     for (kid_sample *s : e.samples) {
+        int rc = kid_sample_reset(s);
+        if (rc != KID_OK) die_kid(rc);
+    }
+    for (kid_sample *s : e.confident) {
         int rc = kid_sample_reset(s);
         if (rc != KID_OK) die_kid(rc);
     }
@@ -287,6 +305,60 @@ bool hits_option(int argc, char **argv)
     return false;
 }
 
+[[noreturn]] static void support_usage(const char *prog, const char *option, const char *what)
+{
+    std::cerr << prog << ": " << option << " " << what << "\n";
+    exit(2);
+}
+
+SupportRule support_option(int argc, char **argv, const char *prog)
+{
+    SupportRule r;
+    for (int i = 1; i < argc; i++) {
+        const bool hits = strcmp(argv[i], "--min-hits") == 0;
+        if (!hits && strcmp(argv[i], "--confidence") != 0) continue;
+        const char *opt = argv[i];
+        if (i + 1 >= argc) support_usage(prog, opt, "needs a value");
+        const char *v = argv[++i];
+        auto digit = [](char c) { return c >= '0' && c <= '9'; };
+        unsigned long long whole = 0;
+        size_t at = 0;
+        for (; digit(v[at]); at++) {
+            whole = whole * 10 + (unsigned)(v[at] - '0');
+            if (whole > 0xFFFFFFFFull) support_usage(prog, opt, "is out of range");
+        }
+        if (at == 0) support_usage(prog, opt, hits ? "takes a number >= 0" : "takes a decimal in [0, 1], e.g. 0.02");
+        r.on = true;
+        if (hits) {
+            if (v[at] != 0) support_usage(prog, opt, "takes a number >= 0");
+            r.min_hits = (uint32_t)whole;
+            continue;
+        }
+        // F -> permille, from its digits: the whole part, then up to three fractional digits padded with zeros
+        unsigned frac = 0, nfrac = 0;
+        if (v[at] == '.') {
+            for (at++; digit(v[at]); at++, nfrac++) {
+                if (nfrac == 3) support_usage(prog, opt, "takes at most three fractional digits");
+                frac = frac * 10 + (unsigned)(v[at] - '0');
+            }
+            if (nfrac == 0) support_usage(prog, opt, "takes a decimal in [0, 1], e.g. 0.02");
+            for (unsigned j = nfrac; j < 3; j++) frac *= 10;
+        }
+        if (v[at] != 0) support_usage(prog, opt, "takes a decimal in [0, 1], e.g. 0.02");
+        if (whole * 1000 + frac > 1000) support_usage(prog, opt, "takes a decimal in [0, 1]");
+        r.min_permille = (uint32_t)(whole * 1000 + frac);
+    }
+    return r;
+}
+
+std::string confident_path_for(const std::string &result_path)
+{
+    std::string p = result_path;
+    const size_t at = p.rfind("result");
+    if (at != std::string::npos) p.replace(at, 6, "confident");
+    return p;
+}
+
 std::string hits_path_for(const std::string &result_path)
 {
     std::string p = result_path;
@@ -354,6 +426,17 @@ static void hit_lines_of(kid_db *db, const ReadBatch &b, const std::vector<uint3
     }
 }
 
+// The support pass of one classified batch on its device: nothing comes back, the batch is tallied into `tally` under the rule
+static void tally_batch(kid_db *db, kid_sample *tally, const SupportRule &rule, const ReadBatch &b)
+{
+    const size_t nr = b.size();
+    int rc = b.fq ? kid_db_read_support_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, rule.min_hits,
+                                              rule.min_permille, nullptr, tally)
+                  : kid_db_read_support(db, b.bases.data(), b.offsets.data(), b.start.data(), b.stop.data(), nr, rule.min_hits,
+                                        rule.min_permille, nullptr, tally);
+    if (rc != KID_OK) die_kid(rc);
+}
+
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file,
                     const std::function<void(size_t, long long)> &done, HitsWriter *hits)
 {
@@ -368,6 +451,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         uint64_t ticket = 0;
         kid_sample *sample = nullptr;
         kid_db *db = nullptr;
+        kid_sample *confident = nullptr;
         size_t file = 0;
     };
     std::string lines;
@@ -387,6 +471,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             hit_lines_of(f.db, *f.batch, f.final_targ, e.k, lines);
             hits->add(saver_file + f.file, lines);
         }
+        if (f.confident) tally_batch(f.db, f.confident, e.support, *f.batch);
         q.pop_front();
     };
     try {
@@ -401,6 +486,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             const size_t nr = f.batch->size();
             f.sample = e.samples[e.next_sample]; // batches are dealt round-robin over the devices
             f.db = e.dbs[e.next_sample];
+            f.confident = e.support.on ? e.confident[e.next_sample] : nullptr;
             e.next_sample = (e.next_sample + 1) % e.samples.size();
             int rc;
             const auto t_sub = std::chrono::steady_clock::now();
@@ -466,6 +552,7 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
         if (a == "--db-cache") o.db_cache = v;
     }
     o.hits = hits_option(argc, argv);
+    o.support = support_option(argc, argv, argv[0]);
     return o;
 }
 
@@ -525,6 +612,11 @@ void finish_sample(Engine &e, const std::string &result_path)
                                   : kid_sample_end(e.sample, g.data(), u.data());
     if (rc != KID_OK) die_kid(rc);
     write_result(result_path, g, u);
+    if (!e.support.on) return;
+    rc = e.confident.size() > 1 ? kid_sample_end_merged(e.confident.data(), (int)e.confident.size(), g.data(), u.data())
+                                : kid_sample_end(e.confident[0], g.data(), u.data());
+    if (rc != KID_OK) die_kid(rc);
+    write_result(confident_path_for(result_path), g, u);
 }
 
 } // namespace kidhost

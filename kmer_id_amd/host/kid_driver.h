@@ -12,6 +12,21 @@
 
 namespace kidhost {
 
+// --min-hits N / --confidence F (shared by the three front-ends): call reads by k-mer support.  Either option switches
+// the feature on, the one not given is 0.  A sample / job then gets a confident result file beside its result file, named
+// like it with "result" replaced by "confident" and in its format: the counters of a second sample per device that is
+// tallied with every batch under the rule (kid_db_read_support*: gcount[confident]++ where the result file has
+// gcount[final]++).  Nothing else changes: the result, reads and hits files and stdout are what they are without.
+struct SupportRule {
+    bool on = false;
+    uint32_t min_hits = 0, min_permille = 0;
+};
+// The one place that reads the two options.  N: a decimal number up to 2^32-1.  F: a decimal in [0, 1] with at most three
+// fractional digits, turned into permille from its digits.  Anything else (a missing value too) is a usage error:
+// a message on stderr and exit code 2.  The options are checked, then ignored, with --dry-run.
+SupportRule support_option(int argc, char **argv, const char *prog);
+std::string confident_path_for(const std::string &result_path); // ".../x_result.txt" -> ".../x_confident.txt"
+
 struct Engine {
     kid_db *db = nullptr;         // the database on the first device
     kid_sample *sample = nullptr; // ... and its sample
@@ -21,6 +36,9 @@ struct Engine {
     std::vector<kid_db *> dbs;
     std::vector<kid_sample *> samples;
     size_t next_sample = 0;
+    // --min-hits / --confidence: the rule and one tallied sample per device (engine_support); empty without
+    SupportRule support;
+    std::vector<kid_sample *> confident;
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -51,6 +69,9 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 // exits with 1).
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
+// Switch the confident result file on (rule.on) for an engine that is open: one more sample per device, reset, closed and
+// destroyed with the others.  A worker of engine_worker() inherits it.
+void engine_support(Engine &e, const SupportRule &rule);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
 std::vector<int> parse_devices(int device, const std::string &list);
 // newkmer_10nx.cpp:1017-1019 on every replica
@@ -104,7 +125,8 @@ private:
 // -f1 and -f2 of kmer_read_m3).  done(f, handed), if given, is called for every file first + f in file order once all of
 // them are through, with the number of its reads handed to process_read.  Returns the reads handed of all the files.
 // `hits`, if given and on, receives the hit lines of every batch: the hit pass (kid_db_read_hits*) of a batch runs on the
-// device that classified it, once its final targets are back.
+// device that classified it, once its final targets are back.  With e.support on, the support pass of a batch runs at the
+// same place and tallies into that device's confident sample.
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file = 0,
                     const std::function<void(size_t, long long)> &done = nullptr, HitsWriter *hits = nullptr);
 
@@ -123,6 +145,7 @@ struct ReaderOptions {
     std::string dry_run;     // --dry-run FILE: host stages only (no GPU), for the CPU test-suite
     std::string db_cache;    // --db-cache FILE: binary cache of the parsed database
     bool hits = false;       // --hits: a hits file beside the result file (ignored with --dry-run)
+    SupportRule support;     // --min-hits / --confidence: a confident result file beside the result file (ignored with --dry-run)
 };
 ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 
@@ -132,7 +155,8 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 int write_dry_run(const std::string &path, const char *prog, const std::vector<int32_t> &parent, const ProbeSet &ps,
                   const std::vector<std::string> &labels, const std::vector<SourceOpener> &files, size_t batch_reads, int k);
 
-// gcount / ucount of the sample -> "<i>,<g>,<u>" lines
+// gcount / ucount of the sample -> "<i>,<g>,<u>" lines; with e.support on, those of the tallied sample(s) -> the
+// confident file beside it
 void finish_sample(Engine &e, const std::string &result_path);
 
 } // namespace kidhost

@@ -6,6 +6,8 @@
 // What reaches the kernel: lookups give up after MAXREPROBE = 16 probes (:42,:232), so the table is
 // built sequentially on the host with the reference's exact cell geometry (results depend on it).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
+//   --min-hits N  --confidence F   also write DIR/confident.txt: the reads called by k-mer support (kid_driver.h)
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <fstream>
@@ -61,12 +63,14 @@ int main(int argc, char **argv)
         Engine eng;
         eng.batch_reads = opt.batch_reads;
         if (!engine_open(eng, ps, parent, k, opt.log2_slots, /*MAXREPROBE*/ 16, 0, parse_devices(opt.device, opt.device_list))) return 1;
+        engine_support(eng, opt.support);
         ps = ProbeSet();
 
         if (r1name.empty()) throw Fatal{134, "no -f1 given (std::out_of_range in the reference, :1080)"};
         std::cout << r1name.length() << " : " << r1name[r1name.length() - 1] << std::endl;
         Prefetcher pf(std::move(files), opt.threads, eng.batch_reads, eng.batch_bases);
         HitsWriter hits(opt.hits ? hits_path_for(wdir + "result.txt") : "");
+        if (opt.support.on) remove(confident_path_for(wdir + "result.txt").c_str()); // (one left there by an earlier run)
         ReadSaver saver("", num_targ); // the reads file is commented out in this program (:612-621)
         auto is_fagz = [](const std::string &n) { return ends_with(n, ".fasta.gz"); };
         if (is_fagz(r1name)) std::cout << "true" << std::endl; // process_fagz, :789

@@ -16,6 +16,9 @@
 //   --db-cache FILE  binary cache of the parsed database: read if valid, (re)written otherwise
 //   --samples-in-flight N (threads / 2)  samples read and classified at the same time, each with its own counters on the GPU
 //   --hits               also write <prefix>_hits.txt: every read's k-mer hits (kid_driver.h)
+//   --min-hits N  --confidence F   also write <prefix>_confident.txt, the result file of the reads called by k-mer support:
+//                    a read counts under the first node of its target's root path whose clade holds at least N of its k-mer
+//                    hits and F (a decimal in [0, 1], three fractional digits) of its k-mers, under 0 if none does (kid_driver.h)
 //   --timing         one JSON line on stderr when the run ends: seconds of the start-up phases (probes inflate / parse,
 //                    cache read / write, upload + table build on the GPU, first batch classified) and of the read files
 //   --dry-run FILE   host stages only (no GPU): parse the DB text files and the files a run would read (FASTQ, or
@@ -82,6 +85,7 @@ int main(int argc, char **argv)
         else if (a == "--timing") timing = true;
         else if (a == "--samples-in-flight") in_flight = atoi(val("--samples-in-flight"));
         else if (a == "--hits") {} // (hits_option below: the one place that reads it, shared with the sibling programs)
+        else if (a == "--min-hits" || a == "--confidence") { if (i + 1 < argc) i++; } // (support_option below, likewise)
         else if (dname.empty()) dname = a;
         else { std::cerr << "nk10: unexpected argument " << a << "\n"; return 2; }
     }
@@ -90,6 +94,7 @@ int main(int argc, char **argv)
         return 2;
     }
     const bool want_hits = hits_option(argc, argv); // <prefix>_hits.txt beside <prefix>_result.txt (ignored with --dry-run)
+    const SupportRule support = support_option(argc, argv, "nk10"); // <prefix>_confident.txt likewise
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
     if (batch_reads < 1) batch_reads = 1;
     if (threads < 1) threads = 1;
@@ -180,6 +185,7 @@ int main(int argc, char **argv)
         const std::vector<int> devices = parse_devices(device, device_list);
         if (gpu_warm.joinable()) gpu_warm.join();
         if (!engine_open(eng, ps, parent, k, log2_slots, 0, 0, devices)) return 1; // :256-260
+        engine_support(eng, support);
         // file text goes into page-locked memory from here on: uploads by DMA, not through a CPU copy
         static int pin_device = devices[0];
         set_text_allocator([](size_t n) -> void * { void *p = nullptr; return kid_host_alloc(pin_device, n, &p) == KID_OK ? p : nullptr; },
@@ -244,6 +250,7 @@ int main(int argc, char **argv)
             long long tct = 0;
             const std::string result_path = dname + prefix + "_result.txt";
             HitsWriter hits(want_hits ? hits_path_for(result_path) : "");
+            if (support.on) remove(confident_path_for(result_path).c_str()); // (one left there by an earlier run)
             {
                 ReadSaver saver(dname + prefix + "_reads.txt", ntar);
                 if (fasta_mode) {
@@ -323,9 +330,11 @@ int main(int argc, char **argv)
                     remove((dname + fnames[f] + "_result.txt").c_str());
                     remove((dname + fnames[f] + "_reads.txt").c_str());
                     remove((dname + fnames[f] + "_hits.txt").c_str());
-                } else if (behind && want_hits) {
-                    // never started: a hits file an earlier run left would stand beside no result of this one
-                    remove((dname + fnames[f] + "_hits.txt").c_str());
+                    remove((dname + fnames[f] + "_confident.txt").c_str());
+                } else if (behind) {
+                    // never started: a hits / confident file an earlier run left would stand beside no result of this one
+                    if (want_hits) remove((dname + fnames[f] + "_hits.txt").c_str());
+                    if (support.on) remove((dname + fnames[f] + "_confident.txt").c_str());
                 }
                 if (outs[f].failed) behind = true;
             }

@@ -8,6 +8,8 @@
 // Differences to nk10 that reach the kernel: U/u count as T (:496-500,521-525) and the number of
 // targets comes from the data file (:1073-1084).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
+//   --min-hits N  --confidence F   also write ./JOBS/<job>_confident.txt: the reads called by k-mer support (kid_driver.h)
+#include <stdio.h>
 #include <stdlib.h>
 
 #include <iostream>
@@ -65,6 +67,7 @@ int main(int argc, char **argv)
         Engine eng;
         eng.batch_reads = opt.batch_reads;
         if (!engine_open(eng, ps, parent, k, opt.log2_slots, 0, KID_FLAG_U_IS_T, parse_devices(opt.device, opt.device_list))) return 1;
+        engine_support(eng, opt.support);
         ps = ProbeSet();
 
         Prefetcher pf(std::move(files), opt.threads, eng.batch_reads, eng.batch_bases);
@@ -75,6 +78,7 @@ int main(int argc, char **argv)
             const std::string base = "./" + jname + "/" + jstr;
             long long tct = 0;
             HitsWriter hits(opt.hits ? hits_path_for(base + "_result.txt") : "");
+            if (opt.support.on) remove(confident_path_for(base + "_result.txt").c_str()); // (one left there by an earlier run)
             {
                 ReadSaver saver(base + "_reads.txt", num_targ, save_target > 0 ? base + "_target_reads.txt" : "",
                                 (uint32_t)(save_target > 0 ? save_target : 0), save_target == 0);
