@@ -22,6 +22,19 @@ def _as(a, dtype):
     return a
 
 
+def _offsets_batch(bases, offsets, start, stop):
+    """a batch of reads as the C ABI takes it -> (bases, offsets, start, stop, n)"""
+    offsets = _as(offsets, np.uint64)
+    return _as(bases, np.uint8), offsets, _as(start, np.int32), _as(stop, np.int32), offsets.size - 1
+
+
+def _fastq_block(text, recs):
+    """a block of FASTQ text (bytes or an array) and its line index as the C ABI takes them -> (text, recs, n)"""
+    text = _as(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8)
+    recs = _as(recs, np.uint32).reshape(-1, 4)
+    return text, recs, recs.shape[0]
+
+
 def hash_keys(keys, device=0):
     """Hashtable::integerHash (fmix64) of every key, computed on the GPU."""
     lib = _lib.load()
@@ -166,20 +179,14 @@ class KmerDB:
     def read_hits(self, bases, offsets, start=None, stop=None):
         """The k-mer hits of every read of a batch held in host memory (what process_read folds, newkmer_10nx.cpp:526-595),
         in read-position order -> ReadHits.  Pure: no sample is touched."""
-        bases = _as(bases, np.uint8)
-        offsets = _as(offsets, np.uint64)
-        start = _as(start, np.int32)
-        stop = _as(stop, np.int32)
-        n = offsets.size - 1
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
         return self._read_hits(lambda o, nk, h, cap, tot: self._lib.kid_db_read_hits(
             self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, o, nk, h, cap, tot), n)
 
     def read_hits_fastq(self, text, recs):
         """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): process_qual
         runs on the GPU; a record that fails stop - start >= k has no window and no hit."""
-        text = _as(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8)
-        recs = _as(recs, np.uint32).reshape(-1, 4)
-        n = recs.shape[0]
+        text, recs, n = _fastq_block(text, recs)
         return self._read_hits(lambda o, nk, h, cap, tot: self._lib.kid_db_read_hits_fastq(
             self._h, _ptr(text), text.size, _ptr(recs), n, o, nk, h, cap, tot), n)
 
@@ -192,11 +199,14 @@ class KmerDB:
                                                 C.c_void_p(d_hits or None), cap, C.c_void_p(d_n_hits),
                                                 C.c_void_p(stream or None)))
 
+    def _time(self, query):
+        ms, calls, reads = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        check(query(self._h, C.byref(ms), C.byref(calls), C.byref(reads)))
+        return ms.value, calls.value, reads.value
+
     def read_hits_time(self):
         """-> (device ms, calls, reads) of the hits kernels since the last query (HIP events around every call)"""
-        ms, calls, reads = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
-        check(self._lib.kid_db_read_hits_time(self._h, C.byref(ms), C.byref(calls), C.byref(reads)))
-        return ms.value, calls.value, reads.value
+        return self._time(self._lib.kid_db_read_hits_time)
 
     def read_support(self, bases, offsets, start=None, stop=None, min_hits=0, min_permille=0, tally=None):
         """Call the reads of a batch held in host memory by k-mer support (kid_db_read_support): -> a structured array
@@ -204,11 +214,7 @@ class KmerDB:
         the first node on final's root path whose clade holds at least min_hits hits and min_permille / 1000 of the
         read's k-mers, 0 if none does.  tally: a Sample of this database that is counted as if the batch had been
         classified under the rule (gcount[confident]++, seen bits of the hits of reads with confident > 0)."""
-        bases = _as(bases, np.uint8)
-        offsets = _as(offsets, np.uint64)
-        start = _as(start, np.int32)
-        stop = _as(stop, np.int32)
-        n = offsets.size - 1
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
         out = np.zeros(n, SUPPORT_DTYPE)
         check(self._lib.kid_db_read_support(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
                                             _ptr(out), tally._h if tally is not None else None))
@@ -217,9 +223,7 @@ class KmerDB:
     def read_support_fastq(self, text, recs, min_hits=0, min_permille=0, tally=None):
         """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
         fails stop - start >= k has no window and no hit, and a tally counts it nowhere."""
-        text = _as(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8)
-        recs = _as(recs, np.uint32).reshape(-1, 4)
-        n = recs.shape[0]
+        text, recs, n = _fastq_block(text, recs)
         out = np.zeros(n, SUPPORT_DTYPE)
         check(self._lib.kid_db_read_support_fastq(self._h, _ptr(text), text.size, _ptr(recs), n, min_hits, min_permille, _ptr(out),
                                                   tally._h if tally is not None else None))
@@ -234,9 +238,7 @@ class KmerDB:
 
     def read_support_time(self):
         """-> (device ms, calls, reads) of the support kernel alone since the last query"""
-        ms, calls, reads = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
-        check(self._lib.kid_db_read_support_time(self._h, C.byref(ms), C.byref(calls), C.byref(reads)))
-        return ms.value, calls.value, reads.value
+        return self._time(self._lib.kid_db_read_support_time)
 
     def gather_ceiling(self, n_loads=1 << 28, inflight=4, iters=3):
         """Random gather rate over this DB's table: (ms per launch, loads per launch).  inflight 101 / 108: random
@@ -293,11 +295,7 @@ class Sample:
 
     def classify(self, bases, offsets, start=None, stop=None, want_final=True):
         """process_read for a batch held in host memory; returns final_targ per read."""
-        bases = _as(bases, np.uint8)
-        offsets = _as(offsets, np.uint64)
-        n = offsets.size - 1
-        start = _as(start, np.int32)
-        stop = _as(stop, np.int32)
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
         out = np.empty(n, np.uint32) if want_final else None
         check(self._lib.kid_classify_batch(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, _ptr(out)))
         return out
@@ -329,9 +327,7 @@ class Sample:
     def classify_fastq(self, text, recs):
         """A block of FASTQ text with its line index (uint32[n, 4]: seq_off, seq_len, qual_off, qual_len): process_qual,
         the >= k test and process_read on the GPU (kid_classify_fastq_async).  -> (final_targ, start, stop)"""
-        text = _as(np.frombuffer(text, np.uint8) if isinstance(text, (bytes, bytearray)) else text, np.uint8)
-        recs = _as(recs, np.uint32).reshape(-1, 4)
-        n = recs.shape[0]
+        text, recs, n = _fastq_block(text, recs)
         final = np.empty(n, np.uint32)
         start = np.empty(n, np.int32)
         stop = np.empty(n, np.int32)

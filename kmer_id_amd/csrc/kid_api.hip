@@ -275,6 +275,20 @@ static int kid_seenlog_pace(kid_sample *s, uint64_t n_reads, hipStream_t stream)
     return KID_OK;
 }
 
+// The kernels that count into a sample run one after the other (they share the sample's counters' timing stamps and
+// argument blocks): work issued on another stream than the one before is made to wait for it.
+static int kid_sample_order_behind(kid_sample *s, hipStream_t stream)
+{
+    if (s->has_last_stream && s->last_stream != stream) {
+        if (!s->order_ev.e) KID_HIP(s->order_ev.create(hipEventDisableTiming));
+        KID_HIP(hipEventRecord(s->order_ev.e, s->last_stream));
+        KID_HIP(hipStreamWaitEvent(stream, s->order_ev.e, 0));
+    }
+    s->last_stream = stream;
+    s->has_last_stream = true;
+    return KID_OK;
+}
+
 // a runtime bool as a template argument: f(std::true_type) or f(std::false_type)
 template <class F> static inline void kid_lift(bool v, F &&f)
 {
@@ -306,17 +320,9 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
     const uint32_t long_cut = (long_records && !fastq && s->long_kmers > 0 && s->long_kmers < 0xFFFFFFFFll &&
                                bases_nbytes > (uint64_t)s->long_kmers) ? (uint32_t)s->long_kmers : 0u;
     if (long_cut) max_kmers = -1; // (the host's number counts the hidden records too: the device's does not)
-    // The classify kernels of a sample's batches run one after the other (they share the sample's counters' timing
-    // stamps and argument blocks): a batch issued on another stream than the one before is made to wait for it.
-    if (s->has_last_stream && s->last_stream != stream) {
-        if (!s->order_ev.e) KID_HIP(s->order_ev.create(hipEventDisableTiming));
-        KID_HIP(hipEventRecord(s->order_ev.e, s->last_stream));
-        KID_HIP(hipStreamWaitEvent(stream, s->order_ev.e, 0));
-    }
-    s->last_stream = stream;
-    s->has_last_stream = true;
     {
-        int rc = kid_seenlog_pace(s, b.n, stream);
+        int rc = kid_sample_order_behind(s, stream);
+        if (rc == KID_OK) rc = kid_seenlog_pace(s, b.n, stream);
         if (rc != KID_OK) return rc;
     }
     unsigned long long *const gcount = s->gcount.as<unsigned long long>(), *const stats = s->stats_p();

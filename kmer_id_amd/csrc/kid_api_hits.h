@@ -1,4 +1,7 @@
 // kid_api_hits.h -- every read's k-mer hits: the scratch of a database's hit passes and kid_db_read_hits*.
+// What the host-buffer forms of kid_db_read_support* (kid_api_support.h) share with those of kid_db_read_hits* is here
+// once: KidSpanTimer, the argument checks and the staging of a batch (kid_hits_check_* / kid_hits_stage_*, one pair per
+// input form) and the hit pass into the library's own buffers (kid_hits_host_pass).
 #pragma once
 #include "kid_api_db.h"
 #include "kid_hits.hip.h"
@@ -8,6 +11,50 @@
 // one kid_db run one after the other: a call first waits for the kernels of the call before).  Per batch: 16 B per
 // read (descriptors) + 8 B per read (first tile) + 16 B per tile of 64 windows (mask, first hit) + 8 B per 1024 of
 // either (scan totals); the host-buffer forms add a device copy of their inputs and outputs.
+// The device time between two events on a stream, added up over the calls since somebody took it
+struct __attribute__((visibility("hidden"))) KidSpanTimer {
+    KidEvent ev0, ev1;
+    bool pending = false;
+    double ms = 0;
+    uint64_t calls = 0, reads = 0;
+    hipError_t create()
+    {
+        const hipError_t e = ev0.create();
+        return e != hipSuccess ? e : ev1.create();
+    }
+    int begin(hipStream_t stream)
+    {
+        KID_HIP(hipEventRecord(ev0.e, stream));
+        return KID_OK;
+    }
+    int end(hipStream_t stream, uint64_t n_reads)
+    {
+        KID_HIP(hipEventRecord(ev1.e, stream));
+        pending = true;
+        calls++;
+        reads += n_reads;
+        return KID_OK;
+    }
+    // the elapsed time of the span before (and with it: what ran inside it is through)
+    int settle()
+    {
+        if (!pending) return KID_OK;
+        KID_HIP(hipEventSynchronize(ev1.e));
+        float span = 0;
+        KID_HIP(hipEventElapsedTime(&span, ev0.e, ev1.e));
+        ms += span;
+        pending = false;
+        return KID_OK;
+    }
+    void take(double *device_ms, uint64_t *n_calls, uint64_t *n_reads)
+    {
+        if (device_ms) *device_ms = ms;
+        if (n_calls) *n_calls = calls;
+        if (n_reads) *n_reads = reads;
+        ms = 0; calls = 0; reads = 0;
+    }
+};
+
 struct KidHitsState {
     KidDevBuf desc, tile_off, rsum, tile_mask, tile_hit_off, tsum, trim_start, trim_stop;          // every form
     KidDevBuf in_bases, in_offsets, in_start, in_stop, in_recs, out_offsets, out_nk, out_hits;      // host-buffer forms
@@ -16,17 +63,10 @@ struct KidHitsState {
     // correction, [35] batches with more tiles than the scratch was sized for,
     // then a KidRareArgs (the prepare kernels announce the batch's longest read there; nobody reads it)
     KidDevBuf ctl_buf;
-    KidEvent ev0, ev1;
-    bool pending = false;
-    double ms = 0;
-    uint64_t calls = 0, reads = 0;
     uint32_t seq = 0;
-    // kid_db_read_support* (kid_api_support.h): the host forms' records, and the events around the support kernel alone
-    KidDevBuf out_support;
-    KidEvent sup_ev0, sup_ev1;
-    bool sup_pending = false;
-    double sup_ms = 0;
-    uint64_t sup_calls = 0, sup_reads = 0;
+    KidDevBuf out_support; // kid_db_read_support* (kid_api_support.h): the host forms' records
+    KidSpanTimer pass;     // the hit pass of every call, a kid_db_read_support* host call's included
+    KidSpanTimer support;  // the support kernel alone
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
 #define KID_HITS_CTL_WORDS 36u
@@ -36,18 +76,7 @@ kid_db::~kid_db() {}
 // a little slack: batches of a file differ slightly in size
 static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensure(nbytes, ((nbytes + nbytes / 8) + 255u) & ~255ull); }
 
-// the elapsed time of the call before (and with it: its kernels are through, the scratch is free)
-static int kid_hits_settle(KidHitsState *h)
-{
-    if (!h->pending) return KID_OK;
-    KID_HIP(hipEventSynchronize(h->ev1.e));
-    float ms = 0;
-    KID_HIP(hipEventElapsedTime(&ms, h->ev0.e, h->ev1.e));
-    h->ms += ms;
-    h->pending = false;
-    return KID_OK;
-}
-
+// the scratch, free: the hit pass of the call before is through
 static int kid_hits_state(kid_db *db, KidHitsState **out)
 {
     if (!db->hits) {
@@ -55,12 +84,33 @@ static int kid_hits_state(kid_db *db, KidHitsState **out)
         const size_t nb = KID_HITS_CTL_WORDS * 8 + sizeof(KidRareArgs);
         KID_HIP(h->ctl_buf.alloc(nb));
         KID_HIP(hipMemset(h->ctl(), 0, nb));
-        KID_HIP(h->ev0.create());
-        KID_HIP(h->ev1.create());
+        KID_HIP(h->pass.create());
+        KID_HIP(h->support.create());
         db->hits = std::move(h);
     }
     *out = db->hits.get();
-    return kid_hits_settle(*out);
+    return (*out)->pass.settle();
+}
+
+static KidHitsTiles kid_hits_tiles(const KidHitsState *h, const KidBatch &b)
+{
+    KidHitsTiles a{};
+    a.bases = b.bases;
+    a.desc = h->desc.as<KidReadDesc>();
+    a.tile_off = h->tile_off.as<uint64_t>();
+    a.n_reads = b.n;
+    a.tile_mask = h->tile_mask.as<unsigned long long>();
+    return a;
+}
+
+// the fill pass on its own: the host-buffer forms learn the number of hits first and then size their device buffer
+static int kid_hits_launch_fill(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, KidHit *d_hits,
+                                uint64_t cap, hipStream_t stream)
+{
+    hipLaunchKernelGGL(kid_hits_fill_kernel, dim3(kid_grid_for(max_tiles, KID_HITS_WG_TILES, db->num_cu * 32)), dim3(256), 0, stream, db->d,
+                       kid_hits_tiles(h, b), (const uint64_t *)h->tile_hit_off.as<uint64_t>(), b.offsets, recs, d_hits, cap);
+    KID_HIP(hipGetLastError());
+    return KID_OK;
 }
 
 // The kernels of one batch on `stream`, everything on the device.  b: bases / offsets / start / stop (recs: a FASTQ
@@ -85,7 +135,8 @@ static int kid_hits_launch(kid_db *db, KidHitsState *h, const KidBatch &b, const
     KidReadDesc *desc = h->desc.as<KidReadDesc>();
     uint64_t *tile_off = h->tile_off.as<uint64_t>(), *tile_hit_off = h->tile_hit_off.as<uint64_t>();
     const int cu = db->num_cu;
-    KID_HIP(hipEventRecord(h->ev0.e, stream));
+    int rc = h->pass.begin(stream);
+    if (rc != KID_OK) return rc;
     if (recs)
         hipLaunchKernelGGL(kid_prepare_fastq_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, b.bases, recs, n, db->info.k,
                            desc, const_cast<int32_t *>(b.start), const_cast<int32_t *>(b.stop), (uint32_t *)nullptr, stats, h->ctl() + 34, rare,
@@ -100,12 +151,7 @@ static int kid_hits_launch(kid_db *db, KidHitsState *h, const KidBatch &b, const
                        max_tiles, h->ctl() + 35);
     hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, tile_off,
                        (const uint64_t *)h->rsum.as<uint64_t>(), (const uint64_t *)nullptr, n, (const uint64_t *)n_tiles);
-    KidHitsTiles a{};
-    a.bases = b.bases;
-    a.desc = desc;
-    a.tile_off = tile_off;
-    a.n_reads = n;
-    a.tile_mask = h->tile_mask.as<unsigned long long>();
+    const KidHitsTiles a = kid_hits_tiles(h, b);
     const int tile_grid = kid_grid_for(max_tiles, KID_HITS_WG_TILES, cu * 32);
     hipLaunchKernelGGL(kid_hits_count_kernel, dim3(tile_grid), dim3(256), 0, stream, db->d, a, d_n_kmers);
     // hits per tile -> first hit of every tile
@@ -117,35 +163,8 @@ static int kid_hits_launch(kid_db *db, KidHitsState *h, const KidBatch &b, const
                        (const uint64_t *)h->tsum.as<uint64_t>(), (const uint64_t *)n_tiles, 0ull, (const uint64_t *)n_hits);
     hipLaunchKernelGGL(kid_hits_offsets_kernel, dim3(kid_grid_for(n + 1, 256, cu * 8)), dim3(256), 0, stream, (const uint64_t *)tile_off,
                        (const uint64_t *)tile_hit_off, n, d_hit_offsets, d_n_hits);
-    if (fill && d_hits && cap)
-        hipLaunchKernelGGL(kid_hits_fill_kernel, dim3(tile_grid), dim3(256), 0, stream, db->d, a, (const uint64_t *)tile_hit_off, b.offsets, recs,
-                           d_hits, cap);
+    if (fill && d_hits && cap) return kid_hits_launch_fill(db, h, b, recs, max_tiles, d_hits, cap, stream);
     KID_HIP(hipGetLastError());
-    return KID_OK;
-}
-
-// the fill pass on its own: the host-buffer forms learn the number of hits first and then size their device buffer
-static int kid_hits_launch_fill(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, KidHit *d_hits,
-                                uint64_t cap, hipStream_t stream)
-{
-    KidHitsTiles a{};
-    a.bases = b.bases;
-    a.desc = h->desc.as<KidReadDesc>();
-    a.tile_off = h->tile_off.as<uint64_t>();
-    a.n_reads = b.n;
-    a.tile_mask = h->tile_mask.as<unsigned long long>();
-    hipLaunchKernelGGL(kid_hits_fill_kernel, dim3(kid_grid_for(max_tiles, KID_HITS_WG_TILES, db->num_cu * 32)), dim3(256), 0, stream, db->d, a,
-                       (const uint64_t *)h->tile_hit_off.as<uint64_t>(), b.offsets, recs, d_hits, cap);
-    KID_HIP(hipGetLastError());
-    return KID_OK;
-}
-
-static int kid_hits_close(KidHitsState *h, uint64_t n_reads, hipStream_t stream)
-{
-    KID_HIP(hipEventRecord(h->ev1.e, stream));
-    h->pending = true;
-    h->calls++;
-    h->reads += n_reads;
     return KID_OK;
 }
 
@@ -164,11 +183,12 @@ static int kid_hits_check(KidHitsState *h)
     return kid_fail(KID_ERR_FORMAT, "%llu FASTQ records have a quality line shorter than the sequence (qual.at() throws in the reference)", st[8]);
 }
 
-// the host-buffer forms behind their uploads: kernels, the count, the fill if the caller's buffer holds it, downloads
-static int kid_hits_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, uint64_t *hit_offsets,
-                             uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
+// The hit pass of a host-buffer form into the library's own buffers (out_offsets, out_nk, out_hits) on stream 0: the
+// count pass, the number of hits read back, the fill pass if that number is neither 0 nor more than `limit`.
+#define KID_HITS_NO_LIMIT (~0ull)
+static int kid_hits_host_pass(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, uint64_t limit,
+                              uint64_t *n_hits)
 {
-    static_assert(sizeof(kid_hit) == sizeof(KidHit), "kid_hit is the device record");
     const uint64_t n = b.n;
     int rc;
     KID_HIP(kid_hits_ensure(h->out_offsets, (n + 1) * 8));
@@ -179,46 +199,67 @@ static int kid_hits_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, con
     uint64_t total = 0;
     KID_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, 0));
     KID_HIP(hipStreamSynchronize(0));
-    const bool fill = hits && total > 0 && total <= cap;
-    if (fill) {
+    if (total > 0 && total <= limit) {
         KID_HIP(kid_hits_ensure(h->out_hits, total * sizeof(KidHit)));
         if ((rc = kid_hits_launch_fill(db, h, b, recs, max_tiles, h->out_hits.as<KidHit>(), total, 0)) != KID_OK) return rc;
     }
-    if ((rc = kid_hits_close(h, n, 0)) != KID_OK) return rc;
+    *n_hits = total;
+    return h->pass.end(0, n);
+}
+
+// the host-buffer forms behind their uploads: the hit pass, the fill if the caller's buffer holds it, downloads
+static int kid_hits_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, uint64_t *hit_offsets,
+                             uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
+{
+    static_assert(sizeof(kid_hit) == sizeof(KidHit), "kid_hit is the device record");
+    const uint64_t n = b.n, limit = hits ? cap : 0;
+    uint64_t total = 0;
+    int rc = kid_hits_host_pass(db, h, b, recs, max_tiles, limit, &total);
+    if (rc != KID_OK) return rc;
     KID_HIP(hipMemcpy(hit_offsets, h->out_offsets.p, (n + 1) * 8, hipMemcpyDeviceToHost));
     if (n_kmers) KID_HIP(hipMemcpy(n_kmers, h->out_nk.p, n * 4, hipMemcpyDeviceToHost));
-    if (fill) KID_HIP(hipMemcpy(hits, h->out_hits.p, total * sizeof(KidHit), hipMemcpyDeviceToHost));
+    if (total > 0 && total <= limit) KID_HIP(hipMemcpy(hits, h->out_hits.p, total * sizeof(KidHit), hipMemcpyDeviceToHost));
     if ((rc = kid_hits_check(h)) != KID_OK) return rc;
     *n_hits = total;
     return KID_OK;
 }
 
-static int kid_hits_upload_text(KidHitsState *h, const uint8_t *src, uint64_t nbytes)
+// The host-buffer forms, one pair of functions per input form.  kid_hits_check_*: what the host can refuse about the
+// arguments of a batch that has reads, then the database's device selected; *max_tiles: what the tile arrays are sized
+// for.  kid_hits_stage_*: the batch copied into the scratch (synchronous copies on stream 0) -> the KidBatch of the copy.
+static int kid_hits_check_offsets(const kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                                  uint64_t n_reads, uint64_t *max_tiles)
 {
-    KID_HIP(kid_hits_ensure(h->in_bases, kid_text_bytes(nbytes)));
-    return kid_upload_text(h->in_bases, src, nbytes, 0);
-}
-
-extern "C" int kid_db_read_hits(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
-                                uint64_t n_reads, uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
-{
-    if (!db || !hit_offsets || !n_hits) return kid_fail(KID_ERR_ARG, "null argument");
-    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
-    if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
-    if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
     if (!bases || !offsets) return kid_fail(KID_ERR_ARG, "null argument");
     if ((start == nullptr) != (stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
     int64_t max_kmers = 0;
-    uint64_t max_tiles = 0;
-    int rc = kid_check_offsets_batch(offsets, start, stop, n_reads, db->info.k, &max_kmers, KID_HITS_TILE, &max_tiles);
+    int rc = kid_check_offsets_batch(offsets, start, stop, n_reads, db->info.k, &max_kmers, KID_HITS_TILE, max_tiles);
     if (rc != KID_OK) return rc;
-    rc = kid_use_device(db->device);
+    return kid_use_device(db->device);
+}
+
+static int kid_hits_check_fastq(const kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                                uint64_t *max_tiles)
+{
+    if (!text || !recs) return kid_fail(KID_ERR_ARG, "null argument");
+    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, KID_HITS_TILE, max_tiles);
     if (rc != KID_OK) return rc;
-    std::lock_guard<std::mutex> lock(db->hits_mu);
-    KidHitsState *h = nullptr;
-    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
+    return kid_use_device(db->device);
+}
+
+static int kid_hits_stage_text(KidHitsState *h, const uint8_t *src, uint64_t nbytes, KidBatch *b)
+{
+    KID_HIP(kid_hits_ensure(h->in_bases, kid_text_bytes(nbytes)));
+    b->bases = h->in_bases.as<uint8_t>();
+    return kid_upload_text(h->in_bases, src, nbytes, 0);
+}
+
+static int kid_hits_stage_offsets(KidHitsState *h, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                                  uint64_t n_reads, KidBatch *b)
+{
     const uint64_t base0 = offsets[0], nbytes = offsets[n_reads] - base0;
-    if ((rc = kid_hits_upload_text(h, bases + base0, nbytes)) != KID_OK) return rc;
+    int rc = kid_hits_stage_text(h, bases + base0, nbytes, b);
+    if (rc != KID_OK) return rc;
     KID_HIP(kid_hits_ensure(h->in_offsets, (n_reads + 1) * 8));
     std::vector<uint64_t> rel; // (a synchronous copy reads it)
     const uint64_t *off_src = kid_rebased_offsets(offsets, n_reads, rel);
@@ -229,12 +270,44 @@ extern "C" int kid_db_read_hits(kid_db *db, const uint8_t *bases, const uint64_t
         KID_HIP(hipMemcpy(h->in_start.p, start, n_reads * 4, hipMemcpyHostToDevice));
         KID_HIP(hipMemcpy(h->in_stop.p, stop, n_reads * 4, hipMemcpyHostToDevice));
     }
+    b->offsets = h->in_offsets.as<uint64_t>();
+    b->start = start ? h->in_start.as<int32_t>() : nullptr;
+    b->stop = start ? h->in_stop.as<int32_t>() : nullptr;
+    b->n = n_reads;
+    return KID_OK;
+}
+
+static int kid_hits_stage_fastq(KidHitsState *h, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                                KidBatch *b, const KidFastqRec **d_recs)
+{
+    int rc = kid_hits_stage_text(h, text, text_nbytes, b);
+    if (rc != KID_OK) return rc;
+    KID_HIP(kid_hits_ensure(h->in_recs, n_reads * sizeof(KidFastqRec)));
+    KID_HIP(kid_hits_ensure(h->trim_start, n_reads * 4));
+    KID_HIP(kid_hits_ensure(h->trim_stop, n_reads * 4));
+    KID_HIP(hipMemcpy(h->in_recs.p, recs, n_reads * sizeof(KidFastqRec), hipMemcpyHostToDevice));
+    b->start = h->trim_start.as<int32_t>(); // (outputs of the prepare kernel here)
+    b->stop = h->trim_stop.as<int32_t>();
+    b->n = n_reads;
+    *d_recs = h->in_recs.as<KidFastqRec>();
+    return KID_OK;
+}
+
+extern "C" int kid_db_read_hits(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                                uint64_t n_reads, uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
+{
+    if (!db || !hit_offsets || !n_hits) return kid_fail(KID_ERR_ARG, "null argument");
+    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
+    if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
+    if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
+    uint64_t max_tiles = 0;
+    int rc = kid_hits_check_offsets(db, bases, offsets, start, stop, n_reads, &max_tiles);
+    if (rc != KID_OK) return rc;
+    std::lock_guard<std::mutex> lock(db->hits_mu);
+    KidHitsState *h = nullptr;
     KidBatch b{};
-    b.bases = h->in_bases.as<uint8_t>();
-    b.offsets = h->in_offsets.as<uint64_t>();
-    b.start = start ? h->in_start.as<int32_t>() : nullptr;
-    b.stop = start ? h->in_stop.as<int32_t>() : nullptr;
-    b.n = n_reads;
+    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
+    if ((rc = kid_hits_stage_offsets(h, bases, offsets, start, stop, n_reads, &b)) != KID_OK) return rc;
     return kid_hits_host_run(db, h, b, nullptr, max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
 }
 
@@ -245,26 +318,16 @@ extern "C" int kid_db_read_hits_fastq(kid_db *db, const uint8_t *text, uint64_t 
     if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
     if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
     if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
-    if (!text || !recs) return kid_fail(KID_ERR_ARG, "null argument");
     uint64_t max_tiles = 0;
-    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, KID_HITS_TILE, &max_tiles);
-    if (rc != KID_OK) return rc;
-    rc = kid_use_device(db->device);
+    int rc = kid_hits_check_fastq(db, text, text_nbytes, recs, n_reads, &max_tiles);
     if (rc != KID_OK) return rc;
     std::lock_guard<std::mutex> lock(db->hits_mu);
     KidHitsState *h = nullptr;
-    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
-    if ((rc = kid_hits_upload_text(h, text, text_nbytes)) != KID_OK) return rc;
-    KID_HIP(kid_hits_ensure(h->in_recs, n_reads * sizeof(KidFastqRec)));
-    KID_HIP(kid_hits_ensure(h->trim_start, n_reads * 4));
-    KID_HIP(kid_hits_ensure(h->trim_stop, n_reads * 4));
-    KID_HIP(hipMemcpy(h->in_recs.p, recs, n_reads * sizeof(KidFastqRec), hipMemcpyHostToDevice));
     KidBatch b{};
-    b.bases = h->in_bases.as<uint8_t>();
-    b.start = h->trim_start.as<int32_t>(); // (outputs of the prepare kernel here)
-    b.stop = h->trim_stop.as<int32_t>();
-    b.n = n_reads;
-    return kid_hits_host_run(db, h, b, h->in_recs.as<KidFastqRec>(), max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
+    const KidFastqRec *d_recs = nullptr;
+    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
+    if ((rc = kid_hits_stage_fastq(h, text, text_nbytes, recs, n_reads, &b, &d_recs)) != KID_OK) return rc;
+    return kid_hits_host_run(db, h, b, d_recs, max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
 }
 
 extern "C" int kid_db_read_hits_device(kid_db *db, const void *d_bases, uint64_t bases_nbytes, const void *d_offsets, const void *d_start,
@@ -296,10 +359,12 @@ extern "C" int kid_db_read_hits_device(kid_db *db, const void *d_bases, uint64_t
     rc = kid_hits_launch(db, h, b, nullptr, bases_nbytes / KID_HITS_TILE + n_reads, (uint64_t *)d_hit_offsets, (uint32_t *)d_n_kmers, (KidHit *)d_hits, cap,
                          (uint64_t *)d_n_hits, st, true);
     if (rc != KID_OK) return rc;
-    return kid_hits_close(h, n_reads, st);
+    return h->pass.end(st, n_reads);
 }
 
-extern "C" int kid_db_read_hits_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads)
+// kid_db_read_hits_time / kid_db_read_support_time: one of the state's timers, settled and taken; check: report what
+// the prepare kernels refused since the last query as well
+static int kid_hits_take_time(kid_db *db, KidSpanTimer KidHitsState::*timer, bool check, double *device_ms, uint64_t *calls, uint64_t *reads)
 {
     if (!db) return kid_fail(KID_ERR_ARG, "null argument");
     if (device_ms) *device_ms = 0;
@@ -310,10 +375,12 @@ extern "C" int kid_db_read_hits_time(kid_db *db, double *device_ms, uint64_t *ca
     if (!h) return KID_OK;
     int rc = kid_use_device(db->device);
     if (rc != KID_OK) return rc;
-    if ((rc = kid_hits_settle(h)) != KID_OK) return rc;
-    if (device_ms) *device_ms = h->ms;
-    if (calls) *calls = h->calls;
-    if (reads) *reads = h->reads;
-    h->ms = 0; h->calls = 0; h->reads = 0;
-    return kid_hits_check(h);
+    if ((rc = (h->*timer).settle()) != KID_OK) return rc;
+    (h->*timer).take(device_ms, calls, reads);
+    return check ? kid_hits_check(h) : KID_OK;
+}
+
+extern "C" int kid_db_read_hits_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads)
+{
+    return kid_hits_take_time(db, &KidHitsState::pass, true, device_ms, calls, reads);
 }

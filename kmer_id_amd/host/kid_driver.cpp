@@ -64,10 +64,18 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 
 Engine::~Engine()
 {
-    for (kid_sample *s : samples) kid_sample_destroy(s);
-    for (kid_sample *s : confident) kid_sample_destroy(s);
+    for (const std::vector<kid_sample *> *list : {&samples, &confident})
+        for (kid_sample *s : *list) kid_sample_destroy(s);
     if (owns_dbs)
         for (kid_db *d : dbs) kid_db_destroy(d);
+}
+
+static kid_sample *begin_sample_or_die(kid_db *db)
+{
+    kid_sample *s = nullptr;
+    int rc = kid_sample_begin(db, &s);
+    if (rc != KID_OK) die_kid(rc);
+    return s;
 }
 
 std::unique_ptr<Engine> engine_worker(const Engine &owner)
@@ -80,12 +88,7 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
     e->k = owner.k;
     e->batch_reads = owner.batch_reads;
     e->batch_bases = owner.batch_bases;
-    for (kid_db *d : e->dbs) {
-        kid_sample *s = nullptr;
-        int rc = kid_sample_begin(d, &s);
-        if (rc != KID_OK) die_kid(rc);
-        e->samples.push_back(s);
-    }
+    for (kid_db *d : e->dbs) e->samples.push_back(begin_sample_or_die(d));
     e->sample = e->samples[0];
     engine_support(*e, owner.support);
     return e;
@@ -95,12 +98,7 @@ void engine_support(Engine &e, const SupportRule &rule)
 {
     e.support = rule;
     if (!rule.on) return;
-    for (kid_db *d : e.dbs) {
-        kid_sample *s = nullptr;
-        int rc = kid_sample_begin(d, &s);
-        if (rc != KID_OK) die_kid(rc);
-        e.confident.push_back(s);
-    }
+    for (kid_db *d : e.dbs) e.confident.push_back(begin_sample_or_die(d));
 }
 
 std::vector<int> parse_devices(int device, const std::string &list)
@@ -119,14 +117,11 @@ std::vector<int> parse_devices(int device, const std::string &list)
 
 void engine_reset(Engine &e)
 {
-    for (kid_sample *s : e.samples) {
-        int rc = kid_sample_reset(s);
-        if (rc != KID_OK) die_kid(rc);
-    }
-    for (kid_sample *s : e.confident) {
-        int rc = kid_sample_reset(s);
-        if (rc != KID_OK) die_kid(rc);
-    }
+    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
+        for (kid_sample *s : *list) {
+            int rc = kid_sample_reset(s);
+            if (rc != KID_OK) die_kid(rc);
+        }
     e.next_sample = 0;
 }
 
@@ -143,8 +138,7 @@ bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &pare
         return false;
     }
     if (rc != KID_OK) die_kid(rc);
-    rc = kid_sample_begin(e.db, &e.sample);
-    if (rc != KID_OK) die_kid(rc);
+    e.sample = begin_sample_or_die(e.db);
     e.dbs.assign(1, e.db);
     e.samples.assign(1, e.sample);
     for (size_t i = 1; i < devices.size(); i++) { // the reference, pinned into every GPU's HBM: device-to-device copies of the one built table
@@ -152,10 +146,7 @@ bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &pare
         rc = kid_db_replicate(e.db, devices[i], &r);
         if (rc != KID_OK) die_kid(rc);
         e.dbs.push_back(r);
-        kid_sample *s = nullptr;
-        rc = kid_sample_begin(r, &s);
-        if (rc != KID_OK) die_kid(rc);
-        e.samples.push_back(s);
+        e.samples.push_back(begin_sample_or_die(r));
     }
     return true;
 }
@@ -351,19 +342,11 @@ SupportRule support_option(int argc, char **argv, const char *prog)
     return r;
 }
 
-std::string confident_path_for(const std::string &result_path)
+std::string sibling_path_for(const std::string &result_path, const char *word)
 {
     std::string p = result_path;
     const size_t at = p.rfind("result");
-    if (at != std::string::npos) p.replace(at, 6, "confident");
-    return p;
-}
-
-std::string hits_path_for(const std::string &result_path)
-{
-    std::string p = result_path;
-    const size_t at = p.rfind("result");
-    if (at != std::string::npos) p.replace(at, 6, "hits");
+    if (at != std::string::npos) p.replace(at, 6, word);
     return p;
 }
 
@@ -616,7 +599,7 @@ void finish_sample(Engine &e, const std::string &result_path)
     rc = e.confident.size() > 1 ? kid_sample_end_merged(e.confident.data(), (int)e.confident.size(), g.data(), u.data())
                                 : kid_sample_end(e.confident[0], g.data(), u.data());
     if (rc != KID_OK) die_kid(rc);
-    write_result(confident_path_for(result_path), g, u);
+    write_result(sibling_path_for(result_path, "confident"), g, u);
 }
 
 } // namespace kidhost

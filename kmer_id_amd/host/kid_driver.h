@@ -25,7 +25,9 @@ struct SupportRule {
 // fractional digits, turned into permille from its digits.  Anything else (a missing value too) is a usage error:
 // a message on stderr and exit code 2.  The options are checked, then ignored, with --dry-run.
 SupportRule support_option(int argc, char **argv, const char *prog);
-std::string confident_path_for(const std::string &result_path); // ".../x_result.txt" -> ".../x_confident.txt"
+// The file beside a result file: its path with the last "result" replaced by `word` (".../x_result.txt", "confident"
+// -> ".../x_confident.txt"; "hits" names the hits file of --hits, below)
+std::string sibling_path_for(const std::string &result_path, const char *word);
 
 struct Engine {
     kid_db *db = nullptr;         // the database on the first device
@@ -107,7 +109,6 @@ private:
 // order by close() -- what is held is the hits file itself (reads without a hit leave nothing), nothing else.  A
 // writer that is not closed (its sample failed) leaves no file; one made with an empty path does nothing.
 bool hits_option(int argc, char **argv);                 // is --hits among the arguments
-std::string hits_path_for(const std::string &result_path); // ".../x_result.txt" -> ".../x_hits.txt"
 class HitsWriter {
 public:
     explicit HitsWriter(const std::string &path); // removes a file left there by an earlier run

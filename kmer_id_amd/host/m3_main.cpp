@@ -69,8 +69,8 @@ int main(int argc, char **argv)
         if (r1name.empty()) throw Fatal{134, "no -f1 given (std::out_of_range in the reference, :1080)"};
         std::cout << r1name.length() << " : " << r1name[r1name.length() - 1] << std::endl;
         Prefetcher pf(std::move(files), opt.threads, eng.batch_reads, eng.batch_bases);
-        HitsWriter hits(opt.hits ? hits_path_for(wdir + "result.txt") : "");
-        if (opt.support.on) remove(confident_path_for(wdir + "result.txt").c_str()); // (one left there by an earlier run)
+        HitsWriter hits(opt.hits ? sibling_path_for(wdir + "result.txt", "hits") : "");
+        if (opt.support.on) remove(sibling_path_for(wdir + "result.txt", "confident").c_str()); // (one left there by an earlier run)
         ReadSaver saver("", num_targ); // the reads file is commented out in this program (:612-621)
         auto is_fagz = [](const std::string &n) { return ends_with(n, ".fasta.gz"); };
         if (is_fagz(r1name)) std::cout << "true" << std::endl; // process_fagz, :789

@@ -249,8 +249,8 @@ int main(int argc, char **argv)
             out += prefix + "\n";
             long long tct = 0;
             const std::string result_path = dname + prefix + "_result.txt";
-            HitsWriter hits(want_hits ? hits_path_for(result_path) : "");
-            if (support.on) remove(confident_path_for(result_path).c_str()); // (one left there by an earlier run)
+            HitsWriter hits(want_hits ? sibling_path_for(result_path, "hits") : "");
+            if (support.on) remove(sibling_path_for(result_path, "confident").c_str()); // (one left there by an earlier run)
             {
                 ReadSaver saver(dname + prefix + "_reads.txt", ntar);
                 if (fasta_mode) {

@@ -77,8 +77,8 @@ int main(int argc, char **argv)
             engine_reset(eng);
             const std::string base = "./" + jname + "/" + jstr;
             long long tct = 0;
-            HitsWriter hits(opt.hits ? hits_path_for(base + "_result.txt") : "");
-            if (opt.support.on) remove(confident_path_for(base + "_result.txt").c_str()); // (one left there by an earlier run)
+            HitsWriter hits(opt.hits ? sibling_path_for(base + "_result.txt", "hits") : "");
+            if (opt.support.on) remove(sibling_path_for(base + "_result.txt", "confident").c_str()); // (one left there by an earlier run)
             {
                 ReadSaver saver(base + "_reads.txt", num_targ, save_target > 0 ? base + "_target_reads.txt" : "",
                                 (uint32_t)(save_target > 0 ? save_target : 0), save_target == 0);

@@ -1,4 +1,5 @@
 """Shared helpers for the test-suite (imports the oracle: test infrastructure)."""
+import ctypes as C
 import gzip
 import os
 import sys
@@ -9,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-from kmer_id_amd import synth  # noqa: E402
+from kmer_id_amd import _lib, synth  # noqa: E402
 from oracle import binding as ob  # noqa: E402
 
 K = 30
@@ -75,3 +76,59 @@ def concat_reads(seqs):
     off = np.zeros(len(seqs) + 1, np.uint64)
     off[1:] = np.cumsum([len(s) for s in seqs])
     return data, off
+
+
+def fastq_block(seqs, quals, eol=b"\n", blank_every=0):
+    """FASTQ text of the records (seqs[i], quals[i]: bytes) -> (text uint8[], recs uint32[n, 4]: seq_off, seq_len,
+    qual_off, qual_len; the lines without their line end).  eol: the line end; blank_every: a blank line (and a bare
+    '\\n') behind every blank_every-th record, the first included"""
+    text, recs = bytearray(), []
+    for i, (s, q) in enumerate(zip(seqs, quals)):
+        text += b"@r%d" % i + eol
+        so = len(text)
+        text += s + eol + b"+" + eol
+        qo = len(text)
+        text += q + eol
+        if blank_every and i % blank_every == 0:
+            text += eol + b"\n"
+        recs.append((so, len(s), qo, len(q)))
+    return np.frombuffer(bytes(text), np.uint8), np.array(recs, np.uint32)
+
+
+class DeviceBatch:
+    """a batch resident in HBM with the output buffers of kid_db_read_hits_device (hits: a canary-filled kid_hit[cap + 4])"""
+
+    def __init__(self, bases, off, cap):
+        self.lib = _lib.load()
+        self.n, self.nbytes, self.bufs = off.size - 1, bases.size, []
+        padded = np.zeros(((bases.size + 15) // 16) * 16 + 32, np.uint8)
+        padded[:bases.size] = bases
+        self.canary = np.full((cap + 4) * 3, 0xA5A5A5A5, np.uint32)
+        self.d_bases, self.d_off = self.dev(padded.nbytes, padded), self.dev(off.nbytes, off)
+        self.d_ho, self.d_nk, self.d_tot = self.dev((self.n + 1) * 8), self.dev(max(self.n, 1) * 4), self.dev(8)
+        self.d_hits = self.dev(self.canary.nbytes, self.canary)
+
+    def dev(self, nbytes, src=None):
+        p = C.c_void_p()
+        _lib.check(self.lib.kid_dev_alloc(0, nbytes, C.byref(p)))
+        self.bufs.append(p)
+        if src is not None:
+            _lib.check(self.lib.kid_dev_upload(0, p, src.ctypes.data_as(C.c_void_p), src.nbytes))
+        return p
+
+    def down(self, p, dtype, count):
+        out = np.empty(count, dtype)
+        _lib.check(self.lib.kid_dev_download(0, out.ctypes.data_as(C.c_void_p), p, out.nbytes))
+        return out
+
+    def run(self, db, cap, nbytes=None):
+        db.read_hits_device(self.d_bases.value, self.nbytes if nbytes is None else nbytes, self.d_off.value, self.n, self.d_ho.value,
+                            self.d_tot.value, d_n_kmers=self.d_nk.value, d_hits=self.d_hits.value if cap else 0, cap=cap)
+        _lib.check(self.lib.kid_dev_sync(0))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for p in self.bufs:
+            self.lib.kid_dev_free(0, p)

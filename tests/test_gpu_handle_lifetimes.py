@@ -6,29 +6,18 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import K, ob, oracle_db, small_db, synth
+from helpers import K, concat_reads, fastq_block, ob, oracle_db, small_db, synth
 from kmer_id_amd import KidError, KmerDB, PinnedBuffer, _lib
+from kmer_id_amd.api import ReadHits
 from kmer_id_amd.builder import device_mem_info
 from read_hits_model import HitModel, trim_ranges
+from read_support_model import SupportModel
 
 pytestmark = pytest.mark.gpu
 
 LOG2_SLOTS = 16
 N, L = 9000, 150       # the largest batch; the others are its first 64, 2 000 and 5 000 reads
 KID_ERR_ARG = -1
-
-
-def fastq_block(bases, quals, n):
-    """the first n reads as FASTQ text -> (text uint8[], recs uint32[n, 4])"""
-    text, recs = bytearray(), []
-    for i in range(n):
-        text += b"@r%d\n" % i
-        so = len(text)
-        text += bases[i].tobytes() + b"\n+\n"
-        qo = len(text)
-        text += quals[i].tobytes() + b"\n"
-        recs.append((so, L, qo, L))
-    return np.frombuffer(bytes(text), np.uint8), np.array(recs, np.uint32)
 
 
 class World:
@@ -65,7 +54,7 @@ class World:
 
     def block(self, n):
         if n not in self.blocks:
-            self.blocks[n] = fastq_block(self.bases, self.quals, n)
+            self.blocks[n] = fastq_block([b.tobytes() for b in self.bases[:n]], [q.tobytes() for q in self.quals[:n]])
         return self.blocks[n]
 
     def counts(self, whole, trimmed):
@@ -124,6 +113,83 @@ def test_buffers_follow_batches_that_grow_and_shrink(world):
     eg, eu = w.counts(sizes, sizes)
     assert np.array_equal(g, eg) and np.array_equal(u, eu)
     s.close(); db.close()
+
+
+class Mixed:
+    """n reads of the world from read `first` on, three of them cut short: fewer than k bases (no window, no tile),
+    exactly 64 windows (one tile) and 65 windows (two tiles); as an offsets batch and as a FASTQ block, each with the
+    model's hits.  The cut reads get a flawless quality line, so that process_qual leaves them their windows."""
+
+    def __init__(self, w, model, first, n, cut):
+        seqs = [w.bases[first + i].tobytes() for i in range(n)]
+        quals = [w.quals[first + i].tobytes() for i in range(n)]
+        for i, length in cut.items():
+            seqs[i], quals[i] = seqs[i][:length], b"I" * length
+        self.n = n
+        self.flat, self.off = concat_reads(seqs)
+        self.text, self.recs = fastq_block(seqs, quals)
+        self.hits = model.batch(self.flat, self.off)
+        start, stop, self.keep = trim_ranges(quals, [len(s) for s in seqs], K)
+        start[~self.keep], stop[~self.keep] = 1, 0   # no range: no window, no hit
+        self.hits_fq = model.batch(self.flat, self.off, start, stop)
+        for h in (self.hits, self.hits_fq):
+            assert sorted(int(h.n_kmers[i]) for i in cut) == [0, 64, 65][3 - len(cut):]
+
+
+def hits_in_one_call(call, n):
+    """kid_db_read_hits* once, into a buffer with room for a hit at every window of n reads of L bases -> ReadHits"""
+    cap = n * (L - K + 1)
+    offsets, n_kmers, hits, total = np.empty(n + 1, np.uint64), np.empty(n, np.uint32), np.empty(cap * 3, np.uint32), C.c_uint64(0)
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    _lib.check(call(n, p(offsets), p(n_kmers), p(hits), cap, C.byref(total)))
+    return ReadHits(offsets, n_kmers, hits[:total.value * 3])
+
+
+def same_support(got, exp, what):
+    for f in exp.dtype.names:
+        assert np.array_equal(got[f], exp[f]), "%s: %s" % (what, f)
+
+
+def test_hits_and_support_calls_interleave_on_one_database(world):
+    """read_hits, read_support, read_hits_fastq, read_support_fastq with a tally, read_hits on one handle, 1025, 7, 1,
+    1025 and 7 reads: the calls share the database's grow-only scratch (1025 reads cross the 1024-element scan block)
+    and its two timers.  Every hits step is one library call, so that the hit-pass timer counts one call per step."""
+    w = world
+    lib = _lib.load()
+    model = HitModel(w.odb, w.keys, w.targets, K)
+    support = SupportModel(model, w.parent)
+    big = Mixed(w, model, 0, 1025, {3: K - 10, 500: 64 + K - 1, 1024: 65 + K - 1})
+    small = Mixed(w, model, 1126, 7, {1: K - 1, 3: 64 + K - 1, 6: 65 + K - 1})
+    one = Mixed(w, model, 3, 1, {0: 65 + K - 1})
+    assert int(small.hits.offsets[-1]) >= 8 and int(one.hits_fq.offsets[-1]) >= 2
+    assert int(big.hits.offsets[-1]) > 100 and int(big.hits_fq.offsets[-1]) > 100 and 0 < int((~big.keep).sum()) < 1025 // 4
+    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    db = w.new_db()
+    t = db.sample()
+
+    def read_hits(b):
+        return hits_in_one_call(lambda n, *out: lib.kid_db_read_hits(db._h, p(b.flat), p(b.off), None, None, n, *out), b.n)
+
+    same_prefix(read_hits(big), big.hits, big.n, "1. read_hits, 1025 reads")
+    rule = (2, 25)
+    exp = support.batch_identity(small.hits, rule, support.finals(small.hits))
+    same_support(db.read_support(small.flat, small.off, min_hits=rule[0], min_permille=rule[1]), exp, "2. read_support, 7 reads")
+    got = hits_in_one_call(lambda n, *out: lib.kid_db_read_hits_fastq(db._h, p(one.text), one.text.size, p(one.recs), n, *out), one.n)
+    same_prefix(got, one.hits_fq, one.n, "3. read_hits_fastq, 1 read")
+    rule = (1, 10)
+    exp = support.batch_identity(big.hits_fq, rule, support.finals(big.hits_fq))
+    same_support(db.read_support_fastq(big.text, big.recs, min_hits=rule[0], min_permille=rule[1], tally=t), exp,
+                 "4. read_support_fastq, 1025 reads")
+    same_prefix(read_hits(small), small.hits, small.n, "5. read_hits, 7 reads")
+    g, u = t.end()
+    eg, eu = support.tally(big.hits_fq, exp, big.keep, w.targets)   # a record process_qual drops is counted nowhere
+    assert np.array_equal(g, eg) and np.array_equal(u, eu) and int(g.sum()) == int(big.keep.sum()) and int(u.sum()) > 0
+    ms, calls, reads = db.read_hits_time()   # a read_support call runs the hit pass too
+    assert (calls, reads) == (5, 1025 + 7 + 1 + 1025 + 7) and ms > 0
+    ms, calls, reads = db.read_support_time()
+    assert (calls, reads) == (2, 7 + 1025) and ms > 0
+    assert db.read_hits_time() == (0.0, 0, 0) and db.read_support_time() == (0.0, 0, 0)
+    t.close(); db.close()
 
 
 def refused(call, fragment):

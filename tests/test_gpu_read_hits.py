@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import read_hits_cases as cases
-from helpers import concat_reads, ob, oracle_db
+from helpers import DeviceBatch, concat_reads, fastq_block, ob, oracle_db
 from kmer_id_amd import KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KID_FLAG_U_IS_T, KidError, KmerDB, _lib, synth
 from read_hits_model import HitModel, trim_ranges, windows
 
@@ -323,18 +323,6 @@ def test_any_split_into_calls_concatenates(contract):
         assert np.array_equal(np.concatenate(counts), np.diff(ref.offsets.astype(np.int64)))
 
 
-def fastq_block(seqs, quals):
-    text, recs = bytearray(), []
-    for i, (s, q) in enumerate(zip(seqs, quals)):
-        text += b"@r%d\n" % i
-        so = len(text)
-        text += s + b"\n+\n"
-        qo = len(text)
-        text += q + b"\n"
-        recs.append((so, len(s), qo, len(q)))
-    return np.frombuffer(bytes(text), np.uint8), np.array(recs, np.uint32)
-
-
 def test_fastq_block_form_equals_host_form(contract):
     db, parent, cum, keys, targets = contract[:5]
     n, length = 1500, 150
@@ -382,45 +370,6 @@ def test_argument_errors(contract):
     ho = np.zeros(1, np.uint64)
     rc = lib.kid_db_read_hits(db._h, None, None, None, None, 1 << 31, ho.ctypes.data_as(C.c_void_p), None, None, 0, C.byref(tot))
     assert rc == -1  # more than 2^31-1 reads
-
-
-class DeviceBatch:
-    """a batch resident in HBM with the output buffers of kid_db_read_hits_device (hits: a canary-filled kid_hit[cap + 4])"""
-
-    def __init__(self, bases, off, cap):
-        self.lib = _lib.load()
-        self.n, self.nbytes, self.bufs = off.size - 1, bases.size, []
-        padded = np.zeros(((bases.size + 15) // 16) * 16 + 32, np.uint8)
-        padded[:bases.size] = bases
-        self.canary = np.full((cap + 4) * 3, 0xA5A5A5A5, np.uint32)
-        self.d_bases, self.d_off = self.dev(padded.nbytes, padded), self.dev(off.nbytes, off)
-        self.d_ho, self.d_nk, self.d_tot = self.dev((self.n + 1) * 8), self.dev(max(self.n, 1) * 4), self.dev(8)
-        self.d_hits = self.dev(self.canary.nbytes, self.canary)
-
-    def dev(self, nbytes, src=None):
-        p = C.c_void_p()
-        _lib.check(self.lib.kid_dev_alloc(0, nbytes, C.byref(p)))
-        self.bufs.append(p)
-        if src is not None:
-            _lib.check(self.lib.kid_dev_upload(0, p, src.ctypes.data_as(C.c_void_p), src.nbytes))
-        return p
-
-    def down(self, p, dtype, count):
-        out = np.empty(count, dtype)
-        _lib.check(self.lib.kid_dev_download(0, out.ctypes.data_as(C.c_void_p), p, out.nbytes))
-        return out
-
-    def run(self, db, cap, nbytes=None):
-        db.read_hits_device(self.d_bases.value, self.nbytes if nbytes is None else nbytes, self.d_off.value, self.n, self.d_ho.value,
-                            self.d_tot.value, d_n_kmers=self.d_nk.value, d_hits=self.d_hits.value if cap else 0, cap=cap)
-        _lib.check(self.lib.kid_dev_sync(0))
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        for p in self.bufs:
-            self.lib.kid_dev_free(0, p)
 
 
 def test_device_form_equals_host_form(contract):

@@ -7,12 +7,11 @@ import numpy as np
 import pytest
 
 import read_support_cases as sc
-from helpers import ROOT, concat_reads, oracle_db
+from helpers import ROOT, DeviceBatch, concat_reads, fastq_block, oracle_db
 from kmer_id_amd import KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KidError, KmerDB, _lib, end_merged
 from kmer_id_amd.api import SUPPORT_DTYPE
 from read_hits_model import HitModel, trim_ranges, windows
 from read_support_model import RULES, SupportModel
-from test_gpu_read_hits import DeviceBatch
 
 pytestmark = pytest.mark.gpu
 
@@ -217,19 +216,6 @@ def test_tally_under_rule_00_equals_classifying(world, db):
     s.close(), t.close()
 
 
-def crlf_block(seqs, quals):
-    """FASTQ text with CRLF line ends and blank lines between the records -> text, recs (lines without their '\\r')"""
-    text, recs = bytearray(), []
-    for i, (s, q) in enumerate(zip(seqs, quals)):
-        text += b"@r%d\r\n" % i
-        so = len(text)
-        text += s + b"\r\n+\r\n"
-        qo = len(text)
-        text += q + b"\r\n" + (b"\r\n\n" if i % 5 == 0 else b"")
-        recs.append((so, len(s), qo, len(q)))
-    return np.frombuffer(bytes(text), np.uint8), np.array(recs, np.uint32)
-
-
 def test_tally_of_a_fastq_block_counts_what_classifying_counts(world, db):
     from kmer_id_amd import synth
     n, length = 1200, 150
@@ -240,7 +226,7 @@ def test_tally_of_a_fastq_block_counts_what_classifying_counts(world, db):
     quals += [b"I" * 20, b"", b"I" * 31]
     start, stop, keep = trim_ranges(quals, [len(s) for s in seqs], 30)
     assert 0 < int((~keep).sum()) and int(keep.sum()) > 800
-    text, recs = crlf_block(seqs, quals)
+    text, recs = fastq_block(seqs, quals, eol=b"\r\n", blank_every=5)  # CRLF line ends, blank lines between records
     s, t = db.sample(), db.sample()
     final, st, sp = s.classify_fastq(text, recs)
     rec = db.read_support_fastq(text, recs, tally=t)
@@ -345,7 +331,7 @@ def test_error_statuses(world, db):
     start, stop = np.zeros(n, np.int32), (np.diff(off[:n + 1].astype(np.int64)) - 1).astype(np.int32)
     stop[2] += 1  # one past the read
     assert status(lambda: db.read_support(bases, off[:n + 1], start, stop, tally=t)) == -1
-    text, recs = crlf_block([bases[int(off[3]):int(off[4])].tobytes()] * 4, [b"I" * int(off[4] - off[3])] * 4)
+    text, recs = fastq_block([bases[int(off[3]):int(off[4])].tobytes()] * 4, [b"I" * int(off[4] - off[3])] * 4, eol=b"\r\n", blank_every=5)
     recs[2, 3] -= 1  # a quality line shorter than its sequence
     assert status(lambda: db.read_support_fastq(text, recs, tally=t)) == -9
     assert int(t.end()[0].sum()) == 0
