@@ -14,6 +14,8 @@
 #include "../../include/kmer_id_amd.h"
 #include "kid_kernels.hip.h"
 #include "kid_build.hip.h"
+#include "kid_tile.hip.h"
+#include "kid_long.hip.h"
 #include "kid_hits.hip.h"
 #include "kid_support.hip.h"
 #include "kid_api_core.h"

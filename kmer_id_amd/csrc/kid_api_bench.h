@@ -9,6 +9,7 @@
 #include <stdlib.h>
 
 #include "kid_api_db.h"
+#include "kid_bench.hip.h"
 
 // ---------------------------------------------------------------- synthetic workload
 extern "C" int kid_synth_db_keys_host(uint64_t seed, int k, const uint64_t *cum, int32_t ntar, uint64_t j0, uint64_t n,

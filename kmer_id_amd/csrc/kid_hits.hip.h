@@ -6,7 +6,7 @@
 // The reads come as the descriptors of kid_prepare_kernel / kid_prepare_fastq_kernel, i.e. trimming, the "stop - start
 // >= k" rule and the range checks are decided by the code that decides them for the classify path.  A read is cut into
 // tiles of 64 consecutive windows; one wave takes a tile, one lane a window (text packed in registers, minimizers staged
-// in LDS: the scheme of kid_long_hits_kernel at wave size, so that a 121-window read costs two tiles, not one of 256).
+// in LDS: the tile of kid_tile.hip.h at wave size, so that a 121-window read costs two tiles, not one of 256).
 //
 //   kid_hits_scan_*          tiles per read -> first tile of every read                       (exclusive scan)
 //   kid_hits_count_kernel    every window is looked up ONCE; a tile leaves the 64-bit mask of its hit lanes
@@ -21,6 +21,7 @@
 // Everything is integer and every output place is a pure function of the batch: the result is byte-identical across
 // runs, across any split of the reads into calls and across table geometries.
 #pragma once
+#include "kid_tile.hip.h"
 
 #define KID_HITS_TILE 64u        // windows per tile = lanes per wave
 #define KID_HITS_WAVE_TILES 4u   // consecutive tiles a wave takes per round (one search for the read of the first)
@@ -46,16 +47,6 @@ __device__ __forceinline__ uint64_t kid_hits_scan_src(const void *src, uint64_t 
     return (uint64_t)__popcll(static_cast<const unsigned long long *>(src)[i]);
 }
 
-__device__ __forceinline__ uint64_t kid_hits_wave_incscan(uint64_t x)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, (unsigned)o);
-        if ((int)(threadIdx.x & 63u) >= o) x += y;
-    }
-    return x;
-}
-
 template <int SRC>
 __global__ __launch_bounds__(256) void kid_hits_scan_local_kernel(const void *src, const uint64_t *n_dev, uint64_t n_host, uint64_t *out,
                                                                    uint64_t *bsum, uint32_t *zero /* nullable: [n] cleared on the way */)
@@ -65,26 +56,18 @@ __global__ __launch_bounds__(256) void kid_hits_scan_local_kernel(const void *sr
     const uint64_t nblk = (n + KID_HITS_SCAN_BLOCK - 1u) / KID_HITS_SCAN_BLOCK;
     for (uint64_t blk = blockIdx.x; blk < nblk; blk += gridDim.x) {
         const uint64_t i0 = blk * KID_HITS_SCAN_BLOCK + 4u * threadIdx.x;
-        uint64_t x[4], sum = 0;
+        uint64_t x[4];
 #pragma unroll
         for (int j = 0; j < 4; j++) {
             x[j] = i0 + j < n ? kid_hits_scan_src<SRC>(src, i0 + j) : 0ull;
-            sum += x[j];
             if (zero && i0 + j < n) zero[i0 + j] = 0u;
         }
-        const uint64_t inc = kid_hits_wave_incscan(sum);
-        if ((threadIdx.x & 63u) == 63u) wave_tot[threadIdx.x >> 6] = inc;
-        __syncthreads();
-        uint64_t before = 0;
-        for (uint32_t w = 0; w < (threadIdx.x >> 6); w++) before += wave_tot[w];
-        uint64_t run = before + inc - sum;
+        const uint64_t upto = kid_block_exscan4(x, wave_tot);
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
-            if (i0 + j < n) out[i0 + j] = run;
-            run += x[j];
-        }
-        if (threadIdx.x == 255u) bsum[blk] = run;
-        __syncthreads();
+        for (int j = 0; j < 4; j++)
+            if (i0 + j < n) out[i0 + j] = x[j];
+        if (threadIdx.x == 255u) bsum[blk] = upto;
+        __syncthreads(); // wave_tot[] is rewritten by the next round
     }
 }
 
@@ -100,7 +83,7 @@ __global__ __launch_bounds__(1024) void kid_hits_scan_top_kernel(uint64_t *bsum,
     for (uint64_t c0 = 0; c0 < nblk; c0 += 1024u) {
         const uint64_t i = c0 + threadIdx.x;
         const uint64_t v = i < nblk ? bsum[i] : 0ull;
-        const uint64_t inc = kid_hits_wave_incscan(v);
+        const uint64_t inc = kid_wave_incscan(v);
         if ((threadIdx.x & 63u) == 63u) wave_tot[threadIdx.x >> 6] = inc;
         __syncthreads();
         uint64_t before = 0, tot = 0;
@@ -150,40 +133,11 @@ __device__ __forceinline__ uint64_t kid_hits_read_of(const KidHitsTiles &a, uint
     return lo;
 }
 
-// the packed words (and invalid-base masks) of the up to 8 chunks of 16 bases a tile's windows and m-mers touch
-__device__ __forceinline__ void kid_hits_stage(const KidHitsTiles &a, const KidDevDb &db, const KidReadDesc &d, uint64_t p0, uint32_t lane,
-                                               uint32_t *W, uint32_t *IM)
-{
-    if (lane < 8u) {
-        const uint64_t c0 = p0 >> 4, c_last = (d.first_base + (uint64_t)(uint32_t)d.n_kmers + (uint64_t)db.k - 2u) >> 4;
-        uint32_t cw = 0, ci = 0;
-        if (c0 + lane <= c_last) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(a.bases + 16ull * (c0 + lane));
-            kid_pack16(v, db.u_is_t, cw, ci);
-        }
-        W[lane] = cw;
-        if (IM) IM[lane] = ci;
-    }
-}
-
-// 32 bases starting at `base`, first base in the top bits (c0 = chunk of the tile's first base)
-__device__ __forceinline__ uint64_t kid_hits_window(const uint32_t *W, uint64_t c0, uint64_t base)
-{
-    const uint32_t w0 = (uint32_t)((base >> 4) - c0);
-    const uint32_t o2 = (uint32_t)(base & 15u) * 2u;
-    const uint64_t A = ((uint64_t)W[w0] << 32) | W[w0 + 1];
-    const uint64_t B = W[w0 + 2];
-    return (A << o2) | ((B << o2) >> 32);
-}
-
 // Pass 1: every window looked up once.  tile_mask[t] = its hit lanes; n_kmers[r] += the windows of the tile that hold
 // a k-mer (no base that is not ACGTacgt(Uu): the read's share of the classify path's "lookups").
 __global__ __launch_bounds__(256) void kid_hits_count_kernel(const KidDevDb db, const KidHitsTiles a, uint32_t *n_kmers /* nullable, zeroed */)
 {
     __shared__ uint32_t W[4][8], IM[4][8], mm[4][KID_HITS_TILE + 16];
-    const int k = db.k;
-    const uint32_t win = (uint32_t)kid_min_window(k);
-    const int mlen = kid_min_mlen(k);
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint64_t n_tiles = a.tile_off[a.n_reads];
     for (uint64_t base = (uint64_t)blockIdx.x * KID_HITS_WG_TILES; base < n_tiles; base += (uint64_t)gridDim.x * KID_HITS_WG_TILES) {
@@ -191,49 +145,24 @@ __global__ __launch_bounds__(256) void kid_hits_count_kernel(const KidDevDb db, 
         uint64_t r = t < n_tiles ? kid_hits_read_of(a, t) : 0ull;
         for (uint32_t q = 0; q < KID_HITS_WAVE_TILES; q++, t++) {
             const bool active = t < n_tiles; // wave-uniform
-            KidReadDesc d{};
-            uint64_t p0 = 0;
-            uint32_t t0 = 0;
+            uint64_t p0 = 0, end = 0;
             if (active) {
                 while (a.tile_off[r + 1] <= t) r++;
-                d = a.desc[r];
-                t0 = (uint32_t)(t - a.tile_off[r]) * KID_HITS_TILE; // first window of the tile within the read
-                p0 = d.first_base + t0;
-                kid_hits_stage(a, db, d, p0, lane, W[wv], IM[wv]);
+                const KidReadDesc d = a.desc[r];
+                p0 = d.first_base + (t - a.tile_off[r]) * KID_HITS_TILE; // the tile's first window
+                end = d.first_base + (uint64_t)(uint32_t)d.n_kmers;
+                kid_tile_stage<KID_HITS_TILE, 8u>(a.bases, db, p0, end, lane, W[wv], IM[wv]);
             }
             __syncthreads();
-            const uint64_t c0 = p0 >> 4;
-            if (active && db.minloc) { // hashed m-mers of positions p0 .. p0 + 63 + win - 1, clamped to the read's last m-mer
-                const uint64_t last_m = d.first_base + (uint64_t)(uint32_t)d.n_kmers + (uint64_t)k - 1u - (uint64_t)mlen;
-                for (uint32_t j = lane; j < KID_HITS_TILE + win - 1u; j += 64u) {
-                    uint64_t p = p0 + j;
-                    p = p < last_m ? p : last_m;
-                    mm[wv][j] = kid_mmer_hash((uint32_t)(kid_hits_window(W[wv], c0, p) >> (64 - 2 * mlen)), mlen);
-                }
-            }
+            if (active && db.minloc) kid_tile_mmers<KID_HITS_TILE>(db, W[wv], p0, end, lane, mm[wv]);
             __syncthreads();
             if (active) {
-                const uint32_t i = t0 + lane;
+                const uint64_t p = p0 + lane;
                 bool valid = false, hit = false;
-                if (i < (uint32_t)d.n_kmers) {
-                    const uint64_t p = p0 + lane;
-                    // a window touching a base that is not ACGTacgt(Uu) holds no k-mer (newkmer_10nx.cpp:520-526,604)
-                    const uint32_t iw = (uint32_t)((p >> 4) - c0);
-                    uint64_t im = (uint64_t)IM[wv][iw] | ((uint64_t)IM[wv][iw + 1] << 16) | ((uint64_t)IM[wv][iw + 2] << 32);
-                    im >>= (p & 15u);
-                    if ((im & ((1ull << k) - 1ull)) == 0) {
-                        valid = true;
-                        const uint64_t key = kid_canonical(kid_hits_window(W[wv], c0, p) >> (64 - 2 * k), k);
-                        uint32_t slot = 0, nc = 0, tgt;
-                        if (db.minloc) {
-                            uint32_t g = 0xFFFFFFFFu;
-                            for (uint32_t w = 0; w < win; w++) g = mm[wv][lane + w] < g ? mm[wv][lane + w] : g;
-                            tgt = kid_bucket_lookup(db, key, g, slot, nc);
-                        } else {
-                            tgt = kid_dev_lookup(db, key, slot, nc);
-                        }
-                        hit = tgt > 0;
-                    }
+                if (p < end && kid_tile_is_kmer(IM[wv], p0 >> 4, p, db.k)) {
+                    valid = true;
+                    uint32_t slot = 0, nc = 0;
+                    hit = kid_tile_lookup(db, W[wv], p0 >> 4, p, mm[wv] + lane, slot, nc) > 0;
                 }
                 const unsigned long long hm = __ballot(hit), vm = __ballot(valid);
                 if (lane == 0) {
@@ -267,7 +196,6 @@ __global__ __launch_bounds__(256) void kid_hits_fill_kernel(const KidDevDb db, c
                                                              KidHit *hits, uint64_t cap)
 {
     __shared__ uint32_t W[4][8];
-    const int k = db.k;
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
     const uint64_t n_tiles = a.tile_off[a.n_reads];
     if (tile_hit_off[n_tiles] > cap) return;
@@ -277,23 +205,19 @@ __global__ __launch_bounds__(256) void kid_hits_fill_kernel(const KidDevDb db, c
         bool searched = false;
         for (uint32_t q = 0; q < KID_HITS_WAVE_TILES; q++, t++) {
             const unsigned long long hm = t < n_tiles ? a.tile_mask[t] : 0ull; // wave-uniform
-            KidReadDesc d{};
             uint64_t p0 = 0;
-            uint32_t t0 = 0;
             if (hm) {
                 if (!searched) { r = kid_hits_read_of(a, t); searched = true; }
                 while (a.tile_off[r + 1] <= t) r++;
-                d = a.desc[r];
-                t0 = (uint32_t)(t - a.tile_off[r]) * KID_HITS_TILE;
-                p0 = d.first_base + t0;
-                kid_hits_stage(a, db, d, p0, lane, W[wv], nullptr);
+                const KidReadDesc d = a.desc[r];
+                p0 = d.first_base + (t - a.tile_off[r]) * KID_HITS_TILE;
+                kid_tile_stage<KID_HITS_TILE, 8u>(a.bases, db, p0, d.first_base + (uint64_t)(uint32_t)d.n_kmers, lane, W[wv], nullptr);
             }
             __syncthreads();
             if ((hm >> lane) & 1ull) {
                 const uint64_t p = p0 + lane;
-                const uint64_t key = kid_canonical(kid_hits_window(W[wv], p0 >> 4, p) >> (64 - 2 * k), k);
                 uint32_t slot = 0, nc = 0;
-                const uint32_t tgt = kid_dev_lookup(db, key, slot, nc);
+                const uint32_t tgt = kid_dev_lookup(db, kid_tile_key(W[wv], p0 >> 4, p, db.k), slot, nc); // (no strip here)
                 const uint64_t origin = offsets ? offsets[r] : (uint64_t)recs[r].seq_off;
                 KidHit h;
                 h.pos = (uint32_t)(p - origin);

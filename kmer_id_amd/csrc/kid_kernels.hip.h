@@ -1000,7 +1000,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                     ufr.z = (uint32_t)__builtin_amdgcn_readlane((int)fr.z, h);
                     ufr.w = (uint32_t)__builtin_amdgcn_readlane((int)fr.w, h);
                     uint64_t rem = hitm & (e >= 64u ? ~0ull : ((1ull << e) - 1ull)) & ~((1ull << h) - 1ull);
-                    while (rem) {
+                    while (rem) { // (kid_jump_fold of kid_tile.hip.h, written out on this loop's registers)
                         uint32_t rj = tgt;
                         uint4 roj = row;
                         if (uf != 0 && tgt != uf) { // (first hit: :592-595; msca(x,x) = x)
@@ -1836,217 +1836,6 @@ __global__ void kid_build_firstwins_kernel(uint4 *table, uint32_t slot_mask, con
     }
 }
 
-// ------------------------------------------------------------------ very long records (FASTA contigs classified whole)
-// A record is one left fold over its hits (newkmer_10nx.cpp:588-595; msca is not associative), which the classify
-// kernels run inside ONE wave: 9.7 ms per megabase when the batch holds few records.  When the host sees few long
-// records in a batch it hands them to two kernels instead:
-//   kid_long_hits_kernel   every k-mer of every long record is looked up by a lane of its own, all over the chip; a hit
-//                          leaves its target in hits[position] (and its bit in the seen-bitmap)
-//   kid_long_fold_kernel   one workgroup per record compacts the hits in position order and folds them, 64 at a time,
-//                          jumping from change to change of the running result like the resolver does
-// Plain code: this path runs a few hundred times per batch, not a hundred million times.
-// The list -> the plan: where every long record's hits go.  One thread: the list is short.  A record that does not fit
-// the hit array any more is handed back to the classify kernels (its descriptor gets its k-mers back).
-__global__ void kid_long_plan_kernel(KidLongList *list, KidLongPlan *plan, KidReadDesc *desc, KidRareArgs *rare, uint32_t seq,
-                                     uint64_t hits_cap, uint64_t tiles_cap)
-{
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    const uint32_t n = list->n < KID_LONG_MAX ? list->n : KID_LONG_MAX;
-    uint64_t off = 0, tiles = 0;
-    uint32_t m = 0, back = 0;
-    for (uint32_t i = 0; i < n; i++) {
-        const KidLongList::Item it = list->e[i];
-        const uint64_t nt = ((uint64_t)it.n_kmers + 255u) / 256u;
-        if (off + it.n_kmers > hits_cap || tiles + nt > tiles_cap) {
-            desc[it.read].n_kmers = (int32_t)it.n_kmers;
-            back = it.n_kmers > back ? it.n_kmers : back;
-            continue;
-        }
-        KidLongRec r;
-        r.first_base = it.first_base; r.hits_off = off; r.n_kmers = it.n_kmers; r.read = it.read; r.tile0 = tiles;
-        plan->recs[m++] = r;
-        off += it.n_kmers;
-        tiles += nt;
-    }
-    plan->n_recs = m;
-    plan->n_tiles = tiles;
-    plan->total_kmers = off;
-    list->n = 0; // for the batch that uses this set next
-    if (back) { // (the kernels pick themselves by the longest read of the batch)
-        const unsigned long long v = ((unsigned long long)seq << 32) | back;
-        if (v > rare->batch_max) rare->batch_max = v;
-    }
-}
-
-// Every k-mer of every long record is looked up by a lane of its own.  A tile = 256 consecutive k-mers of one record:
-// its 256 + k - 1 bases are read as text (16 bytes per thread by the first 20 threads), packed in registers and staged
-// in LDS, like the classify kernels' general loops stage a segment.
-__global__ __launch_bounds__(256) void kid_long_hits_kernel(const KidDevDb db, const uint8_t *bases, const KidLongPlan *plan,
-                                                             uint32_t *hits, uint8_t *tile_any, uint32_t *seen,
-                                                             unsigned long long *stats)
-{
-    __shared__ uint32_t mm[256 + 32];
-    __shared__ uint32_t W[24], IM[24]; // the tile's packed words and invalid masks (20 chunks + what a window reads beyond)
-    const int k = db.k;
-    const uint32_t win = (uint32_t)kid_min_window(k);
-    const int mlen = kid_min_mlen(k);
-    const uint32_t n_recs = plan->n_recs;
-    const uint64_t n_tiles = plan->n_tiles;
-    const KidLongRec *recs = plan->recs;
-    unsigned long long n_lookups = 0, n_cells = 0, n_hits = 0;
-    for (uint64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        // the record this tile belongs to (recs are few: binary search over tile0)
-        uint32_t lo = 0, hi = n_recs;
-        while (hi - lo > 1) { const uint32_t mid = (lo + hi) >> 1; if (recs[mid].tile0 <= tile) lo = mid; else hi = mid; }
-        const KidLongRec rc = recs[lo];
-        const uint32_t t0 = (uint32_t)(tile - rc.tile0) * 256u; // first k-mer of the tile within the record
-        const uint32_t j = threadIdx.x;
-        // the tile's text: chunks c0 .. of 16 bases, never beyond the chunk that holds the record's last base
-        const uint64_t c0 = (rc.first_base + t0) >> 4, c_last = (rc.first_base + (uint64_t)rc.n_kmers + (uint64_t)k - 2u) >> 4;
-        if (j < 24u) {
-            uint32_t cw = 0, ci = 0;
-            if (c0 + j <= c_last && j < 21u) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(bases + 16ull * (c0 + j));
-                kid_pack16(v, db.u_is_t, cw, ci);
-            }
-            W[j] = cw;
-            IM[j] = ci;
-        }
-        __syncthreads();
-        auto window = [&](uint64_t base) -> uint64_t { // 32 bases starting at `base`, first base in the top bits
-            const uint32_t w0 = (uint32_t)((base >> 4) - c0);
-            const uint32_t o2 = (uint32_t)(base & 15u) * 2u;
-            const uint64_t A = ((uint64_t)W[w0] << 32) | W[w0 + 1];
-            const uint64_t B = W[w0 + 2];
-            return (A << o2) | ((B << o2) >> 32);
-        };
-        // hashed m-mers of positions t0 .. t0 + 255 + win - 1 (clamped to the last m-mer inside the record)
-        const uint64_t last_m = rc.first_base + (uint64_t)rc.n_kmers + (uint64_t)k - 1u - (uint64_t)mlen;
-        if (db.minloc) // (workgroup-uniform; the reference placement has no minimizers, and for k < 15 there is no m-mer to hash)
-            for (uint32_t q = j; q < 256u + win - 1u; q += 256u) {
-                uint64_t p = rc.first_base + t0 + q;
-                p = p < last_m ? p : last_m;
-                mm[q] = kid_mmer_hash((uint32_t)(window(p) >> (64 - 2 * mlen)), mlen);
-            }
-        __syncthreads();
-        const uint32_t i = t0 + j;
-        bool hit = false;
-        uint32_t hit_t = 0;
-        if (i < rc.n_kmers) {
-            const uint64_t p = rc.first_base + i;
-            // a window touching a base that is not ACGTacgt(Uu) holds no k-mer (newkmer_10nx.cpp:520-526,604)
-            const uint32_t iw = (uint32_t)((p >> 4) - c0);
-            uint64_t im = (uint64_t)IM[iw] | ((uint64_t)IM[iw + 1] << 16) | ((uint64_t)IM[iw + 2] << 32);
-            im >>= (p & 15u);
-            if ((im & ((1ull << k) - 1ull)) == 0) {
-                const uint64_t keyF = window(p) >> (64 - 2 * k);
-                const uint64_t key = kid_canonical(keyF, k);
-                uint32_t slot = 0, nc = 0, tgt;
-                if (db.minloc) {
-                    uint32_t g = 0xFFFFFFFFu;
-                    for (uint32_t w = 0; w < win; w++) g = mm[j + w] < g ? mm[j + w] : g;
-                    tgt = kid_bucket_lookup(db, key, g, slot, nc);
-                } else {
-                    tgt = kid_dev_lookup(db, key, slot, nc);
-                }
-                n_lookups++;
-                n_cells += nc;
-                if (tgt > 0) {
-                    n_hits++;
-                    hit = true;
-                    if (tgt > 1) atomicOr(&seen[slot >> 5], 1u << (slot & 31u));
-                }
-                hit_t = tgt;
-            }
-        }
-        if (i < rc.n_kmers) hits[rc.hits_off + i] = hit_t; // (every position: the array is not cleared between batches)
-        const int any = __syncthreads_or(hit ? 1 : 0); // (also: mm[], W[] and IM[] are free for the next tile)
-        if (threadIdx.x == 0) tile_any[tile] = any ? 1 : 0; // the fold skips tiles without hits unseen
-    }
-    // one set of atomics per workgroup (see kid_classify_kernel)
-    __shared__ unsigned long long tot[3];
-    if (threadIdx.x < 3) tot[threadIdx.x] = 0;
-    __syncthreads();
-    if (n_lookups) atomicAdd(&tot[0], n_lookups);
-    if (n_cells) atomicAdd(&tot[1], n_cells);
-    if (n_hits) atomicAdd(&tot[2], n_hits);
-    __syncthreads();
-    if (threadIdx.x < 3 && tot[threadIdx.x]) atomicAdd(&stats[1 + threadIdx.x], tot[threadIdx.x]);
-}
-
-__global__ __launch_bounds__(256) void kid_long_fold_kernel(const KidDevDb db, const KidLongPlan *plan, const uint32_t *hits,
-                                                             const uint8_t *tile_any, unsigned long long *gcount,
-                                                             uint32_t *out_final)
-{
-    if (blockIdx.x >= plan->n_recs) return; // (a grid of KID_LONG_MAX workgroups: the host does not know how many there are)
-    const KidLongRec *recs = plan->recs;
-    __shared__ uint32_t list[256];
-    __shared__ uint32_t wcount[4];
-    __shared__ uint8_t flags[256];
-    const KidLongRec rc = recs[blockIdx.x];
-    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
-    uint32_t uf = 0; // the running result (wave 0)
-    uint4 ufr = make_uint4(0, 0, 0, 0);
-    const uint32_t ntile = (rc.n_kmers + 255u) / 256u;
-    for (uint32_t tg = 0; tg < ntile; tg += 256u) { // 256 tiles = 65 536 positions at a time: most hold no hit at all
-      const uint32_t myt = tg + threadIdx.x;
-      const uint8_t fl = myt < ntile ? tile_any[rc.tile0 + myt] : (uint8_t)0;
-      flags[threadIdx.x] = fl;
-      if (!__syncthreads_or(fl)) continue;
-      for (uint32_t tt = 0; tt < 256u && tg + tt < ntile; tt++) {
-        if (!flags[tt]) continue; // (workgroup-uniform)
-        const uint32_t t0 = (tg + tt) * 256u;
-        {
-        const uint32_t i = t0 + threadIdx.x;
-        const uint32_t h = i < rc.n_kmers ? hits[rc.hits_off + i] : 0u;
-        const uint64_t bm = __ballot(h != 0);
-        if (lane == 0) wcount[wv] = (uint32_t)__popcll(bm);
-        __syncthreads();
-        uint32_t before = 0, total = 0;
-        for (uint32_t w = 0; w < 4; w++) { const uint32_t c = wcount[w]; if (w < wv) before += c; total += c; }
-        if (h != 0) list[before + __builtin_amdgcn_mbcnt_hi((uint32_t)(bm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm, 0u))] = h;
-        __syncthreads();
-        if (wv == 0) {
-            for (uint32_t c0 = 0; c0 < total; c0 += 64u) {
-                const uint32_t n = total - c0 < 64u ? total - c0 : 64u;
-                const uint32_t tgt = lane < n ? list[c0 + lane] : 0u;
-                uint4 row = make_uint4(0, 0, 0, 0);
-                if (db.rows && tgt) row = db.rows[tgt];
-                uint64_t rem = n >= 64u ? ~0ull : ((1ull << n) - 1ull);
-                while (rem) { // every lane: the step its own hit would make from the current result; jump to the first change
-                    uint32_t rj = tgt;
-                    uint4 roj = row;
-                    if (uf != 0 && tgt != uf && tgt != 0) {
-                        if (db.rows) rj = kid_msca_rows(tgt, row, uf, ufr, roj);
-                        else rj = kid_msca_climb(db, tgt, uf);
-                    }
-                    const uint64_t ch = __ballot(rj != uf) & rem;
-                    if (!ch) break;
-                    const int jj = __builtin_ctzll(ch);
-                    uf = (uint32_t)__builtin_amdgcn_readlane((int)rj, jj);
-                    ufr.x = (uint32_t)__builtin_amdgcn_readlane((int)roj.x, jj);
-                    ufr.y = (uint32_t)__builtin_amdgcn_readlane((int)roj.y, jj);
-                    ufr.z = (uint32_t)__builtin_amdgcn_readlane((int)roj.z, jj);
-                    ufr.w = (uint32_t)__builtin_amdgcn_readlane((int)roj.w, jj);
-                    rem &= jj >= 63 ? 0ull : ~((2ull << jj) - 1ull);
-                }
-            }
-        }
-        __syncthreads();
-        }
-      }
-      __syncthreads(); // flags[] is rewritten by the next round
-    }
-    if (threadIdx.x == 0) {
-        // the classify kernels counted the record under target 0 (they saw it without k-mers)
-        if (uf != 0) {
-            atomicAdd(&gcount[uf], 1ull);
-            atomicAdd(&gcount[0], ~0ull); // - 1
-        }
-        if (out_final) out_final[rc.read] = uf;
-    }
-}
-
 // ------------------------------------------------------------------ the hit log -> seen-bitmap
 // The classify kernels append the entry ordinals of their hits to KID_LOG_SHARDS log regions.  Setting 2.5 M random
 // bits of a 13.6 MB bitmap costs one memory-side atomic each however it is done from the classify kernel; here the
@@ -2129,6 +1918,34 @@ __global__ __launch_bounds__(1024) void kid_seenlog_scan_kernel(const KidLogArgs
     c[threadIdx.x] = part[threadIdx.x] - v;
     if (threadIdx.x == KID_LOG_WGS - 1u) a.bin_total[blockIdx.x] = part[threadIdx.x];
 }
+// inclusive scan over the 64 lanes of a wave
+template <class T>
+__device__ __forceinline__ T kid_wave_incscan(T x)
+{
+    using S = typename std::conditional<sizeof(T) == 8, unsigned long long, int>::type; // (what __shfl_up moves)
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const T y = (T)__shfl_up((S)x, (unsigned)o);
+        if ((int)(threadIdx.x & 63u) >= o) x += y;
+    }
+    return x;
+}
+// Exclusive scan over the 4 x 256 values of a workgroup of 256 threads, thread t holding values 4t .. 4t + 3 in x[]:
+// x[j] becomes the sum of everything before it; returns the sum up to and including the thread's own (thread 255: the
+// total).  wave_tot: LDS [4], the waves' totals afterwards; the caller's barrier comes before it is written again.
+template <class T>
+__device__ __forceinline__ T kid_block_exscan4(T (&x)[4], T *wave_tot)
+{
+    const uint32_t wv = threadIdx.x >> 6;
+    const T sum = x[0] + x[1] + x[2] + x[3], inc = kid_wave_incscan(sum);
+    if ((threadIdx.x & 63u) == 63u) wave_tot[wv] = inc;
+    __syncthreads();
+    T run = inc - sum;
+    for (uint32_t w = 0; w < wv; w++) run += wave_tot[w];
+#pragma unroll
+    for (int j = 0; j < 4; j++) { const T v = x[j]; x[j] = run; run += v; }
+    return run;
+}
 // where the bins start in `sorted`: exclusive scan of bin_total (<= 1024 bins) into LDS; returns the grand total
 __device__ __forceinline__ uint32_t kid_log_bin_bases(const KidLogArgs &a, uint32_t *bases /* nbins + 1 */)
 {
@@ -2137,9 +1954,7 @@ __device__ __forceinline__ uint32_t kid_log_bin_bases(const KidLogArgs &a, uint3
         uint32_t run = 0;
         for (uint32_t i0 = 0; i0 < a.nbins; i0 += 64u) {
             const uint32_t i = i0 + threadIdx.x;
-            uint32_t v = i < a.nbins ? a.bin_total[i] : 0u, x = v;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)x, o); if ((int)threadIdx.x >= o) x += y; }
+            const uint32_t v = i < a.nbins ? a.bin_total[i] : 0u, x = kid_wave_incscan(v);
             if (i < a.nbins) bases[i] = run + x - v;
             run += (uint32_t)__shfl((int)x, 63);
         }
@@ -2151,20 +1966,13 @@ __device__ __forceinline__ uint32_t kid_log_bin_bases(const KidLogArgs &a, uint3
 // exclusive scan of v[0 .. n) (n <= 4 x blockDim) into out[0 .. n), by a workgroup of 256 threads; returns the total
 __device__ __forceinline__ uint32_t kid_block_exscan(const uint32_t *v, uint32_t *out, const uint32_t n, uint32_t *wave_tot /* [5] */)
 {
-    const uint32_t t = threadIdx.x, i0 = 4u * t;
-    uint32_t x[4], sum = 0;
+    const uint32_t i0 = 4u * threadIdx.x;
+    uint32_t x[4];
 #pragma unroll
-    for (int j = 0; j < 4; j++) { x[j] = i0 + j < n ? v[i0 + j] : 0u; sum += x[j]; }
-    uint32_t inc = sum;
+    for (int j = 0; j < 4; j++) x[j] = i0 + j < n ? v[i0 + j] : 0u;
+    kid_block_exscan4(x, wave_tot);
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t y = (uint32_t)__shfl_up((int)inc, o); if ((int)(t & 63u) >= o) inc += y; }
-    if ((t & 63u) == 63u) wave_tot[t >> 6] = inc;
-    __syncthreads();
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < (t >> 6); w++) before += wave_tot[w];
-    uint32_t run = before + inc - sum;
-#pragma unroll
-    for (int j = 0; j < 4; j++) { if (i0 + j < n) out[i0 + j] = run; run += x[j]; }
+    for (int j = 0; j < 4; j++) if (i0 + j < n) out[i0 + j] = x[j];
     const uint32_t total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
     __syncthreads();
     return total;
@@ -2295,70 +2103,4 @@ __global__ void kid_or_kernel(uint32_t *dst, const uint32_t *src, uint64_t nword
 {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < nwords; i += (uint64_t)gridDim.x * blockDim.x)
         dst[i] |= src[i];
-}
-
-// ------------------------------------------------------------------ synthetic data
-__global__ void kid_synth_keys_kernel(uint64_t seed, int k, const uint64_t *cum, int32_t ntar, uint64_t j0, uint64_t n,
-                                      uint64_t *keys, uint32_t *targets)
-{
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        keys[i] = kid_synth_db_key(seed, k, j0 + i);
-        targets[i] = kid_synth_target_of(cum, ntar, j0 + i);
-    }
-}
-
-__global__ void kid_synth_reads_kernel(uint64_t db_seed, uint64_t read_seed, int k, const uint64_t *cum,
-                                       const int32_t *parent, int32_t ntar, uint64_t r0, uint64_t n, uint32_t len,
-                                       uint8_t *bases)
-{
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        kid_synth_read(db_seed, read_seed, k, cum, parent, ntar, r0 + i, len, bases + i * (uint64_t)len);
-}
-
-// ------------------------------------------------------------------ random-gather ceiling
-// INF independent 16-byte loads per lane per round from uniformly random cells
-// The same question asked the way the classify kernel asks it: random 128-byte LINES of the table (cell 0 of a line),
-// RUN consecutive lanes on one line (1: 64 distinct lines per load; 8: what the headers of neighbouring k-mers look like),
-// four loads in flight per lane, issued from inline assembly and waited for once.
-template <int RUN, int MODE = 0> // MODE bit 0: a random cell of the line instead of cell 0; bit 1: the compiler's load and wait instead of inline assembly
-__global__ __launch_bounds__(256) void kid_gather_lines_kernel(const uint4 *table, uint32_t line_mask, uint64_t rounds, uint32_t *sink)
-{
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
-    uint32_t acc = 0;
-    uint64_t ctr = wave * 0x9E3779B97F4A7C15ULL + 12345;
-    for (uint64_t r = 0; r < rounds; r++) {
-        kid_u4 a[4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}};
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            ctr += 0xD1B54A32D192ED03ULL;
-            const uint32_t line = (uint32_t)kid_fmix64(ctr ^ ((uint64_t)(lane / (uint32_t)RUN) << 48)) & line_mask;
-            const uint4 *p = table + (uint64_t)line * KID_LINE_CELLS + ((MODE & 1) ? (uint32_t)(ctr >> 40) & 7u : 0u);
-            if (MODE & 2) { const uint4 v = *p; a[u] = kid_u4{v.x, v.y, v.z, v.w}; }
-            else asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(a[u]) : "v"(p) : "memory");
-        }
-        if (!(MODE & 2)) asm volatile("s_waitcnt vmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : : "memory");
-#pragma unroll
-        for (int u = 0; u < 4; u++) acc ^= a[u].x ^ a[u].z;
-    }
-    if (acc == 0x12345678u) sink[0] = acc;
-}
-
-template <int INF>
-__global__ __launch_bounds__(256) void kid_gather_kernel(const uint4 *table, uint32_t slot_mask, uint64_t rounds, uint32_t *sink)
-{
-    const uint64_t tid = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
-    uint32_t acc = 0;
-    uint64_t ctr = tid * 0x9E3779B97F4A7C15ULL;
-    for (uint64_t r = 0; r < rounds; r++) {
-        uint4 c[INF];
-#pragma unroll
-        for (int u = 0; u < INF; u++) {
-            ctr += 0xD1B54A32D192ED03ULL;
-            c[u] = table[(uint32_t)kid_fmix64(ctr) & slot_mask];
-        }
-#pragma unroll
-        for (int u = 0; u < INF; u++) acc ^= c[u].x ^ c[u].z;
-    }
-    if (acc == 0x12345678u) sink[0] = acc; // never true in practice; keeps the loads alive
 }

@@ -15,11 +15,13 @@
 //
 // Work split: a wave takes 64 consecutive reads.  A lane takes one read of at most KID_SUPPORT_LANE_HITS hits (0 - 4 in a
 // metagenomic sample); reads with more are then taken by the whole wave one after the other: the lanes stride over the
-// hits to count, and the ordered fold jumps from change to change of the running result (the scheme of
-// kid_long_fold_kernel) -- a left fold in hit order either way.  Pure and without atomics: byte-identical across runs.
+// hits to count, and the ordered fold jumps from change to change of the running result (kid_jump_fold of
+// kid_tile.hip.h) -- a left fold in hit order either way.  Pure and without atomics: byte-identical across runs.
 // The TALLY variant also counts the batch into a sample as if it had been classified under the rule: gcount[confident]++
 // per counted read, and for reads with confident > 0 the seen bit of every hit with target > 1 (plain global atomics).
 #pragma once
+#include "kid_tile.hip.h"
+#include "kid_hits.hip.h"
 
 #define KID_SUPPORT_LANE_HITS 8u // a read with more hits than this is taken by the whole wave
 
@@ -141,26 +143,7 @@ __device__ __forceinline__ void kid_support_wave(const KidDevDb &db, const KidHi
         const uint32_t tgt = lane < n ? kid_support_target(db, h[(uint64_t)c0 + lane].target) : 0u;
         uint4 row = make_uint4(0, 0, 0, 0);
         if (ROWS && tgt) row = db.rows[tgt];
-        uint64_t rem = n >= 64u ? ~0ull : ((1ull << n) - 1ull);
-        while (rem) { // every lane: the step its own hit would make from the current result; jump to the first change
-            uint32_t rj = tgt;
-            uint4 roj = row;
-            if (uf != 0 && tgt != uf && tgt != 0) {
-                if (ROWS) rj = kid_msca_rows(tgt, row, uf, ufr, roj);
-                else rj = kid_msca_climb(db, tgt, uf);
-            }
-            const uint64_t ch = __ballot(rj != uf) & rem;
-            if (!ch) break;
-            const int jj = __builtin_ctzll(ch);
-            uf = (uint32_t)__builtin_amdgcn_readlane((int)rj, jj);
-            if (ROWS) {
-                ufr.x = (uint32_t)__builtin_amdgcn_readlane((int)roj.x, jj);
-                ufr.y = (uint32_t)__builtin_amdgcn_readlane((int)roj.y, jj);
-                ufr.z = (uint32_t)__builtin_amdgcn_readlane((int)roj.z, jj);
-                ufr.w = (uint32_t)__builtin_amdgcn_readlane((int)roj.w, jj);
-            }
-            rem &= jj >= 63 ? 0ull : ~((2ull << jj) - 1ull);
-        }
+        kid_jump_fold<ROWS>(db, tgt, row, n >= 64u ? ~0ull : ((1ull << n) - 1ull), uf, ufr);
     }
     if (ROWS) {
         uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
