@@ -117,6 +117,10 @@ int kid_sample_begin(kid_db *db, kid_sample **out);
 #define KID_OPT_LONG_RECORD_KMERS 2 /* value: records of more k-mers than this (default 65536; 0 = never) are classified by
                                       the long-record kernels -- every k-mer looked up by a lane of its own, one ordered
                                       fold per record -- instead of by one wavefront (FASTA contigs, kmer_read_vf6.cpp:803-861) */
+#define KID_OPT_MIN_BASE_QUALITY 3 /* value Q in 0..93 (KID_ERR_ARG beyond), 0 = off (the default): the FASTQ blocks handed to
+                                     kid_classify_fastq_async after the call have every base of quality below Q read as 'N'
+                                     ("mask low-quality bases" below).  Like the other options it stays until it is set again;
+                                     kid_sample_reset does not change it */
 int kid_sample_set_option(kid_sample *s, int option, int value);
 int kid_sample_reset(kid_sample *s);
 void kid_sample_destroy(kid_sample *s);
@@ -192,6 +196,45 @@ int kid_classify_fixed_device(kid_sample *s, const void *d_bases, uint32_t read_
  * keep[r] = 1 if the reference would call process_read (stop-start >= k).        */
 int kid_trim_batch(kid_db *db, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads,
                    int32_t *start, int32_t *stop, uint8_t *keep);
+
+/* ---- mask low-quality bases -----------------------------------------------------------
+ * process_qual lets the quality line decide only how much of each END of a read is cut off: a Q2 base in the middle of a
+ * read takes part in 30 k-mers like any other.  With a minimum base quality Q (1..93; 0 = off, nothing runs) and
+ * T = Q + 33, base i (0 <= i < seq_len) of a FASTQ record with qual_len >= seq_len is MASKED when its quality byte, read
+ * as signed char exactly as process_qual reads it, is < T -- so bytes >= 128 are masked.  Quality bytes beyond seq_len are
+ * ignored; the whole sequence line is covered, not only the trimmed range; a masked base behaves in every respect like a
+ * byte that is not ACGTacgt.  The defining property: with the option on, every output of a call (final targets, start /
+ * stop, gcount, ucount, seen bits, hits and their offsets, n_kmers, support records, tallies) is what the same call returns
+ * with the option off on a text whose masked sequence bytes were replaced by 'N'.  start / stop do not change (trimming
+ * reads the quality line alone), pos stays counted from the first byte of the read, n_kmers shrinks, and the support
+ * rule's n is that smaller n_kmers.
+ * One streaming kernel overwrites the masked bytes in the library's DEVICE copy of the text, in front of the kernels
+ * that read it; the caller's text is never modified.  Because it writes in place, the FASTQ forms refuse, while an
+ * option is > 0, a block whose lines are not in ascending order without overlap (KID_ERR_ARG): seq_off + seq_len <=
+ * qual_off and qual_off + qual_len <= the next record's seq_off, as every indexer of a real file leaves them.
+ *   KID_OPT_MIN_BASE_QUALITY     the sample's option, above: kid_classify_fastq_async (the mask kernel runs on the stream
+ *                                of the prepare kernel, behind the upload of the block and in front of its classify kernels)
+ *   KID_DB_OPT_MIN_BASE_QUALITY  the database's: kid_db_read_hits_fastq and kid_db_read_support_fastq, whose staged text is
+ *                                masked in front of the hit pass (outside the interval kid_db_read_hits_time reports).  It
+ *                                obeys the one-call-at-a-time rule of a kid_db and is NOT copied by kid_db_replicate.
+ * The offsets and device forms of those calls have no quality text and are unaffected: mask their text first with the
+ * two calls below.                                                                                                  */
+#define KID_DB_OPT_MIN_BASE_QUALITY 1
+int kid_db_set_option(kid_db *db, int option, int value);
+/* bases masked in the sample's FASTQ blocks since kid_sample_begin / kid_sample_reset (synchronises).  Records with
+ * qual_len < seq_len are not masked and not counted.  kid_sample_stats keeps its four fields.                       */
+int kid_sample_masked_bases(kid_sample *s, uint64_t *out);
+/* The companion of kid_trim_batch, host buffers: quals laid out like bases.  out_bases (laid out like bases, may equal
+ * bases) receives the text of the reads with the masked bases replaced by 'N'; *n_masked (nullable) their number.
+ * min_base_quality = 0 copies the text and reports 0; outside 0..93: KID_ERR_ARG.                                   */
+int kid_mask_batch(kid_db *db, const uint8_t *bases, const uint8_t *quals, const uint64_t *offsets, uint64_t n_reads,
+                   int min_base_quality, uint8_t *out_bases, uint64_t *n_masked);
+/* In place on text resident in HBM, asynchronous on `stream`: use it in front of kid_classify_batch_device /
+ * kid_db_read_hits_device on the same stream.  d_offsets: uint64[n_reads + 1], reads back to back (the bytes
+ * offsets[0] .. offsets[n_reads] of d_bases are masked by the same bytes of d_quals); no alignment is asked of either.
+ * d_n_masked: nullable; one uint64 that the number of bases masked is ADDED to (it is not reset).                    */
+int kid_mask_batch_device(kid_db *db, void *d_bases, const void *d_quals, const void *d_offsets, uint64_t n_reads,
+                          int min_base_quality, void *d_n_masked, void *stream);
 
 /* ---- every read's k-mer hits ------------------------------------------------------
  * What process_read folds (newkmer_10nx.cpp:526-595), handed out instead of folded: for every read, in read-position

@@ -58,6 +58,10 @@ PROTOTYPES = {
                                             C.c_void_p, C.c_void_p]),
     "kid_classify_fixed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
     "kid_trim_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kid_db_set_option": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "kid_sample_masked_bases": (C.c_int, [C.c_void_p, c_u64p]),
+    "kid_mask_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, c_u64p]),
+    "kid_mask_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
     "kid_db_read_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_uint64, c_u64p]),
     "kid_db_read_hits_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -113,6 +117,8 @@ PROTOTYPES = {
 
 KID_OPT_INPUTS_READY = 1
 KID_OPT_LONG_RECORD_KMERS = 2
+KID_OPT_MIN_BASE_QUALITY = 3
+KID_DB_OPT_MIN_BASE_QUALITY = 1
 KID_FLAG_U_IS_T = 1
 KID_FLAG_HOST_BUILD = 2
 KID_FLAG_REF_GEOMETRY = 4

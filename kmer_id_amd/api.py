@@ -165,6 +165,29 @@ class KmerDB:
         check(self._lib.kid_trim_batch(self._h, _ptr(quals), _ptr(offsets), n, _ptr(start), _ptr(stop), _ptr(keep)))
         return start, stop, keep
 
+    def set_option(self, option, value):
+        """kid_db_set_option, e.g. (KID_DB_OPT_MIN_BASE_QUALITY, Q): read_hits_fastq and read_support_fastq read every
+        base of quality below Q as 'N'."""
+        check(self._lib.kid_db_set_option(self._h, option, value))
+
+    def mask_low_quality(self, bases, quals, offsets, q):
+        """Bases whose quality byte (quals laid out like bases), read as signed char, is below q + 33 become 'N'
+        (kid_mask_batch) -> (masked copy of bases, number of bases masked).  q = 0: the text as it is and 0."""
+        bases = _as(bases, np.uint8)
+        quals = _as(quals, np.uint8)
+        offsets = _as(offsets, np.uint64)
+        out = bases.copy()
+        n_masked = C.c_uint64(0)
+        check(self._lib.kid_mask_batch(self._h, _ptr(bases), _ptr(quals), _ptr(offsets), offsets.size - 1, q, _ptr(out),
+                                       C.byref(n_masked)))
+        return out, n_masked.value
+
+    def mask_low_quality_device(self, d_bases, d_quals, d_offsets, n_reads, q, d_n_masked=0, stream=0):
+        """The same in place on text resident in HBM (raw pointers), asynchronous on `stream`: kid_mask_batch_device.
+        d_n_masked: one uint64 in HBM that the number of bases masked is added to (or 0)."""
+        check(self._lib.kid_mask_batch_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_quals), C.c_void_p(d_offsets), n_reads, q,
+                                              C.c_void_p(d_n_masked or None), C.c_void_p(stream or None)))
+
     def _read_hits(self, call, n):
         """the sizing call, then the call that fills a buffer of exactly that size"""
         offsets = np.empty(n + 1, np.uint64)
@@ -292,6 +315,12 @@ class Sample:
 
     def set_option(self, option, value=1):
         check(self._lib.kid_sample_set_option(self._h, option, value))
+
+    def masked_bases(self):
+        """-> bases masked under KID_OPT_MIN_BASE_QUALITY since the sample began or was last reset"""
+        n = C.c_uint64(0)
+        check(self._lib.kid_sample_masked_bases(self._h, C.byref(n)))
+        return n.value
 
     def classify(self, bases, offsets, start=None, stop=None, want_final=True):
         """process_read for a batch held in host memory; returns final_targ per read."""

@@ -18,8 +18,10 @@
 #include "kid_long.hip.h"
 #include "kid_hits.hip.h"
 #include "kid_support.hip.h"
+#include "kid_mask.hip.h"
 #include "kid_api_core.h"
 #include "kid_api_db.h"
+#include "kid_api_mask.h"
 #include "kid_api_hits.h"
 #include "kid_api_builder.h"
 #include "kid_api_bench.h"
@@ -58,6 +60,8 @@ struct kid_sample {
     Scratch sets[NSET];
     uint32_t next_set = 0;
     bool inputs_ready = false;
+    int min_base_quality = 0; // KID_OPT_MIN_BASE_QUALITY: FASTQ blocks have their low-quality bases masked behind the upload (kid_mask.hip.h)
+    KidDevBuf masked;         // unsigned long long: bases masked since the last reset
     int64_t long_kmers = 65536; // records of more k-mers than this take the long-record kernels (KID_OPT_LONG_RECORD_KMERS)
     // fixed-layout batches have no descriptors and no prepare kernel: one argument block of their own, rewritten (a
     // one-thread kernel in stream order) only when a launch differs from what the block holds
@@ -126,6 +130,7 @@ extern "C" int kid_sample_reset(kid_sample *s)
     KID_HIP(hipMemset(s->gcount.p, 0, nt * 8));
     KID_HIP(hipMemset(s->ucount.p, 0, nt * 8));
     KID_HIP(hipMemset(s->stats.p, 0, 256));
+    KID_HIP(hipMemset(s->masked.p, 0, 8));
     {   // device-clock stamps of a launch: [30] first workgroup start (min), [31] last end (max); see kid_classify_kernel
         const unsigned long long never = ~0ull;
         KID_HIP(hipMemcpy(s->stats_p() + 30, &never, 8, hipMemcpyHostToDevice));
@@ -165,6 +170,7 @@ extern "C" int kid_sample_begin(kid_db *db, kid_sample **out)
     KID_HIP(s->gcount.alloc(nt * 8));
     KID_HIP(s->ucount.alloc(nt * 8));
     KID_HIP(s->stats.alloc(256));
+    KID_HIP(s->masked.alloc(8));
     KID_HIP(s->seen.alloc(s->seen_words * 4));
     KID_HIP(s->stream.create());
     // the hit log: for the minimizer-localised table (its resolver is the one that logs), bitmaps of up to 1024 pieces
@@ -497,6 +503,11 @@ extern "C" int kid_sample_set_option(kid_sample *s, int option, int value)
         if (value < 0) return kid_fail(KID_ERR_ARG, "KID_OPT_LONG_RECORD_KMERS: negative threshold");
         s->long_kmers = value;
         return KID_OK;
+    case KID_OPT_MIN_BASE_QUALITY: {
+        int rc = kid_mask_check_q(value);
+        if (rc == KID_OK) s->min_base_quality = value;
+        return rc;
+    }
     default: return kid_fail(KID_ERR_ARG, "unknown option %d", option);
     }
 }
@@ -739,7 +750,9 @@ extern "C" int kid_classify_fastq_async(kid_sample *s, const uint8_t *text, uint
     if (ticket) *ticket = 0;
     if (n_reads == 0) return KID_OK;
     if (!text || !recs || !out_start || !out_stop) return kid_fail(KID_ERR_ARG, "null argument");
-    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, 0, nullptr);
+    const int mask_q = s->min_base_quality;
+    uint32_t longest = 0;
+    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, 0, nullptr, mask_q > 0, &longest);
     if (rc != KID_OK) return rc;
     rc = kid_use_device(s->db->device);
     if (rc != KID_OK) return rc;
@@ -753,6 +766,14 @@ extern "C" int kid_classify_fastq_async(kid_sample *s, const uint8_t *text, uint
     rc = kid_upload_text(sl.bases, text, text_nbytes, cs);
     if (rc != KID_OK) return rc;
     KID_HIP(hipMemcpyAsync(sl.recs.p, recs, n_reads * sizeof(KidFastqRec), hipMemcpyHostToDevice, cs));
+    // low-quality bases -> 'N' in the slot's copy of the text: on the copy stream, behind the upload and in front of the
+    // prepare kernel, whose event the batch's classify kernels wait for (the prepare kernel reads quality bytes alone,
+    // which the mask kernel does not write)
+    if (mask_q > 0) {
+        rc = kid_mask_launch_fastq(s->db, sl.bases.as<uint8_t>(), sl.recs.as<KidFastqRec>(), n_reads, longest, mask_q,
+                                   s->masked.as<unsigned long long>(), cs);
+        if (rc != KID_OK) return rc;
+    }
     KidBatch b{};
     b.bases = sl.bases.as<uint8_t>();
     b.start = sl.start.as<int32_t>(); // (outputs of the prepare kernel here)
@@ -910,6 +931,16 @@ extern "C" int kid_sample_stats(kid_sample *s, uint64_t out[4])
     unsigned long long st[8];
     KID_HIP(hipMemcpy(st, s->stats.p, 64, hipMemcpyDeviceToHost));
     for (int i = 0; i < 4; i++) out[i] = st[i];
+    return KID_OK;
+}
+
+extern "C" int kid_sample_masked_bases(kid_sample *s, uint64_t *out)
+{
+    if (!s || !out) return kid_fail(KID_ERR_ARG, "null argument");
+    int rc = kid_use_device(s->db->device);
+    if (rc != KID_OK) return rc;
+    KID_HIP(hipDeviceSynchronize());
+    KID_HIP(hipMemcpy(out, s->masked.p, 8, hipMemcpyDeviceToHost));
     return KID_OK;
 }
 

@@ -108,17 +108,30 @@ static int kid_check_offsets_batch(const uint64_t *offsets, const int32_t *start
 }
 
 // ... of a block of FASTQ text with the host's line index.  *max_tiles (null: not wanted) is added up over the records:
-// they may share or overlap sequence bytes.
-static int kid_check_fastq_block(const kid_fastq_rec *recs, uint64_t n_reads, uint64_t text_nbytes, uint32_t tile, uint64_t *max_tiles)
+// they may share or overlap sequence bytes -- unless `masking` (a min_base_quality option is on: low-quality bases are
+// overwritten in the device copy of the text, kid_mask.hip.h): then the lines must lie in ascending order without
+// overlap, sequence, quality, next sequence, .., as every indexer of a real file leaves them, so that no byte one record
+// writes is a byte any record's decision reads.  *longest (with `masking`): the longest sequence line.
+static int kid_check_fastq_block(const kid_fastq_rec *recs, uint64_t n_reads, uint64_t text_nbytes, uint32_t tile, uint64_t *max_tiles,
+                                 bool masking = false, uint32_t *longest = nullptr)
 {
     if (text_nbytes >= 0xFFFFFFFFull) return kid_fail(KID_ERR_ARG, "a FASTQ block of 4 GiB or more");
-    uint64_t mt = 0;
+    uint64_t mt = 0, free_from = 0;
+    uint32_t lg = 0;
     for (uint64_t r = 0; r < n_reads; r++) {
         if ((uint64_t)recs[r].seq_off + recs[r].seq_len > text_nbytes || (uint64_t)recs[r].qual_off + recs[r].qual_len > text_nbytes)
             return kid_fail(KID_ERR_ARG, "record %llu lies outside the text block", (unsigned long long)r);
         if (max_tiles) mt += recs[r].seq_len / tile + 1;
+        if (masking) {
+            if (recs[r].seq_off < free_from || (uint64_t)recs[r].seq_off + recs[r].seq_len > recs[r].qual_off)
+                return kid_fail(KID_ERR_ARG, "record %llu: with min_base_quality on, the lines of a block must be in ascending order and "
+                                             "must not overlap", (unsigned long long)r);
+            free_from = (uint64_t)recs[r].qual_off + recs[r].qual_len;
+            if (recs[r].seq_len > lg) lg = recs[r].seq_len;
+        }
     }
     if (max_tiles) *max_tiles = mt;
+    if (longest) *longest = lg;
     return KID_OK;
 }
 

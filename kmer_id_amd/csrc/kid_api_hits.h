@@ -4,6 +4,7 @@
 // input form) and the hit pass into the library's own buffers (kid_hits_host_pass).
 #pragma once
 #include "kid_api_db.h"
+#include "kid_api_mask.h"
 #include "kid_hits.hip.h"
 
 // ---------------------------------------------------------------- every read's k-mer hits (kid_hits.hip.h)
@@ -238,11 +239,13 @@ static int kid_hits_check_offsets(const kid_db *db, const uint8_t *bases, const 
     return kid_use_device(db->device);
 }
 
+// (called with the database's lock held: db->min_base_quality, under which the block's lines must be in order; *longest:
+// the longest sequence line, for the mask kernel)
 static int kid_hits_check_fastq(const kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
-                                uint64_t *max_tiles)
+                                uint64_t *max_tiles, uint32_t *longest)
 {
     if (!text || !recs) return kid_fail(KID_ERR_ARG, "null argument");
-    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, KID_HITS_TILE, max_tiles);
+    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, KID_HITS_TILE, max_tiles, db->min_base_quality > 0, longest);
     if (rc != KID_OK) return rc;
     return kid_use_device(db->device);
 }
@@ -277,8 +280,9 @@ static int kid_hits_stage_offsets(KidHitsState *h, const uint8_t *bases, const u
     return KID_OK;
 }
 
-static int kid_hits_stage_fastq(KidHitsState *h, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
-                                KidBatch *b, const KidFastqRec **d_recs)
+// (under KID_DB_OPT_MIN_BASE_QUALITY the staged text is masked here, in front of the hit pass: the caller's is not touched)
+static int kid_hits_stage_fastq(const kid_db *db, KidHitsState *h, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs,
+                                uint64_t n_reads, uint32_t longest, KidBatch *b, const KidFastqRec **d_recs)
 {
     int rc = kid_hits_stage_text(h, text, text_nbytes, b);
     if (rc != KID_OK) return rc;
@@ -290,6 +294,8 @@ static int kid_hits_stage_fastq(KidHitsState *h, const uint8_t *text, uint64_t t
     b->stop = h->trim_stop.as<int32_t>();
     b->n = n_reads;
     *d_recs = h->in_recs.as<KidFastqRec>();
+    if (db->min_base_quality > 0)
+        return kid_mask_launch_fastq(db, h->in_bases.as<uint8_t>(), *d_recs, n_reads, longest, db->min_base_quality, nullptr, 0);
     return KID_OK;
 }
 
@@ -319,14 +325,15 @@ extern "C" int kid_db_read_hits_fastq(kid_db *db, const uint8_t *text, uint64_t 
     if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
     if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
     uint64_t max_tiles = 0;
-    int rc = kid_hits_check_fastq(db, text, text_nbytes, recs, n_reads, &max_tiles);
-    if (rc != KID_OK) return rc;
+    uint32_t longest = 0;
     std::lock_guard<std::mutex> lock(db->hits_mu);
+    int rc = kid_hits_check_fastq(db, text, text_nbytes, recs, n_reads, &max_tiles, &longest);
+    if (rc != KID_OK) return rc;
     KidHitsState *h = nullptr;
     KidBatch b{};
     const KidFastqRec *d_recs = nullptr;
     if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
-    if ((rc = kid_hits_stage_fastq(h, text, text_nbytes, recs, n_reads, &b, &d_recs)) != KID_OK) return rc;
+    if ((rc = kid_hits_stage_fastq(db, h, text, text_nbytes, recs, n_reads, longest, &b, &d_recs)) != KID_OK) return rc;
     return kid_hits_host_run(db, h, b, d_recs, max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
 }
 

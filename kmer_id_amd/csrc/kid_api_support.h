@@ -107,13 +107,14 @@ extern "C" int kid_db_read_support_fastq(kid_db *db, const uint8_t *text, uint64
     if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
     if (n_reads == 0) return KID_OK;
     uint64_t max_tiles = 0;
-    if ((rc = kid_hits_check_fastq(db, text, text_nbytes, recs, n_reads, &max_tiles)) != KID_OK) return rc;
+    uint32_t longest = 0;
     std::lock_guard<std::mutex> lock(db->hits_mu);
+    if ((rc = kid_hits_check_fastq(db, text, text_nbytes, recs, n_reads, &max_tiles, &longest)) != KID_OK) return rc;
     KidHitsState *h = nullptr;
     KidBatch b{};
     const KidFastqRec *d_recs = nullptr;
     if ((rc = kid_support_state(db, &h)) != KID_OK) return rc;
-    if ((rc = kid_hits_stage_fastq(h, text, text_nbytes, recs, n_reads, &b, &d_recs)) != KID_OK) return rc;
+    if ((rc = kid_hits_stage_fastq(db, h, text, text_nbytes, recs, n_reads, longest, &b, &d_recs)) != KID_OK) return rc;
     return kid_support_host_run(db, h, b, d_recs, max_tiles, KidSupportRule{min_hits, min_permille}, out, tally);
 }
 

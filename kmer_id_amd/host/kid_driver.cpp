@@ -91,6 +91,7 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
     for (kid_db *d : e->dbs) e->samples.push_back(begin_sample_or_die(d));
     e->sample = e->samples[0];
     engine_support(*e, owner.support);
+    engine_base_quality(*e, owner.min_base_quality);
     return e;
 }
 
@@ -99,6 +100,22 @@ void engine_support(Engine &e, const SupportRule &rule)
     e.support = rule;
     if (!rule.on) return;
     for (kid_db *d : e.dbs) e.confident.push_back(begin_sample_or_die(d));
+}
+
+void engine_base_quality(Engine &e, int q)
+{
+    e.min_base_quality = q;
+    if (q == 0) return;
+    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
+        for (kid_sample *s : *list) {
+            int rc = kid_sample_set_option(s, KID_OPT_MIN_BASE_QUALITY, q);
+            if (rc != KID_OK) die_kid(rc);
+        }
+    if (!e.owns_dbs) return; // (a worker: its owner has set it)
+    for (kid_db *d : e.dbs) {
+        int rc = kid_db_set_option(d, KID_DB_OPT_MIN_BASE_QUALITY, q);
+        if (rc != KID_OK) die_kid(rc);
+    }
 }
 
 std::vector<int> parse_devices(int device, const std::string &list)
@@ -342,6 +359,26 @@ SupportRule support_option(int argc, char **argv, const char *prog)
     return r;
 }
 
+int base_quality_option(int argc, char **argv, const char *prog)
+{
+    int q = 0;
+    for (int i = 1; i < argc; i++) {
+        if (strcmp(argv[i], "--min-base-quality") != 0) continue;
+        const char *opt = argv[i];
+        if (i + 1 >= argc) support_usage(prog, opt, "needs a value");
+        const char *v = argv[++i];
+        unsigned whole = 0;
+        size_t at = 0;
+        for (; v[at] >= '0' && v[at] <= '9'; at++) {
+            whole = whole * 10 + (unsigned)(v[at] - '0');
+            if (whole > 93u) support_usage(prog, opt, "takes a quality from 0 to 93");
+        }
+        if (at == 0 || v[at] != 0) support_usage(prog, opt, "takes a quality from 0 to 93");
+        q = (int)whole;
+    }
+    return q;
+}
+
 std::string sibling_path_for(const std::string &result_path, const char *word)
 {
     std::string p = result_path;
@@ -373,7 +410,8 @@ void HitsWriter::close()
 
 // The hit lines of one classified batch (its start / stop / final targets are known): kid_db_read_hits* on the batch's
 // device -- the sizing call, then the call that fills a buffer of that size.
-static void hit_lines_of(kid_db *db, const ReadBatch &b, const std::vector<uint32_t> &final_targ, int k, std::string &out)
+// (bases: the text of a batch of reads that was classified -- the batch's own, or its masked copy under --min-base-quality)
+static void hit_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, const std::vector<uint32_t> &final_targ, int k, std::string &out)
 {
     const size_t nr = b.size();
     std::vector<uint64_t> off(nr + 1);
@@ -383,7 +421,7 @@ static void hit_lines_of(kid_db *db, const ReadBatch &b, const std::vector<uint3
     auto call = [&](kid_hit *h, uint64_t cap) {
         int rc = b.fq ? kid_db_read_hits_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, off.data(),
                                                nk.data(), h, cap, &total)
-                      : kid_db_read_hits(db, b.bases.data(), b.offsets.data(), b.start.data(), b.stop.data(), nr, off.data(), nk.data(),
+                      : kid_db_read_hits(db, bases, b.offsets.data(), b.start.data(), b.stop.data(), nr, off.data(), nk.data(),
                                          h, cap, &total);
         if (rc != KID_OK) die_kid(rc);
     };
@@ -410,12 +448,12 @@ static void hit_lines_of(kid_db *db, const ReadBatch &b, const std::vector<uint3
 }
 
 // The support pass of one classified batch on its device: nothing comes back, the batch is tallied into `tally` under the rule
-static void tally_batch(kid_db *db, kid_sample *tally, const SupportRule &rule, const ReadBatch &b)
+static void tally_batch(kid_db *db, kid_sample *tally, const SupportRule &rule, const ReadBatch &b, const uint8_t *bases)
 {
     const size_t nr = b.size();
     int rc = b.fq ? kid_db_read_support_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, rule.min_hits,
                                               rule.min_permille, nullptr, tally)
-                  : kid_db_read_support(db, b.bases.data(), b.offsets.data(), b.start.data(), b.stop.data(), nr, rule.min_hits,
+                  : kid_db_read_support(db, bases, b.offsets.data(), b.start.data(), b.stop.data(), nr, rule.min_hits,
                                         rule.min_permille, nullptr, tally);
     if (rc != KID_OK) die_kid(rc);
 }
@@ -430,6 +468,11 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
     struct InFlight {
         std::unique_ptr<ReadBatch> batch;
         std::vector<uint32_t> final_targ;
+        // --min-base-quality on a batch of reads with their qualities (a plain FASTQ file, tokenised and trimmed on the
+        // host): the copy of the text with the low-quality bases masked (kid_mask_batch) that is classified in its place --
+        // the read saver prints the batch's own text
+        std::vector<uint8_t> masked;
+        const uint8_t *bases() const { return masked.empty() ? batch->bases.data() : masked.data(); }
         HostBuf io;
         uint64_t ticket = 0;
         kid_sample *sample = nullptr;
@@ -451,10 +494,10 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         handed[f.file] += saver.add_batch_of(saver_file + f.file, *f.batch, f.final_targ, e.k);
         if (hits && hits->on()) {
             lines.clear();
-            hit_lines_of(f.db, *f.batch, f.final_targ, e.k, lines);
+            hit_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.k, lines);
             hits->add(saver_file + f.file, lines);
         }
-        if (f.confident) tally_batch(f.db, f.confident, e.support, *f.batch);
+        if (f.confident) tally_batch(f.db, f.confident, e.support, *f.batch, f.bases());
         q.pop_front();
     };
     try {
@@ -477,8 +520,15 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
                 rc = submit_fastq_block(f.sample, *f.batch, f.io, &f.ticket);
             } else {
                 f.final_targ.resize(nr);
-                rc = kid_classify_batch_async(f.sample, f.batch->bases.data(), f.batch->offsets.data(), f.batch->start.data(),
-                                              f.batch->stop.data(), nr, f.final_targ.data(), &f.ticket);
+                rc = KID_OK;
+                if (e.min_base_quality > 0 && !f.batch->quals.empty()) {
+                    f.masked.resize(f.batch->bases.size());
+                    rc = kid_mask_batch(f.db, f.batch->bases.data(), f.batch->quals.data(), f.batch->offsets.data(), nr, e.min_base_quality,
+                                        f.masked.data(), nullptr);
+                }
+                if (rc == KID_OK)
+                    rc = kid_classify_batch_async(f.sample, f.bases(), f.batch->offsets.data(), f.batch->start.data(),
+                                                  f.batch->stop.data(), nr, f.final_targ.data(), &f.ticket);
             }
             e.submit_s += seconds_since(t_sub);
             if (rc != KID_OK) die_kid(rc);
@@ -536,6 +586,7 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
     }
     o.hits = hits_option(argc, argv);
     o.support = support_option(argc, argv, argv[0]);
+    o.min_base_quality = base_quality_option(argc, argv, argv[0]);
     return o;
 }
 

@@ -28,6 +28,15 @@ SupportRule support_option(int argc, char **argv, const char *prog);
 // The file beside a result file: its path with the last "result" replaced by `word` (".../x_result.txt", "confident"
 // -> ".../x_confident.txt"; "hits" names the hits file of --hits, below)
 std::string sibling_path_for(const std::string &result_path, const char *word);
+// --min-base-quality Q (shared by the three front-ends): the bases of FASTQ input whose quality is below Q are read as
+// 'N' by everything that runs on the GPU (KID_OPT_MIN_BASE_QUALITY / KID_DB_OPT_MIN_BASE_QUALITY): the result, hits and
+// confident files and stdout are what they would be on input files with those bases replaced by N; the reads file prints
+// the sequences as they are in the input.  FASTQ.gz blocks are masked by the library behind their upload; the batches of a
+// plain FASTQ file carry their qualities (ReadBatch::quals) and are masked through kid_mask_batch before they are
+// classified (run_files).  FASTA input has no qualities: the option is accepted and changes nothing.
+// The one place that reads it.  Q: digits only, 0..93 (0 = off, the default); anything else (a missing value too) is a
+// usage error: a message on stderr and exit code 2.  Checked, then ignored, with --dry-run.
+int base_quality_option(int argc, char **argv, const char *prog);
 
 struct Engine {
     kid_db *db = nullptr;         // the database on the first device
@@ -41,6 +50,7 @@ struct Engine {
     // --min-hits / --confidence: the rule and one tallied sample per device (engine_support); empty without
     SupportRule support;
     std::vector<kid_sample *> confident;
+    int min_base_quality = 0; // --min-base-quality (engine_base_quality)
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -74,6 +84,9 @@ bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &pare
 // Switch the confident result file on (rule.on) for an engine that is open: one more sample per device, reset, closed and
 // destroyed with the others.  A worker of engine_worker() inherits it.
 void engine_support(Engine &e, const SupportRule &rule);
+// --min-base-quality Q for an engine that is open, behind engine_support: the option of every sample, the tallied ones
+// included, and of every replica of the database.  A worker of engine_worker() inherits it for its samples.
+void engine_base_quality(Engine &e, int q);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
 std::vector<int> parse_devices(int device, const std::string &list);
 // newkmer_10nx.cpp:1017-1019 on every replica
@@ -147,6 +160,7 @@ struct ReaderOptions {
     std::string db_cache;    // --db-cache FILE: binary cache of the parsed database
     bool hits = false;       // --hits: a hits file beside the result file (ignored with --dry-run)
     SupportRule support;     // --min-hits / --confidence: a confident result file beside the result file (ignored with --dry-run)
+    int min_base_quality = 0; // --min-base-quality: FASTQ bases below it are read as N (ignored with --dry-run)
 };
 ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 

@@ -568,6 +568,7 @@ bool PlainTokenStream::fill(ReadBatch &out, size_t max_reads, size_t max_bases)
                     int st, sp;
                     if (trim_read(seq_, lseq_, k_, st, sp)) {
                         out.bases.insert(out.bases.end(), seq_.begin(), seq_.end());
+                        out.quals.insert(out.quals.end(), lseq_.begin(), lseq_.begin() + (std::ptrdiff_t)seq_.size()); // (trim_read: not shorter)
                         out.offsets.push_back(out.bases.size());
                         out.start.push_back(st);
                         out.stop.push_back(sp);

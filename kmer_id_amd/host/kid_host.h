@@ -135,9 +135,10 @@ struct ReadBatch {
     std::vector<uint64_t> offsets;  // n+1
     std::vector<int32_t> start, stop; // process_qual's range per read (FASTQ blocks: filled in by the GPU)
     std::vector<std::string> acc;   // header lines (with the leading '@'), for _reads.txt
+    std::vector<uint8_t> quals;     // plain FASTQ files: the quality of every base, laid out like `bases` (--min-base-quality); else empty
     std::unique_ptr<FastqBlock> fq; // set: the batch is a FASTQ text block, the vectors above are not used (start / stop receive results)
     size_t size() const { return fq ? fq->recs.size() : start.size(); }
-    void clear() { bases.clear(); offsets.assign(1, 0); start.clear(); stop.clear(); acc.clear(); fq.reset(); }
+    void clear() { bases.clear(); offsets.assign(1, 0); start.clear(); stop.clear(); acc.clear(); quals.clear(); fq.reset(); }
 };
 
 // A file of reads delivered as batches.  fill() clears `out`, appends reads until max_reads reads or

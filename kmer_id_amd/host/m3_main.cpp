@@ -7,6 +7,7 @@
 // built sequentially on the host with the reference's exact cell geometry (results depend on it).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
 //   --min-hits N  --confidence F   also write DIR/confident.txt: the reads called by k-mer support (kid_driver.h)
+//   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N (kid_driver.h)
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -64,6 +65,7 @@ int main(int argc, char **argv)
         eng.batch_reads = opt.batch_reads;
         if (!engine_open(eng, ps, parent, k, opt.log2_slots, /*MAXREPROBE*/ 16, 0, parse_devices(opt.device, opt.device_list))) return 1;
         engine_support(eng, opt.support);
+        engine_base_quality(eng, opt.min_base_quality);
         ps = ProbeSet();
 
         if (r1name.empty()) throw Fatal{134, "no -f1 given (std::out_of_range in the reference, :1080)"};

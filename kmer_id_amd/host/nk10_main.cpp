@@ -19,6 +19,9 @@
 //   --min-hits N  --confidence F   also write <prefix>_confident.txt, the result file of the reads called by k-mer support:
 //                    a read counts under the first node of its target's root path whose clade holds at least N of its k-mer
 //                    hits and F (a decimal in [0, 1], three fractional digits) of its k-mers, under 0 if none does (kid_driver.h)
+//   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
+//                    what they would be on FASTQ files with those bases replaced by N; <prefix>_reads.txt prints the
+//                    sequences as they are (kid_driver.h)
 //   --timing         one JSON line on stderr when the run ends: seconds of the start-up phases (probes inflate / parse,
 //                    cache read / write, upload + table build on the GPU, first batch classified) and of the read files
 //   --dry-run FILE   host stages only (no GPU): parse the DB text files and the files a run would read (FASTQ, or
@@ -86,6 +89,7 @@ int main(int argc, char **argv)
         else if (a == "--samples-in-flight") in_flight = atoi(val("--samples-in-flight"));
         else if (a == "--hits") {} // (hits_option below: the one place that reads it, shared with the sibling programs)
         else if (a == "--min-hits" || a == "--confidence") { if (i + 1 < argc) i++; } // (support_option below, likewise)
+        else if (a == "--min-base-quality") { if (i + 1 < argc) i++; } // (base_quality_option below, likewise)
         else if (dname.empty()) dname = a;
         else { std::cerr << "nk10: unexpected argument " << a << "\n"; return 2; }
     }
@@ -95,6 +99,7 @@ int main(int argc, char **argv)
     }
     const bool want_hits = hits_option(argc, argv); // <prefix>_hits.txt beside <prefix>_result.txt (ignored with --dry-run)
     const SupportRule support = support_option(argc, argv, "nk10"); // <prefix>_confident.txt likewise
+    const int min_base_quality = base_quality_option(argc, argv, "nk10"); // (checked, then ignored, with --dry-run and --fasta)
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
     if (batch_reads < 1) batch_reads = 1;
     if (threads < 1) threads = 1;
@@ -186,6 +191,7 @@ int main(int argc, char **argv)
         if (gpu_warm.joinable()) gpu_warm.join();
         if (!engine_open(eng, ps, parent, k, log2_slots, 0, 0, devices)) return 1; // :256-260
         engine_support(eng, support);
+        engine_base_quality(eng, min_base_quality);
         // file text goes into page-locked memory from here on: uploads by DMA, not through a CPU copy
         static int pin_device = devices[0];
         set_text_allocator([](size_t n) -> void * { void *p = nullptr; return kid_host_alloc(pin_device, n, &p) == KID_OK ? p : nullptr; },

@@ -9,6 +9,7 @@
 // targets comes from the data file (:1073-1084).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
 //   --min-hits N  --confidence F   also write ./JOBS/<job>_confident.txt: the reads called by k-mer support (kid_driver.h)
+//   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N (kid_driver.h)
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -68,6 +69,7 @@ int main(int argc, char **argv)
         eng.batch_reads = opt.batch_reads;
         if (!engine_open(eng, ps, parent, k, opt.log2_slots, 0, KID_FLAG_U_IS_T, parse_devices(opt.device, opt.device_list))) return 1;
         engine_support(eng, opt.support);
+        engine_base_quality(eng, opt.min_base_quality);
         ps = ProbeSet();
 
         Prefetcher pf(std::move(files), opt.threads, eng.batch_reads, eng.batch_bases);
