@@ -214,7 +214,7 @@ int kid_trim_batch(kid_db *db, const uint8_t *quals, const uint64_t *offsets, ui
  * qual_off and qual_off + qual_len <= the next record's seq_off, as every indexer of a real file leaves them.
  *   KID_OPT_MIN_BASE_QUALITY     the sample's option, above: kid_classify_fastq_async (the mask kernel runs on the stream
  *                                of the prepare kernel, behind the upload of the block and in front of its classify kernels)
- *   KID_DB_OPT_MIN_BASE_QUALITY  the database's: kid_db_read_hits_fastq and kid_db_read_support_fastq, whose staged text is
+ *   KID_DB_OPT_MIN_BASE_QUALITY  the database's: kid_db_read_hits_fastq, _support_fastq and _segments_fastq, whose staged text is
  *                                masked in front of the hit pass (outside the interval kid_db_read_hits_time reports).  It
  *                                obeys the one-call-at-a-time rule of a kid_db and is NOT copied by kid_db_replicate.
  * The offsets and device forms of those calls have no quality text and are unaffected: mask their text first with the
@@ -331,6 +331,63 @@ int kid_db_support_from_hits_device(kid_db *db, const void *d_hit_offsets, const
 /* Device time of the support kernel ALONE since the last query (HIP events around it), its calls and reads; the hit pass
  * of the host forms is in kid_db_read_hits_time.  Synchronises with the last call.                                  */
 int kid_db_read_support_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
+
+/* ---- calling records in segments ------------------------------------------------------
+ * kid_db_read_support* gives a record one answer.  A contig that is one species for its first 1.4 Mb and another after
+ * that, a chimeric long read or a transferred island folds to an ancestor and nothing says where the change is.  These
+ * calls cut every record into segments and call each segment by its own hits under the same rule.
+ * "Window" keeps its meaning (one k-mer position of a read).  For one read with the trimmed range [start, stop]:
+ *   P          = max(0, stop - start + 1 - (k - 1)) window positions (0 as well for a FASTQ record process_qual drops);
+ *                position q in 0..P-1 is the window whose first base is byte start + q of the read
+ *   seg_len    >= 1, in window positions; seg_step in 1..seg_len; seg_len <= 1024 * seg_step
+ *              (KID_SEGMENT_MAX_OVERLAP: a position lies in at most 1024 segments); anything else is KID_ERR_ARG
+ *   n_seg      0 if P = 0; 1 if P <= seg_len; otherwise 1 + ceil((P - seg_len) / seg_step)
+ *   segment j  covers the positions [j * seg_step, min(j * seg_step + seg_len, P)): every position is covered, only the
+ *              last segment may be shorter than seg_len, it ends at P, and no segment lies inside the one before it
+ * The record of a segment:
+ *   pos        start + j * seg_step: counted from the first byte of the read, as kid_hit.pos is
+ *   n_pos      the positions it covers
+ *   the rest   the kid_support record kid_db_read_support returns under the same (min_hits, min_permille) for that read
+ *              with the range [pos, pos + n_pos + k - 2]: n_kmers counts the covered positions whose window holds a
+ *              k-mer and is the n of the permille test; the hits are those of kid_db_read_hits with pos in
+ *              [pos, pos + n_pos), folded in position order
+ * With seg_len >= every read's P each read with P > 0 has exactly one segment: its kid_support record, pos = start,
+ * n_pos = P.  The segment list is dense: segments without a hit are there, with final = confident = 0.
+ *   seg_offsets[n_reads + 1]   CSR: the segments of read r are segments[seg_offsets[r] .. seg_offsets[r + 1]); always complete
+ *   segments[cap], *n_segments *n_segments = seg_offsets[n_reads], always; segments is filled only if *n_segments <= cap,
+ *                              otherwise nothing is written to it and the call still returns KID_OK (segments = NULL,
+ *                              cap = 0 is the sizing call): the convention of kid_db_read_hits
+ * The calls are pure (no sample, no tally, no atomics); the output is byte-identical across runs, across any split of the
+ * reads into calls and across the table kinds.  A segment's numbers come from two prefix arrays over the tiles of the hit
+ * pass and cost the same whatever its length; its hits are folded by kid_db_read_support's code.
+ * Errors as for kid_db_read_hits*, plus the parameter errors above and min_permille > 1000 (KID_ERR_ARG).  The calls obey
+ * the one-call-at-a-time rule of a kid_db's scratch, to which they add 16 B per tile of 64 windows (valid mask and its
+ * scan), 8 B per read (first segment) and 32 B per segment (host forms); it is released by kid_db_destroy.            */
+#define KID_SEGMENT_MAX_OVERLAP 1024u
+typedef struct kid_segment {
+    uint32_t pos, n_pos, final, confident, n_kmers, n_hits, s_final, s_confident;
+} kid_segment;
+/* host buffers; offsets/start/stop as for kid_db_read_hits */
+int kid_db_read_segments(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                         uint64_t n_reads, uint32_t seg_len, uint32_t seg_step, uint32_t min_hits, uint32_t min_permille,
+                         uint64_t *seg_offsets, kid_segment *segments, uint64_t cap, uint64_t *n_segments);
+/* a FASTQ text block as for kid_db_read_hits_fastq (KID_DB_OPT_MIN_BASE_QUALITY is honoured the same way); a dropped
+ * record has no segment */
+int kid_db_read_segments_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                               uint32_t seg_len, uint32_t seg_step, uint32_t min_hits, uint32_t min_permille, uint64_t *seg_offsets,
+                               kid_segment *segments, uint64_t cap, uint64_t *n_segments);
+/* Everything resident in HBM, asynchronous on `stream`; inputs as for kid_db_read_hits_device.  d_hits / hits_cap: the
+ * caller's scratch for the hits (kid_hit[hits_cap]); d_seg_offsets: uint64[n_reads + 1]; d_segments: kid_segment[seg_cap];
+ * d_n_hits, d_n_segments: one uint64 each, written on the device.  If the hits exceed hits_cap or the segments seg_cap
+ * no segment is written; both counts and d_seg_offsets are still complete.  What the host cannot check is reported by
+ * the next kid_db_read_hits_time, as for kid_db_read_hits_device (such a batch has no segment).                     */
+int kid_db_read_segments_device(kid_db *db, const void *d_bases, uint64_t bases_nbytes, const void *d_offsets, const void *d_start,
+                                const void *d_stop, uint64_t n_reads, uint32_t seg_len, uint32_t seg_step, uint32_t min_hits,
+                                uint32_t min_permille, void *d_hits, uint64_t hits_cap, void *d_seg_offsets, void *d_segments,
+                                uint64_t seg_cap, void *d_n_hits, void *d_n_segments, void *stream);
+/* Device time of the segment kernels ALONE since the last query (the two scans and the segments kernel; the host forms
+ * read the number of segments back in between), their calls and reads; the hit pass is in kid_db_read_hits_time.     */
+int kid_db_read_segments_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
 
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).

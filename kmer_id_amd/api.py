@@ -93,6 +93,25 @@ class ReadHits:
 SUPPORT_DTYPE = np.dtype([("final", np.uint32), ("confident", np.uint32), ("n_kmers", np.uint32), ("n_hits", np.uint32),
                           ("s_final", np.uint32), ("s_confident", np.uint32)])
 
+# kid_segment: one record per segment (kid_db_read_segments*); the six fields behind n_pos are SUPPORT_DTYPE's
+SEGMENT_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in SUPPORT_DTYPE.names])
+
+
+class ReadSegments:
+    """Every read's segments in read order (kid_db_read_segments*): CSR `offsets` (uint64[n + 1]) over `records`
+    (SEGMENT_DTYPE).  The list is dense: segments without a hit are there, with final = confident = 0."""
+
+    def __init__(self, offsets, records):
+        self.offsets = offsets
+        self.records = records
+
+    def __len__(self):
+        return self.offsets.size - 1
+
+    def of(self, r):
+        """-> the records of read r"""
+        return self.records[int(self.offsets[r]):int(self.offsets[r + 1])]
+
 
 class KmerDB:
     """Replaces `new Hashtable()` + `new Tree1()` + the add_kmer/add_edge load loops."""
@@ -262,6 +281,49 @@ class KmerDB:
     def read_support_time(self):
         """-> (device ms, calls, reads) of the support kernel alone since the last query"""
         return self._time(self._lib.kid_db_read_support_time)
+
+    def _read_segments(self, call, n):
+        """the sizing call, then the call that fills a buffer of exactly that size"""
+        offsets = np.empty(n + 1, np.uint64)
+        total = C.c_uint64(0)
+        check(call(_ptr(offsets), None, 0, C.byref(total)))
+        records = np.zeros(total.value, SEGMENT_DTYPE)
+        if total.value:
+            check(call(_ptr(offsets), _ptr(records), total.value, C.byref(total)))
+        return ReadSegments(offsets, records)
+
+    def read_segments(self, bases, offsets, start=None, stop=None, seg_len=1000, seg_step=None, min_hits=0, min_permille=0):
+        """Call the records of a batch held in host memory in segments (kid_db_read_segments) -> ReadSegments.  A read
+        with P window positions is cut into segments of seg_len positions, seg_step apart (None: seg_len; seg_len <=
+        1024 * seg_step); each is called by its own hits under (min_hits, min_permille) as read_support calls a whole
+        read.  `pos` is counted from the first byte of the read.  Pure: no sample is touched."""
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        step = seg_len if seg_step is None else seg_step
+        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segments(
+            self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n)
+
+    def read_segments_fastq(self, text, recs, seg_len=1000, seg_step=None, min_hits=0, min_permille=0):
+        """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
+        fails stop - start >= k has no segment; KID_DB_OPT_MIN_BASE_QUALITY applies as in read_hits_fastq."""
+        text, recs, n = _fastq_block(text, recs)
+        step = seg_len if seg_step is None else seg_step
+        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segments_fastq(
+            self._h, _ptr(text), text.size, _ptr(recs), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n)
+
+    def read_segments_device(self, d_bases, bases_nbytes, d_offsets, n_reads, seg_len, seg_step, d_seg_offsets, d_n_hits, d_n_segments,
+                             d_start=0, d_stop=0, min_hits=0, min_permille=0, d_hits=0, hits_cap=0, d_segments=0, seg_cap=0, stream=0):
+        """Asynchronous, everything resident in HBM (raw pointers): kid_db_read_segments_device.  d_hits / hits_cap is the
+        caller's scratch for the hits; no segment is written when the hits or the segments exceed their cap."""
+        check(self._lib.kid_db_read_segments_device(self._h, C.c_void_p(d_bases), bases_nbytes, C.c_void_p(d_offsets),
+                                                    C.c_void_p(d_start or None), C.c_void_p(d_stop or None), n_reads, seg_len,
+                                                    seg_len if seg_step is None else seg_step, min_hits, min_permille,
+                                                    C.c_void_p(d_hits or None), hits_cap, C.c_void_p(d_seg_offsets),
+                                                    C.c_void_p(d_segments or None), seg_cap, C.c_void_p(d_n_hits),
+                                                    C.c_void_p(d_n_segments), C.c_void_p(stream or None)))
+
+    def read_segments_time(self):
+        """-> (device ms, calls, reads) of the segment kernels alone since the last query"""
+        return self._time(self._lib.kid_db_read_segments_time)
 
     def gather_ceiling(self, n_loads=1 << 28, inflight=4, iters=3):
         """Random gather rate over this DB's table: (ms per launch, loads per launch).  inflight 101 / 108: random

@@ -11,7 +11,8 @@
 // Scratch of the hit pass: grow-only device buffers sized by the largest batch seen, one set per database (calls on
 // one kid_db run one after the other: a call first waits for the kernels of the call before).  Per batch: 16 B per
 // read (descriptors) + 8 B per read (first tile) + 16 B per tile of 64 windows (mask, first hit) + 8 B per 1024 of
-// either (scan totals); the host-buffer forms add a device copy of their inputs and outputs.
+// either (scan totals); the host-buffer forms add a device copy of their inputs and outputs.  kid_db_read_segments* add
+// 16 B per tile (valid mask, its scan), 8 B per read (first segment) and 32 B per segment (host forms).
 // The device time between two events on a stream, added up over the calls since somebody took it
 struct __attribute__((visibility("hidden"))) KidSpanTimer {
     KidEvent ev0, ev1;
@@ -68,6 +69,12 @@ struct KidHitsState {
     KidDevBuf out_support; // kid_db_read_support* (kid_api_support.h): the host forms' records
     KidSpanTimer pass;     // the hit pass of every call, a kid_db_read_support* host call's included
     KidSpanTimer support;  // the support kernel alone
+    // kid_db_read_segments* (kid_api_segments.h): per tile the mask of its lanes that hold a k-mer and their scan (the hit
+    // pass stores the mask while want_valid is set: the buffer is sized for the batch then), [0] the batch's segments and
+    // [1] its valid windows, the host forms' offsets and records
+    KidDevBuf tile_valid, tile_valid_off, seg_ctl, out_seg_offsets, out_segments;
+    bool want_valid = false;
+    KidSpanTimer segments; // the segment kernels alone
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
 #define KID_HITS_CTL_WORDS 36u
@@ -77,7 +84,7 @@ kid_db::~kid_db() {}
 // a little slack: batches of a file differ slightly in size
 static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensure(nbytes, ((nbytes + nbytes / 8) + 255u) & ~255ull); }
 
-// the scratch, free: the hit pass of the call before is through
+// the scratch, free: the hit pass of the call before, and the segment kernels behind it, are through
 static int kid_hits_state(kid_db *db, KidHitsState **out)
 {
     if (!db->hits) {
@@ -87,10 +94,12 @@ static int kid_hits_state(kid_db *db, KidHitsState **out)
         KID_HIP(hipMemset(h->ctl(), 0, nb));
         KID_HIP(h->pass.create());
         KID_HIP(h->support.create());
+        KID_HIP(h->segments.create());
         db->hits = std::move(h);
     }
     *out = db->hits.get();
-    return (*out)->pass.settle();
+    const int rc = (*out)->pass.settle();
+    return rc != KID_OK ? rc : (*out)->segments.settle(); // (the segment kernels read the tiles' scratch behind the pass)
 }
 
 static KidHitsTiles kid_hits_tiles(const KidHitsState *h, const KidBatch &b)
@@ -101,6 +110,7 @@ static KidHitsTiles kid_hits_tiles(const KidHitsState *h, const KidBatch &b)
     a.tile_off = h->tile_off.as<uint64_t>();
     a.n_reads = b.n;
     a.tile_mask = h->tile_mask.as<unsigned long long>();
+    a.tile_valid = h->want_valid ? h->tile_valid.as<unsigned long long>() : nullptr;
     return a;
 }
 

@@ -35,7 +35,8 @@ struct KidHit {
 // ------------------------------------------------------------------ exclusive scans over the batch
 // out[i] = sum of src[0 .. i), out[n] = the total; 64-bit sums (a batch may hold 2^31 reads of 2^31 windows).
 // Three small kernels: scan inside blocks of 1024, scan of the block totals by one workgroup, add.
-// SRC 0: tiles of read i (from its descriptor); SRC 1: hits of tile i (popcount of its mask).
+// SRC 0: tiles of read i (from its descriptor); SRC 1: hits of tile i (popcount of its mask); SRC 2: the uint64 src[i]
+// itself (kid_segments.hip.h: segments of read i, scanned in place).
 // n is on the host (reads) or on the device (tiles: only the device knows how many a batch resident in HBM has).
 template <int SRC>
 __device__ __forceinline__ uint64_t kid_hits_scan_src(const void *src, uint64_t i)
@@ -44,6 +45,7 @@ __device__ __forceinline__ uint64_t kid_hits_scan_src(const void *src, uint64_t 
         const int32_t nk = static_cast<const KidReadDesc *>(src)[i].n_kmers;
         return nk > 0 ? ((uint64_t)(uint32_t)nk + KID_HITS_TILE - 1u) / KID_HITS_TILE : 0ull;
     }
+    if (SRC == 2) return static_cast<const uint64_t *>(src)[i];
     return (uint64_t)__popcll(static_cast<const unsigned long long *>(src)[i]);
 }
 
@@ -120,6 +122,7 @@ struct KidHitsTiles {
     const uint64_t *tile_off;   // [n_reads + 1]: first tile of read r; [n_reads] = tiles of the batch
     uint64_t n_reads;
     unsigned long long *tile_mask; // [tiles]: lanes (windows) of the tile that hit
+    unsigned long long *tile_valid; // nullable; [tiles]: lanes of the tile that hold a k-mer (kid_segments.hip.h asks for it)
 };
 
 // the read of tile t: tile_off[r] <= t < tile_off[r + 1] (reads without a window own no tile)
@@ -167,6 +170,7 @@ __global__ __launch_bounds__(256) void kid_hits_count_kernel(const KidDevDb db, 
                 const unsigned long long hm = __ballot(hit), vm = __ballot(valid);
                 if (lane == 0) {
                     a.tile_mask[t] = hm;
+                    if (a.tile_valid) a.tile_valid[t] = vm;
                     if (n_kmers && vm) atomicAdd(&n_kmers[r], (uint32_t)__popcll(vm));
                 }
             }

@@ -92,6 +92,7 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
     e->sample = e->samples[0];
     engine_support(*e, owner.support);
     engine_base_quality(*e, owner.min_base_quality);
+    e->segments = owner.segments;
     return e;
 }
 
@@ -379,6 +380,38 @@ int base_quality_option(int argc, char **argv, const char *prog)
     return q;
 }
 
+SegmentsOption segments_option(int argc, char **argv, const char *prog)
+{
+    SegmentsOption o;
+    for (int i = 1; i < argc; i++) {
+        if (strcmp(argv[i], "--segments") != 0) continue;
+        const char *opt = argv[i];
+        if (i + 1 >= argc) support_usage(prog, opt, "needs a value");
+        const char *v = argv[++i];
+        const char *const what = "takes LEN[:STEP], digits only: LEN in 1..2147483647, STEP in 1..LEN with LEN <= 1024 * STEP";
+        unsigned long long part[2] = {0, 0};
+        int np = 0;
+        for (size_t at = 0;; np++) {
+            if (np == 2) support_usage(prog, opt, what); // a second colon
+            const size_t from = at;
+            for (; v[at] >= '0' && v[at] <= '9'; at++) {
+                part[np] = part[np] * 10 + (unsigned)(v[at] - '0');
+                if (part[np] > 0x7FFFFFFFull) support_usage(prog, opt, what);
+            }
+            if (at == from) support_usage(prog, opt, what); // an empty part
+            if (v[at] == 0) { np++; break; }
+            if (v[at] != ':') support_usage(prog, opt, what);
+            at++;
+        }
+        if (np == 1) part[1] = part[0];
+        if (part[0] < 1 || part[1] < 1 || part[1] > part[0] || part[0] > 1024ull * part[1]) support_usage(prog, opt, what);
+        o.on = true;
+        o.seg_len = (uint32_t)part[0];
+        o.seg_step = (uint32_t)part[1];
+    }
+    return o;
+}
+
 std::string sibling_path_for(const std::string &result_path, const char *word)
 {
     std::string p = result_path;
@@ -447,6 +480,49 @@ static void hit_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, c
     }
 }
 
+// The segment lines of one classified batch: kid_db_read_segments* on the batch's device under the rule -- the sizing
+// call, then the call that fills a buffer of that size.  A read whose segments hold no hit leaves no line.
+static void segment_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, const std::vector<uint32_t> &final_targ,
+                             const SegmentsOption &o, const SupportRule &rule, std::string &out)
+{
+    const size_t nr = b.size();
+    std::vector<uint64_t> off(nr + 1);
+    std::vector<kid_segment> segs;
+    uint64_t total = 0;
+    auto call = [&](kid_segment *s, uint64_t cap) {
+        int rc = b.fq ? kid_db_read_segments_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, o.seg_len,
+                                                   o.seg_step, rule.min_hits, rule.min_permille, off.data(), s, cap, &total)
+                      : kid_db_read_segments(db, bases, b.offsets.data(), b.start.data(), b.stop.data(), nr, o.seg_len, o.seg_step,
+                                             rule.min_hits, rule.min_permille, off.data(), s, cap, &total);
+        if (rc != KID_OK) die_kid(rc);
+    };
+    call(nullptr, 0);
+    if (total == 0) return;
+    segs.resize(total);
+    call(segs.data(), total);
+    char num[96];
+    for (size_t r = 0; r < nr; r++) {
+        uint64_t with_hit = 0;
+        for (uint64_t i = off[r]; i < off[r + 1]; i++) with_hit += segs[i].n_hits > 0;
+        if (with_hit == 0) continue;
+        int n = snprintf(num, sizeof(num), "%u\t%d\t%llu\t%llu\t", final_targ[r], b.stop[r] - b.start[r] + 1,
+                         (unsigned long long)(off[r + 1] - off[r]), (unsigned long long)with_hit);
+        out.append(num, (size_t)n);
+        bool first = true;
+        for (uint64_t i = off[r]; i < off[r + 1]; i++) {
+            const kid_segment &s = segs[i];
+            if (s.n_hits == 0) continue;
+            n = snprintf(num, sizeof(num), "%s%u:%u:%u:%u:%u:%u", first ? "" : " ", s.pos, s.n_pos, s.n_kmers, s.n_hits, s.final, s.confident);
+            out.append(num, (size_t)n);
+            first = false;
+        }
+        out += '\t';
+        if (b.fq) out.append(b.fq->text.data() + b.fq->acc_off[r], b.fq->acc_len[r]);
+        else out += b.acc[r];
+        out += '\n';
+    }
+}
+
 // The support pass of one classified batch on its device: nothing comes back, the batch is tallied into `tally` under the rule
 static void tally_batch(kid_db *db, kid_sample *tally, const SupportRule &rule, const ReadBatch &b, const uint8_t *bases)
 {
@@ -459,7 +535,7 @@ static void tally_batch(kid_db *db, kid_sample *tally, const SupportRule &rule, 
 }
 
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file,
-                    const std::function<void(size_t, long long)> &done, HitsWriter *hits)
+                    const std::function<void(size_t, long long)> &done, HitsWriter *hits, HitsWriter *segments)
 {
     // Two batches in flight per device: while the GPU classifies batch b, batch b + 1 is uploaded and the results of
     // batch b - 1 go through the read saver -- in file order, which is what decides the "first 12 reads of a target"
@@ -498,6 +574,11 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             hits->add(saver_file + f.file, lines);
         }
         if (f.confident) tally_batch(f.db, f.confident, e.support, *f.batch, f.bases());
+        if (segments && segments->on() && e.segments.on) {
+            lines.clear();
+            segment_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.segments, e.support, lines);
+            segments->add(saver_file + f.file, lines);
+        }
         q.pop_front();
     };
     try {
@@ -587,6 +668,7 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
     o.hits = hits_option(argc, argv);
     o.support = support_option(argc, argv, argv[0]);
     o.min_base_quality = base_quality_option(argc, argv, argv[0]);
+    o.segments = segments_option(argc, argv, argv[0]);
     return o;
 }
 

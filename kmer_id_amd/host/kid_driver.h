@@ -37,6 +37,21 @@ std::string sibling_path_for(const std::string &result_path, const char *word);
 // The one place that reads it.  Q: digits only, 0..93 (0 = off, the default); anything else (a missing value too) is a
 // usage error: a message on stderr and exit code 2.  Checked, then ignored, with --dry-run.
 int base_quality_option(int argc, char **argv, const char *prog);
+// --segments LEN[:STEP] (shared by the three front-ends): call long records in segments (kid_db_read_segments*).  A
+// sample / job gets a segments file beside its result file, named like it with "result" replaced by "segments": one
+// line per read that was handed to process_read and has at least one k-mer hit, in the order of the hits file,
+// tab-separated, the header line last:
+//   <final_targ> <trimmed length> <n_segments> <segments with a hit> <pos>:<n_pos>:<n_kmers>:<n_hits>:<final>:<confident> ... <header>
+// Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0):
+// confident = final.  --min-base-quality applies as it does to the hits file.  Every other output is what it is without.
+// The one place that reads the option.  Digits only; LEN in 1..2147483647 window positions; STEP (default LEN) in 1..LEN
+// with LEN <= 1024 * STEP.  Anything else (a missing value, an empty part, a second colon) is a usage error: a message
+// on stderr and exit code 2.  Checked, then ignored, with --dry-run.
+struct SegmentsOption {
+    bool on = false;
+    uint32_t seg_len = 0, seg_step = 0;
+};
+SegmentsOption segments_option(int argc, char **argv, const char *prog);
 
 struct Engine {
     kid_db *db = nullptr;         // the database on the first device
@@ -51,6 +66,7 @@ struct Engine {
     SupportRule support;
     std::vector<kid_sample *> confident;
     int min_base_quality = 0; // --min-base-quality (engine_base_quality)
+    SegmentsOption segments;  // --segments (set by the front-end; a worker of engine_worker() inherits it)
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -121,6 +137,7 @@ private:
 // The batches of files read at the same time interleave: the lines are held in memory per file and written in file
 // order by close() -- what is held is the hits file itself (reads without a hit leave nothing), nothing else.  A
 // writer that is not closed (its sample failed) leaves no file; one made with an empty path does nothing.
+// (The class holds lines per file, whatever they are: the segments file of --segments has a second one.)
 bool hits_option(int argc, char **argv);                 // is --hits among the arguments
 class HitsWriter {
 public:
@@ -140,9 +157,11 @@ private:
 // them are through, with the number of its reads handed to process_read.  Returns the reads handed of all the files.
 // `hits`, if given and on, receives the hit lines of every batch: the hit pass (kid_db_read_hits*) of a batch runs on the
 // device that classified it, once its final targets are back.  With e.support on, the support pass of a batch runs at the
-// same place and tallies into that device's confident sample.
+// same place and tallies into that device's confident sample.  `segments`, if given and on, receives the segment lines of
+// every batch under e.segments and e.support: the segments pass (kid_db_read_segments*) runs at the same place too.
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file = 0,
-                    const std::function<void(size_t, long long)> &done = nullptr, HitsWriter *hits = nullptr);
+                    const std::function<void(size_t, long long)> &done = nullptr, HitsWriter *hits = nullptr,
+                    HitsWriter *segments = nullptr);
 
 // One opener per path, each by `open`, which sets its bool when the file is a plain FASTA that is not there (the
 // reference's "nark <name>"): missing[f] holds it for file f once that file is through.  `missing` must not move
@@ -161,6 +180,7 @@ struct ReaderOptions {
     bool hits = false;       // --hits: a hits file beside the result file (ignored with --dry-run)
     SupportRule support;     // --min-hits / --confidence: a confident result file beside the result file (ignored with --dry-run)
     int min_base_quality = 0; // --min-base-quality: FASTQ bases below it are read as N (ignored with --dry-run)
+    SegmentsOption segments;  // --segments: a segments file beside the result file (ignored with --dry-run)
 };
 ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 

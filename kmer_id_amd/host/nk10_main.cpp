@@ -19,6 +19,8 @@
 //   --min-hits N  --confidence F   also write <prefix>_confident.txt, the result file of the reads called by k-mer support:
 //                    a read counts under the first node of its target's root path whose clade holds at least N of its k-mer
 //                    hits and F (a decimal in [0, 1], three fractional digits) of its k-mers, under 0 if none does (kid_driver.h)
+//   --segments LEN[:STEP]   also write <prefix>_segments.txt: every read with a hit called in segments of LEN window
+//                    positions, STEP apart (default LEN; LEN <= 1024 * STEP), under the rule of --min-hits / --confidence (kid_driver.h)
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
 //                    what they would be on FASTQ files with those bases replaced by N; <prefix>_reads.txt prints the
 //                    sequences as they are (kid_driver.h)
@@ -90,6 +92,7 @@ int main(int argc, char **argv)
         else if (a == "--hits") {} // (hits_option below: the one place that reads it, shared with the sibling programs)
         else if (a == "--min-hits" || a == "--confidence") { if (i + 1 < argc) i++; } // (support_option below, likewise)
         else if (a == "--min-base-quality") { if (i + 1 < argc) i++; } // (base_quality_option below, likewise)
+        else if (a == "--segments") { if (i + 1 < argc) i++; } // (segments_option below, likewise)
         else if (dname.empty()) dname = a;
         else { std::cerr << "nk10: unexpected argument " << a << "\n"; return 2; }
     }
@@ -100,6 +103,7 @@ int main(int argc, char **argv)
     const bool want_hits = hits_option(argc, argv); // <prefix>_hits.txt beside <prefix>_result.txt (ignored with --dry-run)
     const SupportRule support = support_option(argc, argv, "nk10"); // <prefix>_confident.txt likewise
     const int min_base_quality = base_quality_option(argc, argv, "nk10"); // (checked, then ignored, with --dry-run and --fasta)
+    const SegmentsOption segments = segments_option(argc, argv, "nk10"); // <prefix>_segments.txt (checked, then ignored, with --dry-run)
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
     if (batch_reads < 1) batch_reads = 1;
     if (threads < 1) threads = 1;
@@ -192,6 +196,7 @@ int main(int argc, char **argv)
         if (!engine_open(eng, ps, parent, k, log2_slots, 0, 0, devices)) return 1; // :256-260
         engine_support(eng, support);
         engine_base_quality(eng, min_base_quality);
+        eng.segments = segments;
         // file text goes into page-locked memory from here on: uploads by DMA, not through a CPU copy
         static int pin_device = devices[0];
         set_text_allocator([](size_t n) -> void * { void *p = nullptr; return kid_host_alloc(pin_device, n, &p) == KID_OK ? p : nullptr; },
@@ -256,11 +261,12 @@ int main(int argc, char **argv)
             long long tct = 0;
             const std::string result_path = dname + prefix + "_result.txt";
             HitsWriter hits(want_hits ? sibling_path_for(result_path, "hits") : "");
+            HitsWriter segs(segments.on ? sibling_path_for(result_path, "segments") : "");
             if (support.on) remove(sibling_path_for(result_path, "confident").c_str()); // (one left there by an earlier run)
             {
                 ReadSaver saver(dname + prefix + "_reads.txt", ntar);
                 if (fasta_mode) {
-                    tct += run_files(e, pf, fi0, 1, saver, 0, nullptr, &hits);
+                    tct += run_files(e, pf, fi0, 1, saver, 0, nullptr, &hits, &segs);
                     if (missing[fi0]) out += "nark " + paths[fi0] + "\n";
                     out += std::to_string(tct) + " reads loaded\n";
                 } else {
@@ -272,12 +278,13 @@ int main(int argc, char **argv)
                         if (t_first_file < 0) t_first_file = since_start();
                         t_file_done[mate] = since_start();
                         out += std::to_string(tct) + " reads loaded\n";
-                    }, &hits);
+                    }, &hits, &segs);
                 }
             }
             const double t_reads_written = since_start();
             finish_sample(e, result_path);
             hits.close();
+            segs.close();
             if (timing) {
                 char buf[256];
                 snprintf(buf, sizeof(buf), "{\"sample\": %zu, \"begin_s\": %.3f, \"r1_through_s\": %.3f, \"r2_through_s\": %.3f, \"reads_txt_written_s\": %.3f, "
@@ -337,10 +344,12 @@ int main(int argc, char **argv)
                     remove((dname + fnames[f] + "_reads.txt").c_str());
                     remove((dname + fnames[f] + "_hits.txt").c_str());
                     remove((dname + fnames[f] + "_confident.txt").c_str());
+                    remove((dname + fnames[f] + "_segments.txt").c_str());
                 } else if (behind) {
                     // never started: a hits / confident file an earlier run left would stand beside no result of this one
                     if (want_hits) remove((dname + fnames[f] + "_hits.txt").c_str());
                     if (support.on) remove((dname + fnames[f] + "_confident.txt").c_str());
+                    if (segments.on) remove((dname + fnames[f] + "_segments.txt").c_str());
                 }
                 if (outs[f].failed) behind = true;
             }
