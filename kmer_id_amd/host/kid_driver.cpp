@@ -90,22 +90,16 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
     e->batch_bases = owner.batch_bases;
     for (kid_db *d : e->dbs) e->samples.push_back(begin_sample_or_die(d));
     e->sample = e->samples[0];
-    engine_support(*e, owner.support);
-    engine_base_quality(*e, owner.min_base_quality);
-    e->segments = owner.segments;
+    engine_configure(*e, owner.side);
     return e;
 }
 
-void engine_support(Engine &e, const SupportRule &rule)
+void engine_configure(Engine &e, const SideOptions &side)
 {
-    e.support = rule;
-    if (!rule.on) return;
-    for (kid_db *d : e.dbs) e.confident.push_back(begin_sample_or_die(d));
-}
-
-void engine_base_quality(Engine &e, int q)
-{
-    e.min_base_quality = q;
+    e.side = side;
+    if (side.support.on)
+        for (kid_db *d : e.dbs) e.confident.push_back(begin_sample_or_die(d));
+    const int q = side.min_base_quality;
     if (q == 0) return;
     for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
         for (kid_sample *s : *list) {
@@ -307,112 +301,112 @@ static void collect_fastq_block(ReadBatch &b, const HostBuf &io, std::vector<uin
     b.stop.assign(stop, stop + nr);
 }
 
-bool hits_option(int argc, char **argv)
-{
-    for (int i = 1; i < argc; i++)
-        if (strcmp(argv[i], "--hits") == 0) return true;
-    return false;
-}
-
-[[noreturn]] static void support_usage(const char *prog, const char *option, const char *what)
+[[noreturn]] static void usage_error(const char *prog, const char *option, const char *what)
 {
     std::cerr << prog << ": " << option << " " << what << "\n";
     exit(2);
 }
 
-SupportRule support_option(int argc, char **argv, const char *prog)
+// The run of decimal digits at v[at]: its value into `value`, `at` moved behind it.  Returns the number of digits (0: there
+// is none), or -1 as soon as the value is above `max`.
+static int digits_up_to(unsigned long long max, const char *v, size_t &at, unsigned long long &value)
 {
-    SupportRule r;
-    for (int i = 1; i < argc; i++) {
-        const bool hits = strcmp(argv[i], "--min-hits") == 0;
-        if (!hits && strcmp(argv[i], "--confidence") != 0) continue;
-        const char *opt = argv[i];
-        if (i + 1 >= argc) support_usage(prog, opt, "needs a value");
-        const char *v = argv[++i];
-        auto digit = [](char c) { return c >= '0' && c <= '9'; };
-        unsigned long long whole = 0;
-        size_t at = 0;
-        for (; digit(v[at]); at++) {
-            whole = whole * 10 + (unsigned)(v[at] - '0');
-            if (whole > 0xFFFFFFFFull) support_usage(prog, opt, "is out of range");
-        }
-        if (at == 0) support_usage(prog, opt, hits ? "takes a number >= 0" : "takes a decimal in [0, 1], e.g. 0.02");
-        r.on = true;
-        if (hits) {
-            if (v[at] != 0) support_usage(prog, opt, "takes a number >= 0");
-            r.min_hits = (uint32_t)whole;
-            continue;
-        }
-        // F -> permille, from its digits: the whole part, then up to three fractional digits padded with zeros
-        unsigned frac = 0, nfrac = 0;
-        if (v[at] == '.') {
-            for (at++; digit(v[at]); at++, nfrac++) {
-                if (nfrac == 3) support_usage(prog, opt, "takes at most three fractional digits");
-                frac = frac * 10 + (unsigned)(v[at] - '0');
-            }
-            if (nfrac == 0) support_usage(prog, opt, "takes a decimal in [0, 1], e.g. 0.02");
-            for (unsigned j = nfrac; j < 3; j++) frac *= 10;
-        }
-        if (v[at] != 0) support_usage(prog, opt, "takes a decimal in [0, 1], e.g. 0.02");
-        if (whole * 1000 + frac > 1000) support_usage(prog, opt, "takes a decimal in [0, 1]");
-        r.min_permille = (uint32_t)(whole * 1000 + frac);
+    int n = 0;
+    for (value = 0; v[at] >= '0' && v[at] <= '9'; at++, n++) {
+        value = value * 10 + (unsigned)(v[at] - '0');
+        if (value > max) return -1;
     }
-    return r;
+    return n;
 }
 
-int base_quality_option(int argc, char **argv, const char *prog)
+static void read_min_hits(SideOptions &o, const char *prog, const char *opt, const char *v)
 {
-    int q = 0;
-    for (int i = 1; i < argc; i++) {
-        if (strcmp(argv[i], "--min-base-quality") != 0) continue;
-        const char *opt = argv[i];
-        if (i + 1 >= argc) support_usage(prog, opt, "needs a value");
-        const char *v = argv[++i];
-        unsigned whole = 0;
-        size_t at = 0;
-        for (; v[at] >= '0' && v[at] <= '9'; at++) {
-            whole = whole * 10 + (unsigned)(v[at] - '0');
-            if (whole > 93u) support_usage(prog, opt, "takes a quality from 0 to 93");
-        }
-        if (at == 0 || v[at] != 0) support_usage(prog, opt, "takes a quality from 0 to 93");
-        q = (int)whole;
-    }
-    return q;
+    unsigned long long n = 0;
+    size_t at = 0;
+    const int nd = digits_up_to(0xFFFFFFFFull, v, at, n);
+    if (nd < 0) usage_error(prog, opt, "is out of range");
+    if (nd == 0 || v[at] != 0) usage_error(prog, opt, "takes a number >= 0");
+    o.support.on = true;
+    o.support.min_hits = (uint32_t)n;
 }
 
-SegmentsOption segments_option(int argc, char **argv, const char *prog)
+// F -> permille, from its digits: the whole part, then up to three fractional digits padded with zeros
+static void read_confidence(SideOptions &o, const char *prog, const char *opt, const char *v)
 {
-    SegmentsOption o;
-    for (int i = 1; i < argc; i++) {
-        if (strcmp(argv[i], "--segments") != 0) continue;
-        const char *opt = argv[i];
-        if (i + 1 >= argc) support_usage(prog, opt, "needs a value");
-        const char *v = argv[++i];
-        const char *const what = "takes LEN[:STEP], digits only: LEN in 1..2147483647, STEP in 1..LEN with LEN <= 1024 * STEP";
-        unsigned long long part[2] = {0, 0};
-        int np = 0;
-        for (size_t at = 0;; np++) {
-            if (np == 2) support_usage(prog, opt, what); // a second colon
-            const size_t from = at;
-            for (; v[at] >= '0' && v[at] <= '9'; at++) {
-                part[np] = part[np] * 10 + (unsigned)(v[at] - '0');
-                if (part[np] > 0x7FFFFFFFull) support_usage(prog, opt, what);
-            }
-            if (at == from) support_usage(prog, opt, what); // an empty part
-            if (v[at] == 0) { np++; break; }
-            if (v[at] != ':') support_usage(prog, opt, what);
-            at++;
-        }
-        if (np == 1) part[1] = part[0];
-        if (part[0] < 1 || part[1] < 1 || part[1] > part[0] || part[0] > 1024ull * part[1]) support_usage(prog, opt, what);
-        o.on = true;
-        o.seg_len = (uint32_t)part[0];
-        o.seg_step = (uint32_t)part[1];
+    const char *const what = "takes a decimal in [0, 1], e.g. 0.02";
+    unsigned long long whole = 0, frac = 0;
+    size_t at = 0;
+    const int nd = digits_up_to(0xFFFFFFFFull, v, at, whole);
+    if (nd < 0) usage_error(prog, opt, "is out of range");
+    if (nd == 0) usage_error(prog, opt, what);
+    if (v[at] == '.') {
+        const int nfrac = digits_up_to(999, v, ++at, frac);
+        if (nfrac < 0 || nfrac > 3) usage_error(prog, opt, "takes at most three fractional digits");
+        if (nfrac == 0) usage_error(prog, opt, what);
+        for (int j = nfrac; j < 3; j++) frac *= 10;
     }
+    if (v[at] != 0) usage_error(prog, opt, what);
+    if (whole * 1000 + frac > 1000) usage_error(prog, opt, "takes a decimal in [0, 1]");
+    o.support.on = true;
+    o.support.min_permille = (uint32_t)(whole * 1000 + frac);
+}
+
+static void read_base_quality(SideOptions &o, const char *prog, const char *opt, const char *v)
+{
+    unsigned long long q = 0;
+    size_t at = 0;
+    if (digits_up_to(93, v, at, q) <= 0 || v[at] != 0) usage_error(prog, opt, "takes a quality from 0 to 93");
+    o.min_base_quality = (int)q;
+}
+
+static void read_segments(SideOptions &o, const char *prog, const char *opt, const char *v)
+{
+    const char *const what = "takes LEN[:STEP], digits only: LEN in 1..2147483647, STEP in 1..LEN with LEN <= 1024 * STEP";
+    unsigned long long len = 0, step = 0;
+    size_t at = 0;
+    if (digits_up_to(0x7FFFFFFFull, v, at, len) <= 0) usage_error(prog, opt, what); // (an empty part too)
+    step = len;
+    if (v[at] == ':' && digits_up_to(0x7FFFFFFFull, v, ++at, step) <= 0) usage_error(prog, opt, what);
+    if (v[at] != 0) usage_error(prog, opt, what); // (a second colon too)
+    if (len < 1 || step < 1 || step > len || len > 1024ull * step) usage_error(prog, opt, what);
+    o.segments = SegmentsOption{true, (uint32_t)len, (uint32_t)step};
+}
+
+// The side options: their words, the pass of side_options() that reads each, what reads its value (none: a switch)
+static const struct {
+    const char *name;
+    int pass;
+    void (*read)(SideOptions &, const char *prog, const char *opt, const char *v);
+} kSideOptions[] = {{"--hits", 0, nullptr},
+                    {"--min-hits", 0, read_min_hits},
+                    {"--confidence", 0, read_confidence},
+                    {"--min-base-quality", 1, read_base_quality},
+                    {"--segments", 2, read_segments}};
+
+int side_option_values(const char *word)
+{
+    for (const auto &so : kSideOptions)
+        if (strcmp(word, so.name) == 0) return so.read ? 1 : 0;
+    return -1;
+}
+
+SideOptions side_options(int argc, char **argv, const char *prog)
+{
+    SideOptions o;
+    // one pass over the words per step of the order in which malformed options are reported
+    for (int pass = 0; pass < 3; pass++)
+        for (int i = 1; i < argc; i++)
+            for (const auto &so : kSideOptions) {
+                if (so.pass != pass || strcmp(argv[i], so.name) != 0) continue;
+                if (!so.read) { o.hits = true; continue; }
+                if (i + 1 >= argc) usage_error(prog, so.name, "needs a value");
+                so.read(o, prog, so.name, argv[i + 1]);
+            }
     return o;
 }
 
-std::string sibling_path_for(const std::string &result_path, const char *word)
+// The file beside a result file: its path with the last "result" replaced by `word`
+static std::string sibling_path_for(const std::string &result_path, const char *word)
 {
     std::string p = result_path;
     const size_t at = p.rfind("result");
@@ -420,48 +414,101 @@ std::string sibling_path_for(const std::string &result_path, const char *word)
     return p;
 }
 
-HitsWriter::HitsWriter(const std::string &path) : path_(path)
+// The side files beside a result file: the one place that has their names
+struct SidePaths { std::string hits, confident, segments; };
+static SidePaths side_paths(const std::string &r)
 {
-    if (on()) remove(path_.c_str());
+    return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments")};
 }
 
-void HitsWriter::add(size_t file, const std::string &lines)
+void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
 {
-    if (parts_.size() <= file) parts_.resize(file + 1);
-    parts_[file] += lines;
+    const SidePaths p = side_paths(result_path);
+    if (all || side.hits) remove(p.hits.c_str());
+    if (all || side.segments.on) remove(p.segments.c_str());
+    if (all || side.support.on) remove(p.confident.c_str());
 }
 
-void HitsWriter::close()
+SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
 {
-    if (!on()) return;
-    FILE *f = fopen(path_.c_str(), "w");
-    if (!f) throw Fatal{2, "cannot write " + path_};
-    for (const std::string &p : parts_) fwrite(p.data(), 1, p.size(), f);
+    remove_side_files(result_path, side);
+}
+
+void SampleOutputs::add(Lines &to, size_t file, const std::string &lines)
+{
+    if (to.size() <= file) to.resize(file + 1);
+    to[file] += lines;
+}
+
+static void write_lines(const std::string &path, const std::vector<std::string> &parts)
+{
+    FILE *f = fopen(path.c_str(), "w");
+    if (!f) throw Fatal{2, "cannot write " + path};
+    for (const std::string &p : parts) fwrite(p.data(), 1, p.size(), f);
     fclose(f);
-    parts_.clear();
 }
 
-// The hit lines of one classified batch (its start / stop / final targets are known): kid_db_read_hits* on the batch's
-// device -- the sizing call, then the call that fills a buffer of that size.
+// gcount / ucount of a sample (one per device, merged) -> "<i>,<g>,<u>" lines
+static void write_counters(std::vector<kid_sample *> &samples, int ntar, const std::string &path)
+{
+    std::vector<int64_t> g((size_t)ntar), u((size_t)ntar);
+    int rc = samples.size() > 1 ? kid_sample_end_merged(samples.data(), (int)samples.size(), g.data(), u.data())
+                                : kid_sample_end(samples[0], g.data(), u.data());
+    if (rc != KID_OK) die_kid(rc);
+    write_result(path, g, u);
+}
+
+void SampleOutputs::finish(Engine &e)
+{
+    const SidePaths p = side_paths(result_path_);
+    write_counters(e.samples, e.ntar, result_path_);
+    if (side_.support.on) write_counters(e.confident, e.ntar, p.confident);
+    if (side_.hits) write_lines(p.hits, hits_);
+    if (side_.segments.on) write_lines(p.segments, segments_);
+    hits_.clear();
+    segments_.clear();
+}
+
+// One call of the kid_db_read_* family on a classified batch (its start / stop / final targets are known) on the batch's
+// device: the FASTQ-block form for a block, else the offsets form; `rest` are the arguments behind the number of reads.
 // (bases: the text of a batch of reads that was classified -- the batch's own, or its masked copy under --min-base-quality)
+template <class BlockForm, class OffsetsForm, class... Rest>
+static void read_pass(BlockForm block_form, OffsetsForm offsets_form, kid_db *db, const ReadBatch &b, const uint8_t *bases, Rest... rest)
+{
+    const size_t nr = b.size();
+    int rc = b.fq ? block_form(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, rest...)
+                  : offsets_form(db, bases, b.offsets.data(), b.start.data(), b.stop.data(), nr, rest...);
+    if (rc != KID_OK) die_kid(rc);
+}
+// ... of one whose last arguments are (items, cap, &total): the sizing call, then the call that fills a buffer of that size
+template <class Item, class BlockForm, class OffsetsForm, class... Middle>
+static std::vector<Item> read_items(BlockForm block_form, OffsetsForm offsets_form, kid_db *db, const ReadBatch &b, const uint8_t *bases,
+                                    Middle... middle)
+{
+    std::vector<Item> items;
+    uint64_t total = 0;
+    read_pass(block_form, offsets_form, db, b, bases, middle..., (Item *)nullptr, (uint64_t)0, &total);
+    items.resize(total);
+    if (total) read_pass(block_form, offsets_form, db, b, bases, middle..., items.data(), total, &total);
+    return items;
+}
+// The end of a read's line: its header line as in _reads.txt
+static void append_header(std::string &out, const ReadBatch &b, size_t r)
+{
+    out += '\t';
+    if (b.fq) out.append(b.fq->text.data() + b.fq->acc_off[r], b.fq->acc_len[r]);
+    else out += b.acc[r];
+    out += '\n';
+}
+
+// The hit lines of one classified batch: kid_db_read_hits*
 static void hit_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, const std::vector<uint32_t> &final_targ, int k, std::string &out)
 {
     const size_t nr = b.size();
     std::vector<uint64_t> off(nr + 1);
     std::vector<uint32_t> nk(nr);
-    std::vector<kid_hit> hits;
-    uint64_t total = 0;
-    auto call = [&](kid_hit *h, uint64_t cap) {
-        int rc = b.fq ? kid_db_read_hits_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, off.data(),
-                                               nk.data(), h, cap, &total)
-                      : kid_db_read_hits(db, bases, b.offsets.data(), b.start.data(), b.stop.data(), nr, off.data(), nk.data(),
-                                         h, cap, &total);
-        if (rc != KID_OK) die_kid(rc);
-    };
-    call(nullptr, 0);
-    if (total == 0) return;
-    hits.resize(total);
-    call(hits.data(), total);
+    const std::vector<kid_hit> hits = read_items<kid_hit>(kid_db_read_hits_fastq, kid_db_read_hits, db, b, bases, off.data(), nk.data());
+    if (hits.empty()) return;
     char num[64];
     for (size_t r = 0; r < nr; r++) {
         if (off[r + 1] == off[r]) continue;
@@ -473,33 +520,20 @@ static void hit_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, c
             n = snprintf(num, sizeof(num), "%s%u:%u:%u", i > off[r] ? " " : "", hits[i].pos, hits[i].target, hits[i].entry);
             out.append(num, (size_t)n);
         }
-        out += '\t';
-        if (b.fq) out.append(b.fq->text.data() + b.fq->acc_off[r], b.fq->acc_len[r]);
-        else out += b.acc[r];
-        out += '\n';
+        append_header(out, b, r);
     }
 }
 
-// The segment lines of one classified batch: kid_db_read_segments* on the batch's device under the rule -- the sizing
-// call, then the call that fills a buffer of that size.  A read whose segments hold no hit leaves no line.
+// The segment lines of one classified batch: kid_db_read_segments* under the rule.  A read whose segments hold no hit
+// leaves no line.
 static void segment_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, const std::vector<uint32_t> &final_targ,
                              const SegmentsOption &o, const SupportRule &rule, std::string &out)
 {
     const size_t nr = b.size();
     std::vector<uint64_t> off(nr + 1);
-    std::vector<kid_segment> segs;
-    uint64_t total = 0;
-    auto call = [&](kid_segment *s, uint64_t cap) {
-        int rc = b.fq ? kid_db_read_segments_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, o.seg_len,
-                                                   o.seg_step, rule.min_hits, rule.min_permille, off.data(), s, cap, &total)
-                      : kid_db_read_segments(db, bases, b.offsets.data(), b.start.data(), b.stop.data(), nr, o.seg_len, o.seg_step,
-                                             rule.min_hits, rule.min_permille, off.data(), s, cap, &total);
-        if (rc != KID_OK) die_kid(rc);
-    };
-    call(nullptr, 0);
-    if (total == 0) return;
-    segs.resize(total);
-    call(segs.data(), total);
+    const std::vector<kid_segment> segs = read_items<kid_segment>(kid_db_read_segments_fastq, kid_db_read_segments, db, b, bases, o.seg_len,
+                                                                  o.seg_step, rule.min_hits, rule.min_permille, off.data());
+    if (segs.empty()) return;
     char num[96];
     for (size_t r = 0; r < nr; r++) {
         uint64_t with_hit = 0;
@@ -516,26 +550,12 @@ static void segment_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *base
             out.append(num, (size_t)n);
             first = false;
         }
-        out += '\t';
-        if (b.fq) out.append(b.fq->text.data() + b.fq->acc_off[r], b.fq->acc_len[r]);
-        else out += b.acc[r];
-        out += '\n';
+        append_header(out, b, r);
     }
 }
 
-// The support pass of one classified batch on its device: nothing comes back, the batch is tallied into `tally` under the rule
-static void tally_batch(kid_db *db, kid_sample *tally, const SupportRule &rule, const ReadBatch &b, const uint8_t *bases)
-{
-    const size_t nr = b.size();
-    int rc = b.fq ? kid_db_read_support_fastq(db, (const uint8_t *)b.fq->text.data(), b.fq->used, b.fq->recs.data(), nr, rule.min_hits,
-                                              rule.min_permille, nullptr, tally)
-                  : kid_db_read_support(db, bases, b.offsets.data(), b.start.data(), b.stop.data(), nr, rule.min_hits,
-                                        rule.min_permille, nullptr, tally);
-    if (rc != KID_OK) die_kid(rc);
-}
-
-long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file,
-                    const std::function<void(size_t, long long)> &done, HitsWriter *hits, HitsWriter *segments)
+long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, SampleOutputs &out, size_t saver_file,
+                    const std::function<void(size_t, long long)> &done)
 {
     // Two batches in flight per device: while the GPU classifies batch b, batch b + 1 is uploaded and the results of
     // batch b - 1 go through the read saver -- in file order, which is what decides the "first 12 reads of a target"
@@ -568,16 +588,19 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         if (rc != KID_OK) die_kid(rc);
         if (f.batch->fq) collect_fastq_block(*f.batch, f.io, f.final_targ);
         handed[f.file] += saver.add_batch_of(saver_file + f.file, *f.batch, f.final_targ, e.k);
-        if (hits && hits->on()) {
+        if (out.hits_on()) {
             lines.clear();
             hit_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.k, lines);
-            hits->add(saver_file + f.file, lines);
+            out.add_hits(saver_file + f.file, lines);
         }
-        if (f.confident) tally_batch(f.db, f.confident, e.support, *f.batch, f.bases());
-        if (segments && segments->on() && e.segments.on) {
+        // (the support pass: nothing comes back, the batch is tallied into the device's confident sample under the rule)
+        if (f.confident)
+            read_pass(kid_db_read_support_fastq, kid_db_read_support, f.db, *f.batch, f.bases(), e.side.support.min_hits,
+                      e.side.support.min_permille, (kid_support *)nullptr, f.confident);
+        if (out.segments_on()) {
             lines.clear();
-            segment_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.segments, e.support, lines);
-            segments->add(saver_file + f.file, lines);
+            segment_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.side.segments, e.side.support, lines);
+            out.add_segments(saver_file + f.file, lines);
         }
         q.pop_front();
     };
@@ -593,7 +616,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             const size_t nr = f.batch->size();
             f.sample = e.samples[e.next_sample]; // batches are dealt round-robin over the devices
             f.db = e.dbs[e.next_sample];
-            f.confident = e.support.on ? e.confident[e.next_sample] : nullptr;
+            f.confident = e.side.support.on ? e.confident[e.next_sample] : nullptr;
             e.next_sample = (e.next_sample + 1) % e.samples.size();
             int rc;
             const auto t_sub = std::chrono::steady_clock::now();
@@ -602,9 +625,9 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             } else {
                 f.final_targ.resize(nr);
                 rc = KID_OK;
-                if (e.min_base_quality > 0 && !f.batch->quals.empty()) {
+                if (e.side.min_base_quality > 0 && !f.batch->quals.empty()) {
                     f.masked.resize(f.batch->bases.size());
-                    rc = kid_mask_batch(f.db, f.batch->bases.data(), f.batch->quals.data(), f.batch->offsets.data(), nr, e.min_base_quality,
+                    rc = kid_mask_batch(f.db, f.batch->bases.data(), f.batch->quals.data(), f.batch->offsets.data(), nr, e.side.min_base_quality,
                                         f.masked.data(), nullptr);
                 }
                 if (rc == KID_OK)
@@ -665,10 +688,7 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
         if (a == "--threads") o.threads = atoi(v);
         if (a == "--db-cache") o.db_cache = v;
     }
-    o.hits = hits_option(argc, argv);
-    o.support = support_option(argc, argv, argv[0]);
-    o.min_base_quality = base_quality_option(argc, argv, argv[0]);
-    o.segments = segments_option(argc, argv, argv[0]);
+    o.side = side_options(argc, argv, argv[0]);
     return o;
 }
 
@@ -719,20 +739,6 @@ int write_dry_run(const std::string &path, const char *prog, const std::vector<i
     }
     fclose(f);
     return 0;
-}
-
-void finish_sample(Engine &e, const std::string &result_path)
-{
-    std::vector<int64_t> g((size_t)e.ntar), u((size_t)e.ntar);
-    int rc = e.samples.size() > 1 ? kid_sample_end_merged(e.samples.data(), (int)e.samples.size(), g.data(), u.data())
-                                  : kid_sample_end(e.sample, g.data(), u.data());
-    if (rc != KID_OK) die_kid(rc);
-    write_result(result_path, g, u);
-    if (!e.support.on) return;
-    rc = e.confident.size() > 1 ? kid_sample_end_merged(e.confident.data(), (int)e.confident.size(), g.data(), u.data())
-                                : kid_sample_end(e.confident[0], g.data(), u.data());
-    if (rc != KID_OK) die_kid(rc);
-    write_result(sibling_path_for(result_path, "confident"), g, u);
 }
 
 } // namespace kidhost

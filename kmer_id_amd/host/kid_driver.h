@@ -12,46 +12,42 @@
 
 namespace kidhost {
 
-// --min-hits N / --confidence F (shared by the three front-ends): call reads by k-mer support.  Either option switches
-// the feature on, the one not given is 0.  A sample / job then gets a confident result file beside its result file, named
-// like it with "result" replaced by "confident" and in its format: the counters of a second sample per device that is
-// tallied with every batch under the rule (kid_db_read_support*: gcount[confident]++ where the result file has
-// gcount[final]++).  Nothing else changes: the result, reads and hits files and stdout are what they are without.
+// The side options the three front-ends share: each gives a sample / job one more output beside its result file
+// (SampleOutputs below has the files) or changes what the GPU reads.  All are checked, then ignored, with --dry-run.
+// --min-hits N / --confidence F: call reads by k-mer support.  Either option switches the feature on, the one not given
+// is 0.  N: a decimal number up to 2^32-1.  F: a decimal in [0, 1] with at most three fractional digits, turned into
+// permille from its digits.
 struct SupportRule {
     bool on = false;
     uint32_t min_hits = 0, min_permille = 0;
 };
-// The one place that reads the two options.  N: a decimal number up to 2^32-1.  F: a decimal in [0, 1] with at most three
-// fractional digits, turned into permille from its digits.  Anything else (a missing value too) is a usage error:
-// a message on stderr and exit code 2.  The options are checked, then ignored, with --dry-run.
-SupportRule support_option(int argc, char **argv, const char *prog);
-// The file beside a result file: its path with the last "result" replaced by `word` (".../x_result.txt", "confident"
-// -> ".../x_confident.txt"; "hits" names the hits file of --hits, below)
-std::string sibling_path_for(const std::string &result_path, const char *word);
-// --min-base-quality Q (shared by the three front-ends): the bases of FASTQ input whose quality is below Q are read as
-// 'N' by everything that runs on the GPU (KID_OPT_MIN_BASE_QUALITY / KID_DB_OPT_MIN_BASE_QUALITY): the result, hits and
-// confident files and stdout are what they would be on input files with those bases replaced by N; the reads file prints
-// the sequences as they are in the input.  FASTQ.gz blocks are masked by the library behind their upload; the batches of a
-// plain FASTQ file carry their qualities (ReadBatch::quals) and are masked through kid_mask_batch before they are
-// classified (run_files).  FASTA input has no qualities: the option is accepted and changes nothing.
-// The one place that reads it.  Q: digits only, 0..93 (0 = off, the default); anything else (a missing value too) is a
-// usage error: a message on stderr and exit code 2.  Checked, then ignored, with --dry-run.
-int base_quality_option(int argc, char **argv, const char *prog);
-// --segments LEN[:STEP] (shared by the three front-ends): call long records in segments (kid_db_read_segments*).  A
-// sample / job gets a segments file beside its result file, named like it with "result" replaced by "segments": one
-// line per read that was handed to process_read and has at least one k-mer hit, in the order of the hits file,
-// tab-separated, the header line last:
-//   <final_targ> <trimmed length> <n_segments> <segments with a hit> <pos>:<n_pos>:<n_kmers>:<n_hits>:<final>:<confident> ... <header>
-// Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0):
-// confident = final.  --min-base-quality applies as it does to the hits file.  Every other output is what it is without.
-// The one place that reads the option.  Digits only; LEN in 1..2147483647 window positions; STEP (default LEN) in 1..LEN
-// with LEN <= 1024 * STEP.  Anything else (a missing value, an empty part, a second colon) is a usage error: a message
-// on stderr and exit code 2.  Checked, then ignored, with --dry-run.
+// --segments LEN[:STEP]: call long records in segments (kid_db_read_segments*).  Digits only; LEN in 1..2147483647 window
+// positions; STEP (default LEN) in 1..LEN with LEN <= 1024 * STEP.
 struct SegmentsOption {
     bool on = false;
     uint32_t seg_len = 0, seg_step = 0;
 };
-SegmentsOption segments_option(int argc, char **argv, const char *prog);
+struct SideOptions {
+    bool hits = false;   // --hits: every read's k-mer hits
+    SupportRule support;
+    // --min-base-quality Q (digits only, 0..93; 0 = off, the default): the bases of FASTQ input whose quality is below Q
+    // are read as 'N' by everything that runs on the GPU (KID_OPT_MIN_BASE_QUALITY / KID_DB_OPT_MIN_BASE_QUALITY): the
+    // result, hits and confident files and stdout are what they would be on input files with those bases replaced by N;
+    // the reads file prints the sequences as they are in the input.  FASTQ.gz blocks are masked by the library behind
+    // their upload; the batches of a plain FASTQ file carry their qualities (ReadBatch::quals) and are masked through
+    // kid_mask_batch before they are classified (run_files).  FASTA input has no qualities: the option is accepted and
+    // changes nothing.
+    int min_base_quality = 0;
+    SegmentsOption segments;
+};
+// The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
+// its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
+// of --segments too) is a usage error: "<prog>: <option> <what>" on stderr and exit code 2 -- of several, the first in
+// the order --min-hits / --confidence, --min-base-quality, --segments.
+SideOptions side_options(int argc, char **argv, const char *prog);
+// For a front-end that rejects the words it does not know: the number of value words behind `word` (0 or 1) if it
+// is a side option, else -1
+int side_option_values(const char *word);
 
 struct Engine {
     kid_db *db = nullptr;         // the database on the first device
@@ -62,11 +58,9 @@ struct Engine {
     std::vector<kid_db *> dbs;
     std::vector<kid_sample *> samples;
     size_t next_sample = 0;
-    // --min-hits / --confidence: the rule and one tallied sample per device (engine_support); empty without
-    SupportRule support;
+    // the side options (engine_configure) and, under --min-hits / --confidence, one tallied sample per device
+    SideOptions side;
     std::vector<kid_sample *> confident;
-    int min_base_quality = 0; // --min-base-quality (engine_base_quality)
-    SegmentsOption segments;  // --segments (set by the front-end; a worker of engine_worker() inherits it)
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -97,12 +91,10 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 // exits with 1).
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
-// Switch the confident result file on (rule.on) for an engine that is open: one more sample per device, reset, closed and
-// destroyed with the others.  A worker of engine_worker() inherits it.
-void engine_support(Engine &e, const SupportRule &rule);
-// --min-base-quality Q for an engine that is open, behind engine_support: the option of every sample, the tallied ones
-// included, and of every replica of the database.  A worker of engine_worker() inherits it for its samples.
-void engine_base_quality(Engine &e, int q);
+// The side options for an engine that is open: with a rule one more sample per device (reset, closed and destroyed with
+// the others), then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
+// A worker of engine_worker() inherits them for its samples.
+void engine_configure(Engine &e, const SideOptions &side);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
 std::vector<int> parse_devices(int device, const std::string &list);
 // newkmer_10nx.cpp:1017-1019 on every replica
@@ -130,38 +122,57 @@ private:
     std::unique_ptr<Impl> impl_;
 };
 
-// --hits (shared by the three front-ends): beside its result file a sample / job gets a hits file, named like it with
-// "result" replaced by "hits".  One line per read that was handed to process_read and has at least one k-mer hit, in
-// the reference's read order (all of file 0, then file 1, ...), tab-separated, the header line last:
+// The files a sample / job has beside its result file, each named like it with the last "result" replaced by a word
+// (".../x_result.txt" -> ".../x_hits.txt"), and when they are removed and written.
+//   --hits, "hits": one line per read that was handed to process_read and has at least one k-mer hit, in the
+// reference's read order (all of file 0, then file 1, ...), tab-separated, the header line last:
 //   <final_targ> <trimmed length> <n_kmers> <n_hits> <pos>:<target>:<entry> ... <header line as in _reads.txt>
-// The batches of files read at the same time interleave: the lines are held in memory per file and written in file
-// order by close() -- what is held is the hits file itself (reads without a hit leave nothing), nothing else.  A
-// writer that is not closed (its sample failed) leaves no file; one made with an empty path does nothing.
-// (The class holds lines per file, whatever they are: the segments file of --segments has a second one.)
-bool hits_option(int argc, char **argv);                 // is --hits among the arguments
-class HitsWriter {
+//   --min-hits / --confidence, "confident": a result file in the result file's format, from the counters of a second
+// sample per device that is tallied with every batch under the rule (kid_db_read_support*: gcount[confident]++ where
+// the result file has gcount[final]++).
+//   --segments, "segments": one line per read that was handed to process_read and has at least one k-mer hit, in the
+// order of the hits file, tab-separated, the header line last:
+//   <final_targ> <trimmed length> <n_segments> <segments with a hit> <pos>:<n_pos>:<n_kmers>:<n_hits>:<final>:<confident> ... <header>
+// Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0):
+// confident = final.  --min-base-quality applies as it does to the hits file.
+// Nothing else changes under any of them: the result and reads files and stdout are what they are without.
+// The batches of files read at the same time interleave: the hit and segment lines are held in memory per file and
+// written in file order by finish() -- what is held is the files themselves (reads without a hit leave nothing),
+// nothing else.  One that is not finished (its sample failed) leaves no hits and no segments file.
+class SampleOutputs {
 public:
-    explicit HitsWriter(const std::string &path); // removes a file left there by an earlier run
-    bool on() const { return !path_.empty(); }
-    void add(size_t file, const std::string &lines);
-    void close();
+    // removes the files of the options that are on, left there by an earlier run
+    SampleOutputs(const std::string &result_path, const SideOptions &side);
+    bool hits_on() const { return side_.hits; }
+    bool segments_on() const { return side_.segments.on; }
+    void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
+    void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
+    // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
+    // confident file, then the hits file, then the segments file
+    void finish(Engine &e);
 private:
-    std::string path_;
-    std::vector<std::string> parts_; // [file]
+    using Lines = std::vector<std::string>; // [file]
+    static void add(Lines &to, size_t file, const std::string &lines);
+    SideOptions side_;
+    std::string result_path_;
+    Lines hits_, segments_;
 };
+// For a front-end that takes a sample's outputs back: removes the files beside `result_path` of the options that are on
+// (a sample that never started: one left by an earlier run would stand beside no result) or, with `all`, every one a
+// sample may have written
+void remove_side_files(const std::string &result_path, const SideOptions &side, bool all = false);
 
 // Classify the files [first, first + count) of ONE sample, read at the same time (the two mates of nk10: two inflate
 // threads instead of one after the other); the counters do not care about the order, the read saver restores it.
 // `saver_file` is the saver's index of file `first` (a saver may span several calls: the files of a kmer_read_vf6 job,
 // -f1 and -f2 of kmer_read_m3).  done(f, handed), if given, is called for every file first + f in file order once all of
 // them are through, with the number of its reads handed to process_read.  Returns the reads handed of all the files.
-// `hits`, if given and on, receives the hit lines of every batch: the hit pass (kid_db_read_hits*) of a batch runs on the
-// device that classified it, once its final targets are back.  With e.support on, the support pass of a batch runs at the
-// same place and tallies into that device's confident sample.  `segments`, if given and on, receives the segment lines of
-// every batch under e.segments and e.support: the segments pass (kid_db_read_segments*) runs at the same place too.
-long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, size_t saver_file = 0,
-                    const std::function<void(size_t, long long)> &done = nullptr, HitsWriter *hits = nullptr,
-                    HitsWriter *segments = nullptr);
+// `out` receives the hit lines of every batch when its hits file is on: the hit pass (kid_db_read_hits*) of a batch runs on
+// the device that classified it, once its final targets are back.  With e.side.support on, the support pass of a batch
+// runs at the same place and tallies into that device's confident sample.  When its segments file is on, `out` receives
+// the segment lines of every batch under e.side: the segments pass (kid_db_read_segments*) runs at the same place too.
+long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, SampleOutputs &out, size_t saver_file = 0,
+                    const std::function<void(size_t, long long)> &done = nullptr);
 
 // One opener per path, each by `open`, which sets its bool when the file is a plain FASTA that is not there (the
 // reference's "nark <name>"): missing[f] holds it for file f once that file is through.  `missing` must not move
@@ -177,10 +188,7 @@ struct ReaderOptions {
     size_t batch_reads = 1 << 18;
     std::string dry_run;     // --dry-run FILE: host stages only (no GPU), for the CPU test-suite
     std::string db_cache;    // --db-cache FILE: binary cache of the parsed database
-    bool hits = false;       // --hits: a hits file beside the result file (ignored with --dry-run)
-    SupportRule support;     // --min-hits / --confidence: a confident result file beside the result file (ignored with --dry-run)
-    int min_base_quality = 0; // --min-base-quality: FASTQ bases below it are read as N (ignored with --dry-run)
-    SegmentsOption segments;  // --segments: a segments file beside the result file (ignored with --dry-run)
+    SideOptions side;        // side_options() of the same words
 };
 ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 
@@ -189,9 +197,5 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 // be written (perror(prog)).
 int write_dry_run(const std::string &path, const char *prog, const std::vector<int32_t> &parent, const ProbeSet &ps,
                   const std::vector<std::string> &labels, const std::vector<SourceOpener> &files, size_t batch_reads, int k);
-
-// gcount / ucount of the sample -> "<i>,<g>,<u>" lines; with e.support on, those of the tallied sample(s) -> the
-// confident file beside it
-void finish_sample(Engine &e, const std::string &result_path);
 
 } // namespace kidhost

@@ -6,9 +6,11 @@
 // What reaches the kernel: lookups give up after MAXREPROBE = 16 probes (:42,:232), so the table is
 // built sequentially on the host with the reference's exact cell geometry (results depend on it).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
-//   --min-hits N  --confidence F   also write DIR/confident.txt: the reads called by k-mer support (kid_driver.h)
-//   --segments LEN[:STEP]   also write DIR/segments.txt: long records called in segments (kid_driver.h)
-//   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N (kid_driver.h)
+// and the side options (SideOptions, kid_driver.h), whose files stand beside DIR/result.txt (SampleOutputs):
+//   --hits   every read's k-mer hits
+//   --min-hits N  --confidence F   the reads called by k-mer support
+//   --segments LEN[:STEP]   long records called in segments
+//   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -65,33 +67,27 @@ int main(int argc, char **argv)
         Engine eng;
         eng.batch_reads = opt.batch_reads;
         if (!engine_open(eng, ps, parent, k, opt.log2_slots, /*MAXREPROBE*/ 16, 0, parse_devices(opt.device, opt.device_list))) return 1;
-        engine_support(eng, opt.support);
-        engine_base_quality(eng, opt.min_base_quality);
-        eng.segments = opt.segments;
+        engine_configure(eng, opt.side);
         ps = ProbeSet();
 
         if (r1name.empty()) throw Fatal{134, "no -f1 given (std::out_of_range in the reference, :1080)"};
         std::cout << r1name.length() << " : " << r1name[r1name.length() - 1] << std::endl;
         Prefetcher pf(std::move(files), opt.threads, eng.batch_reads, eng.batch_bases);
-        HitsWriter hits(opt.hits ? sibling_path_for(wdir + "result.txt", "hits") : "");
-        HitsWriter segments(opt.segments.on ? sibling_path_for(wdir + "result.txt", "segments") : "");
-        if (opt.support.on) remove(sibling_path_for(wdir + "result.txt", "confident").c_str()); // (one left there by an earlier run)
+        SampleOutputs outputs(wdir + "result.txt", opt.side);
         ReadSaver saver("", num_targ); // the reads file is commented out in this program (:612-621)
         auto is_fagz = [](const std::string &n) { return ends_with(n, ".fasta.gz"); };
         if (is_fagz(r1name)) std::cout << "true" << std::endl; // process_fagz, :789
-        long long tct = run_files(eng, pf, 0, 1, saver, 0, nullptr, &hits, &segments);
+        long long tct = run_files(eng, pf, 0, 1, saver, outputs, 0);
         if (missing[0]) std::cout << "nark " << r1name << std::endl;
         std::cout << tct << " reads loaded" << std::endl;
         if (have2) {
             if (is_fagz(r2name)) std::cout << "true" << std::endl;
-            tct += run_files(eng, pf, 1, 1, saver, 1, nullptr, &hits, &segments);
+            tct += run_files(eng, pf, 1, 1, saver, outputs, 1);
             if (missing[1]) std::cout << "nark " << r2name << std::endl;
             if (ends_with(r2name, ".fastq.gz")) std::cout << tct << " reads loaded" << std::endl; // printed inside that branch too (:1107)
             std::cout << tct << " reads loaded" << std::endl;
         }
-        finish_sample(eng, wdir + "result.txt");
-        hits.close();
-        segments.close();
+        outputs.finish(eng);
         leave_now(0);
     } catch (const Fatal &f) {
         std::cerr << f.message << "\n";

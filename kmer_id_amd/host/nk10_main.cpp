@@ -89,10 +89,7 @@ int main(int argc, char **argv)
         else if (a == "--fasta") fasta_mode = true;
         else if (a == "--timing") timing = true;
         else if (a == "--samples-in-flight") in_flight = atoi(val("--samples-in-flight"));
-        else if (a == "--hits") {} // (hits_option below: the one place that reads it, shared with the sibling programs)
-        else if (a == "--min-hits" || a == "--confidence") { if (i + 1 < argc) i++; } // (support_option below, likewise)
-        else if (a == "--min-base-quality") { if (i + 1 < argc) i++; } // (base_quality_option below, likewise)
-        else if (a == "--segments") { if (i + 1 < argc) i++; } // (segments_option below, likewise)
+        else if (const int n = side_option_values(argv[i]); n >= 0) { if (i + n < argc) i += n; } // (side_options below reads them and their values)
         else if (dname.empty()) dname = a;
         else { std::cerr << "nk10: unexpected argument " << a << "\n"; return 2; }
     }
@@ -100,10 +97,7 @@ int main(int argc, char **argv)
         std::cerr << "usage: nk10 /path-to-fastq-files/ [--db-dir ./bact10/] [--ntar 5982] [--k 30] [--log2-slots 30] [--device 0]\n";
         return 2;
     }
-    const bool want_hits = hits_option(argc, argv); // <prefix>_hits.txt beside <prefix>_result.txt (ignored with --dry-run)
-    const SupportRule support = support_option(argc, argv, "nk10"); // <prefix>_confident.txt likewise
-    const int min_base_quality = base_quality_option(argc, argv, "nk10"); // (checked, then ignored, with --dry-run and --fasta)
-    const SegmentsOption segments = segments_option(argc, argv, "nk10"); // <prefix>_segments.txt (checked, then ignored, with --dry-run)
+    const SideOptions side = side_options(argc, argv, "nk10"); // (checked, then ignored, with --dry-run; --min-base-quality with --fasta too)
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
     if (batch_reads < 1) batch_reads = 1;
     if (threads < 1) threads = 1;
@@ -194,9 +188,7 @@ int main(int argc, char **argv)
         const std::vector<int> devices = parse_devices(device, device_list);
         if (gpu_warm.joinable()) gpu_warm.join();
         if (!engine_open(eng, ps, parent, k, log2_slots, 0, 0, devices)) return 1; // :256-260
-        engine_support(eng, support);
-        engine_base_quality(eng, min_base_quality);
-        eng.segments = segments;
+        engine_configure(eng, side);
         // file text goes into page-locked memory from here on: uploads by DMA, not through a CPU copy
         static int pin_device = devices[0];
         set_text_allocator([](size_t n) -> void * { void *p = nullptr; return kid_host_alloc(pin_device, n, &p) == KID_OK ? p : nullptr; },
@@ -259,32 +251,27 @@ int main(int argc, char **argv)
             engine_reset(e);
             out += prefix + "\n";
             long long tct = 0;
-            const std::string result_path = dname + prefix + "_result.txt";
-            HitsWriter hits(want_hits ? sibling_path_for(result_path, "hits") : "");
-            HitsWriter segs(segments.on ? sibling_path_for(result_path, "segments") : "");
-            if (support.on) remove(sibling_path_for(result_path, "confident").c_str()); // (one left there by an earlier run)
+            SampleOutputs outputs(dname + prefix + "_result.txt", side);
             {
                 ReadSaver saver(dname + prefix + "_reads.txt", ntar);
                 if (fasta_mode) {
-                    tct += run_files(e, pf, fi0, 1, saver, 0, nullptr, &hits, &segs);
+                    tct += run_files(e, pf, fi0, 1, saver, outputs);
                     if (missing[fi0]) out += "nark " + paths[fi0] + "\n";
                     out += std::to_string(tct) + " reads loaded\n";
                 } else {
                     // the two mates are inflated, indexed and classified at the same time; "<tct> reads loaded" (:1030,:1036)
                     // comes when a file is through, R1 first
-                    run_files(e, pf, fi0, 2, saver, 0, [&](size_t mate, long long handed) {
+                    run_files(e, pf, fi0, 2, saver, outputs, 0, [&](size_t mate, long long handed) {
                         tct += handed;
                         std::lock_guard<std::mutex> lk(om);
                         if (t_first_file < 0) t_first_file = since_start();
                         t_file_done[mate] = since_start();
                         out += std::to_string(tct) + " reads loaded\n";
-                    }, &hits, &segs);
+                    });
                 }
             }
             const double t_reads_written = since_start();
-            finish_sample(e, result_path);
-            hits.close();
-            segs.close();
+            outputs.finish(e);
             if (timing) {
                 char buf[256];
                 snprintf(buf, sizeof(buf), "{\"sample\": %zu, \"begin_s\": %.3f, \"r1_through_s\": %.3f, \"r2_through_s\": %.3f, \"reads_txt_written_s\": %.3f, "
@@ -339,17 +326,14 @@ int main(int argc, char **argv)
             // samples behind the failed one that were already through: the reference never got to them
             bool behind = false;
             for (size_t f = 0; f < n_samples; f++) {
-                if (behind && outs[f].done) {
-                    remove((dname + fnames[f] + "_result.txt").c_str());
-                    remove((dname + fnames[f] + "_reads.txt").c_str());
-                    remove((dname + fnames[f] + "_hits.txt").c_str());
-                    remove((dname + fnames[f] + "_confident.txt").c_str());
-                    remove((dname + fnames[f] + "_segments.txt").c_str());
-                } else if (behind) {
-                    // never started: a hits / confident file an earlier run left would stand beside no result of this one
-                    if (want_hits) remove((dname + fnames[f] + "_hits.txt").c_str());
-                    if (support.on) remove((dname + fnames[f] + "_confident.txt").c_str());
-                    if (segments.on) remove((dname + fnames[f] + "_segments.txt").c_str());
+                if (behind) {
+                    const std::string result_path = dname + fnames[f] + "_result.txt";
+                    if (outs[f].done) {
+                        remove(result_path.c_str());
+                        remove((dname + fnames[f] + "_reads.txt").c_str());
+                    }
+                    // never started: a side file an earlier run left would stand beside no result of this one
+                    remove_side_files(result_path, side, /*all=*/outs[f].done);
                 }
                 if (outs[f].failed) behind = true;
             }

@@ -8,9 +8,11 @@
 // Differences to nk10 that reach the kernel: U/u count as T (:496-500,521-525) and the number of
 // targets comes from the data file (:1073-1084).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
-//   --min-hits N  --confidence F   also write ./JOBS/<job>_confident.txt: the reads called by k-mer support (kid_driver.h)
-//   --segments LEN[:STEP]   also write ./JOBS/<job>_segments.txt: long records called in segments (kid_driver.h)
-//   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N (kid_driver.h)
+// and the side options (SideOptions, kid_driver.h), whose files stand beside ./JOBS/<job>_result.txt (SampleOutputs):
+//   --hits   every read's k-mer hits
+//   --min-hits N  --confidence F   the reads called by k-mer support
+//   --segments LEN[:STEP]   long records called in segments
+//   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -69,9 +71,7 @@ int main(int argc, char **argv)
         Engine eng;
         eng.batch_reads = opt.batch_reads;
         if (!engine_open(eng, ps, parent, k, opt.log2_slots, 0, KID_FLAG_U_IS_T, parse_devices(opt.device, opt.device_list))) return 1;
-        engine_support(eng, opt.support);
-        engine_base_quality(eng, opt.min_base_quality);
-        eng.segments = opt.segments;
+        engine_configure(eng, opt.side);
         ps = ProbeSet();
 
         Prefetcher pf(std::move(files), opt.threads, eng.batch_reads, eng.batch_bases);
@@ -81,22 +81,18 @@ int main(int argc, char **argv)
             engine_reset(eng);
             const std::string base = "./" + jname + "/" + jstr;
             long long tct = 0;
-            HitsWriter hits(opt.hits ? sibling_path_for(base + "_result.txt", "hits") : "");
-            HitsWriter segments(opt.segments.on ? sibling_path_for(base + "_result.txt", "segments") : "");
-            if (opt.support.on) remove(sibling_path_for(base + "_result.txt", "confident").c_str()); // (one left there by an earlier run)
+            SampleOutputs outputs(base + "_result.txt", opt.side);
             {
                 ReadSaver saver(base + "_reads.txt", num_targ, save_target > 0 ? base + "_target_reads.txt" : "",
                                 (uint32_t)(save_target > 0 ? save_target : 0), save_target == 0);
                 for (int i = 0; i < jobs.n_inputs(j); i++, fi++) {
                     std::cout << names[fi] << std::endl;
-                    tct += run_files(eng, pf, fi, 1, saver, (size_t)i, nullptr, &hits, &segments);
+                    tct += run_files(eng, pf, fi, 1, saver, outputs, (size_t)i);
                     if (missing[fi]) std::cout << "nark " << names[fi] << std::endl;
                 }
             }
             std::cout << tct << " reads loaded" << std::endl;
-            finish_sample(eng, base + "_result.txt");
-            hits.close();
-            segments.close();
+            outputs.finish(eng);
         }
         leave_now(0);
     } catch (const Fatal &f) {

@@ -117,23 +117,31 @@ def test_nk10_hits_with_dry_run_is_ignored(nk10, gold_dir, tmp_path):  # noqa: F
     assert os.path.getsize(dump) > 0 and not [f for f in os.listdir(fq) if f.endswith("_hits.txt")]
 
 
-def test_nk10_failing_sample_leaves_no_hits_file(nk10, gold_dir, tmp_path):  # noqa: F811
+@pytest.mark.parametrize("options, words", [(["--hits"], ["hits"]),
+                                            (["--hits", "--min-hits", "2", "--segments", "40:20"], ["hits", "confident", "segments"])],
+                         ids=["hits", "all-side-files"])
+def test_nk10_failing_sample_leaves_no_hits_file(nk10, gold_dir, tmp_path, options, words):  # noqa: F811
     cwd = str(tmp_path)
     src, fq, parent = stage_small(gold_dir, cwd)
     p = os.path.join(fq, "S2_R2_tr.fastq.gz")
     raw = open(p, "rb").read()
     open(p, "wb").write(raw[:len(raw) * 2 // 3])  # cut off: everything in front is read, then "failed gzclose", exit 255
     for prefix in ("S1", "S2"):
-        open(os.path.join(fq, prefix + "_hits.txt"), "w").write("left by an earlier run\n")
-    r = subprocess.run([nk10, fq + "/", "--log2-slots", "22", "--hits", "--samples-in-flight", "1"], cwd=cwd, stdout=subprocess.PIPE,
+        for word in words:
+            open(os.path.join(fq, "%s_%s.txt" % (prefix, word)), "w").write("left by an earlier run\n")
+    r = subprocess.run([nk10, fq + "/", "--log2-slots", "22", "--samples-in-flight", "1"] + options, cwd=cwd, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE)
     assert r.returncode == 255 and b"failed gzclose" in r.stderr
-    assert not os.path.exists(os.path.join(fq, "S2_hits.txt")) and not os.path.exists(os.path.join(fq, "S2_result.txt"))
+    for word in words + ["result"]:
+        assert not os.path.exists(os.path.join(fq, "S2_%s.txt" % word)), word
     # S1 is whole if the directory order put it first, and was never started (or was taken back) otherwise
-    s1 = os.path.join(fq, "S1_hits.txt")
-    assert os.path.exists(s1) == os.path.exists(os.path.join(fq, "S1_result.txt"))
-    if os.path.exists(s1):
-        assert b"left by an earlier run" not in open(s1, "rb").read()
+    whole = os.path.exists(os.path.join(fq, "S1_result.txt"))
+    for word in words:
+        s1 = os.path.join(fq, "S1_%s.txt" % word)
+        assert os.path.exists(s1) == whole, word
+        if whole:
+            assert b"left by an earlier run" not in open(s1, "rb").read(), word
+    if whole:
         assert filecmp.cmp(os.path.join(fq, "S1_result.txt"), os.path.join(src, "S1_result.txt"), shallow=False)
 
 

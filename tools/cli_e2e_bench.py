@@ -2,7 +2,8 @@
 """End-to-end rate of the nk10 program (FASTQ.gz directory in -> _result.txt out) on a GPU box:
 synthetic bact10 DB at a small scale (the text DB load is not what is measured), S samples of P
 pairs, reader-thread counts 1/2/4/8.  Prints reads/s per configuration (wall clock of the whole
-process minus the DB load measured on an empty directory)."""
+process minus the DB load measured on an empty directory).
+   python tools/cli_e2e_bench.py [nk10 binaries to compare on the same inputs, alternated, REPEATS (1) times each]"""
 import os
 import subprocess
 import sys
@@ -15,7 +16,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 from kmer_id_amd import _build, synth  # noqa: E402
 
 S, P, L, K = int(os.environ.get("S", 4)), int(os.environ.get("P", 250000)), 150, 30
-nk10 = _build.build_cli()
+binaries = [os.path.abspath(b) for b in sys.argv[1:]] or [_build.build_cli()]
+REPEATS = int(os.environ.get("REPEATS", 1))
 cwd = tempfile.mkdtemp(prefix="e2e_")
 parent, cnt = synth.load_taxonomy("bact10")
 cum = synth.cumulative(synth.scaled_counts(cnt, 0.01))
@@ -37,13 +39,16 @@ for s in range(S):
         synth.write_fastq_gz(fq + "S%d_R%d_tr.fastq.gz" % (s, mate), synth.reads(cum, parent, P, L, K, r0=r0), synth.qualities(P, L, r0=r0), L, mate=mate)
 print("inputs generated in %.0f s: %d samples x %d pairs, %.0f MB gz" % (time.time() - t0, S, P, sum(os.path.getsize(fq + f) for f in os.listdir(fq)) / 1e6), flush=True)
 cache = os.path.join(cwd, "db.kidx")
-def run(d, threads):
+def run(nk10, d, threads):
     t = time.time()
     subprocess.run([nk10, d, "--log2-slots", "24", "--db-cache", cache, "--threads", str(threads)], cwd=cwd, check=True, stdout=subprocess.DEVNULL)
     return time.time() - t
-run(empty, 1)              # writes the cache
-base = min(run(empty, 1) for _ in range(2))
+run(binaries[0], empty, 1)  # writes the cache
+base = min(run(nk10, empty, 1) for nk10 in binaries for _ in range(2))
 print("startup (DB from cache + table build + GPU init): %.2f s" % base)
 for threads in (1, 2, 4, 8):
-    w = run(fq, threads)
-    print("threads %d: %.2f s wall, %.2f s net -> %.2f M reads/s (%.2f M pairs/s)" % (threads, w, w - base, 2 * S * P / (w - base) / 1e6, S * P / (w - base) / 1e6), flush=True)
+    for r in range(REPEATS):
+        for nk10 in binaries[::1 if r % 2 == 0 else -1]:  # (who goes first takes turns)
+            w = run(nk10, fq, threads)
+            print("%sthreads %d: %.2f s wall, %.2f s net -> %.2f M reads/s (%.2f M pairs/s)" % (
+                nk10 + " " if len(binaries) > 1 else "", threads, w, w - base, 2 * S * P / (w - base) / 1e6, S * P / (w - base) / 1e6), flush=True)
