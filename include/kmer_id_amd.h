@@ -121,6 +121,10 @@ int kid_sample_begin(kid_db *db, kid_sample **out);
                                      kid_classify_fastq_async after the call have every base of quality below Q read as 'N'
                                      ("mask low-quality bases" below).  Like the other options it stays until it is set again;
                                      kid_sample_reset does not change it */
+#define KID_OPT_ENTRY_DEPTH 4 /* value 1: the sample gets one uint32 counter per database entry, zeroed ("k-mer depth per
+                                database entry" below); setting 1 again while it is on changes nothing.  value 0 frees the
+                                counters and loses the counts.  Any other value is KID_ERR_ARG.  kid_sample_reset zeroes the
+                                counters and leaves the option on */
 int kid_sample_set_option(kid_sample *s, int option, int value);
 int kid_sample_reset(kid_sample *s);
 void kid_sample_destroy(kid_sample *s);
@@ -427,6 +431,41 @@ int kid_sample_gcount(kid_sample *s, int64_t *gcount);
 /* ucount contribution of the bitmap bits (entry ordinals) [bit_begin, bit_end): multiples of 128, at most
  * 8 * kid_sample_seen_bytes (byte ranges of the bitmap helpers above are multiples of 16) */
 int kid_sample_ucount_range(kid_sample *s, uint64_t bit_begin, uint64_t bit_end, int64_t *ucount);
+
+/* ---- k-mer depth per database entry -------------------------------------------------
+ * gcount says how many reads a target got and ucount how many of its database k-mers were hit at all.  With
+ * KID_OPT_ENTRY_DEPTH on, a sample also counts HOW OFTEN each was hit: depth[o], one uint32 per database entry in the
+ * numbering of the seen-bitmap and of kid_hit.entry.  A target whose hits are spread evenly over its k-mers is an organism
+ * that is there, and its depth is its abundance; a handful of k-mers hit thousands of times is a conserved or
+ * contaminating region.
+ * Depth is counted by tallies alone: when kid_db_read_support / kid_db_read_support_fastq gets such a sample as `tally`,
+ * every hit with target > 1 of every read it counts with confident > 0 adds 1 to depth[entry] -- exactly the hits whose
+ * seen bit the tally sets; a k-mer that occurs twice in a read adds 2.  kid_classify_* into the same sample add no depth
+ * (they do not visit hits one by one), so for a sample that was only tallied depth[o] > 0 exactly where seen bit o is set.
+ * Counters saturate at 2^32 - 1.  gcount, ucount and the bitmap of the sample are what they are with the option off.
+ * With the option off the calls below return KID_ERR_STATE and nothing is allocated, launched or compared anywhere.
+ * All of them synchronise the sample's queued work first; none changes gcount, the bitmap or whether the sample has
+ * ended, and they may be called before or after kid_sample_end.
+ *   kid_sample_depth_export    the counters of the entries [entry_begin, entry_begin + n) -> dst (uint32[n], host or device);
+ *                              a range beyond the database's n_entries is KID_ERR_ARG
+ *   kid_sample_depth_add       a saturating add of src (uint32[n]) onto the same range: the companion of kid_sample_seen_or
+ *                              and, with the export, the building block of a one-process-per-GPU merge
+ *   kid_sample_depth_spectrum  bins in 2..4096 (KID_ERR_ARG beyond); every output is nullable
+ *       spectrum[ntar * bins]  spectrum[t * bins + b] = the entries o with targets[o] == t and depth[o] == b for
+ *                              b < bins - 1; the last column counts depth[o] >= bins - 1.  Column 0 holds the entries never
+ *                              hit (duplicates of an earlier key and target-0 entries among them): a row sums to the
+ *                              number of entries of that target handed to the builder
+ *       ksum[ntar]             the sum of depth over the target's entries
+ *       dmax[ntar]             the largest depth among them
+ *                              It does not change the sample and may be repeated.
+ *   kid_sample_depth_spectrum_merged  the same for ONE input sample dealt over n DISTINCT kid_sample objects on replicas
+ *                              (a sample named twice: KID_ERR_ARG), every one with the option on: the counters are summed
+ *                              with saturation into scratch on samples[0]'s device and the spectrum is that of the sum.  No
+ *                              sample's counters change; a second call returns the same.                                */
+int kid_sample_depth_export(kid_sample *s, uint64_t entry_begin, uint64_t n, void *dst, int dst_on_device);
+int kid_sample_depth_add(kid_sample *s, uint64_t entry_begin, uint64_t n, const void *src, int src_on_device);
+int kid_sample_depth_spectrum(kid_sample *s, uint32_t bins, uint64_t *spectrum, uint64_t *ksum, uint32_t *dmax);
+int kid_sample_depth_spectrum_merged(kid_sample **samples, int n, uint32_t bins, uint64_t *spectrum, uint64_t *ksum, uint32_t *dmax);
 
 /* ---- probe-database builder ------------------------------------------------------------------------------------
  * Replaces the table of kmer_build_vf6.cpp (Hashtable, :132-215) and its three passes (process_seq, process_seq3,

@@ -361,6 +361,18 @@ def end_merged(samples):
     return g, u
 
 
+def depth_spectrum_merged(samples, bins=256):
+    """The depth spectrum of one sample of the input dealt out over several Sample objects (one per GPU / replica), every
+    one with KID_OPT_ENTRY_DEPTH on -> (spectrum[ntar, bins], ksum, dmax) of the summed counters; no sample changes."""
+    lib = _lib.load()
+    n = len(samples)
+    arr = (C.c_void_p * n)(*[s._h for s in samples])
+    ntar = samples[0].ntar
+    spectrum, ksum, dmax = np.empty((ntar, bins), np.uint64), np.empty(ntar, np.uint64), np.empty(ntar, np.uint32)
+    check(lib.kid_sample_depth_spectrum_merged(arr, n, bins, _ptr(spectrum), _ptr(ksum), _ptr(dmax)))
+    return spectrum, ksum, dmax
+
+
 class Sample:
     """Per-sample counters; replaces the reset at newkmer_10nx.cpp:1017-1019."""
 
@@ -509,6 +521,27 @@ class Sample:
             check(self._lib.kid_sample_seen_or(self._h, byte_off, src.size, _ptr(src), 0))
         else:
             check(self._lib.kid_sample_seen_or(self._h, byte_off, nbytes, C.c_void_p(src), 1 if on_device else 0))
+
+    def depth_spectrum(self, bins=256):
+        """Under KID_OPT_ENTRY_DEPTH -> (spectrum[ntar, bins], ksum[ntar], dmax[ntar]): per target, the number of its
+        database entries hit b times (the last column: bins - 1 times or more; column 0: never), the sum of the counters
+        and the largest (kid_sample_depth_spectrum)."""
+        spectrum, ksum, dmax = np.empty((self.ntar, bins), np.uint64), np.empty(self.ntar, np.uint64), np.empty(self.ntar, np.uint32)
+        check(self._lib.kid_sample_depth_spectrum(self._h, bins, _ptr(spectrum), _ptr(ksum), _ptr(dmax)))
+        return spectrum, ksum, dmax
+
+    def entry_depth(self, begin=0, end=None):
+        """-> uint32[end - begin]: how often the tallies hit the database entries [begin, end) (end=None: the last entry)"""
+        if end is None:
+            end = self.db.info.n_entries
+        out = np.empty(max(int(end) - int(begin), 0), np.uint32)
+        check(self._lib.kid_sample_depth_export(self._h, begin, out.size, _ptr(out), 0))
+        return out
+
+    def depth_add(self, begin, array):
+        """a saturating add of `array` (uint32) onto the counters of the entries from `begin` on (kid_sample_depth_add)"""
+        array = _as(array, np.uint32)
+        check(self._lib.kid_sample_depth_add(self._h, begin, array.size, _ptr(array), 0))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1,7 +1,7 @@
 // kid_api.hip -- C ABI (include/kmer_id_amd.h) over the gfx950 kernels: the one translation unit of the library.
 // Here: the sample handle, the pacing of the hit log, kid_launch_classify and the classify entry points -- the launch
 // path a counter profile depends on.  The other areas are the kid_api_*.h files included below (kid_api_support.h
-// at the end: it counts into a sample; kid_api_segments.h behind it).  Host side only:
+// at the end: it counts into a sample; kid_api_segments.h and kid_api_depth.h behind it).  Host side only:
 // handle bookkeeping and launches; no classification work is done on the CPU.
 #include <hip/hip_runtime.h>
 #include <memory>
@@ -20,6 +20,7 @@
 #include "kid_support.hip.h"
 #include "kid_segments.hip.h"
 #include "kid_mask.hip.h"
+#include "kid_depth.hip.h"
 #include "kid_api_core.h"
 #include "kid_api_db.h"
 #include "kid_api_mask.h"
@@ -37,6 +38,7 @@ struct kid_sample {
     KidDevBuf stats;          // unsigned long long [32]: [0..7] counters, [8..31] KID_PROFILE phase cycles
     KidDevBuf seen;           // uint32: the bitmap
     uint64_t seen_words = 0;
+    KidDevBuf depth;          // uint32 per entry (padded like the bitmap), while KID_OPT_ENTRY_DEPTH is on: kid_api_depth.h
     bool timing = false;
     std::vector<std::pair<KidEvent, KidEvent>> timed; // around each classify launch, while timing is on
     uint64_t timed_batches = 0;
@@ -154,6 +156,7 @@ extern "C" int kid_sample_reset(kid_sample *s)
     s->launches_since_apply = 0;
     s->reads_since_apply = 0;
     KID_HIP(hipMemset(s->seen.p, 0, s->seen_words * 4));
+    if (s->depth.p) KID_HIP(hipMemset(s->depth.p, 0, s->seen_words * 32 * 4));
     KID_HIP(hipDeviceSynchronize());
     return KID_OK;
 }
@@ -495,6 +498,7 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
     return KID_OK;
 }
 
+static int kid_depth_set_option(kid_sample *s, int value); // kid_api_depth.h
 extern "C" int kid_sample_set_option(kid_sample *s, int option, int value)
 {
     if (!s) return kid_fail(KID_ERR_ARG, "null sample");
@@ -509,6 +513,7 @@ extern "C" int kid_sample_set_option(kid_sample *s, int option, int value)
         if (rc == KID_OK) s->min_base_quality = value;
         return rc;
     }
+    case KID_OPT_ENTRY_DEPTH: return kid_depth_set_option(s, value);
     default: return kid_fail(KID_ERR_ARG, "unknown option %d", option);
     }
 }
@@ -989,3 +994,4 @@ extern "C" int kid_sample_seen_or(kid_sample *s, uint64_t byte_off, uint64_t nby
 
 #include "kid_api_support.h"
 #include "kid_api_segments.h"
+#include "kid_api_depth.h"

@@ -16,6 +16,7 @@ struct kid_db {
     KidDevBuf table, rows, parent, depth;
     KidDevBuf ord_target;   // uint32: target of entry o as handed to the builder, padded with zeros to a multiple of 128
     uint64_t seen_bits = 0; // entries rounded up to whole 16-byte groups of the seen-bitmap
+    KidDevBuf entries_per_target; // unsigned long long [ntar]: made under hits_mu by the first depth spectrum (kid_api_depth.h)
     kid_db_info info{};
     std::unique_ptr<struct KidHitsState> hits; // scratch of kid_db_read_hits*, made by the first call (kid_api_hits.h)
     std::mutex hits_mu;

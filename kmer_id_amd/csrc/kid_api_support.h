@@ -35,13 +35,16 @@ static int kid_support_launch(kid_db *db, KidHitsState *h, const uint64_t *d_hit
                               uint64_t n, KidSupportRule rule, KidSupport *d_out, const KidSupportTally *t, hipStream_t stream)
 {
     const dim3 grid(kid_grid_for(n, 256, db->num_cu * 8)), block(256);
-    const KidSupportTally none{nullptr, nullptr, nullptr};
+    const KidSupportTally none{nullptr, nullptr, nullptr, nullptr};
     int rc = h->support.begin(stream);
     if (rc != KID_OK) return rc;
     kid_lift(db->d.rows != nullptr, [&](auto rows) {
         kid_lift(t != nullptr, [&](auto tally) {
-            hipLaunchKernelGGL((kid_support_kernel<decltype(rows)::value, decltype(tally)::value>), grid, block, 0, stream, db->d, d_hit_offsets,
-                               d_hits, d_n_kmers, n, rule, d_out, t ? *t : none);
+            kid_lift(t != nullptr && t->depth != nullptr, [&](auto depth) { // the depth form exists for a tally alone
+                if constexpr (decltype(tally)::value || !decltype(depth)::value)
+                    hipLaunchKernelGGL((kid_support_kernel<decltype(rows)::value, decltype(tally)::value, decltype(depth)::value>), grid, block, 0,
+                                       stream, db->d, d_hit_offsets, d_hits, d_n_kmers, n, rule, d_out, t ? *t : none);
+            });
         });
     });
     KID_HIP(hipGetLastError());
@@ -62,13 +65,14 @@ static int kid_support_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, 
     // what the prepare kernels refuse (a range outside its read, a short quality line) is refused before anything is counted
     if ((rc = kid_hits_check(h)) != KID_OK) return rc;
     hipStream_t st = 0;
-    KidSupportTally t{nullptr, nullptr, nullptr};
+    KidSupportTally t{nullptr, nullptr, nullptr, nullptr};
     if (tally) {
         st = tally->stream.s;
         if ((rc = kid_sample_order_behind(tally, st)) != KID_OK) return rc;
         t.gcount = tally->gcount.as<unsigned long long>();
         t.seen = tally->seen.as<uint32_t>();
         t.fastq_desc = recs ? h->desc.as<KidReadDesc>() : nullptr;
+        t.depth = tally->depth.as<uint32_t>(); // null unless KID_OPT_ENTRY_DEPTH is on
     }
     rc = kid_support_launch(db, h, h->out_offsets.as<uint64_t>(), total ? h->out_hits.as<KidHit>() : nullptr, h->out_nk.as<uint32_t>(), n, rule,
                             out ? h->out_support.as<KidSupport>() : nullptr, tally ? &t : nullptr, st);

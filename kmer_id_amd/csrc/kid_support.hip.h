@@ -19,9 +19,11 @@
 // kid_tile.hip.h) -- a left fold in hit order either way.  Pure and without atomics: byte-identical across runs.
 // The TALLY variant also counts the batch into a sample as if it had been classified under the rule: gcount[confident]++
 // per counted read, and for reads with confident > 0 the seen bit of every hit with target > 1 (plain global atomics).
+// Its DEPTH form (KID_OPT_ENTRY_DEPTH) also adds 1 to depth[entry] beside every seen bit it sets (kid_depth.hip.h).
 #pragma once
 #include "kid_tile.hip.h"
 #include "kid_hits.hip.h"
+#include "kid_depth.hip.h"
 
 #define KID_SUPPORT_LANE_HITS 8u // a read with more hits than this is taken by the whole wave
 
@@ -38,7 +40,18 @@ struct KidSupportTally {
     // nowhere (a kept one has stop - start >= k, i.e. at least two windows).  null: every read of the batch is counted,
     // one shorter than k under target 0.
     const KidReadDesc *fastq_desc;
+    uint32_t *depth; // the DEPTH form alone: one saturating counter per entry
 };
+
+// what a tally does with one hit of a read it counted with confident > 0
+template <bool DEPTH>
+__device__ __forceinline__ void kid_support_tally_hit(const KidSupportTally &tally, const KidHit &h)
+{
+    if (h.target > 1) {
+        atomicOr(&tally.seen[h.entry >> 5], 1u << (h.entry & 31u));
+        if (DEPTH) kid_depth_count(tally.depth, h.entry);
+    }
+}
 
 __device__ __forceinline__ bool kid_support_passes(uint32_t s, uint32_t n, const KidSupportRule &rule)
 {
@@ -176,7 +189,7 @@ __device__ __forceinline__ void kid_support_wave(const KidDevDb &db, const KidHi
     }
 }
 
-template <bool ROWS, bool TALLY>
+template <bool ROWS, bool TALLY, bool DEPTH>
 __global__ __launch_bounds__(256) void kid_support_kernel(const KidDevDb db, const uint64_t *hit_offsets, const KidHit *hits,
                                                            const uint32_t *n_kmers, uint64_t n_reads, const KidSupportRule rule,
                                                            KidSupport *out /* nullable */, const KidSupportTally tally)
@@ -199,10 +212,7 @@ __global__ __launch_bounds__(256) void kid_support_kernel(const KidDevDb db, con
         if (m > 0 && m <= KID_SUPPORT_LANE_HITS) {
             kid_support_lane<ROWS>(db, hits + h0, m, rule, res);
             if (TALLY && counted && res.confident > 0)
-                for (uint32_t i = 0; i < m; i++) {
-                    const KidHit h = hits[h0 + i];
-                    if (h.target > 1) atomicOr(&tally.seen[h.entry >> 5], 1u << (h.entry & 31u));
-                }
+                for (uint32_t i = 0; i < m; i++) kid_support_tally_hit<DEPTH>(tally, hits[h0 + i]);
         }
         uint64_t big = __ballot(m > KID_SUPPORT_LANE_HITS);
         while (big) { // the reads of the 64 with more hits: the whole wave, one after the other
@@ -214,10 +224,7 @@ __global__ __launch_bounds__(256) void kid_support_kernel(const KidDevDb db, con
             kid_support_wave<ROWS>(db, wh, wm, rule, lane, w);
             if (TALLY && w.confident > 0 && ((__ballot(counted) >> j) & 1ull))
                 for (uint32_t c0 = 0; c0 < wm; c0 += 64u)
-                    if (lane < wm - c0) {
-                        const KidHit h = wh[(uint64_t)c0 + lane];
-                        if (h.target > 1) atomicOr(&tally.seen[h.entry >> 5], 1u << (h.entry & 31u));
-                    }
+                    if (lane < wm - c0) kid_support_tally_hit<DEPTH>(tally, wh[(uint64_t)c0 + lane]);
             if (lane == (uint32_t)j) res = w;
         }
         if (have && out) out[r] = res;

@@ -97,8 +97,13 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
 void engine_configure(Engine &e, const SideOptions &side)
 {
     e.side = side;
-    if (side.support.on)
+    if (side.support.on || side.depth)
         for (kid_db *d : e.dbs) e.confident.push_back(begin_sample_or_die(d));
+    if (side.depth)
+        for (kid_sample *s : e.confident) {
+            int rc = kid_sample_set_option(s, KID_OPT_ENTRY_DEPTH, 1);
+            if (rc != KID_OK) die_kid(rc);
+        }
     const int q = side.min_base_quality;
     if (q == 0) return;
     for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
@@ -372,16 +377,19 @@ static void read_segments(SideOptions &o, const char *prog, const char *opt, con
     o.segments = SegmentsOption{true, (uint32_t)len, (uint32_t)step};
 }
 
-// The side options: their words, the pass of side_options() that reads each, what reads its value (none: a switch)
+// The side options: their words, the pass of side_options() that reads each, what reads its value -- or, for a switch,
+// which takes none, the flag it sets
 static const struct {
     const char *name;
     int pass;
     void (*read)(SideOptions &, const char *prog, const char *opt, const char *v);
-} kSideOptions[] = {{"--hits", 0, nullptr},
-                    {"--min-hits", 0, read_min_hits},
-                    {"--confidence", 0, read_confidence},
-                    {"--min-base-quality", 1, read_base_quality},
-                    {"--segments", 2, read_segments}};
+    bool SideOptions::*flag;
+} kSideOptions[] = {{"--hits", 0, nullptr, &SideOptions::hits},
+                    {"--min-hits", 0, read_min_hits, nullptr},
+                    {"--confidence", 0, read_confidence, nullptr},
+                    {"--min-base-quality", 1, read_base_quality, nullptr},
+                    {"--segments", 2, read_segments, nullptr},
+                    {"--depth", 0, nullptr, &SideOptions::depth}};
 
 int side_option_values(const char *word)
 {
@@ -398,7 +406,7 @@ SideOptions side_options(int argc, char **argv, const char *prog)
         for (int i = 1; i < argc; i++)
             for (const auto &so : kSideOptions) {
                 if (so.pass != pass || strcmp(argv[i], so.name) != 0) continue;
-                if (!so.read) { o.hits = true; continue; }
+                if (!so.read) { o.*so.flag = true; continue; }
                 if (i + 1 >= argc) usage_error(prog, so.name, "needs a value");
                 so.read(o, prog, so.name, argv[i + 1]);
             }
@@ -415,10 +423,10 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments; };
+struct SidePaths { std::string hits, confident, segments, depth; };
 static SidePaths side_paths(const std::string &r)
 {
-    return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments")};
+    return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth")};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -427,6 +435,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.hits) remove(p.hits.c_str());
     if (all || side.segments.on) remove(p.segments.c_str());
     if (all || side.support.on) remove(p.confident.c_str());
+    if (all || side.depth) remove(p.depth.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -458,11 +467,41 @@ static void write_counters(std::vector<kid_sample *> &samples, int ntar, const s
     write_result(path, g, u);
 }
 
+// The depth spectrum (256 bins) of the tallied sample (one per device, merged) -> "<i>,<kmer_hits>,<distinct>,<q1>,<q2>,<q3>,<max>"
+// lines: distinct = the target's entries with a hit; q_p = the smallest depth d >= 1 with 4 * #{entries: 1 <= depth <= d}
+// >= p * distinct, the last column taken as d = 255; 0 without a hit
+static void write_depth(std::vector<kid_sample *> &samples, int ntar, const std::string &path)
+{
+    const uint32_t bins = 256;
+    std::vector<uint64_t> spectrum((size_t)ntar * bins), ksum((size_t)ntar);
+    std::vector<uint32_t> dmax((size_t)ntar);
+    int rc = kid_sample_depth_spectrum_merged(samples.data(), (int)samples.size(), bins, spectrum.data(), ksum.data(), dmax.data());
+    if (rc != KID_OK) die_kid(rc);
+    std::string text;
+    char line[160];
+    for (int i = 0; i < ntar; i++) {
+        const uint64_t *row = &spectrum[(size_t)i * bins];
+        uint64_t distinct = 0, below = 0;
+        for (uint32_t d = 1; d < bins; d++) distinct += row[d];
+        uint32_t q[3] = {0, 0, 0};
+        int p = 0;
+        for (uint32_t d = 1; d < bins && p < 3 && distinct; d++) {
+            below += row[d];
+            while (p < 3 && 4 * below >= (uint64_t)(p + 1) * distinct) q[p++] = d;
+        }
+        const int n = snprintf(line, sizeof(line), "%d,%llu,%llu,%u,%u,%u,%u\n", i, (unsigned long long)ksum[(size_t)i],
+                               (unsigned long long)distinct, q[0], q[1], q[2], dmax[(size_t)i]);
+        text.append(line, (size_t)n);
+    }
+    write_lines(path, std::vector<std::string>(1, text));
+}
+
 void SampleOutputs::finish(Engine &e)
 {
     const SidePaths p = side_paths(result_path_);
     write_counters(e.samples, e.ntar, result_path_);
     if (side_.support.on) write_counters(e.confident, e.ntar, p.confident);
+    if (side_.depth) write_depth(e.confident, e.ntar, p.depth);
     if (side_.hits) write_lines(p.hits, hits_);
     if (side_.segments.on) write_lines(p.segments, segments_);
     hits_.clear();
@@ -593,7 +632,8 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             hit_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.k, lines);
             out.add_hits(saver_file + f.file, lines);
         }
-        // (the support pass: nothing comes back, the batch is tallied into the device's confident sample under the rule)
+        // (the support pass: nothing comes back, the batch is tallied into the device's confident sample under the rule --
+        // (0, 0) when --depth runs it without one)
         if (f.confident)
             read_pass(kid_db_read_support_fastq, kid_db_read_support, f.db, *f.batch, f.bases(), e.side.support.min_hits,
                       e.side.support.min_permille, (kid_support *)nullptr, f.confident);
@@ -616,7 +656,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             const size_t nr = f.batch->size();
             f.sample = e.samples[e.next_sample]; // batches are dealt round-robin over the devices
             f.db = e.dbs[e.next_sample];
-            f.confident = e.side.support.on ? e.confident[e.next_sample] : nullptr;
+            f.confident = e.confident.empty() ? nullptr : e.confident[e.next_sample];
             e.next_sample = (e.next_sample + 1) % e.samples.size();
             int rc;
             const auto t_sub = std::chrono::steady_clock::now();

@@ -39,6 +39,9 @@ struct SideOptions {
     // changes nothing.
     int min_base_quality = 0;
     SegmentsOption segments;
+    // --depth (no value): k-mer depth per database entry (KID_OPT_ENTRY_DEPTH), summed up per target in a depth file.  The
+    // support pass runs for it under the rule of --min-hits / --confidence when given, else (0, 0).
+    bool depth = false;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
@@ -58,7 +61,8 @@ struct Engine {
     std::vector<kid_db *> dbs;
     std::vector<kid_sample *> samples;
     size_t next_sample = 0;
-    // the side options (engine_configure) and, under --min-hits / --confidence, one tallied sample per device
+    // the side options (engine_configure) and, under --min-hits / --confidence or --depth, one tallied sample per device
+    // (with the depth counters on under --depth)
     SideOptions side;
     std::vector<kid_sample *> confident;
     int ntar = 0, k = 30;
@@ -91,8 +95,8 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 // exits with 1).
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
-// The side options for an engine that is open: with a rule one more sample per device (reset, closed and destroyed with
-// the others), then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
+// The side options for an engine that is open: with a rule or --depth one more sample per device (reset, closed and
+// destroyed with the others; --depth switches its depth counters on), then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
 // A worker of engine_worker() inherits them for its samples.
 void engine_configure(Engine &e, const SideOptions &side);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
@@ -133,6 +137,11 @@ private:
 //   --segments, "segments": one line per read that was handed to process_read and has at least one k-mer hit, in the
 // order of the hits file, tab-separated, the header line last:
 //   <final_targ> <trimmed length> <n_segments> <segments with a hit> <pos>:<n_pos>:<n_kmers>:<n_hits>:<final>:<confident> ... <header>
+//   --depth, "depth": ntar lines <i>,<kmer_hits>,<distinct>,<q1>,<q2>,<q3>,<max>, integers, from the depth spectrum
+// (256 bins) of the tallied sample(s): the hits on the target's database k-mers by the reads the rule calls, how many of
+// its k-mers were hit, the quartiles of their depth (the smallest d >= 1 with 4 * #{1 <= depth <= d} >= p * distinct;
+// depths of 255 and more count as 255; 0 without a hit) and the largest depth.  Its column 3 is the column 3 of the
+// confident file, or of the result file without a rule.
 // Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0):
 // confident = final.  --min-base-quality applies as it does to the hits file.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
@@ -148,7 +157,7 @@ public:
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
-    // confident file, then the hits file, then the segments file
+    // confident file, then the depth file, then the hits file, then the segments file
     void finish(Engine &e);
 private:
     using Lines = std::vector<std::string>; // [file]
@@ -168,8 +177,8 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
 // -f1 and -f2 of kmer_read_m3).  done(f, handed), if given, is called for every file first + f in file order once all of
 // them are through, with the number of its reads handed to process_read.  Returns the reads handed of all the files.
 // `out` receives the hit lines of every batch when its hits file is on: the hit pass (kid_db_read_hits*) of a batch runs on
-// the device that classified it, once its final targets are back.  With e.side.support on, the support pass of a batch
-// runs at the same place and tallies into that device's confident sample.  When its segments file is on, `out` receives
+// the device that classified it, once its final targets are back.  With e.side.support or e.side.depth on, the support
+// pass of a batch runs at the same place and tallies into that device's confident sample.  When its segments file is on, `out` receives
 // the segment lines of every batch under e.side: the segments pass (kid_db_read_segments*) runs at the same place too.
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, SampleOutputs &out, size_t saver_file = 0,
                     const std::function<void(size_t, long long)> &done = nullptr);

@@ -10,6 +10,7 @@
 //   --hits   every read's k-mer hits
 //   --min-hits N  --confidence F   the reads called by k-mer support
 //   --segments LEN[:STEP]   long records called in segments
+//   --depth   k-mer depth per target (the depth file of kid_driver.h)
 //   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N
 #include <stdio.h>
 #include <stdlib.h>

@@ -21,6 +21,9 @@
 //                    hits and F (a decimal in [0, 1], three fractional digits) of its k-mers, under 0 if none does (kid_driver.h)
 //   --segments LEN[:STEP]   also write <prefix>_segments.txt: every read with a hit called in segments of LEN window
 //                    positions, STEP apart (default LEN; LEN <= 1024 * STEP), under the rule of --min-hits / --confidence (kid_driver.h)
+//   --depth              also write <prefix>_depth.txt: per target, the hits on its database k-mers by the reads called (under the
+//                    rule of --min-hits / --confidence when given), how many of them were hit, the quartiles of their depth and
+//                    the largest (kid_driver.h)
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
 //                    what they would be on FASTQ files with those bases replaced by N; <prefix>_reads.txt prints the
 //                    sequences as they are (kid_driver.h)
