@@ -395,7 +395,9 @@ int kid_db_read_segments_time(kid_db *db, double *device_ms, uint64_t *calls, ui
 
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).
- * Synchronises the sample's outstanding work first.                             */
+ * Synchronises the sample's outstanding work first.  The sample has ended then:
+ * a kid_classify_* call or a tally into it is KID_ERR_STATE (and counts nothing)
+ * until kid_sample_reset; the counters may be read again in any way.             */
 int kid_sample_end(kid_sample *s, int64_t *gcount, int64_t *ucount);
 /* The same for ONE sample whose batches were dealt out over n DISTINCT kid_sample objects (a sample named twice is
  * KID_ERR_ARG: its reads would count twice), one per GPU, each on its own replica of the database (kid_db_replicate):

@@ -40,6 +40,13 @@ int kid_bench_gather(struct kid_db *db, uint64_t n_loads, int inflight, int iter
  * three loops of its configuration, and the two the batch is not for return at once.                                 */
 int kid_sample_kernel_variants(struct kid_sample *s, uint64_t *mask);
 
+/* the state of the sample's hit log, for tests that must prove which regime they reached.  Synchronises the device; reads
+ * only: the log is not applied, and neither the pacing of the passes nor any counter changes.
+ *   passes   passes over the log queued since the sample began or was last reset (by the pace or by a reader)
+ *   has_log  the sample has a log at all (minimizer-localised table, bitmap of at most 1024 pieces)
+ *   logging  has_log and no pass has switched the log off: the device's own word, as of the synchronise          */
+int kid_sample_log_state(struct kid_sample *s, uint32_t *passes, int *has_log, int *logging);
+
 /* device memory helpers so that a host language without a HIP binding can stage buffers */
 int kid_dev_alloc(int device, uint64_t nbytes, void **d_ptr);
 int kid_dev_free(int device, void *d_ptr);

@@ -108,6 +108,7 @@ PROTOTYPES = {
     "kid_synth_reads_device": (C.c_int, [C.c_uint64, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64,
                                          C.c_uint64, C.c_uint32, C.c_void_p, C.c_int]),
     "kid_sample_kernel_variants": (C.c_int, [C.c_void_p, c_u64p]),
+    "kid_sample_log_state": (C.c_int, [C.c_void_p, c_u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "kid_bench_gather": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_float), c_u64p]),
     "kid_dev_alloc": (C.c_int, [C.c_int, C.c_uint64, c_void_pp]),
     "kid_dev_free": (C.c_int, [C.c_int, C.c_void_p]),

@@ -502,6 +502,14 @@ class Sample:
         check(self._lib.kid_sample_kernel_variants(self._h, C.byref(m)))
         return {(b >> 3 & 1, b >> 2 & 1, b >> 1 & 1, 30 if b & 1 else 0, b >> 4) for b in range(64) if m.value >> b & 1}
 
+    def log_state(self):
+        """-> {"passes", "has_log", "logging"}: passes over the hit log queued since the sample began or was last reset,
+        whether the sample has a log, and whether the device still logs (kid_sample_log_state).  Synchronises; applies
+        nothing and changes nothing."""
+        passes, has_log, logging = C.c_uint32(0), C.c_int(0), C.c_int(0)
+        check(self._lib.kid_sample_log_state(self._h, C.byref(passes), C.byref(has_log), C.byref(logging)))
+        return {"passes": passes.value, "has_log": bool(has_log.value), "logging": bool(logging.value)}
+
     def seen_bytes(self):
         n = C.c_uint64(0)
         check(self._lib.kid_sample_seen_bytes(self._h, C.byref(n)))

@@ -86,7 +86,7 @@ struct kid_sample {
     // very long records: one word per k-mer position for the hits, one byte per tile of 256 positions ("holds a hit").
     // They grow together: long_tiles holds 16 bytes more than the tiles it is said to have.
     KidDevBuf long_hits, long_tiles;
-    bool ended = false; // kid_sample_end* has read the counters and no reset has followed: a tally is refused (kid_api_support.h)
+    bool ended = false; // kid_sample_end* has read the counters and no reset has followed: classify calls and tallies are refused
     uint64_t reads_submitted = 0; // since the last reset: checked against the device's count when results are read
     uint64_t kernel_variants = 0; // since the last reset: one bit per kid_classify_kernel instantiation launched (kid_sample_kernel_variants)
     // the scratch below is one set per sample: batches on different streams are ordered behind each other
@@ -352,7 +352,11 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
         if (long_cut) {
             if (!sc.long_plan.p) {
                 KID_HIP(sc.long_list.alloc(sizeof(KidLongList)));
-                KID_HIP(hipMemset(sc.long_list.p, 0, 16));
+                // (in front of the prepare kernel that counts into it, on its stream: a hipMemset runs on the null stream,
+                //  behind everything the sample's stream holds and not ordered with the non-blocking copy stream at all --
+                //  it emptied the list after the prepare kernel of the set's first batch had filled it, and the batch's
+                //  long records came back as reads without k-mers)
+                KID_HIP(hipMemsetAsync(sc.long_list.p, 0, 16, prep_stream));
                 KID_HIP(sc.long_plan.alloc(sizeof(KidLongPlan)));
             }
             // one word per k-mer position of the long records, one flag per 256: as many as the batch has bases (a bound
@@ -518,6 +522,13 @@ extern "C" int kid_sample_set_option(kid_sample *s, int option, int value)
     }
 }
 
+// kid_sample_end* has read the counters: nothing more is counted into the sample until kid_sample_reset (KID_ERR_STATE)
+static int kid_sample_check_open(const kid_sample *s)
+{
+    if (s->ended) return kid_fail(KID_ERR_STATE, "classify after kid_sample_end without kid_sample_reset");
+    return KID_OK;
+}
+
 // pack + prepare stream of the *_device entry points
 static int kid_prep_stream_for(kid_sample *s, hipStream_t stream, hipStream_t *out)
 {
@@ -532,6 +543,18 @@ extern "C" int kid_sample_kernel_variants(kid_sample *s, uint64_t *mask)
 {
     if (!s || !mask) return kid_fail(KID_ERR_ARG, "null argument");
     *mask = s->kernel_variants;
+    return KID_OK;
+}
+
+extern "C" int kid_sample_log_state(kid_sample *s, uint32_t *passes, int *has_log, int *logging)
+{
+    if (!s || !passes || !has_log || !logging) return kid_fail(KID_ERR_ARG, "null argument");
+    int rc = kid_use_device(s->db->device);
+    if (rc != KID_OK) return rc;
+    KID_HIP(hipDeviceSynchronize()); // every pass queued so far has run: the flag below is the device's last word
+    *passes = s->passes_done;
+    *has_log = s->seen_log.p != nullptr;
+    *logging = *has_log && *s->log_off_flag() == 0; // (not s->log_off: the host learns of a switch only at its next launch)
     return KID_OK;
 }
 
@@ -585,7 +608,8 @@ extern "C" int kid_classify_batch_device(kid_sample *s, const void *d_bases, uin
     if (!s || (n_reads && (!d_bases || !d_offsets))) return kid_fail(KID_ERR_ARG, "null argument");
     if (((uintptr_t)d_bases & 15u) != 0) return kid_fail(KID_ERR_ARG, "d_bases must be 16-byte aligned");
     if ((d_start == nullptr) != (d_stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
-    int rc = kid_use_device(s->db->device);
+    int rc = kid_sample_check_open(s);
+    if (rc == KID_OK) rc = kid_use_device(s->db->device);
     if (rc != KID_OK) return rc;
     KidBatch b{};
     b.bases = (const uint8_t *)d_bases;
@@ -607,7 +631,8 @@ extern "C" int kid_classify_fixed_device(kid_sample *s, const void *d_bases, uin
     if (!s || (n_reads && !d_bases)) return kid_fail(KID_ERR_ARG, "null argument");
     if (((uintptr_t)d_bases & 15u) != 0) return kid_fail(KID_ERR_ARG, "d_bases must be 16-byte aligned");
     if (read_len == 0 || read_len > 0x7FFFFFFFu) return kid_fail(KID_ERR_ARG, "read_len out of range");
-    int rc = kid_use_device(s->db->device);
+    int rc = kid_sample_check_open(s);
+    if (rc == KID_OK) rc = kid_use_device(s->db->device);
     if (rc != KID_OK) return rc;
     KidBatch b{};
     b.bases = (const uint8_t *)d_bases;
@@ -689,7 +714,9 @@ extern "C" int kid_classify_batch_async(kid_sample *s, const uint8_t *bases, con
     if (!bases || !offsets) return kid_fail(KID_ERR_ARG, "null argument");
     if ((start == nullptr) != (stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
     int64_t max_kmers = 0;
-    int rc = kid_check_offsets_batch(offsets, start, stop, n_reads, s->db->info.k, &max_kmers, 0, nullptr);
+    int rc = kid_sample_check_open(s);
+    if (rc != KID_OK) return rc;
+    rc = kid_check_offsets_batch(offsets, start, stop, n_reads, s->db->info.k, &max_kmers, 0, nullptr);
     if (rc != KID_OK) return rc;
     // A record of more than s->long_kmers k-mers is a long record (a FASTA contig, kmer_read_vf6.cpp:803-861): the classify
     // kernels would give it to one wave; the launch sorts those out on the device (kid_long_*).
@@ -727,7 +754,8 @@ extern "C" int kid_classify_fixed_async(kid_sample *s, const uint8_t *bases, uin
     if (n_reads == 0) return KID_OK;
     if (!bases) return kid_fail(KID_ERR_ARG, "null argument");
     if (read_len == 0 || read_len > 0x7FFFFFFFu) return kid_fail(KID_ERR_ARG, "read_len out of range");
-    int rc = kid_use_device(s->db->device);
+    int rc = kid_sample_check_open(s);
+    if (rc == KID_OK) rc = kid_use_device(s->db->device);
     if (rc != KID_OK) return rc;
     const uint64_t nbytes = n_reads * (uint64_t)read_len;
     kid_sample::Slot *slp = nullptr;
@@ -758,7 +786,9 @@ extern "C" int kid_classify_fastq_async(kid_sample *s, const uint8_t *text, uint
     if (!text || !recs || !out_start || !out_stop) return kid_fail(KID_ERR_ARG, "null argument");
     const int mask_q = s->min_base_quality;
     uint32_t longest = 0;
-    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, 0, nullptr, mask_q > 0, &longest);
+    int rc = kid_sample_check_open(s);
+    if (rc != KID_OK) return rc;
+    rc = kid_check_fastq_block(recs, n_reads, text_nbytes, 0, nullptr, mask_q > 0, &longest);
     if (rc != KID_OK) return rc;
     rc = kid_use_device(s->db->device);
     if (rc != KID_OK) return rc;
