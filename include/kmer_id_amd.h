@@ -469,6 +469,36 @@ int kid_sample_depth_add(kid_sample *s, uint64_t entry_begin, uint64_t n, const 
 int kid_sample_depth_spectrum(kid_sample *s, uint32_t bins, uint64_t *spectrum, uint64_t *ksum, uint32_t *dmax);
 int kid_sample_depth_spectrum_merged(kid_sample **samples, int n, uint32_t bins, uint64_t *spectrum, uint64_t *ksum, uint32_t *dmax);
 
+/* ---- k-mers shared between samples ---------------------------------------------------
+ * ucount says how many of a target's database k-mers a sample saw; two samples that both report 40 000 of 90 000 may
+ * have seen the same 40 000 (one strain in both) or nearly disjoint sets (two strains).  What decides it is the
+ * intersection of their seen-bitmaps, per target.  A bitmap is kid_sample_seen_bytes bytes in the layout of
+ * kid_sample_seen_export: bit o (entry o as handed to the builder, with target T[o]) is bit o % 32 of the little-endian
+ * 32-bit word o / 32.  For n bitmaps b_0 .. b_{n-1}
+ *   shared[(i * n + j) * ntar + t] = #{ o in [0, n_entries) : bit o of b_i is set, bit o of b_j is set, T[o] == t }
+ * -- a pure function of the bits and of T.  A bit at or beyond n_entries (the padding up to 128) is ignored, whatever it
+ * holds; a bit a sample would never set (target 0 or 1, the duplicate of an earlier key) counts under its T[o] like any
+ * other.  The matrix is symmetric and full; shared[i][i][t] is the number of bits of b_i under t, which for the bitmap
+ * of a real sample is its ucount[t]; the same bitmap may be named twice.  Sums are 64-bit integers: the result does not
+ * depend on any order of additions.  Jaccard and containment follow from shared and its diagonal.
+ * One pass over the entries serves all pairs (kid_shared.hip.h): n * bytes + 4 * n_entries bytes are read once.
+ *   bitmaps[n]   n in 1..KID_SHARED_MAX_SAMPLES (KID_ERR_ARG beyond, and for a null pointer); all in host memory
+ *                (on_device = 0) or all in the memory of the database's device (1: 16-byte aligned, and at rest)
+ *   shared       host memory, int64[n * n * ntar]; nothing is written to it when the call fails on its arguments
+ * kid_db_shared_kmers is one of the calls of a kid_db that run one after the other (kid_db_read_hits above).  Both calls
+ * synchronise before they return; neither touches a sample; their scratch (a device copy of host bitmaps, the matrix)
+ * lives for the call.
+ * kid_shared_kmers is the same without a kid_db, for a tool that has the probes but needs no table: targets[n_entries] in
+ * host memory, as handed to kid_db_build (a targets[o] >= ntar: KID_ERR_TARGET); the bitmaps have the padded size a
+ * kid_db of n_entries would report, ((n_entries + 127) / 128) * 16 bytes, 16 for no entries.
+ * kid_shared_kmers_time: device time (HIP events) of the kernels of both calls, in this process, since the last query,
+ * and the number of calls; copies and the clearing of the matrix are not in it.                                        */
+#define KID_SHARED_MAX_SAMPLES 64
+int kid_db_shared_kmers(kid_db *db, const void *const *bitmaps, int n, int on_device, int64_t *shared);
+int kid_shared_kmers(int device, const uint32_t *targets, uint64_t n_entries, int32_t ntar, const void *const *bitmaps,
+                     int n, int on_device, int64_t *shared);
+int kid_shared_kmers_time(double *device_ms, uint64_t *calls);
+
 /* ---- probe-database builder ------------------------------------------------------------------------------------
  * Replaces the table of kmer_build_vf6.cpp (Hashtable, :132-215) and its three passes (process_seq, process_seq3,
  * process_seq2: :353-457, :553-640): 2^log2_cells uint32 cells, direct mapped by fmix64 of the canonical 30-mer, no key

@@ -99,6 +99,9 @@ PROTOTYPES = {
     "kid_sample_depth_add": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int]),
     "kid_sample_depth_spectrum": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kid_sample_depth_spectrum_merged": (C.c_int, [c_void_pp, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kid_db_shared_kmers": (C.c_int, [C.c_void_p, c_void_pp, C.c_int, C.c_int, C.c_void_p]),
+    "kid_shared_kmers": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int32, c_void_pp, C.c_int, C.c_int, C.c_void_p]),
+    "kid_shared_kmers_time": (C.c_int, [C.POINTER(C.c_double), c_u64p]),
     "kid_synth_db_keys_host": (C.c_int, [C.c_uint64, C.c_int, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p,
                                          C.c_void_p]),
     "kid_synth_db_keys_device": (C.c_int, [C.c_uint64, C.c_int, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p,
@@ -133,6 +136,7 @@ KID_OPT_LONG_RECORD_KMERS = 2
 KID_OPT_MIN_BASE_QUALITY = 3
 KID_OPT_ENTRY_DEPTH = 4
 KID_DB_OPT_MIN_BASE_QUALITY = 1
+KID_SHARED_MAX_SAMPLES = 64
 KID_FLAG_U_IS_T = 1
 KID_FLAG_HOST_BUILD = 2
 KID_FLAG_REF_GEOMETRY = 4

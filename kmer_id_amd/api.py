@@ -4,6 +4,7 @@ keeps in globals (`ht`, `taxonomy`, `gcount`, `ucount`, `kmer_seen`,
 newkmer_10nx.cpp:59-64,156,266).  numpy arrays in, numpy arrays out.
 """
 import ctypes as C
+import struct
 
 import numpy as np
 
@@ -325,6 +326,16 @@ class KmerDB:
         """-> (device ms, calls, reads) of the segment kernels alone since the last query"""
         return self._time(self._lib.kid_db_read_segments_time)
 
+    def shared_kmers(self, items):
+        """K-mers shared between samples (kid_db_shared_kmers) -> int64[n, n, ntar]: [i, j, t] = the database entries of
+        target t that items i and j both have a bit for; the diagonal is an item's own bits per target (a sample's
+        ucount).  An item is a Sample (of this database or of a replica: its bitmap is exported to the host first) or a
+        uint8 array of seen_bytes bytes in the layout of Sample.seen_export.  No sample changes."""
+        info = self.info
+        nbytes = max((info.n_entries + 127) // 128, 1) * 16
+        return _shared_kmers(items, nbytes, info.ntar,
+                             lambda ptrs, n, out: self._lib.kid_db_shared_kmers(self._h, ptrs, n, 0, _ptr(out)))
+
     def gather_ceiling(self, n_loads=1 << 28, inflight=4, iters=3):
         """Random gather rate over this DB's table: (ms per launch, loads per launch).  inflight 101 / 108: random
         128-byte lines asked for the way the classify kernel asks (64 per load / runs of 8 lanes), 4 loads in flight;
@@ -347,6 +358,66 @@ class KmerDB:
             self.close()
         except Exception:
             pass
+
+
+def _shared_kmers(items, nbytes, ntar, call):
+    """the items of a shared_kmers call as host bitmaps of nbytes bytes -> int64[n, n, ntar] from call(ptrs, n, out)"""
+    maps = []
+    for it in items:
+        a = it.seen_export(0, it.seen_bytes()) if isinstance(it, Sample) else np.ascontiguousarray(it, np.uint8).reshape(-1)
+        if a.size != nbytes:
+            raise ValueError("a bitmap of %d bytes where the database's have %d" % (a.size, nbytes))
+        maps.append(a)
+    n = len(maps)
+    ptrs = (C.c_void_p * max(n, 1))(*[a.ctypes.data for a in maps])
+    out = np.zeros((n, n, ntar), np.int64)
+    check(call(ptrs, n, out))
+    return out
+
+
+def shared_kmers(targets, ntar, bitmaps, device=0):
+    """K-mers shared between samples without a database (kid_shared_kmers): targets[n_entries] as handed to the builder,
+    bitmaps of ((n_entries + 127) // 128) * 16 bytes each (16 for no entries) -> int64[n, n, ntar] as KmerDB.shared_kmers."""
+    lib = _lib.load()
+    targets = _as(targets, np.uint32)
+    nbytes = max((targets.size + 127) // 128, 1) * 16
+    return _shared_kmers(bitmaps, nbytes, ntar,
+                         lambda ptrs, n, out: lib.kid_shared_kmers(device, _ptr(targets), targets.size, ntar, ptrs, n, 0, _ptr(out)))
+
+
+def shared_kmers_time():
+    """-> (device ms, calls) of the kernels of the shared_kmers calls of this process since the last query"""
+    ms, calls = C.c_double(0), C.c_uint64(0)
+    check(_lib.load().kid_shared_kmers_time(C.byref(ms), C.byref(calls)))
+    return ms.value, calls.value
+
+
+SEEN_MAGIC = b"KIDSEEN1"
+
+
+def write_seen_file(path, bitmap, n_entries, ntar, k):
+    """A seen file (what --seen writes beside a result file): a 32-byte little-endian header -- the 8 bytes KIDSEEN1, uint64
+    n_entries, int32 ntar, int32 k, uint64 nbytes -- and nbytes bytes of bitmap."""
+    bitmap = np.ascontiguousarray(bitmap, np.uint8).reshape(-1)
+    with open(path, "wb") as f:
+        f.write(SEEN_MAGIC + struct.pack("<QiiQ", n_entries, ntar, k, bitmap.size))
+        f.write(bitmap.tobytes())
+
+
+def read_seen_file(path):
+    """-> (bitmap uint8[nbytes], n_entries, ntar, k) of a seen file; ValueError for a bad magic, a size that does not fit
+    n_entries, or a truncated file."""
+    with open(path, "rb") as f:
+        head = f.read(32)
+        if len(head) < 32 or head[:8] != SEEN_MAGIC:
+            raise ValueError("%s is not a seen file (bad magic)" % path)
+        n_entries, ntar, k, nbytes = struct.unpack("<QiiQ", head[8:])
+        if nbytes != max((n_entries + 127) // 128, 1) * 16:
+            raise ValueError("%s: %d bytes of bitmap do not fit %d entries" % (path, nbytes, n_entries))
+        data = f.read(nbytes + 1)
+    if len(data) != nbytes:
+        raise ValueError("%s is truncated or has bytes behind its bitmap" % path)
+    return np.frombuffer(data, np.uint8).copy(), n_entries, ntar, k
 
 
 def end_merged(samples):

@@ -389,7 +389,8 @@ static const struct {
                     {"--confidence", 0, read_confidence, nullptr},
                     {"--min-base-quality", 1, read_base_quality, nullptr},
                     {"--segments", 2, read_segments, nullptr},
-                    {"--depth", 0, nullptr, &SideOptions::depth}};
+                    {"--depth", 0, nullptr, &SideOptions::depth},
+                    {"--seen", 0, nullptr, &SideOptions::seen}};
 
 int side_option_values(const char *word)
 {
@@ -423,10 +424,14 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments, depth; };
+struct SidePaths { std::string hits, confident, segments, depth, seen; };
 static SidePaths side_paths(const std::string &r)
 {
-    return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth")};
+    std::string seen = r; // the final "result.txt" becomes "seen.bin"
+    const size_t at = seen.rfind("result.txt");
+    if (at != std::string::npos) seen.replace(at, 10, "seen.bin");
+    else seen += ".seen.bin";
+    return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -436,6 +441,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.segments.on) remove(p.segments.c_str());
     if (all || side.support.on) remove(p.confident.c_str());
     if (all || side.depth) remove(p.depth.c_str());
+    if (all || side.seen) remove(p.seen.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -496,12 +502,43 @@ static void write_depth(std::vector<kid_sample *> &samples, int ntar, const std:
     write_lines(path, std::vector<std::string>(1, text));
 }
 
+const char kSeenMagic[9] = "KIDSEEN1";
+
+// The bitmap of a sample that has been closed (with several devices the first one's holds the union: kid_sample_end_merged)
+// -> a seen file
+static void write_seen(kid_sample *s, const Engine &e, const std::string &path)
+{
+    kid_db_info info;
+    uint64_t nbytes = 0;
+    int rc = kid_db_get_info(e.db, &info);
+    if (rc == KID_OK) rc = kid_sample_seen_bytes(s, &nbytes);
+    if (rc != KID_OK) die_kid(rc);
+    std::vector<uint8_t> bitmap(nbytes);
+    if ((rc = kid_sample_seen_export(s, 0, nbytes, bitmap.data(), 0)) != KID_OK) die_kid(rc);
+    const uint64_t n_entries = info.n_entries;
+    const int32_t ntar = e.ntar, k = e.k;
+    char head[32];
+    memcpy(head, kSeenMagic, 8);
+    memcpy(head + 8, &n_entries, 8);
+    memcpy(head + 16, &ntar, 4);
+    memcpy(head + 20, &k, 4);
+    memcpy(head + 24, &nbytes, 8);
+    FILE *f = fopen(path.c_str(), "wb");
+    if (!f) throw Fatal{2, "cannot write " + path};
+    const bool ok = fwrite(head, 1, 32, f) == 32 && fwrite(bitmap.data(), 1, bitmap.size(), f) == bitmap.size();
+    if (fclose(f) != 0 || !ok) {
+        remove(path.c_str());
+        throw Fatal{2, "cannot write " + path};
+    }
+}
+
 void SampleOutputs::finish(Engine &e)
 {
     const SidePaths p = side_paths(result_path_);
     write_counters(e.samples, e.ntar, result_path_);
     if (side_.support.on) write_counters(e.confident, e.ntar, p.confident);
     if (side_.depth) write_depth(e.confident, e.ntar, p.depth);
+    if (side_.seen) write_seen(side_.support.on ? e.confident[0] : e.samples[0], e, p.seen);
     if (side_.hits) write_lines(p.hits, hits_);
     if (side_.segments.on) write_lines(p.segments, segments_);
     hits_.clear();

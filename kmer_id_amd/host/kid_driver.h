@@ -42,6 +42,8 @@ struct SideOptions {
     // --depth (no value): k-mer depth per database entry (KID_OPT_ENTRY_DEPTH), summed up per target in a depth file.  The
     // support pass runs for it under the rule of --min-hits / --confidence when given, else (0, 0).
     bool depth = false;
+    // --seen (no value): the sample's seen-bitmap in a seen file, for kmer_shared to compare samples by
+    bool seen = false;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
@@ -142,6 +144,11 @@ private:
 // its k-mers were hit, the quartiles of their depth (the smallest d >= 1 with 4 * #{1 <= depth <= d} >= p * distinct;
 // depths of 255 and more count as 255; 0 without a hit) and the largest depth.  Its column 3 is the column 3 of the
 // confident file, or of the result file without a rule.
+//   --seen, "seen": the final "result.txt" of the name becomes "seen.bin".  A 32-byte little-endian header (SeenHeader) and
+// the seen-bitmap, one bit per database entry in the layout of kid_sample_seen_export: the union over the devices, of the
+// tallied sample(s) under a rule (--min-hits / --confidence), else of the classified one(s) -- the convention of the depth
+// file's `distinct` column, so its bits per target are column 3 of the confident file under a rule, of the result file
+// without.  It does not depend on how the reads were batched, threaded or dealt over devices.
 // Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0):
 // confident = final.  --min-base-quality applies as it does to the hits file.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
@@ -157,7 +164,7 @@ public:
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
-    // confident file, then the depth file, then the hits file, then the segments file
+    // confident file, then the depth file, then the seen file, then the hits file, then the segments file
     void finish(Engine &e);
 private:
     using Lines = std::vector<std::string>; // [file]
@@ -166,6 +173,14 @@ private:
     std::string result_path_;
     Lines hits_, segments_;
 };
+// The head of a seen file: the 8 bytes "KIDSEEN1", then these fields, little-endian, 32 bytes in all; nbytes bytes of
+// bitmap follow (the padded size of a database of n_entries: ((n_entries + 127) / 128) * 16, 16 for none)
+struct SeenHeader {
+    uint64_t n_entries = 0;
+    int32_t ntar = 0, k = 0;
+    uint64_t nbytes = 0;
+};
+extern const char kSeenMagic[9];
 // For a front-end that takes a sample's outputs back: removes the files beside `result_path` of the options that are on
 // (a sample that never started: one left by an earlier run would stand beside no result) or, with `all`, every one a
 // sample may have written

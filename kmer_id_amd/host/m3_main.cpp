@@ -11,6 +11,7 @@
 //   --min-hits N  --confidence F   the reads called by k-mer support
 //   --segments LEN[:STEP]   long records called in segments
 //   --depth   k-mer depth per target (the depth file of kid_driver.h)
+//   --seen   the seen-bitmap in a seen file (<...>seen.bin beside <...>result.txt), for kmer_shared
 //   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N
 #include <stdio.h>
 #include <stdlib.h>

@@ -24,6 +24,8 @@
 //   --depth              also write <prefix>_depth.txt: per target, the hits on its database k-mers by the reads called (under the
 //                    rule of --min-hits / --confidence when given), how many of them were hit, the quartiles of their depth and
 //                    the largest (kid_driver.h)
+//   --seen               also write <prefix>_seen.bin: the sample's seen-bitmap, one bit per database k-mer (of the reads called
+//                    under the rule of --min-hits / --confidence when given), for kmer_shared to compare samples by (kid_driver.h)
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
 //                    what they would be on FASTQ files with those bases replaced by N; <prefix>_reads.txt prints the
 //                    sequences as they are (kid_driver.h)
