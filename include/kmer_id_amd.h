@@ -336,6 +336,61 @@ int kid_db_support_from_hits_device(kid_db *db, const void *d_hit_offsets, const
  * of the host forms is in kid_db_read_hits_time.  Synchronises with the last call.                                  */
 int kid_db_read_support_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
 
+/* ---- one call per fragment ------------------------------------------------------------
+ * kid_db_read_support* judges every read on its own.  Two reads that are mates of one sequenced fragment are one piece
+ * of evidence: these calls call the pair as one unit.  A fragment is an ordered pair of reads, mate 1 and mate 2.
+ * Either may be absent, or may have no window.
+ *   hits       Let a_1 .. a_p be the hits of mate 1 and b_1 .. b_q those of mate 2.  They are exactly what
+ *              kid_db_read_hits reports for each mate: the same pos, target and entry, in read-position order, targets
+ *              equal to 1 included.  They are taken under the mate's own trimmed range.  n_1 and n_2 are the mates'
+ *              n_kmers.
+ *   sequence   The fragment's hit sequence is a_1 .. a_p, b_1 .. b_q: mate 1 first.  Let m = p + q and n = n_1 + n_2.
+ *              No window spans the two mates.  Nothing is reverse-complemented beyond what the lookup already does per
+ *              k-mer.
+ *   six fields final, confident, n_kmers, n_hits, s_final and s_confident are exactly the kid_support record above,
+ *              applied to that sequence with that n, under (min_hits, min_permille).
+ *   per mate   final_1 is the left fold of a_1 .. a_p alone, and final_2 that of b_1 .. b_q alone.  Each is 0 without a
+ *              hit.  These are what kid_classify_* returns for each mate.
+ * msca is not associative, so final is NOT msca(final_1, final_2) in general.  Take mate 1 = [8] and mate 2 = [X, 6],
+ * with 6 an ancestor of 8 and X outside that lineage.  The pair folds 8 -> 1 -> 6, while msca(8, msca(X, 6)) =
+ * msca(8, 1) = 8.  The fold is one left fold over m hits that continues from final_1 into mate 2's hits.
+ * One kernel turns the hits of a batch into one record per fragment; it is a pure function of the hits (no atomics): the
+ * records are byte-identical across runs and splits of the batch into calls.                                          */
+typedef struct kid_fragment {
+    uint32_t final, confident, n_kmers /* n */, n_hits /* m */, s_final, s_confident, final_1, final_2;
+} kid_fragment;
+/* Host buffers, as kid_db_read_support.  The batch holds n_reads = 2 F reads in interleaved order: read 2i is mate 1 of
+ * fragment i, and read 2i + 1 is its mate 2 (an absent mate is an empty read).  n_reads odd is KID_ERR_ARG;
+ * min_permille > 1000 and null pointers are KID_ERR_ARG; n_reads = 0 returns KID_OK and launches nothing.
+ *   out[n_reads / 2]  nullable with a tally
+ *   tally             nullable: a sample OF THIS kid_db (another's: KID_ERR_ARG; one that has ended: KID_ERR_STATE).  A
+ *                     counted fragment adds 1 to gcount[confident]: once per fragment, under 0 when confident = 0.
+ *                     When confident > 0, the fragment sets the seen bit of every hit of BOTH mates with target > 1.
+ *                     Under KID_OPT_ENTRY_DEPTH, the same fragment adds 1 to depth[entry] per such hit; a k-mer present
+ *                     in both mates adds 2.  In the offsets and device forms every fragment is counted.  In the FASTQ
+ *                     form a fragment is counted when at least one of its mates is kept by process_qual; a dropped mate
+ *                     contributes no hit and no window, and a fragment with both mates dropped is counted nowhere.
+ *                     kid_sample_stats is NOT updated.  A batch the hit pass refuses is not counted at all.           */
+int kid_db_read_fragments(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                          uint64_t n_reads, uint32_t min_hits, uint32_t min_permille, kid_fragment *out, kid_sample *tally);
+/* Two blocks of FASTQ text with their line indexes: record i of recs1 is mate 1 of fragment i and record i of recs2 its
+ * mate 2.  Either recs pointer may point into the middle of a block's record index.  A record with seq_len = 0 and
+ * qual_len = 0 is an absent mate.  The blocks are staged as one text with one interleaved index: nbytes1 + nbytes2 must
+ * stay below 4 GiB (KID_ERR_ARG).  KID_DB_OPT_MIN_BASE_QUALITY applies as in kid_db_read_support_fastq; its "lines
+ * ascending, no overlap" check runs per block.  A quality line shorter than its sequence in either block is
+ * KID_ERR_FORMAT.                                                                                                    */
+int kid_db_read_fragments_fastq(kid_db *db, const uint8_t *text1, uint64_t nbytes1, const kid_fastq_rec *recs1, const uint8_t *text2,
+                                uint64_t nbytes2, const kid_fastq_rec *recs2, uint64_t n_fragments, uint32_t min_hits,
+                                uint32_t min_permille, kid_fragment *out, kid_sample *tally);
+/* The kernel alone on an interleaved CSR in HBM (the companion of kid_db_support_from_hits_device, same arguments):
+ * d_hit_offsets uint64[n_reads + 1], d_n_kmers uint32[n_reads], d_out kid_fragment[n_reads / 2].  Asynchronous on
+ * `stream`; no tally.  A target outside (0, ntar) in d_hits is read as the root.                                     */
+int kid_db_fragments_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
+                                      uint32_t min_hits, uint32_t min_permille, void *d_out, void *stream);
+/* Device time of the fragment kernel ALONE since the last query, its calls and fragments.  Synchronises with the last
+ * call.                                                                                                              */
+int kid_db_read_fragments_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *fragments);
+
 /* ---- calling records in segments ------------------------------------------------------
  * kid_db_read_support* gives a record one answer.  A contig that is one species for its first 1.4 Mb and another after
  * that, a chimeric long read or a transferred island folds to an ancestor and nothing says where the change is.  These

@@ -94,6 +94,9 @@ class ReadHits:
 SUPPORT_DTYPE = np.dtype([("final", np.uint32), ("confident", np.uint32), ("n_kmers", np.uint32), ("n_hits", np.uint32),
                           ("s_final", np.uint32), ("s_confident", np.uint32)])
 
+# kid_fragment: one record per fragment (kid_db_read_fragments*); the first six fields are SUPPORT_DTYPE's
+FRAGMENT_DTYPE = np.dtype([(name, np.uint32) for name in SUPPORT_DTYPE.names] + [("final_1", np.uint32), ("final_2", np.uint32)])
+
 # kid_segment: one record per segment (kid_db_read_segments*); the six fields behind n_pos are SUPPORT_DTYPE's
 SEGMENT_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in SUPPORT_DTYPE.names])
 
@@ -282,6 +285,49 @@ class KmerDB:
     def read_support_time(self):
         """-> (device ms, calls, reads) of the support kernel alone since the last query"""
         return self._time(self._lib.kid_db_read_support_time)
+
+    def read_fragments(self, bases, offsets, start=None, stop=None, min_hits=0, min_permille=0, tally=None):
+        """Call mate pairs as one fragment (kid_db_read_fragments): -> a structured array (FRAGMENT_DTYPE: final, confident,
+        n_kmers, n_hits, s_final, s_confident, final_1, final_2), one record per fragment.  The batch holds 2 F reads in
+        interleaved order: read 2i is mate 1 of fragment i, and read 2i + 1 is its mate 2.  The fragment's hit sequence
+        is a_1 .. a_p, b_1 .. b_q: mate 1 first, m = p + q and n = n_1 + n_2.  final, confident, n_kmers, n_hits, s_final
+        and s_confident are exactly the read_support record applied to that sequence with that n, under (min_hits,
+        min_permille).  final_1 is the left fold of a_1 .. a_p alone, and final_2 that of b_1 .. b_q alone; each is 0
+        without a hit.  msca is not associative, so final is not msca(final_1, final_2) in general.
+        tally: a Sample of this database.  A counted fragment adds 1 to gcount[confident]: once per fragment, under 0
+        when confident = 0.  When confident > 0, the fragment sets the seen bit of every hit of both mates with
+        target > 1 (and under KID_OPT_ENTRY_DEPTH adds 1 to depth[entry] per such hit)."""
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        out = np.zeros(n // 2, FRAGMENT_DTYPE)
+        check(self._lib.kid_db_read_fragments(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
+                                              _ptr(out), tally._h if tally is not None else None))
+        return out
+
+    def read_fragments_fastq(self, text1, recs1, text2, recs2, min_hits=0, min_permille=0, tally=None):
+        """The same for two blocks of FASTQ text with their line indexes (uint32[n, 4] each, as Sample.classify_fastq):
+        record i of recs1 is mate 1 and record i of recs2 is mate 2.  A record with seq_len = 0 and qual_len = 0 is an
+        absent mate.  A fragment is counted when at least one of its mates is kept by process_qual; a dropped mate
+        contributes no hit and no window."""
+        text1, recs1, n = _fastq_block(text1, recs1)
+        text2, recs2, n2 = _fastq_block(text2, recs2)
+        if n != n2:
+            raise ValueError("recs1 and recs2 must hold one record per fragment each")
+        out = np.zeros(n, FRAGMENT_DTYPE)
+        check(self._lib.kid_db_read_fragments_fastq(self._h, _ptr(text1), text1.size, _ptr(recs1), _ptr(text2), text2.size, _ptr(recs2), n,
+                                                    min_hits, min_permille, _ptr(out), tally._h if tally is not None else None))
+        return out
+
+    def fragments_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
+        """The fragment kernel alone on an interleaved CSR of n_reads = 2 F reads resident in HBM (raw pointers, as
+        kid_db_read_hits_device left it); asynchronous on `stream`: kid_db_fragments_from_hits_device.
+        d_out: kid_fragment[n_reads / 2] (FRAGMENT_DTYPE)."""
+        check(self._lib.kid_db_fragments_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
+                                                          C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
+                                                          C.c_void_p(stream or None)))
+
+    def read_fragments_time(self):
+        """-> (device ms, calls, fragments) of the fragment kernel alone since the last query"""
+        return self._time(self._lib.kid_db_read_fragments_time)
 
     def _read_segments(self, call, n):
         """the sizing call, then the call that fills a buffer of exactly that size"""

@@ -69,6 +69,8 @@ struct KidHitsState {
     KidDevBuf out_support; // kid_db_read_support* (kid_api_support.h): the host forms' records
     KidSpanTimer pass;     // the hit pass of every call, a kid_db_read_support* host call's included
     KidSpanTimer support;  // the support kernel alone
+    KidDevBuf out_fragments; // kid_db_read_fragments* (kid_api_fragments.h): the host forms' records
+    KidSpanTimer fragments;  // the fragment kernel alone
     // kid_db_read_segments* (kid_api_segments.h): per tile the mask of its lanes that hold a k-mer and their scan (the hit
     // pass stores the mask while want_valid is set: the buffer is sized for the batch then), [0] the batch's segments and
     // [1] its valid windows, the host forms' offsets and records
@@ -94,6 +96,7 @@ static int kid_hits_state(kid_db *db, KidHitsState **out)
         KID_HIP(hipMemset(h->ctl(), 0, nb));
         KID_HIP(h->pass.create());
         KID_HIP(h->support.create());
+        KID_HIP(h->fragments.create());
         KID_HIP(h->segments.create());
         db->hits = std::move(h);
     }

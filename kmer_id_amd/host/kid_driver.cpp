@@ -64,7 +64,7 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 
 Engine::~Engine()
 {
-    for (const std::vector<kid_sample *> *list : {&samples, &confident})
+    for (const std::vector<kid_sample *> *list : {&samples, &confident, &fragments})
         for (kid_sample *s : *list) kid_sample_destroy(s);
     if (owns_dbs)
         for (kid_db *d : dbs) kid_db_destroy(d);
@@ -104,6 +104,8 @@ void engine_configure(Engine &e, const SideOptions &side)
             int rc = kid_sample_set_option(s, KID_OPT_ENTRY_DEPTH, 1);
             if (rc != KID_OK) die_kid(rc);
         }
+    if (side.fragments) // (tallied through the database's hit pass: KID_DB_OPT_MIN_BASE_QUALITY below is what masks for them)
+        for (kid_db *d : e.dbs) e.fragments.push_back(begin_sample_or_die(d));
     const int q = side.min_base_quality;
     if (q == 0) return;
     for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
@@ -134,12 +136,13 @@ std::vector<int> parse_devices(int device, const std::string &list)
 
 void engine_reset(Engine &e)
 {
-    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
+    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident, &e.fragments})
         for (kid_sample *s : *list) {
             int rc = kid_sample_reset(s);
             if (rc != KID_OK) die_kid(rc);
         }
     e.next_sample = 0;
+    e.next_fragments = 0;
 }
 
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
@@ -390,7 +393,8 @@ static const struct {
                     {"--min-base-quality", 1, read_base_quality, nullptr},
                     {"--segments", 2, read_segments, nullptr},
                     {"--depth", 0, nullptr, &SideOptions::depth},
-                    {"--seen", 0, nullptr, &SideOptions::seen}};
+                    {"--seen", 0, nullptr, &SideOptions::seen},
+                    {"--fragments", 0, nullptr, &SideOptions::fragments}};
 
 int side_option_values(const char *word)
 {
@@ -424,14 +428,15 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments, depth, seen; };
+struct SidePaths { std::string hits, confident, segments, depth, seen, fragments; };
 static SidePaths side_paths(const std::string &r)
 {
     std::string seen = r; // the final "result.txt" becomes "seen.bin"
     const size_t at = seen.rfind("result.txt");
     if (at != std::string::npos) seen.replace(at, 10, "seen.bin");
     else seen += ".seen.bin";
-    return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen};
+    return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen,
+            sibling_path_for(r, "fragments")};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -442,6 +447,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.support.on) remove(p.confident.c_str());
     if (all || side.depth) remove(p.depth.c_str());
     if (all || side.seen) remove(p.seen.c_str());
+    if (all || side.fragments) remove(p.fragments.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -537,6 +543,7 @@ void SampleOutputs::finish(Engine &e)
     const SidePaths p = side_paths(result_path_);
     write_counters(e.samples, e.ntar, result_path_);
     if (side_.support.on) write_counters(e.confident, e.ntar, p.confident);
+    if (side_.fragments) write_counters(e.fragments, e.ntar, p.fragments);
     if (side_.depth) write_depth(e.confident, e.ntar, p.depth);
     if (side_.seen) write_seen(side_.support.on ? e.confident[0] : e.samples[0], e, p.seen);
     if (side_.hits) write_lines(p.hits, hits_);
@@ -656,6 +663,46 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
     std::deque<InFlight> q;
     std::vector<long long> handed(count, 0);
     const size_t max_in_flight = 2 * e.samples.size();
+    // --fragments: the blocks of each mate file that are through, in file order, until their records have been paired
+    struct HeldBlock {
+        std::unique_ptr<ReadBatch> batch;
+        size_t paired = 0; // records of the block that have been handed on
+    };
+    const bool fragments = out.fragments_on() && count == 2 && !e.fragments.empty();
+    std::deque<HeldBlock> held[2];
+    unsigned long long mate_records[2] = {0, 0};
+    std::vector<kid_fastq_rec> absent;
+    // record j of one file with record j of the other: the longest common run of the two front blocks, until one of the
+    // queues is empty; with `flush` (both files are through) what is left of one has absent mates
+    auto pair_up = [&](bool flush) {
+        for (;;) {
+            for (std::deque<HeldBlock> &h : held)
+                while (!h.empty() && h.front().paired == h.front().batch->size()) h.pop_front();
+            const bool have[2] = {!held[0].empty(), !held[1].empty()};
+            if (!have[0] && !have[1]) return;
+            if (!(have[0] && have[1]) && !flush) return;
+            size_t n = (size_t)-1;
+            for (int m = 0; m < 2; m++)
+                if (have[m] && held[m].front().batch->size() - held[m].front().paired < n) n = held[m].front().batch->size() - held[m].front().paired;
+            if (!(have[0] && have[1])) absent.assign(n, kid_fastq_rec{0, 0, 0, 0});
+            const uint8_t *text[2];
+            uint64_t nbytes[2];
+            const kid_fastq_rec *recs[2];
+            for (int m = 0; m < 2; m++) {
+                const FastqBlock *fq = have[m] ? held[m].front().batch->fq.get() : nullptr;
+                text[m] = fq ? (const uint8_t *)fq->text.data() : nullptr;
+                nbytes[m] = fq ? fq->used : 0;
+                recs[m] = fq ? fq->recs.data() + held[m].front().paired : absent.data();
+            }
+            const size_t dev = e.next_fragments;
+            e.next_fragments = (e.next_fragments + 1) % e.fragments.size();
+            int rc = kid_db_read_fragments_fastq(e.dbs[dev], text[0], nbytes[0], recs[0], text[1], nbytes[1], recs[1], n, e.side.support.min_hits,
+                                                 e.side.support.min_permille, (kid_fragment *)nullptr, e.fragments[dev]);
+            if (rc != KID_OK) die_kid(rc);
+            for (int m = 0; m < 2; m++)
+                if (have[m]) held[m].front().paired += n;
+        }
+    };
     auto retire = [&]() {
         InFlight &f = q.front();
         const auto t0 = std::chrono::steady_clock::now();
@@ -678,6 +725,11 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             lines.clear();
             segment_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.side.segments, e.side.support, lines);
             out.add_segments(saver_file + f.file, lines);
+        }
+        if (fragments && f.batch->fq) {
+            mate_records[f.file] += f.batch->size();
+            held[f.file].push_back(HeldBlock{std::move(f.batch), 0});
+            pair_up(false);
         }
         q.pop_front();
     };
@@ -722,6 +774,14 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         throw;
     }
     while (!q.empty()) retire();
+    if (fragments) {
+        pair_up(true);
+        if (mate_records[0] != mate_records[1]) {
+            const unsigned long long a = mate_records[0], b = mate_records[1];
+            fprintf(stderr, "kmer_id_amd: --fragments: %s: the mate files hold %llu and %llu records: %llu fragments have an absent mate\n",
+                    out.result_path().c_str(), a, b, a > b ? a - b : b - a);
+        }
+    }
     long long n = 0;
     for (size_t f = 0; f < count; f++) {
         saver.file_done(saver_file + f);
@@ -766,6 +826,7 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
         if (a == "--db-cache") o.db_cache = v;
     }
     o.side = side_options(argc, argv, argv[0]);
+    if (o.side.fragments) usage_error(argv[0], "--fragments", "is an option of nk10 alone: the inputs of this program are read one file after the other");
     return o;
 }
 

@@ -44,6 +44,9 @@ struct SideOptions {
     bool depth = false;
     // --seen (no value): the sample's seen-bitmap in a seen file, for kmer_shared to compare samples by
     bool seen = false;
+    // --fragments (no value; nk10 alone, whose two mate files are read side by side): the mate pairs called as one
+    // fragment each (kid_db_read_fragments_fastq), counted into a fragments file
+    bool fragments = false;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
@@ -67,6 +70,8 @@ struct Engine {
     // (with the depth counters on under --depth)
     SideOptions side;
     std::vector<kid_sample *> confident;
+    std::vector<kid_sample *> fragments; // under --fragments: one sample per device that the fragments are tallied into
+    size_t next_fragments = 0;           // ... dealt round-robin over the devices
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -98,7 +103,7 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
 // The side options for an engine that is open: with a rule or --depth one more sample per device (reset, closed and
-// destroyed with the others; --depth switches its depth counters on), then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
+// destroyed with the others; --depth switches its depth counters on), under --fragments one more for the fragments, then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
 // A worker of engine_worker() inherits them for its samples.
 void engine_configure(Engine &e, const SideOptions &side);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
@@ -151,6 +156,13 @@ private:
 // without.  It does not depend on how the reads were batched, threaded or dealt over devices.
 // Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0):
 // confident = final.  --min-base-quality applies as it does to the hits file.
+//   --fragments, "fragments" (nk10): a result file in the result file's format, <i>,<fragments>,<unique_kmers>, from the
+// counters of one more sample per device that every fragment is tallied into (kid_db_read_fragments_fastq): record j
+// of the R1 file and record j of the R2 file are one fragment, j counting the 4-line records of each file, those that
+// process_qual drops included; header names are not compared.  The surplus records of the longer file (all of them
+// when R2 is missing) are fragments with an absent mate, and one line on stderr gives both counts.  The rule is that of
+// --min-hits / --confidence when given, else (0, 0); --min-base-quality applies as it does to the confident file.  It
+// does not depend on how the files were cut into blocks, batched, threaded or dealt over devices.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
 // The batches of files read at the same time interleave: the hit and segment lines are held in memory per file and
 // written in file order by finish() -- what is held is the files themselves (reads without a hit leave nothing),
@@ -161,10 +173,13 @@ public:
     SampleOutputs(const std::string &result_path, const SideOptions &side);
     bool hits_on() const { return side_.hits; }
     bool segments_on() const { return side_.segments.on; }
+    bool fragments_on() const { return side_.fragments; }
+    const std::string &result_path() const { return result_path_; }
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
-    // confident file, then the depth file, then the seen file, then the hits file, then the segments file
+    // confident file, then the fragments file, then the depth file, then the seen file, then the hits file, then the
+    // segments file
     void finish(Engine &e);
 private:
     using Lines = std::vector<std::string>; // [file]
@@ -195,6 +210,10 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
 // the device that classified it, once its final targets are back.  With e.side.support or e.side.depth on, the support
 // pass of a batch runs at the same place and tallies into that device's confident sample.  When its segments file is on, `out` receives
 // the segment lines of every batch under e.side: the segments pass (kid_db_read_segments*) runs at the same place too.
+// With out.fragments_on() and count == 2 the two files are the mates of a sample: the FASTQ blocks of each that are
+// through wait in a queue until the partner's records have arrived; the longest common run of records is handed to
+// kid_db_read_fragments_fastq with a device's fragment sample as its tally, and a block goes as soon as its last record
+// has: none is held longer than the other file lags.
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, SampleOutputs &out, size_t saver_file = 0,
                     const std::function<void(size_t, long long)> &done = nullptr);
 

@@ -26,6 +26,11 @@
 //                    the largest (kid_driver.h)
 //   --seen               also write <prefix>_seen.bin: the sample's seen-bitmap, one bit per database k-mer (of the reads called
 //                    under the rule of --min-hits / --confidence when given), for kmer_shared to compare samples by (kid_driver.h)
+//   --fragments          also write <prefix>_fragments.txt: the result file of the mate pairs called as one fragment each -- record j
+//                    of the R1 file with record j of the R2 file, under the rule of --min-hits / --confidence when given
+//                    (kid_driver.h).  Not with --fasta
+//   --block-bytes N      the size of the FASTQ text blocks the files are cut into (8 MiB; at least 32 KiB are taken): no output
+//                    depends on it
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
 //                    what they would be on FASTQ files with those bases replaced by N; <prefix>_reads.txt prints the
 //                    sequences as they are (kid_driver.h)
@@ -51,7 +56,11 @@
 
 using namespace kidhost;
 
-static std::unique_ptr<ReadSource> open_fastq(const std::string &path, int k, bool *) { return std::unique_ptr<ReadSource>(new FastqStream(path, k)); }
+static size_t g_block_bytes = (size_t)8 << 20; // --block-bytes
+static std::unique_ptr<ReadSource> open_fastq(const std::string &path, int k, bool *)
+{
+    return std::unique_ptr<ReadSource>(new FastqStream(path, k, g_block_bytes));
+}
 // process_fa (:877-913): no '\r' is removed
 static std::unique_ptr<ReadSource> open_fasta(const std::string &path, int k, bool *missing)
 {
@@ -94,6 +103,14 @@ int main(int argc, char **argv)
         else if (a == "--fasta") fasta_mode = true;
         else if (a == "--timing") timing = true;
         else if (a == "--samples-in-flight") in_flight = atoi(val("--samples-in-flight"));
+        else if (a == "--block-bytes") {
+            const char *v = val("--block-bytes");
+            unsigned long long n = 0;
+            size_t nd = 0;
+            for (; v[nd] >= '0' && v[nd] <= '9' && nd < 18; nd++) n = n * 10 + (unsigned)(v[nd] - '0');
+            if (nd == 0 || v[nd] != 0 || n < 1) { std::cerr << "nk10: --block-bytes takes a number of bytes >= 1, digits only\n"; return 2; }
+            g_block_bytes = (size_t)n;
+        }
         else if (const int n = side_option_values(argv[i]); n >= 0) { if (i + n < argc) i += n; } // (side_options below reads them and their values)
         else if (dname.empty()) dname = a;
         else { std::cerr << "nk10: unexpected argument " << a << "\n"; return 2; }
@@ -103,6 +120,10 @@ int main(int argc, char **argv)
         return 2;
     }
     const SideOptions side = side_options(argc, argv, "nk10"); // (checked, then ignored, with --dry-run; --min-base-quality with --fasta too)
+    if (side.fragments && fasta_mode) {
+        std::cerr << "nk10: --fragments needs the two FASTQ files of a sample: not with --fasta\n";
+        return 2;
+    }
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
     if (batch_reads < 1) batch_reads = 1;
     if (threads < 1) threads = 1;
