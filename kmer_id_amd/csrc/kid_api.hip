@@ -606,20 +606,13 @@ extern "C" int kid_classify_batch_device(kid_sample *s, const void *d_bases, uin
                                          const void *d_start, const void *d_stop, uint64_t n_reads, void *d_out_final_targ,
                                          void *stream)
 {
-    if (!s || (n_reads && (!d_bases || !d_offsets))) return kid_fail(KID_ERR_ARG, "null argument");
-    if (((uintptr_t)d_bases & 15u) != 0) return kid_fail(KID_ERR_ARG, "d_bases must be 16-byte aligned");
-    if ((d_start == nullptr) != (d_stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
-    int rc = kid_sample_check_open(s);
+    if (!s) return kid_fail(KID_ERR_ARG, "null argument");
+    KidBatch b{};
+    int rc = kid_check_device_batch(d_bases, d_offsets, d_start, d_stop, n_reads, &b);
+    if (rc == KID_OK) rc = kid_sample_check_open(s);
     if (rc == KID_OK) rc = kid_use_device(s->db->device);
     if (rc != KID_OK) return rc;
-    KidBatch b{};
-    b.bases = (const uint8_t *)d_bases;
-    b.offsets = (const uint64_t *)d_offsets;
-    b.start = (const int32_t *)d_start;
-    b.stop = (const int32_t *)d_stop;
     b.out_final = (uint32_t *)d_out_final_targ;
-    b.n = n_reads;
-    b.fixed_len = 0;
     hipStream_t prep;
     rc = kid_prep_stream_for(s, (hipStream_t)stream, &prep);
     if (rc != KID_OK) return rc;

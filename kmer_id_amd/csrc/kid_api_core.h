@@ -107,31 +107,32 @@ static int kid_check_offsets_batch(const uint64_t *offsets, const int32_t *start
     return KID_OK;
 }
 
-// ... of a block of FASTQ text with the host's line index.  *max_tiles (null: not wanted) is added up over the records:
+// ... of a block of FASTQ text with the host's line index.  *max_tiles (null: not wanted) has the records' tiles added:
 // they may share or overlap sequence bytes -- unless `masking` (a min_base_quality option is on: low-quality bases are
 // overwritten in the device copy of the text, kid_mask.hip.h): then the lines must lie in ascending order without
 // overlap, sequence, quality, next sequence, .., as every indexer of a real file leaves them, so that no byte one record
-// writes is a byte any record's decision reads.  *longest (with `masking`): the longest sequence line.
+// writes is a byte any record's decision reads.  *longest (with `masking`): raised to the longest sequence line.
+// mate: null, or "mate 1, " / "mate 2, " in front of the messages about one block of a call that has two (its caller has
+// checked the size of both together; an absent mate, seq_len = qual_len = 0, has no line to be in order).
 static int kid_check_fastq_block(const kid_fastq_rec *recs, uint64_t n_reads, uint64_t text_nbytes, uint32_t tile, uint64_t *max_tiles,
-                                 bool masking = false, uint32_t *longest = nullptr)
+                                 bool masking = false, uint32_t *longest = nullptr, const char *mate = nullptr)
 {
-    if (text_nbytes >= 0xFFFFFFFFull) return kid_fail(KID_ERR_ARG, "a FASTQ block of 4 GiB or more");
-    uint64_t mt = 0, free_from = 0;
-    uint32_t lg = 0;
+    if (!mate && text_nbytes >= 0xFFFFFFFFull) return kid_fail(KID_ERR_ARG, "a FASTQ block of 4 GiB or more");
+    const char *pre = mate ? mate : "";
+    uint64_t free_from = 0;
     for (uint64_t r = 0; r < n_reads; r++) {
-        if ((uint64_t)recs[r].seq_off + recs[r].seq_len > text_nbytes || (uint64_t)recs[r].qual_off + recs[r].qual_len > text_nbytes)
-            return kid_fail(KID_ERR_ARG, "record %llu lies outside the text block", (unsigned long long)r);
-        if (max_tiles) mt += recs[r].seq_len / tile + 1;
-        if (masking) {
-            if (recs[r].seq_off < free_from || (uint64_t)recs[r].seq_off + recs[r].seq_len > recs[r].qual_off)
-                return kid_fail(KID_ERR_ARG, "record %llu: with min_base_quality on, the lines of a block must be in ascending order and "
-                                             "must not overlap", (unsigned long long)r);
-            free_from = (uint64_t)recs[r].qual_off + recs[r].qual_len;
-            if (recs[r].seq_len > lg) lg = recs[r].seq_len;
+        const kid_fastq_rec &c = recs[r];
+        if ((uint64_t)c.seq_off + c.seq_len > text_nbytes || (uint64_t)c.qual_off + c.qual_len > text_nbytes)
+            return kid_fail(KID_ERR_ARG, "%srecord %llu lies outside the text block", pre, (unsigned long long)r);
+        if (max_tiles) *max_tiles += c.seq_len / tile + 1;
+        if (masking && !(mate && c.seq_len == 0 && c.qual_len == 0)) {
+            if (c.seq_off < free_from || (uint64_t)c.seq_off + c.seq_len > c.qual_off)
+                return kid_fail(KID_ERR_ARG, "%srecord %llu: with min_base_quality on, the lines of a block must be in ascending order and "
+                                             "must not overlap", pre, (unsigned long long)r);
+            free_from = (uint64_t)c.qual_off + c.qual_len;
+            if (longest && c.seq_len > *longest) *longest = c.seq_len;
         }
     }
-    if (max_tiles) *max_tiles = mt;
-    if (longest) *longest = lg;
     return KID_OK;
 }
 
@@ -139,11 +140,14 @@ static int kid_check_fastq_block(const kid_fastq_rec *recs, uint64_t n_reads, ui
 // this many bytes, zero from the last whole group on.
 static inline uint64_t kid_text_bytes(uint64_t nbytes) { return ((nbytes + 15) & ~15ull) + 32; }
 
-static int kid_upload_text(const KidDevBuf &buf, const uint8_t *src, uint64_t nbytes, hipStream_t stream)
+// (src2: a second part that goes right behind the first, as one text)
+static int kid_upload_text(const KidDevBuf &buf, const uint8_t *src, uint64_t nbytes, hipStream_t stream, const uint8_t *src2 = nullptr,
+                           uint64_t nbytes2 = 0)
 {
-    const uint64_t tail = nbytes & ~15ull;
-    KID_HIP(hipMemsetAsync(buf.as<uint8_t>() + tail, 0, kid_text_bytes(nbytes) - tail, stream));
+    const uint64_t all = nbytes + nbytes2, tail = all & ~15ull;
+    KID_HIP(hipMemsetAsync(buf.as<uint8_t>() + tail, 0, kid_text_bytes(all) - tail, stream));
     if (nbytes) KID_HIP(hipMemcpyAsync(buf.p, src, nbytes, hipMemcpyHostToDevice, stream));
+    if (nbytes2) KID_HIP(hipMemcpyAsync(buf.as<uint8_t>() + nbytes, src2, nbytes2, hipMemcpyHostToDevice, stream));
     return KID_OK;
 }
 
@@ -156,4 +160,28 @@ static const uint64_t *kid_rebased_offsets(const uint64_t *offsets, uint64_t n_r
     rel.resize(n_reads + 1);
     for (uint64_t r = 0; r <= n_reads; r++) rel[r] = offsets[r] - base0;
     return rel.data();
+}
+
+// ---------------------------------------------------------------- batches in device memory
+static int kid_check_n_reads(uint64_t n_reads)
+{
+    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
+    return KID_OK;
+}
+
+// What every device form refuses about its batch, in the order callers see, and the KidBatch of the rest.  (The limit
+// on n_reads is not here: the classify form meets it later, in kid_launch_classify, than the hit-pass forms do.)
+static int kid_check_device_batch(const void *d_bases, const void *d_offsets, const void *d_start, const void *d_stop, uint64_t n_reads,
+                                  KidBatch *b)
+{
+    if (n_reads && (!d_bases || !d_offsets)) return kid_fail(KID_ERR_ARG, "null argument");
+    if (((uintptr_t)d_bases & 15u) != 0) return kid_fail(KID_ERR_ARG, "d_bases must be 16-byte aligned");
+    if ((d_start == nullptr) != (d_stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
+    *b = KidBatch{};
+    b->bases = (const uint8_t *)d_bases;
+    b->offsets = (const uint64_t *)d_offsets;
+    b->start = (const int32_t *)d_start;
+    b->stop = (const int32_t *)d_stop;
+    b->n = n_reads;
+    return KID_OK;
 }

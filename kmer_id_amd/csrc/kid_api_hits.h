@@ -1,7 +1,10 @@
 // kid_api_hits.h -- every read's k-mer hits: the scratch of a database's hit passes and kid_db_read_hits*.
-// What the host-buffer forms of kid_db_read_support* (kid_api_support.h) share with those of kid_db_read_hits* is here
-// once: KidSpanTimer, the argument checks and the staging of a batch (kid_hits_check_* / kid_hits_stage_*, one pair per
-// input form) and the hit pass into the library's own buffers (kid_hits_host_pass).
+// What the other families over the hit pass -- kid_db_read_support* (kid_api_support.h), kid_db_read_fragments*
+// (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h) -- share with kid_db_read_hits* is here once:
+// KidSpanTimer, kid_hits_state (the scratch, free: the timers a family settles), kid_hits_scan (the three-kernel
+// exclusive scan), KidOpenBatch and kid_hits_open_* (a host-buffer batch checked, locked and staged, one function per
+// input form over kid_hits_stage_*), the hit pass into the library's own buffers (kid_hits_host_pass), the checks of
+// a CSR output.
 #pragma once
 #include "kid_api_db.h"
 #include "kid_api_mask.h"
@@ -86,8 +89,12 @@ kid_db::~kid_db() {}
 // a little slack: batches of a file differ slightly in size
 static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensure(nbytes, ((nbytes + nbytes / 8) + 255u) & ~255ull); }
 
-// the scratch, free: the hit pass of the call before, and the segment kernels behind it, are through
-static int kid_hits_state(kid_db *db, KidHitsState **out)
+// The scratch, free: the hit pass of the call before, and the segment kernels behind it, are through (they read the
+// tiles' scratch behind the pass) -- and of the kernels that read the pass's CSR alone those that `settle` names: a call
+// waits for the timers its family has always waited for, no more (a device-form caller that queues hits -> support on
+// a stream of its own does not block in the next kid_db_read_hits_device).
+enum : unsigned { KID_SETTLE_SUPPORT = 1u, KID_SETTLE_FRAGMENTS = 2u };
+static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
 {
     if (!db->hits) {
         std::unique_ptr<KidHitsState> h(new KidHitsState());
@@ -100,10 +107,24 @@ static int kid_hits_state(kid_db *db, KidHitsState **out)
         KID_HIP(h->segments.create());
         db->hits = std::move(h);
     }
-    *out = db->hits.get();
-    const int rc = (*out)->pass.settle();
-    return rc != KID_OK ? rc : (*out)->segments.settle(); // (the segment kernels read the tiles' scratch behind the pass)
+    KidHitsState *h = *out = db->hits.get();
+    int rc = h->pass.settle();
+    if (rc == KID_OK) rc = h->segments.settle();
+    if (rc == KID_OK && (settle & KID_SETTLE_SUPPORT)) rc = h->support.settle();
+    if (rc == KID_OK && (settle & KID_SETTLE_FRAGMENTS)) rc = h->fragments.settle();
+    return rc;
 }
+
+// A batch of a host-buffer form, opened (kid_hits_open_offsets / _fastq below): checked, the database's lock taken and
+// held while this lives, the scratch free, the batch staged in it.
+struct KidOpenBatch {
+    std::unique_lock<std::mutex> lock;
+    KidHitsState *h = nullptr;
+    KidBatch b{};                        // the staged copy
+    const KidFastqRec *d_recs = nullptr; // FASTQ form: its records (b.start and b.stop are outputs of the prepare kernel then)
+    uint64_t max_tiles = 0;              // what the tile arrays are sized for (kid_hits_launch)
+    uint32_t longest = 0;                // FASTQ form under min_base_quality: the longest sequence line, for the mask kernel
+};
 
 static KidHitsTiles kid_hits_tiles(const KidHitsState *h, const KidBatch &b)
 {
@@ -115,6 +136,23 @@ static KidHitsTiles kid_hits_tiles(const KidHitsState *h, const KidBatch &b)
     a.tile_mask = h->tile_mask.as<unsigned long long>();
     a.tile_valid = h->want_valid ? h->tile_valid.as<unsigned long long>() : nullptr;
     return a;
+}
+
+// Exclusive scan on `stream` of the values kid_hits_scan_local_kernel<SRC> finds in `src` (0: tiles of a read's
+// descriptor, 1: set bits of a tile's mask, 2: the number itself): out[i] = the sum in front of value i, *total = the
+// sum of all.  d_n: their number where only the device knows it -- n is then the bound the grids are sized for -- or
+// null: n values.  sums: one word per KID_HITS_SCAN_BLOCK values.  A total above `limit` is set to 0 and counted in
+// *overflow; clear[n] is zeroed on the way.
+template <int SRC>
+static void kid_hits_scan(int cu, hipStream_t stream, const void *src, const uint64_t *d_n, uint64_t n, uint64_t *out, uint64_t *sums,
+                          uint64_t *total, uint64_t limit = ~0ull, unsigned long long *overflow = nullptr, uint32_t *clear = nullptr)
+{
+    const uint64_t n_host = d_n ? 0ull : n;
+    hipLaunchKernelGGL(kid_hits_scan_local_kernel<SRC>, dim3(kid_grid_for(n, KID_HITS_SCAN_BLOCK, cu * 8)), dim3(256), 0, stream, src, d_n,
+                       n_host, out, sums, clear);
+    hipLaunchKernelGGL(kid_hits_scan_top_kernel, dim3(1), dim3(1024), 0, stream, sums, d_n, n_host, total, limit, overflow);
+    hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, out, (const uint64_t *)sums, d_n,
+                       n_host, (const uint64_t *)total);
 }
 
 // the fill pass on its own: the host-buffer forms learn the number of hits first and then size their device buffer
@@ -159,22 +197,12 @@ static int kid_hits_launch(kid_db *db, KidHitsState *h, const KidBatch &b, const
         hipLaunchKernelGGL(kid_prepare_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, b, db->info.k, desc, stats, rare,
                            ++h->seq, 0u, (KidLongList *)nullptr, 0);
     // tiles per read -> first tile of every read (n_kmers is cleared on the way)
-    hipLaunchKernelGGL(kid_hits_scan_local_kernel<0>, dim3(kid_grid_for(n, KID_HITS_SCAN_BLOCK, cu * 8)), dim3(256), 0, stream,
-                       (const void *)desc, (const uint64_t *)nullptr, n, tile_off, h->rsum.as<uint64_t>(), d_n_kmers);
-    hipLaunchKernelGGL(kid_hits_scan_top_kernel, dim3(1), dim3(1024), 0, stream, h->rsum.as<uint64_t>(), (const uint64_t *)nullptr, n, n_tiles,
-                       max_tiles, h->ctl() + 35);
-    hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, tile_off,
-                       (const uint64_t *)h->rsum.as<uint64_t>(), (const uint64_t *)nullptr, n, (const uint64_t *)n_tiles);
+    kid_hits_scan<0>(cu, stream, desc, nullptr, n, tile_off, h->rsum.as<uint64_t>(), n_tiles, max_tiles, h->ctl() + 35, d_n_kmers);
     const KidHitsTiles a = kid_hits_tiles(h, b);
     const int tile_grid = kid_grid_for(max_tiles, KID_HITS_WG_TILES, cu * 32);
     hipLaunchKernelGGL(kid_hits_count_kernel, dim3(tile_grid), dim3(256), 0, stream, db->d, a, d_n_kmers);
     // hits per tile -> first hit of every tile
-    hipLaunchKernelGGL(kid_hits_scan_local_kernel<1>, dim3(kid_grid_for(max_tiles, KID_HITS_SCAN_BLOCK, cu * 8)), dim3(256), 0, stream,
-                       (const void *)a.tile_mask, (const uint64_t *)n_tiles, 0ull, tile_hit_off, h->tsum.as<uint64_t>(), (uint32_t *)nullptr);
-    hipLaunchKernelGGL(kid_hits_scan_top_kernel, dim3(1), dim3(1024), 0, stream, h->tsum.as<uint64_t>(), (const uint64_t *)n_tiles, 0ull, n_hits,
-                       ~0ull, (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(max_tiles, 256, cu * 8)), dim3(256), 0, stream, tile_hit_off,
-                       (const uint64_t *)h->tsum.as<uint64_t>(), (const uint64_t *)n_tiles, 0ull, (const uint64_t *)n_hits);
+    kid_hits_scan<1>(cu, stream, a.tile_mask, n_tiles, max_tiles, tile_hit_off, h->tsum.as<uint64_t>(), n_hits);
     hipLaunchKernelGGL(kid_hits_offsets_kernel, dim3(kid_grid_for(n + 1, 256, cu * 8)), dim3(256), 0, stream, (const uint64_t *)tile_off,
                        (const uint64_t *)tile_hit_off, n, d_hit_offsets, d_n_hits);
     if (fill && d_hits && cap) return kid_hits_launch_fill(db, h, b, recs, max_tiles, d_hits, cap, stream);
@@ -200,35 +228,36 @@ static int kid_hits_check(KidHitsState *h)
 // The hit pass of a host-buffer form into the library's own buffers (out_offsets, out_nk, out_hits) on stream 0: the
 // count pass, the number of hits read back, the fill pass if that number is neither 0 nor more than `limit`.
 #define KID_HITS_NO_LIMIT (~0ull)
-static int kid_hits_host_pass(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, uint64_t limit,
-                              uint64_t *n_hits)
+static int kid_hits_host_pass(kid_db *db, const KidOpenBatch &ob, uint64_t limit, uint64_t *n_hits)
 {
-    const uint64_t n = b.n;
-    int rc;
+    KidHitsState *h = ob.h;
+    const uint64_t n = ob.b.n;
     KID_HIP(kid_hits_ensure(h->out_offsets, (n + 1) * 8));
     KID_HIP(kid_hits_ensure(h->out_nk, n * 4));
     uint64_t *d_total = reinterpret_cast<uint64_t *>(h->ctl() + 33);
-    rc = kid_hits_launch(db, h, b, recs, max_tiles, h->out_offsets.as<uint64_t>(), h->out_nk.as<uint32_t>(), nullptr, 0, nullptr, 0, false);
+    int rc = kid_hits_launch(db, h, ob.b, ob.d_recs, ob.max_tiles, h->out_offsets.as<uint64_t>(), h->out_nk.as<uint32_t>(), nullptr, 0, nullptr,
+                             0, false);
     if (rc != KID_OK) return rc;
     uint64_t total = 0;
     KID_HIP(hipMemcpyAsync(&total, d_total, 8, hipMemcpyDeviceToHost, 0));
     KID_HIP(hipStreamSynchronize(0));
     if (total > 0 && total <= limit) {
         KID_HIP(kid_hits_ensure(h->out_hits, total * sizeof(KidHit)));
-        if ((rc = kid_hits_launch_fill(db, h, b, recs, max_tiles, h->out_hits.as<KidHit>(), total, 0)) != KID_OK) return rc;
+        if ((rc = kid_hits_launch_fill(db, h, ob.b, ob.d_recs, ob.max_tiles, h->out_hits.as<KidHit>(), total, 0)) != KID_OK) return rc;
     }
     *n_hits = total;
     return h->pass.end(0, n);
 }
 
 // the host-buffer forms behind their uploads: the hit pass, the fill if the caller's buffer holds it, downloads
-static int kid_hits_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, uint64_t *hit_offsets,
-                             uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
+static int kid_hits_host_run(kid_db *db, const KidOpenBatch &ob, uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap,
+                             uint64_t *n_hits)
 {
     static_assert(sizeof(kid_hit) == sizeof(KidHit), "kid_hit is the device record");
-    const uint64_t n = b.n, limit = hits ? cap : 0;
+    KidHitsState *h = ob.h;
+    const uint64_t n = ob.b.n, limit = hits ? cap : 0;
     uint64_t total = 0;
-    int rc = kid_hits_host_pass(db, h, b, recs, max_tiles, limit, &total);
+    int rc = kid_hits_host_pass(db, ob, limit, &total);
     if (rc != KID_OK) return rc;
     KID_HIP(hipMemcpy(hit_offsets, h->out_offsets.p, (n + 1) * 8, hipMemcpyDeviceToHost));
     if (n_kmers) KID_HIP(hipMemcpy(n_kmers, h->out_nk.p, n * 4, hipMemcpyDeviceToHost));
@@ -238,36 +267,16 @@ static int kid_hits_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, con
     return KID_OK;
 }
 
-// The host-buffer forms, one pair of functions per input form.  kid_hits_check_*: what the host can refuse about the
-// arguments of a batch that has reads, then the database's device selected; *max_tiles: what the tile arrays are sized
-// for.  kid_hits_stage_*: the batch copied into the scratch (synchronous copies on stream 0) -> the KidBatch of the copy.
-static int kid_hits_check_offsets(const kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
-                                  uint64_t n_reads, uint64_t *max_tiles)
+// The host-buffer forms.  kid_hits_stage_*, one per input form: the batch copied into the scratch (synchronous copies on
+// stream 0) -> the KidBatch of the copy, the only place that uploads.  kid_hits_open_*, one per input form, in front of
+// them: the database's lock, what the host can refuse about the arguments of a batch that has reads, the database's
+// device selected, the scratch free (kid_hits_state with the family's `settle`), the batch staged.
+static int kid_hits_stage_text(KidHitsState *h, const uint8_t *src, uint64_t nbytes, KidBatch *b, const uint8_t *src2 = nullptr,
+                               uint64_t nbytes2 = 0)
 {
-    if (!bases || !offsets) return kid_fail(KID_ERR_ARG, "null argument");
-    if ((start == nullptr) != (stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
-    int64_t max_kmers = 0;
-    int rc = kid_check_offsets_batch(offsets, start, stop, n_reads, db->info.k, &max_kmers, KID_HITS_TILE, max_tiles);
-    if (rc != KID_OK) return rc;
-    return kid_use_device(db->device);
-}
-
-// (called with the database's lock held: db->min_base_quality, under which the block's lines must be in order; *longest:
-// the longest sequence line, for the mask kernel)
-static int kid_hits_check_fastq(const kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
-                                uint64_t *max_tiles, uint32_t *longest)
-{
-    if (!text || !recs) return kid_fail(KID_ERR_ARG, "null argument");
-    int rc = kid_check_fastq_block(recs, n_reads, text_nbytes, KID_HITS_TILE, max_tiles, db->min_base_quality > 0, longest);
-    if (rc != KID_OK) return rc;
-    return kid_use_device(db->device);
-}
-
-static int kid_hits_stage_text(KidHitsState *h, const uint8_t *src, uint64_t nbytes, KidBatch *b)
-{
-    KID_HIP(kid_hits_ensure(h->in_bases, kid_text_bytes(nbytes)));
+    KID_HIP(kid_hits_ensure(h->in_bases, kid_text_bytes(nbytes + nbytes2)));
     b->bases = h->in_bases.as<uint8_t>();
-    return kid_upload_text(h->in_bases, src, nbytes, 0);
+    return kid_upload_text(h->in_bases, src, nbytes, 0, src2, nbytes2);
 }
 
 static int kid_hits_stage_offsets(KidHitsState *h, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
@@ -294,10 +303,12 @@ static int kid_hits_stage_offsets(KidHitsState *h, const uint8_t *bases, const u
 }
 
 // (under KID_DB_OPT_MIN_BASE_QUALITY the staged text is masked here, in front of the hit pass: the caller's is not touched)
-static int kid_hits_stage_fastq(const kid_db *db, KidHitsState *h, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs,
-                                uint64_t n_reads, uint32_t longest, KidBatch *b, const KidFastqRec **d_recs)
+// (text2: a second block that goes right behind the first; the offsets in recs count from the first's first byte)
+static int kid_hits_stage_fastq(const kid_db *db, KidHitsState *h, const uint8_t *text, uint64_t text_nbytes, const uint8_t *text2,
+                                uint64_t nbytes2, const kid_fastq_rec *recs, uint64_t n_reads, uint32_t longest, KidBatch *b,
+                                const KidFastqRec **d_recs)
 {
-    int rc = kid_hits_stage_text(h, text, text_nbytes, b);
+    int rc = kid_hits_stage_text(h, text, text_nbytes, b, text2, nbytes2);
     if (rc != KID_OK) return rc;
     KID_HIP(kid_hits_ensure(h->in_recs, n_reads * sizeof(KidFastqRec)));
     KID_HIP(kid_hits_ensure(h->trim_start, n_reads * 4));
@@ -312,70 +323,127 @@ static int kid_hits_stage_fastq(const kid_db *db, KidHitsState *h, const uint8_t
     return KID_OK;
 }
 
+// more_scratch (null: none): what a family sizes for the batch between the state and the staging (kid_segments_size)
+typedef int (*KidHitsMoreScratch)(KidHitsState *h, uint64_t max_tiles);
+
+static int kid_hits_open_offsets(KidOpenBatch &ob, kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start,
+                                 const int32_t *stop, uint64_t n_reads, unsigned settle, KidHitsMoreScratch more_scratch = nullptr)
+{
+    ob.lock = std::unique_lock<std::mutex>(db->hits_mu);
+    if (!bases || !offsets) return kid_fail(KID_ERR_ARG, "null argument");
+    if ((start == nullptr) != (stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
+    int64_t max_kmers = 0;
+    int rc = kid_check_offsets_batch(offsets, start, stop, n_reads, db->info.k, &max_kmers, KID_HITS_TILE, &ob.max_tiles);
+    if (rc == KID_OK) rc = kid_use_device(db->device);
+    if (rc == KID_OK) rc = kid_hits_state(db, settle, &ob.h);
+    if (rc == KID_OK && more_scratch) rc = more_scratch(ob.h, ob.max_tiles);
+    if (rc != KID_OK) return rc;
+    return kid_hits_stage_offsets(ob.h, bases, offsets, start, stop, n_reads, &ob.b);
+}
+
+// (shift: the bytes of block 1, which block 2 is staged behind; the two together stay below 4 GiB)
+static std::vector<kid_fastq_rec> kid_fastq_interleave(const kid_fastq_rec *recs1, const kid_fastq_rec *recs2, uint64_t n, uint32_t shift)
+{
+    std::vector<kid_fastq_rec> merged(2 * n);
+    for (uint64_t i = 0; i < n; i++) {
+        merged[2 * i] = recs1[i];
+        kid_fastq_rec c = recs2[i];
+        c.seq_off += shift;
+        c.qual_off += shift;
+        merged[2 * i + 1] = c;
+    }
+    return merged;
+}
+
+// One block of n_reads records, or (recs2 given) two blocks of n_reads / 2 each, the mates of n_reads / 2 fragments: they
+// are staged as one text, block 2 behind block 1, with one record index in interleaved order (read 2i from block 1,
+// read 2i + 1 from block 2 with its offsets shifted), so that one hit pass takes both.  (The lock comes first:
+// db->min_base_quality, under which a block's lines must be in order.)
+static int kid_hits_open_fastq(KidOpenBatch &ob, kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs,
+                               uint64_t n_reads, unsigned settle, KidHitsMoreScratch more_scratch = nullptr, const uint8_t *text2 = nullptr,
+                               uint64_t nbytes2 = 0, const kid_fastq_rec *recs2 = nullptr)
+{
+    ob.lock = std::unique_lock<std::mutex>(db->hits_mu);
+    const bool masking = db->min_base_quality > 0;
+    const uint64_t n_block = recs2 ? n_reads / 2 : n_reads;
+    if (!recs2 && (!text || !recs)) return kid_fail(KID_ERR_ARG, "null argument");
+    int rc = kid_check_fastq_block(recs, n_block, text_nbytes, KID_HITS_TILE, &ob.max_tiles, masking, &ob.longest, recs2 ? "mate 1, " : nullptr);
+    if (rc == KID_OK && recs2) rc = kid_check_fastq_block(recs2, n_block, nbytes2, KID_HITS_TILE, &ob.max_tiles, masking, &ob.longest, "mate 2, ");
+    if (rc == KID_OK) rc = kid_use_device(db->device);
+    if (rc == KID_OK) rc = kid_hits_state(db, settle, &ob.h);
+    if (rc == KID_OK && more_scratch) rc = more_scratch(ob.h, ob.max_tiles);
+    if (rc != KID_OK) return rc;
+    std::vector<kid_fastq_rec> merged; // (a synchronous copy reads it)
+    if (recs2) {
+        merged = kid_fastq_interleave(recs, recs2, n_block, (uint32_t)text_nbytes);
+        recs = merged.data();
+    }
+    return kid_hits_stage_fastq(db, ob.h, text, text_nbytes, text2, nbytes2, recs, n_reads, ob.longest, &ob.b, &ob.d_recs);
+}
+
+// The CSR outputs of a call -- offsets[n_reads + 1], up to `cap` records (`what`), their number -- as the host forms
+// check them, and as a call without reads leaves them, on the host and in device memory (d_n2: a second number).
+static int kid_check_csr_out(const kid_db *db, const uint64_t *out_offsets, const void *records, uint64_t cap, const uint64_t *n_out,
+                             uint64_t n_reads, const char *what)
+{
+    if (!db || !out_offsets || !n_out) return kid_fail(KID_ERR_ARG, "null argument");
+    const int rc = kid_check_n_reads(n_reads);
+    if (rc != KID_OK) return rc;
+    if (cap && !records) return kid_fail(KID_ERR_ARG, "cap without a %s buffer", what);
+    return KID_OK;
+}
+static int kid_csr_out_empty(uint64_t *out_offsets, uint64_t *n_out)
+{
+    out_offsets[0] = 0;
+    *n_out = 0;
+    return KID_OK;
+}
+static int kid_csr_out_empty_device(hipStream_t stream, void *d_out_offsets, void *d_n, void *d_n2 = nullptr)
+{
+    KID_HIP(hipMemsetAsync(d_out_offsets, 0, 8, stream));
+    KID_HIP(hipMemsetAsync(d_n, 0, 8, stream));
+    if (d_n2) KID_HIP(hipMemsetAsync(d_n2, 0, 8, stream));
+    return KID_OK;
+}
+
 extern "C" int kid_db_read_hits(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
                                 uint64_t n_reads, uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
 {
-    if (!db || !hit_offsets || !n_hits) return kid_fail(KID_ERR_ARG, "null argument");
-    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
-    if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
-    if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
-    uint64_t max_tiles = 0;
-    int rc = kid_hits_check_offsets(db, bases, offsets, start, stop, n_reads, &max_tiles);
+    int rc = kid_check_csr_out(db, hit_offsets, hits, cap, n_hits, n_reads, "hits");
     if (rc != KID_OK) return rc;
-    std::lock_guard<std::mutex> lock(db->hits_mu);
-    KidHitsState *h = nullptr;
-    KidBatch b{};
-    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
-    if ((rc = kid_hits_stage_offsets(h, bases, offsets, start, stop, n_reads, &b)) != KID_OK) return rc;
-    return kid_hits_host_run(db, h, b, nullptr, max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
+    if (n_reads == 0) return kid_csr_out_empty(hit_offsets, n_hits);
+    KidOpenBatch ob;
+    if ((rc = kid_hits_open_offsets(ob, db, bases, offsets, start, stop, n_reads, 0)) != KID_OK) return rc;
+    return kid_hits_host_run(db, ob, hit_offsets, n_kmers, hits, cap, n_hits);
 }
 
 extern "C" int kid_db_read_hits_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
                                       uint64_t *hit_offsets, uint32_t *n_kmers, kid_hit *hits, uint64_t cap, uint64_t *n_hits)
 {
-    if (!db || !hit_offsets || !n_hits) return kid_fail(KID_ERR_ARG, "null argument");
-    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
-    if (cap && !hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
-    if (n_reads == 0) { hit_offsets[0] = 0; *n_hits = 0; return KID_OK; }
-    uint64_t max_tiles = 0;
-    uint32_t longest = 0;
-    std::lock_guard<std::mutex> lock(db->hits_mu);
-    int rc = kid_hits_check_fastq(db, text, text_nbytes, recs, n_reads, &max_tiles, &longest);
+    int rc = kid_check_csr_out(db, hit_offsets, hits, cap, n_hits, n_reads, "hits");
     if (rc != KID_OK) return rc;
-    KidHitsState *h = nullptr;
-    KidBatch b{};
-    const KidFastqRec *d_recs = nullptr;
-    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
-    if ((rc = kid_hits_stage_fastq(db, h, text, text_nbytes, recs, n_reads, longest, &b, &d_recs)) != KID_OK) return rc;
-    return kid_hits_host_run(db, h, b, d_recs, max_tiles, hit_offsets, n_kmers, hits, cap, n_hits);
+    if (n_reads == 0) return kid_csr_out_empty(hit_offsets, n_hits);
+    KidOpenBatch ob;
+    if ((rc = kid_hits_open_fastq(ob, db, text, text_nbytes, recs, n_reads, 0)) != KID_OK) return rc;
+    return kid_hits_host_run(db, ob, hit_offsets, n_kmers, hits, cap, n_hits);
 }
 
 extern "C" int kid_db_read_hits_device(kid_db *db, const void *d_bases, uint64_t bases_nbytes, const void *d_offsets, const void *d_start,
                                        const void *d_stop, uint64_t n_reads, void *d_hit_offsets, void *d_n_kmers, void *d_hits,
                                        uint64_t cap, void *d_n_hits, void *stream)
 {
-    if (!db || !d_hit_offsets || !d_n_hits || (n_reads && (!d_bases || !d_offsets))) return kid_fail(KID_ERR_ARG, "null argument");
-    if (((uintptr_t)d_bases & 15u) != 0) return kid_fail(KID_ERR_ARG, "d_bases must be 16-byte aligned");
-    if ((d_start == nullptr) != (d_stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
-    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
-    if (cap && !d_hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
-    int rc = kid_use_device(db->device);
+    if (!db || !d_hit_offsets || !d_n_hits) return kid_fail(KID_ERR_ARG, "null argument");
+    KidBatch b{};
+    int rc = kid_check_device_batch(d_bases, d_offsets, d_start, d_stop, n_reads, &b);
+    if (rc == KID_OK) rc = kid_check_n_reads(n_reads);
     if (rc != KID_OK) return rc;
+    if (cap && !d_hits) return kid_fail(KID_ERR_ARG, "cap without a hits buffer");
+    if ((rc = kid_use_device(db->device)) != KID_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (n_reads == 0) {
-        KID_HIP(hipMemsetAsync(d_hit_offsets, 0, 8, st));
-        KID_HIP(hipMemsetAsync(d_n_hits, 0, 8, st));
-        return KID_OK;
-    }
+    if (n_reads == 0) return kid_csr_out_empty_device(st, d_hit_offsets, d_n_hits);
     std::lock_guard<std::mutex> lock(db->hits_mu);
     KidHitsState *h = nullptr;
-    if ((rc = kid_hits_state(db, &h)) != KID_OK) return rc;
-    KidBatch b{};
-    b.bases = (const uint8_t *)d_bases;
-    b.offsets = (const uint64_t *)d_offsets;
-    b.start = (const int32_t *)d_start;
-    b.stop = (const int32_t *)d_stop;
-    b.n = n_reads;
+    if ((rc = kid_hits_state(db, 0, &h)) != KID_OK) return rc;
     rc = kid_hits_launch(db, h, b, nullptr, bases_nbytes / KID_HITS_TILE + n_reads, (uint64_t *)d_hit_offsets, (uint32_t *)d_n_kmers, (KidHit *)d_hits, cap,
                          (uint64_t *)d_n_hits, st, true);
     if (rc != KID_OK) return rc;

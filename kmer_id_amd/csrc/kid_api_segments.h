@@ -1,9 +1,10 @@
 // kid_api_segments.h -- call records in segments: kid_db_read_segments* over the hit pass and the kernels of
-// kid_segments.hip.h.  The host-buffer forms check and stage their batch and run the hit pass with the functions of
-// kid_api_hits.h (kid_hits_check_*, kid_hits_stage_*, kid_hits_host_pass with every hit filled in); the device form runs
-// kid_hits_launch into the caller's hit buffer.  While one of these calls runs, the hit pass also leaves the tiles'
-// valid masks (KidHitsState::want_valid).  The segment kernels -- segments per read and their scan, the scan of the
-// valid masks, kid_segments_kernel -- follow the pass on its stream and have the third KidSpanTimer of the state.
+// kid_segments.hip.h.  The host-buffer forms open their batch and run the hit pass with the functions of kid_api_hits.h
+// (kid_hits_open_*, kid_hits_host_pass with every hit filled in); the device form runs kid_hits_launch into the caller's
+// hit buffer.  While one of these calls runs, the hit pass also leaves the tiles' valid masks (KidHitsState::want_valid,
+// sized by kid_segments_size).  The segment kernels -- segments per read and their scan, the scan of the valid masks
+// (both kid_hits_scan), kid_segments_kernel -- follow the pass on its stream and have the third KidSpanTimer of the
+// state.  A call settles the pass, segments and support timers, not the fragments one.
 #pragma once
 #include "kid_api_support.h"
 #include "kid_segments.hip.h"
@@ -19,13 +20,10 @@ static int kid_segments_check_rule(uint32_t seg_len, uint32_t seg_step, uint32_t
     return kid_support_check_rule(min_permille);
 }
 
-// the hits scratch, free, and the hit pass told to leave the valid masks of a batch of up to max_tiles tiles; the
-// scratch of the two scans
-static int kid_segments_state(kid_db *db, uint64_t max_tiles, KidHitsState **out)
+// What a segments call sizes between the state and the staging (KidHitsMoreScratch): room for the valid masks of a
+// batch of up to max_tiles tiles and for their scan, the two totals.  The call then sets want_valid for its length.
+static int kid_segments_size(KidHitsState *h, uint64_t max_tiles)
 {
-    int rc = kid_support_state(db, out);
-    if (rc != KID_OK) return rc;
-    KidHitsState *h = *out;
     if (!h->seg_ctl.p) {
         KID_HIP(h->seg_ctl.alloc(16));
         KID_HIP(hipMemset(h->seg_ctl.p, 0, 16));
@@ -46,22 +44,11 @@ static int kid_segments_launch_scans(kid_db *db, KidHitsState *h, uint64_t n, ui
 {
     const int cu = db->num_cu;
     const uint64_t *n_tiles = reinterpret_cast<const uint64_t *>(h->ctl() + 32);
-    uint64_t *totals = h->seg_ctl.as<uint64_t>(), *rsum = h->rsum.as<uint64_t>(), *tsum = h->tsum.as<uint64_t>();
-    uint64_t *valid_off = h->tile_valid_off.as<uint64_t>();
+    uint64_t *totals = h->seg_ctl.as<uint64_t>();
     hipLaunchKernelGGL(kid_segments_count_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream,
                        (const KidReadDesc *)h->desc.as<KidReadDesc>(), (const uint64_t *)h->tile_off.as<uint64_t>(), n, g, d_seg_offsets);
-    hipLaunchKernelGGL(kid_hits_scan_local_kernel<2>, dim3(kid_grid_for(n, KID_HITS_SCAN_BLOCK, cu * 8)), dim3(256), 0, stream,
-                       (const void *)d_seg_offsets, (const uint64_t *)nullptr, n, d_seg_offsets, rsum, (uint32_t *)nullptr);
-    hipLaunchKernelGGL(kid_hits_scan_top_kernel, dim3(1), dim3(1024), 0, stream, rsum, (const uint64_t *)nullptr, n, totals, ~0ull,
-                       (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(n, 256, cu * 8)), dim3(256), 0, stream, d_seg_offsets, (const uint64_t *)rsum,
-                       (const uint64_t *)nullptr, n, (const uint64_t *)totals);
-    hipLaunchKernelGGL(kid_hits_scan_local_kernel<1>, dim3(kid_grid_for(max_tiles, KID_HITS_SCAN_BLOCK, cu * 8)), dim3(256), 0, stream,
-                       (const void *)h->tile_valid.p, n_tiles, 0ull, valid_off, tsum, (uint32_t *)nullptr);
-    hipLaunchKernelGGL(kid_hits_scan_top_kernel, dim3(1), dim3(1024), 0, stream, tsum, n_tiles, 0ull, totals + 1, ~0ull,
-                       (unsigned long long *)nullptr);
-    hipLaunchKernelGGL(kid_hits_scan_add_kernel, dim3(kid_grid_for(max_tiles, 256, cu * 8)), dim3(256), 0, stream, valid_off, (const uint64_t *)tsum,
-                       n_tiles, 0ull, (const uint64_t *)(totals + 1));
+    kid_hits_scan<2>(cu, stream, d_seg_offsets, nullptr, n, d_seg_offsets, h->rsum.as<uint64_t>(), totals);
+    kid_hits_scan<1>(cu, stream, h->tile_valid.p, n_tiles, max_tiles, h->tile_valid_off.as<uint64_t>(), h->tsum.as<uint64_t>(), totals + 1);
     KID_HIP(hipGetLastError());
     return KID_OK;
 }
@@ -95,24 +82,26 @@ static int kid_segments_launch_kernel(kid_db *db, KidHitsState *h, const KidBatc
 
 // The host-buffer forms behind their uploads: the hit pass into the library's scratch, the scans, the number of
 // segments read back, the kernel if the caller's buffer holds them, downloads.
-static int kid_segments_host_run(kid_db *db, KidHitsState *h, const KidBatch &b, const KidFastqRec *recs, uint64_t max_tiles, KidSegGeom g,
-                                 KidSupportRule rule, uint64_t *seg_offsets, kid_segment *segments, uint64_t cap, uint64_t *n_segments)
+static int kid_segments_host_run(kid_db *db, const KidOpenBatch &ob, KidSegGeom g, KidSupportRule rule, uint64_t *seg_offsets,
+                                 kid_segment *segments, uint64_t cap, uint64_t *n_segments)
 {
-    const uint64_t n = b.n, limit = segments ? cap : 0;
+    KidHitsState *h = ob.h;
+    const KidWantValid valid(h);
+    const uint64_t n = ob.b.n, limit = segments ? cap : 0;
     uint64_t n_hits = 0, total = 0;
     int rc;
     KID_HIP(kid_hits_ensure(h->out_seg_offsets, (n + 1) * 8));
-    if ((rc = kid_hits_host_pass(db, h, b, recs, max_tiles, KID_HITS_NO_LIMIT, &n_hits)) != KID_OK) return rc;
+    if ((rc = kid_hits_host_pass(db, ob, KID_HITS_NO_LIMIT, &n_hits)) != KID_OK) return rc;
     if ((rc = kid_hits_check(h)) != KID_OK) return rc;
     uint64_t *d_seg_offsets = h->out_seg_offsets.as<uint64_t>();
     if ((rc = h->segments.begin(0)) != KID_OK) return rc;
-    if ((rc = kid_segments_launch_scans(db, h, n, max_tiles, g, d_seg_offsets, 0)) != KID_OK) return rc;
+    if ((rc = kid_segments_launch_scans(db, h, n, ob.max_tiles, g, d_seg_offsets, 0)) != KID_OK) return rc;
     KID_HIP(hipMemcpyAsync(&total, h->seg_ctl.p, 8, hipMemcpyDeviceToHost, 0));
     KID_HIP(hipStreamSynchronize(0));
     const bool fill = total > 0 && total <= limit;
     if (fill) {
         KID_HIP(kid_hits_ensure(h->out_segments, total * sizeof(KidSegment)));
-        rc = kid_segments_launch_kernel(db, h, b, recs, g, rule, d_seg_offsets, n_hits ? h->out_hits.as<KidHit>() : nullptr, KID_HITS_NO_LIMIT,
+        rc = kid_segments_launch_kernel(db, h, ob.b, ob.d_recs, g, rule, d_seg_offsets, n_hits ? h->out_hits.as<KidHit>() : nullptr, KID_HITS_NO_LIMIT,
                                         h->out_segments.as<KidSegment>(), total, total, 0);
         if (rc != KID_OK) return rc;
     }
@@ -123,55 +112,32 @@ static int kid_segments_host_run(kid_db *db, KidHitsState *h, const KidBatch &b,
     return KID_OK;
 }
 
-static int kid_segments_check_out(const kid_db *db, const uint64_t *seg_offsets, const kid_segment *segments, uint64_t cap, const uint64_t *n_segments,
-                                  uint64_t n_reads)
-{
-    if (!db || !seg_offsets || !n_segments) return kid_fail(KID_ERR_ARG, "null argument");
-    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
-    if (cap && !segments) return kid_fail(KID_ERR_ARG, "cap without a segments buffer");
-    return KID_OK;
-}
-
 extern "C" int kid_db_read_segments(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
                                     uint64_t n_reads, uint32_t seg_len, uint32_t seg_step, uint32_t min_hits, uint32_t min_permille,
                                     uint64_t *seg_offsets, kid_segment *segments, uint64_t cap, uint64_t *n_segments)
 {
-    int rc = kid_segments_check_out(db, seg_offsets, segments, cap, n_segments, n_reads);
+    int rc = kid_check_csr_out(db, seg_offsets, segments, cap, n_segments, n_reads, "segments");
+    if (rc == KID_OK) rc = kid_segments_check_rule(seg_len, seg_step, min_permille);
     if (rc != KID_OK) return rc;
-    if ((rc = kid_segments_check_rule(seg_len, seg_step, min_permille)) != KID_OK) return rc;
-    if (n_reads == 0) { seg_offsets[0] = 0; *n_segments = 0; return KID_OK; }
-    uint64_t max_tiles = 0;
-    if ((rc = kid_hits_check_offsets(db, bases, offsets, start, stop, n_reads, &max_tiles)) != KID_OK) return rc;
-    std::lock_guard<std::mutex> lock(db->hits_mu);
-    KidHitsState *h = nullptr;
-    KidBatch b{};
-    if ((rc = kid_segments_state(db, max_tiles, &h)) != KID_OK) return rc;
-    KidWantValid valid(h);
-    if ((rc = kid_hits_stage_offsets(h, bases, offsets, start, stop, n_reads, &b)) != KID_OK) return rc;
-    return kid_segments_host_run(db, h, b, nullptr, max_tiles, KidSegGeom{seg_len, seg_step}, KidSupportRule{min_hits, min_permille}, seg_offsets,
-                                 segments, cap, n_segments);
+    if (n_reads == 0) return kid_csr_out_empty(seg_offsets, n_segments);
+    KidOpenBatch ob;
+    if ((rc = kid_hits_open_offsets(ob, db, bases, offsets, start, stop, n_reads, KID_SETTLE_SUPPORT, kid_segments_size)) != KID_OK) return rc;
+    return kid_segments_host_run(db, ob, KidSegGeom{seg_len, seg_step}, KidSupportRule{min_hits, min_permille}, seg_offsets, segments, cap,
+                                 n_segments);
 }
 
 extern "C" int kid_db_read_segments_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
                                           uint32_t seg_len, uint32_t seg_step, uint32_t min_hits, uint32_t min_permille, uint64_t *seg_offsets,
                                           kid_segment *segments, uint64_t cap, uint64_t *n_segments)
 {
-    int rc = kid_segments_check_out(db, seg_offsets, segments, cap, n_segments, n_reads);
+    int rc = kid_check_csr_out(db, seg_offsets, segments, cap, n_segments, n_reads, "segments");
+    if (rc == KID_OK) rc = kid_segments_check_rule(seg_len, seg_step, min_permille);
     if (rc != KID_OK) return rc;
-    if ((rc = kid_segments_check_rule(seg_len, seg_step, min_permille)) != KID_OK) return rc;
-    if (n_reads == 0) { seg_offsets[0] = 0; *n_segments = 0; return KID_OK; }
-    uint64_t max_tiles = 0;
-    uint32_t longest = 0;
-    std::lock_guard<std::mutex> lock(db->hits_mu);
-    if ((rc = kid_hits_check_fastq(db, text, text_nbytes, recs, n_reads, &max_tiles, &longest)) != KID_OK) return rc;
-    KidHitsState *h = nullptr;
-    KidBatch b{};
-    const KidFastqRec *d_recs = nullptr;
-    if ((rc = kid_segments_state(db, max_tiles, &h)) != KID_OK) return rc;
-    KidWantValid valid(h);
-    if ((rc = kid_hits_stage_fastq(db, h, text, text_nbytes, recs, n_reads, longest, &b, &d_recs)) != KID_OK) return rc;
-    return kid_segments_host_run(db, h, b, d_recs, max_tiles, KidSegGeom{seg_len, seg_step}, KidSupportRule{min_hits, min_permille}, seg_offsets,
-                                 segments, cap, n_segments);
+    if (n_reads == 0) return kid_csr_out_empty(seg_offsets, n_segments);
+    KidOpenBatch ob;
+    if ((rc = kid_hits_open_fastq(ob, db, text, text_nbytes, recs, n_reads, KID_SETTLE_SUPPORT, kid_segments_size)) != KID_OK) return rc;
+    return kid_segments_host_run(db, ob, KidSegGeom{seg_len, seg_step}, KidSupportRule{min_hits, min_permille}, seg_offsets, segments, cap,
+                                 n_segments);
 }
 
 extern "C" int kid_db_read_segments_device(kid_db *db, const void *d_bases, uint64_t bases_nbytes, const void *d_offsets, const void *d_start,
@@ -179,34 +145,24 @@ extern "C" int kid_db_read_segments_device(kid_db *db, const void *d_bases, uint
                                            uint32_t min_permille, void *d_hits, uint64_t hits_cap, void *d_seg_offsets, void *d_segments,
                                            uint64_t seg_cap, void *d_n_hits, void *d_n_segments, void *stream)
 {
-    if (!db || !d_seg_offsets || !d_n_hits || !d_n_segments || (n_reads && (!d_bases || !d_offsets))) return kid_fail(KID_ERR_ARG, "null argument");
-    if (((uintptr_t)d_bases & 15u) != 0) return kid_fail(KID_ERR_ARG, "d_bases must be 16-byte aligned");
-    if ((d_start == nullptr) != (d_stop == nullptr)) return kid_fail(KID_ERR_ARG, "start and stop must both be given or both be null");
-    if (n_reads > 0x7FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^31-1 reads per batch");
+    if (!db || !d_seg_offsets || !d_n_hits || !d_n_segments) return kid_fail(KID_ERR_ARG, "null argument");
+    KidBatch b{};
+    int rc = kid_check_device_batch(d_bases, d_offsets, d_start, d_stop, n_reads, &b);
+    if (rc == KID_OK) rc = kid_check_n_reads(n_reads);
+    if (rc != KID_OK) return rc;
     if (hits_cap && !d_hits) return kid_fail(KID_ERR_ARG, "hits_cap without a hits buffer");
     if (seg_cap && !d_segments) return kid_fail(KID_ERR_ARG, "seg_cap without a segments buffer");
-    int rc = kid_segments_check_rule(seg_len, seg_step, min_permille);
-    if (rc != KID_OK) return rc;
+    if ((rc = kid_segments_check_rule(seg_len, seg_step, min_permille)) != KID_OK) return rc;
     if ((rc = kid_use_device(db->device)) != KID_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (n_reads == 0) {
-        KID_HIP(hipMemsetAsync(d_seg_offsets, 0, 8, st));
-        KID_HIP(hipMemsetAsync(d_n_hits, 0, 8, st));
-        KID_HIP(hipMemsetAsync(d_n_segments, 0, 8, st));
-        return KID_OK;
-    }
+    if (n_reads == 0) return kid_csr_out_empty_device(st, d_seg_offsets, d_n_hits, d_n_segments);
     const uint64_t max_tiles = bases_nbytes / KID_HITS_TILE + n_reads;
     std::lock_guard<std::mutex> lock(db->hits_mu);
     KidHitsState *h = nullptr;
-    if ((rc = kid_segments_state(db, max_tiles, &h)) != KID_OK) return rc;
+    if ((rc = kid_hits_state(db, KID_SETTLE_SUPPORT, &h)) != KID_OK) return rc;
+    if ((rc = kid_segments_size(h, max_tiles)) != KID_OK) return rc;
     KidWantValid valid(h);
     KID_HIP(kid_hits_ensure(h->out_offsets, (n_reads + 1) * 8)); // (the hit pass wants a place for its CSR offsets)
-    KidBatch b{};
-    b.bases = (const uint8_t *)d_bases;
-    b.offsets = (const uint64_t *)d_offsets;
-    b.start = (const int32_t *)d_start;
-    b.stop = (const int32_t *)d_stop;
-    b.n = n_reads;
     rc = kid_hits_launch(db, h, b, nullptr, max_tiles, h->out_offsets.as<uint64_t>(), nullptr, (KidHit *)d_hits, hits_cap, (uint64_t *)d_n_hits, st, true);
     if (rc != KID_OK) return rc;
     if ((rc = h->pass.end(st, n_reads)) != KID_OK) return rc;
