@@ -391,6 +391,48 @@ int kid_db_fragments_from_hits_device(kid_db *db, const void *d_hit_offsets, con
  * call.                                                                                                              */
 int kid_db_read_fragments_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *fragments);
 
+/* ---- calling reads by root-path votes ----------------------------------------------------
+ * `final` is a left fold with msca, which is neither associative nor symmetric: the lookup is canonical, so a read and
+ * its reverse complement have the same hits in opposite order and can fold to different targets (hits [X, 8, 6] with
+ * 6 -> 8 and X on another lineage fold to 6, [6, 8, X] to 1).  These calls weigh the hits on the tree instead; the
+ * record is a pure function of the MULTISET of the read's hit targets and its n_kmers.  With t_1 .. t_m and n as for
+ * kid_db_read_support (the hits of kid_db_read_hits, targets equal to 1 included):
+ *   w(c)       the number of hits with t_i = c
+ *   P(c)       the number of hits whose target is c or an ancestor of c: the sum of w over c's root path.  A hit at the
+ *              root counts for every node.
+ *   best       the largest P(t_i); L = the distinct hit targets with P = best.  P strictly grows down a lineage of hit
+ *              nodes, so no two members of L lie on one lineage.
+ *   call       the lowest common ancestor of L: the deepest node that is on every member's root path (NOT msca).  With
+ *              one member it is that target; 0 when m = 0.
+ *   S(c), the rule and "c passes" are those of kid_db_read_support.
+ *   confident  the first node on call, parent(call), .., 1 that passes, 0 if none does or call = 0.  Under the rule
+ *              (0, 0) confident = call for every read.
+ * On the tree 5 -> 6 -> 8, 5 -> 35 -> 36: [6, 8] -> call 8, p_best 2; [X, 8, 6] -> 8; [8, 36] -> a tie, call 5,
+ * n_best 2; [X, 8] -> a tie, call 1; [1, X] -> call X, p_best 2; [8, 8, 36, 36, X] -> call 5 (its fold ends at 1).
+ * The records are byte-identical across runs, splits of the batch into calls, table kinds and any permutation of a
+ * read's hits.  Reads of more than a few hundred hits are settled by a second kernel queued behind the first.       */
+typedef struct kid_vote {
+    uint32_t call, confident, n_kmers, n_hits /* m */, p_best /* best, 0 without a hit */, n_best /* |L| */,
+        s_call /* S(call), 0 if call = 0 */, s_confident /* S(confident), 0 if confident = 0 */;
+} kid_vote;
+/* The four forms of kid_db_read_support*, argument for argument: host buffers (32 bytes per read come back), a FASTQ
+ * block (KID_DB_OPT_MIN_BASE_QUALITY applies as in kid_db_read_support_fastq), the kernels alone on a CSR in HBM
+ * (asynchronous on `stream`, no tally; a target outside (0, ntar) is read as the root), and the device time of the vote
+ * kernels ALONE since the last query.  Errors and the one-call-at-a-time rule are theirs: min_permille > 1000 is
+ * KID_ERR_ARG, n_reads = 0 returns KID_OK and launches nothing.
+ *   tally      as in kid_db_read_support with `confident` as defined here: gcount[confident]++ per counted read; for
+ *              reads with confident > 0 the seen bit of every hit with target > 1, and depth[entry] under
+ *              KID_OPT_ENTRY_DEPTH.  A sample of another kid_db is KID_ERR_ARG, one that has ended KID_ERR_STATE.
+ * Scratch beside the hit pass's: 4 bytes per read of the largest batch and one row of 4 * ntar bytes per compute unit,
+ * owned by the kid_db and released by kid_db_destroy.                                                               */
+int kid_db_read_votes(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                      uint64_t n_reads, uint32_t min_hits, uint32_t min_permille, kid_vote *out, kid_sample *tally);
+int kid_db_read_votes_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                            uint32_t min_hits, uint32_t min_permille, kid_vote *out, kid_sample *tally);
+int kid_db_votes_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
+                                  uint32_t min_hits, uint32_t min_permille, void *d_out, void *stream);
+int kid_db_read_votes_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
+
 /* ---- calling records in segments ------------------------------------------------------
  * kid_db_read_support* gives a record one answer.  A contig that is one species for its first 1.4 Mb and another after
  * that, a chimeric long read or a transferred island folds to an ancestor and nothing says where the change is.  These

@@ -97,6 +97,10 @@ SUPPORT_DTYPE = np.dtype([("final", np.uint32), ("confident", np.uint32), ("n_km
 # kid_fragment: one record per fragment (kid_db_read_fragments*); the first six fields are SUPPORT_DTYPE's
 FRAGMENT_DTYPE = np.dtype([(name, np.uint32) for name in SUPPORT_DTYPE.names] + [("final_1", np.uint32), ("final_2", np.uint32)])
 
+# kid_vote: one record per read (kid_db_read_votes*)
+VOTE_DTYPE = np.dtype([("call", np.uint32), ("confident", np.uint32), ("n_kmers", np.uint32), ("n_hits", np.uint32),
+                       ("p_best", np.uint32), ("n_best", np.uint32), ("s_call", np.uint32), ("s_confident", np.uint32)])
+
 # kid_segment: one record per segment (kid_db_read_segments*); the six fields behind n_pos are SUPPORT_DTYPE's
 SEGMENT_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in SUPPORT_DTYPE.names])
 
@@ -285,6 +289,38 @@ class KmerDB:
     def read_support_time(self):
         """-> (device ms, calls, reads) of the support kernel alone since the last query"""
         return self._time(self._lib.kid_db_read_support_time)
+
+    def read_votes(self, bases, offsets, start=None, stop=None, min_hits=0, min_permille=0, tally=None):
+        """Call the reads of a batch held in host memory by root-path votes (kid_db_read_votes): -> a structured array
+        (VOTE_DTYPE: call, confident, n_kmers, n_hits, p_best, n_best, s_call, s_confident), one record per read.  P(c)
+        counts the hits at c or an ancestor of c; `call` is the lowest common ancestor of the hit targets with the largest
+        P (n_best of them, P = p_best): a pure function of the multiset of the read's hits, whatever their order.
+        `confident` climbs from call under the rule as read_support's climbs from final; tally as there."""
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        out = np.zeros(n, VOTE_DTYPE)
+        check(self._lib.kid_db_read_votes(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
+                                          _ptr(out), tally._h if tally is not None else None))
+        return out
+
+    def read_votes_fastq(self, text, recs, min_hits=0, min_permille=0, tally=None):
+        """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
+        fails stop - start >= k has no window and no hit, and a tally counts it nowhere."""
+        text, recs, n = _fastq_block(text, recs)
+        out = np.zeros(n, VOTE_DTYPE)
+        check(self._lib.kid_db_read_votes_fastq(self._h, _ptr(text), text.size, _ptr(recs), n, min_hits, min_permille, _ptr(out),
+                                                tally._h if tally is not None else None))
+        return out
+
+    def votes_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
+        """The vote kernels alone on a CSR resident in HBM (raw pointers, as kid_db_read_hits_device left it);
+        asynchronous on `stream`: kid_db_votes_from_hits_device.  d_out: kid_vote[n_reads] (VOTE_DTYPE)."""
+        check(self._lib.kid_db_votes_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
+                                                      C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
+                                                      C.c_void_p(stream or None)))
+
+    def read_votes_time(self):
+        """-> (device ms, calls, reads) of the vote kernels alone since the last query"""
+        return self._time(self._lib.kid_db_read_votes_time)
 
     def read_fragments(self, bases, offsets, start=None, stop=None, min_hits=0, min_permille=0, tally=None):
         """Call mate pairs as one fragment (kid_db_read_fragments): -> a structured array (FRAGMENT_DTYPE: final, confident,

@@ -1,6 +1,6 @@
 // kid_api_hits.h -- every read's k-mer hits: the scratch of a database's hit passes and kid_db_read_hits*.
 // What the other families over the hit pass -- kid_db_read_support* (kid_api_support.h), kid_db_read_fragments*
-// (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h) -- share with kid_db_read_hits* is here once:
+// (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h), kid_db_read_votes* (kid_api_votes.h) -- share with kid_db_read_hits* is here once:
 // KidSpanTimer, kid_hits_state (the scratch, free: the timers a family settles), kid_hits_scan (the three-kernel
 // exclusive scan), KidOpenBatch and kid_hits_open_* (a host-buffer batch checked, locked and staged, one function per
 // input form over kid_hits_stage_*), the hit pass into the library's own buffers (kid_hits_host_pass), the checks of
@@ -80,6 +80,11 @@ struct KidHitsState {
     KidDevBuf tile_valid, tile_valid_off, seg_ctl, out_seg_offsets, out_segments;
     bool want_valid = false;
     KidSpanTimer segments; // the segment kernels alone
+    // kid_db_read_votes* (kid_api_votes.h): the host forms' records; the reads kid_vote_kernel leaves to
+    // kid_vote_big_kernel (uint32 per read of the largest batch) and their number (one word); one row uint32[ntar] per
+    // workgroup of that kernel, zero between calls
+    KidDevBuf out_votes, vote_list, vote_n_list, vote_rows;
+    KidSpanTimer votes; // the two vote kernels alone
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
 #define KID_HITS_CTL_WORDS 36u
@@ -93,7 +98,7 @@ static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensu
 // tiles' scratch behind the pass) -- and of the kernels that read the pass's CSR alone those that `settle` names: a call
 // waits for the timers its family has always waited for, no more (a device-form caller that queues hits -> support on
 // a stream of its own does not block in the next kid_db_read_hits_device).
-enum : unsigned { KID_SETTLE_SUPPORT = 1u, KID_SETTLE_FRAGMENTS = 2u };
+enum : unsigned { KID_SETTLE_SUPPORT = 1u, KID_SETTLE_FRAGMENTS = 2u, KID_SETTLE_VOTES = 4u };
 static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
 {
     if (!db->hits) {
@@ -105,6 +110,7 @@ static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
         KID_HIP(h->support.create());
         KID_HIP(h->fragments.create());
         KID_HIP(h->segments.create());
+        KID_HIP(h->votes.create());
         db->hits = std::move(h);
     }
     KidHitsState *h = *out = db->hits.get();
@@ -112,6 +118,7 @@ static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
     if (rc == KID_OK) rc = h->segments.settle();
     if (rc == KID_OK && (settle & KID_SETTLE_SUPPORT)) rc = h->support.settle();
     if (rc == KID_OK && (settle & KID_SETTLE_FRAGMENTS)) rc = h->fragments.settle();
+    if (rc == KID_OK && (settle & KID_SETTLE_VOTES)) rc = h->votes.settle(); // (its list and rows are one set per kid_db)
     return rc;
 }
 

@@ -1,8 +1,9 @@
 // kid_api_support.h -- call reads by k-mer support: kid_db_read_support* over the hit pass and kid_support_kernel
 // (kid_support.hip.h) -- and, once, the call path of every family that leaves one record per unit of the batch behind
 // the hit pass (kid_calls_*): the argument checks, the host run with the binding of a tally, the launch between the
-// family's two events, the *_from_hits_device form.  A family is a struct like KidSupportCalls below; the other one is
-// KidFragmentCalls (kid_api_fragments.h), whose unit is two reads.  The host-buffer forms open their batch with
+// family's two events, the *_from_hits_device form.  A family is a struct like KidSupportCalls below; the others are
+// KidFragmentCalls (kid_api_fragments.h), whose unit is two reads, and KidVoteCalls (kid_api_votes.h), which queues two
+// kernels through the hook of kid_calls_queue.  The host-buffer forms open their batch with
 // kid_hits_open_* and run the hit pass with kid_hits_host_pass (kid_api_hits.h).  Included behind the sample handle: a
 // tally counts into one.
 #pragma once
@@ -47,12 +48,29 @@ template <class F> static int kid_calls_check_args(const kid_db *db, uint64_t n_
     return KID_OK;
 }
 
+// What a family queues between its timer's two events.  A family without a hook: its kernel() over the grid.  The
+// optional hook: a static F::queue<ROWS, TALLY, DEPTH>(db, h, grid, stream, the kernel's arguments...) -> status, in
+// which the family binds scratch of its own to the batch and queues what it needs (KidVoteCalls: a second kernel
+// behind the first).  The first overload is the better match and drops out where F has no such member.
+template <class F, bool ROWS, bool TALLY, bool DEPTH, class... A>
+static auto kid_calls_queue(int, kid_db *db, KidHitsState *h, dim3 grid, hipStream_t stream, A... a)
+    -> decltype(F::template queue<ROWS, TALLY, DEPTH>(db, h, grid, stream, a...))
+{
+    return F::template queue<ROWS, TALLY, DEPTH>(db, h, grid, stream, a...);
+}
+template <class F, bool ROWS, bool TALLY, bool DEPTH, class... A>
+static int kid_calls_queue(long, kid_db *, KidHitsState *, dim3 grid, hipStream_t stream, A... a)
+{
+    hipLaunchKernelGGL((F::template kernel<ROWS, TALLY, DEPTH>()), grid, dim3(256), 0, stream, a...);
+    return KID_OK;
+}
+
 // the family's kernel over one batch of n units on `stream` between the two events; t: null, or what a tally needs
 template <class F>
 static int kid_calls_launch(kid_db *db, KidHitsState *h, const uint64_t *d_hit_offsets, const KidHit *d_hits, const uint32_t *d_n_kmers,
                             uint64_t n, KidSupportRule rule, typename F::Rec *d_out, const KidSupportTally *t, hipStream_t stream)
 {
-    const dim3 grid(kid_grid_for(n, 256, db->num_cu * 8)), block(256);
+    const dim3 grid(kid_grid_for(n, 256, db->num_cu * 8));
     KidSpanTimer &timer = h->*F::timer;
     int rc = timer.begin(stream);
     if (rc != KID_OK) return rc;
@@ -60,11 +78,12 @@ static int kid_calls_launch(kid_db *db, KidHitsState *h, const uint64_t *d_hit_o
         kid_lift(t != nullptr, [&](auto tally) {
             kid_lift(t != nullptr && t->depth != nullptr, [&](auto depth) { // the depth form exists for a tally alone
                 if constexpr (decltype(tally)::value || !decltype(depth)::value)
-                    hipLaunchKernelGGL((F::template kernel<decltype(rows)::value, decltype(tally)::value, decltype(depth)::value>()), grid, block,
-                                       0, stream, db->d, d_hit_offsets, d_hits, d_n_kmers, n, rule, d_out, t ? *t : KidSupportTally{});
+                    rc = kid_calls_queue<F, decltype(rows)::value, decltype(tally)::value, decltype(depth)::value>(
+                        0, db, h, grid, stream, db->d, d_hit_offsets, d_hits, d_n_kmers, n, rule, d_out, t ? *t : KidSupportTally{});
             });
         });
     });
+    if (rc != KID_OK) return rc;
     KID_HIP(hipGetLastError());
     return timer.end(stream, n);
 }

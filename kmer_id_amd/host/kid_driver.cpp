@@ -64,7 +64,7 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 
 Engine::~Engine()
 {
-    for (const std::vector<kid_sample *> *list : {&samples, &confident, &fragments})
+    for (const std::vector<kid_sample *> *list : {&samples, &confident, &fragments, &votes})
         for (kid_sample *s : *list) kid_sample_destroy(s);
     if (owns_dbs)
         for (kid_db *d : dbs) kid_db_destroy(d);
@@ -106,6 +106,8 @@ void engine_configure(Engine &e, const SideOptions &side)
         }
     if (side.fragments) // (tallied through the database's hit pass: KID_DB_OPT_MIN_BASE_QUALITY below is what masks for them)
         for (kid_db *d : e.dbs) e.fragments.push_back(begin_sample_or_die(d));
+    if (side.votes) // (tallied through the database's hit pass too)
+        for (kid_db *d : e.dbs) e.votes.push_back(begin_sample_or_die(d));
     const int q = side.min_base_quality;
     if (q == 0) return;
     for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
@@ -136,7 +138,7 @@ std::vector<int> parse_devices(int device, const std::string &list)
 
 void engine_reset(Engine &e)
 {
-    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident, &e.fragments})
+    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident, &e.fragments, &e.votes})
         for (kid_sample *s : *list) {
             int rc = kid_sample_reset(s);
             if (rc != KID_OK) die_kid(rc);
@@ -394,7 +396,8 @@ static const struct {
                     {"--segments", 2, read_segments, nullptr},
                     {"--depth", 0, nullptr, &SideOptions::depth},
                     {"--seen", 0, nullptr, &SideOptions::seen},
-                    {"--fragments", 0, nullptr, &SideOptions::fragments}};
+                    {"--fragments", 0, nullptr, &SideOptions::fragments},
+                    {"--votes", 0, nullptr, &SideOptions::votes}};
 
 int side_option_values(const char *word)
 {
@@ -428,7 +431,7 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments, depth, seen, fragments; };
+struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes; };
 static SidePaths side_paths(const std::string &r)
 {
     std::string seen = r; // the final "result.txt" becomes "seen.bin"
@@ -436,7 +439,7 @@ static SidePaths side_paths(const std::string &r)
     if (at != std::string::npos) seen.replace(at, 10, "seen.bin");
     else seen += ".seen.bin";
     return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen,
-            sibling_path_for(r, "fragments")};
+            sibling_path_for(r, "fragments"), sibling_path_for(r, "votes")};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -448,6 +451,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.depth) remove(p.depth.c_str());
     if (all || side.seen) remove(p.seen.c_str());
     if (all || side.fragments) remove(p.fragments.c_str());
+    if (all || side.votes) remove(p.votes.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -544,6 +548,7 @@ void SampleOutputs::finish(Engine &e)
     write_counters(e.samples, e.ntar, result_path_);
     if (side_.support.on) write_counters(e.confident, e.ntar, p.confident);
     if (side_.fragments) write_counters(e.fragments, e.ntar, p.fragments);
+    if (side_.votes) write_counters(e.votes, e.ntar, p.votes);
     if (side_.depth) write_depth(e.confident, e.ntar, p.depth);
     if (side_.seen) write_seen(side_.support.on ? e.confident[0] : e.samples[0], e, p.seen);
     if (side_.hits) write_lines(p.hits, hits_);
@@ -657,6 +662,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         kid_sample *sample = nullptr;
         kid_db *db = nullptr;
         kid_sample *confident = nullptr;
+        kid_sample *votes = nullptr;
         size_t file = 0;
     };
     std::string lines;
@@ -721,6 +727,10 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         if (f.confident)
             read_pass(kid_db_read_support_fastq, kid_db_read_support, f.db, *f.batch, f.bases(), e.side.support.min_hits,
                       e.side.support.min_permille, (kid_support *)nullptr, f.confident);
+        // (the vote pass, under --votes: the batch is tallied into the device's votes sample under the same rule)
+        if (f.votes)
+            read_pass(kid_db_read_votes_fastq, kid_db_read_votes, f.db, *f.batch, f.bases(), e.side.support.min_hits, e.side.support.min_permille,
+                      (kid_vote *)nullptr, f.votes);
         if (out.segments_on()) {
             lines.clear();
             segment_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.side.segments, e.side.support, lines);
@@ -746,6 +756,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             f.sample = e.samples[e.next_sample]; // batches are dealt round-robin over the devices
             f.db = e.dbs[e.next_sample];
             f.confident = e.confident.empty() ? nullptr : e.confident[e.next_sample];
+            f.votes = e.votes.empty() ? nullptr : e.votes[e.next_sample];
             e.next_sample = (e.next_sample + 1) % e.samples.size();
             int rc;
             const auto t_sub = std::chrono::steady_clock::now();

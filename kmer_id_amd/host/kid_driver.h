@@ -47,6 +47,9 @@ struct SideOptions {
     // --fragments (no value; nk10 alone, whose two mate files are read side by side): the mate pairs called as one
     // fragment each (kid_db_read_fragments_fastq), counted into a fragments file
     bool fragments = false;
+    // --votes (no value): the reads called by root-path votes (kid_db_read_votes*), whatever the order of their hits, and
+    // counted into a votes file
+    bool votes = false;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
@@ -72,6 +75,7 @@ struct Engine {
     std::vector<kid_sample *> confident;
     std::vector<kid_sample *> fragments; // under --fragments: one sample per device that the fragments are tallied into
     size_t next_fragments = 0;           // ... dealt round-robin over the devices
+    std::vector<kid_sample *> votes;     // under --votes: one sample per device that the vote pass of every batch tallies into
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -103,7 +107,8 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
 // The side options for an engine that is open: with a rule or --depth one more sample per device (reset, closed and
-// destroyed with the others; --depth switches its depth counters on), under --fragments one more for the fragments, then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
+// destroyed with the others; --depth switches its depth counters on), under --fragments one more for the fragments, under
+// --votes one more for the vote pass, then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
 // A worker of engine_worker() inherits them for its samples.
 void engine_configure(Engine &e, const SideOptions &side);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
@@ -163,6 +168,12 @@ private:
 // when R2 is missing) are fragments with an absent mate, and one line on stderr gives both counts.  The rule is that of
 // --min-hits / --confidence when given, else (0, 0); --min-base-quality applies as it does to the confident file.  It
 // does not depend on how the files were cut into blocks, batched, threaded or dealt over devices.
+//   --votes, "votes": a result file in the result file's format, <i>,<reads>,<unique_kmers>, from the counters of one more
+// sample per device that the vote pass tallies every batch into (kid_db_read_votes*: gcount[confident]++ with the climb
+// started at the read's call by root-path votes, which does not depend on the order of its hits).  The rule is that of
+// --min-hits / --confidence when given, else (0, 0): confident = call; --min-base-quality applies as it does to the
+// confident file.  It does not depend on how the reads were batched, threaded or dealt over devices, and the depth and
+// seen files keep following the samples they follow without it.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
 // The batches of files read at the same time interleave: the hit and segment lines are held in memory per file and
 // written in file order by finish() -- what is held is the files themselves (reads without a hit leave nothing),
@@ -178,7 +189,7 @@ public:
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
-    // confident file, then the fragments file, then the depth file, then the seen file, then the hits file, then the
+    // confident file, then the fragments file, then the votes file, then the depth file, then the seen file, then the hits file, then the
     // segments file
     void finish(Engine &e);
 private:
@@ -208,7 +219,8 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
 // them are through, with the number of its reads handed to process_read.  Returns the reads handed of all the files.
 // `out` receives the hit lines of every batch when its hits file is on: the hit pass (kid_db_read_hits*) of a batch runs on
 // the device that classified it, once its final targets are back.  With e.side.support or e.side.depth on, the support
-// pass of a batch runs at the same place and tallies into that device's confident sample.  When its segments file is on, `out` receives
+// pass of a batch runs at the same place and tallies into that device's confident sample; with e.side.votes on the vote
+// pass (kid_db_read_votes*) does the same into that device's votes sample.  When its segments file is on, `out` receives
 // the segment lines of every batch under e.side: the segments pass (kid_db_read_segments*) runs at the same place too.
 // With out.fragments_on() and count == 2 the two files are the mates of a sample: the FASTQ blocks of each that are
 // through wait in a queue until the partner's records have arrived; the longest common run of records is handed to

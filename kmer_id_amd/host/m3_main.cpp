@@ -12,6 +12,7 @@
 //   --segments LEN[:STEP]   long records called in segments
 //   --depth   k-mer depth per target (the depth file of kid_driver.h)
 //   --seen   the seen-bitmap in a seen file (<...>seen.bin beside <...>result.txt), for kmer_shared
+//   --votes   the reads called by root-path votes, whatever the order of their hits (the votes file of kid_driver.h)
 //   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N
 #include <stdio.h>
 #include <stdlib.h>

@@ -29,6 +29,8 @@
 //   --fragments          also write <prefix>_fragments.txt: the result file of the mate pairs called as one fragment each -- record j
 //                    of the R1 file with record j of the R2 file, under the rule of --min-hits / --confidence when given
 //                    (kid_driver.h).  Not with --fasta
+//   --votes              also write <prefix>_votes.txt: the result file of the reads called by root-path votes, which do not
+//                    depend on the order of a read's hits, under the rule of --min-hits / --confidence when given (kid_driver.h)
 //   --block-bytes N      the size of the FASTQ text blocks the files are cut into (8 MiB; at least 32 KiB are taken): no output
 //                    depends on it
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
