@@ -132,3 +132,29 @@ class DeviceBatch:
     def __exit__(self, *exc):
         for p in self.bufs:
             self.lib.kid_dev_free(0, p)
+
+
+class DeviceCsr(DeviceBatch):
+    """a hit CSR of the caller's making resident in HBM, as the *_from_hits_device calls take it: offsets uint64[n + 1],
+    hits uint32[total, 3] (kid_hit: pos, target, entry), n_kmers uint32[n]; and canary-filled outputs with GUARD records of
+    canary behind the last one"""
+    CANARY, GUARD = 0xA5A5A5A5, 2
+
+    def __init__(self, offsets, hits, n_kmers):
+        self.lib = _lib.load()
+        self.n, self.bufs = offsets.size - 1, []
+        offsets, n_kmers = np.ascontiguousarray(offsets, np.uint64), np.ascontiguousarray(n_kmers, np.uint32)
+        hits = np.ascontiguousarray(hits, np.uint32)
+        assert hits.shape == (int(offsets[-1]), 3) and n_kmers.size == self.n and np.all(np.diff(offsets.astype(np.int64)) >= 0)
+        self.d_ho, self.d_nk, self.d_hits = self.dev(offsets.nbytes, offsets), self.dev(max(self.n, 1) * 4, n_kmers), self.dev(max(hits.nbytes, 16), hits)
+
+    def out(self, n_records, dtype):
+        """a buffer of n_records + GUARD records of `dtype`, every word the canary"""
+        canary = np.full((n_records + self.GUARD) * dtype.itemsize // 4, self.CANARY, np.uint32)
+        return self.dev(canary.nbytes, canary)
+
+    def records(self, d_out, n_records, dtype):
+        """-> the n_records records; the guard behind them must be untouched"""
+        words = self.down(d_out, np.uint32, (n_records + self.GUARD) * dtype.itemsize // 4)
+        assert np.all(words[n_records * dtype.itemsize // 4:] == self.CANARY), "a write behind the last record"
+        return words[:n_records * dtype.itemsize // 4].view(dtype)
