@@ -596,6 +596,58 @@ int kid_shared_kmers(int device, const uint32_t *targets, uint64_t n_entries, in
                      int n, int on_device, int64_t *shared);
 int kid_shared_kmers_time(double *device_ms, uint64_t *calls);
 
+/* ---- breadth of coverage per organism -------------------------------------------------
+ * ucount says how many of a target's database k-mers a sample saw, not WHERE on the genome they lie.  An organism that
+ * is present leaves its k-mers spread over its whole genome; a conserved gene, a transferred island or a contaminated
+ * assembly leaves them on one locus.  Every probe line is SEQ,target,org,position,strand,count: entry o carries the
+ * organism org[o] and the position pos[o] of the line it came from (a line of more than k bases yields several entries,
+ * each with the line's two values unchanged).  With a bin width of W >= 1 bases:
+ *   bin(o)          = pos[o] / W, as integers
+ *   span_bins[g]    = 1 + max bin(o) over the entries of organism g, 0 when it has none
+ *   B               = the sum of span_bins over the organisms: at most KID_COVERAGE_MAX_BINS, else KID_ERR_ARG before any
+ *                     array of B elements is allocated
+ *   probes[g][b]    = the entries of g in bin b;   seen_i[g][b] = those of them whose bit is set in bitmap i
+ *   a bin is occupied when probes > 0
+ * and per (bitmap i, organism g) one record, out[i * n_orgs + g]:
+ *   n_probes        entries of g                     n_seen      entries of g with their bit set
+ *   span_bins       as above (span_bins * W is roughly the genome length)
+ *   bins            occupied bins                    bins_seen   bins with seen >= 1
+ *   max_gap         take the occupied bins of g in ascending order: the longest run of consecutive elements of that
+ *                   list with seen = 0.  Unoccupied bins neither break nor extend a run; bins when n_seen = 0
+ *   max_bin_seen    the largest seen of any one bin  max_bin     the lowest bin that reaches it; 0 when n_seen = 0
+ * Worked case: W = 1000, one organism with entries at 0, 10, 1500, 3999, 7000, 7001, 12000: bins 0,0,1,3,7,7,12,
+ * span_bins 13, occupied [0,1,3,7,12], bins 5; with the bits of the entries at 10, 7000 and 7001 set, seen per occupied
+ * bin is [1,0,0,2,0]: n_seen 3, bins_seen 2, max_gap 2 (bins 1 and 3: bin 2 is unoccupied and transparent),
+ * max_bin_seen 2, max_bin 7.  An organism without entries has an all-zero record.
+ * The result is a pure function of the bits, org, pos and W: it does not depend on the order of the entries, all values
+ * are integers, and two runs give the same bytes.  Bits at or beyond n_entries are ignored, whatever they hold; a bit no
+ * sample would set (a duplicate key, target 0 or 1) counts like any other (the convention of kid_shared_kmers); the same
+ * bitmap may be named twice.
+ *   org, pos     uint32[n_entries], host memory; an org[o] >= n_orgs is KID_ERR_ARG
+ *   bitmaps[n]   n in 1..KID_SHARED_MAX_SAMPLES, host memory, each of the padded size a kid_db of n_entries would report:
+ *                ((n_entries + 127) / 128) * 16 bytes, 16 for no entries
+ *   out          host memory, kid_coverage[n * n_orgs]
+ * A null pointer, n outside its range, bin_width = 0, an org out of range or B over the cap is KID_ERR_ARG, and nothing
+ * is written.  n_entries = 0 is valid and gives all-zero records.  The calls are stateless like kid_shared_kmers (no
+ * table is built, no sample is touched), take the bitmaps one after the other, synchronise before they return, and
+ * their scratch lives for the call: 8 bytes per entry, one bitmap, 48 bytes per organism and 8 * B bytes.
+ * kid_seen_coverage_bins is the per-bin profile, for plotting: bin_base[n_orgs + 1] (the bins of organism g are
+ * bin_base[g] .. bin_base[g + 1] - 1), probes_per_bin[B] and seen_per_bin[n * B].  With probes_per_bin = seen_per_bin =
+ * NULL and cap = 0 it is the sizing call: it writes *n_bins = B and bin_base.  Otherwise both arrays are given, cap is
+ * the number of bins they have room for, and cap < B is KID_ERR_ARG.
+ * kid_seen_coverage_time: device time (HIP events) of the kernels of both calls, in this process, since the last query,
+ * and the number of calls; copies are not in it.                                                                      */
+typedef struct kid_coverage {
+    uint32_t n_probes, n_seen, span_bins, bins, bins_seen, max_gap, max_bin_seen, max_bin;
+} kid_coverage;
+#define KID_COVERAGE_MAX_BINS (1ull << 28)
+int kid_seen_coverage(int device, const uint32_t *org, const uint32_t *pos, uint64_t n_entries, uint32_t n_orgs,
+                      uint32_t bin_width, const void *const *bitmaps, int n, kid_coverage *out);
+int kid_seen_coverage_bins(int device, const uint32_t *org, const uint32_t *pos, uint64_t n_entries, uint32_t n_orgs,
+                           uint32_t bin_width, const void *const *bitmaps, int n, uint64_t *bin_base,
+                           uint32_t *probes_per_bin, uint32_t *seen_per_bin, uint64_t cap, uint64_t *n_bins);
+int kid_seen_coverage_time(double *device_ms, uint64_t *calls);
+
 /* ---- probe-database builder ------------------------------------------------------------------------------------
  * Replaces the table of kmer_build_vf6.cpp (Hashtable, :132-215) and its three passes (process_seq, process_seq3,
  * process_seq2: :353-457, :553-640): 2^log2_cells uint32 cells, direct mapped by fmix64 of the canonical 30-mer, no key

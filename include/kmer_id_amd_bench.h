@@ -47,6 +47,10 @@ int kid_sample_kernel_variants(struct kid_sample *s, uint64_t *mask);
  *   logging  has_log and no pass has switched the log off: the device's own word, as of the synchronise          */
 int kid_sample_log_state(struct kid_sample *s, uint32_t *passes, int *has_log, int *logging);
 
+/* the share of kid_seen_coverage_time that the count kernels over the bitmaps took (the hot pass: without the span
+ * stage, the probes per bin and the reduce kernels), in this process, since the last query                          */
+int kid_bench_coverage_count_time(double *count_ms);
+
 /* device memory helpers so that a host language without a HIP binding can stage buffers */
 int kid_dev_alloc(int device, uint64_t nbytes, void **d_ptr);
 int kid_dev_free(int device, void *d_ptr);

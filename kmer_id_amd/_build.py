@@ -16,7 +16,8 @@ BIN_DIR = os.path.join(HERE, "bin")
 NK10 = os.path.join(BIN_DIR, "nk10")
 # front-end -> its main file; everything else under host/ is shared
 FRONT_ENDS = {"nk10": "nk10_main.cpp", "kmer_read_vf6": "vf6_main.cpp", "kmer_read_m3": "m3_main.cpp",
-              "kmer_build_vf6": "build_main.cpp", "kmer_shared": "shared_main.cpp"}
+              "kmer_build_vf6": "build_main.cpp", "kmer_shared": "shared_main.cpp",
+              "kmer_coverage": "coverage_main.cpp"}
 
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-value", "-Wno-unused-result"]
 

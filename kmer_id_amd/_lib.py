@@ -116,6 +116,11 @@ PROTOTYPES = {
     "kid_db_shared_kmers": (C.c_int, [C.c_void_p, c_void_pp, C.c_int, C.c_int, C.c_void_p]),
     "kid_shared_kmers": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_int32, c_void_pp, C.c_int, C.c_int, C.c_void_p]),
     "kid_shared_kmers_time": (C.c_int, [C.POINTER(C.c_double), c_u64p]),
+    "kid_seen_coverage": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, c_void_pp, C.c_int, C.c_void_p]),
+    "kid_seen_coverage_bins": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, c_void_pp, C.c_int,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
+    "kid_seen_coverage_time": (C.c_int, [C.POINTER(C.c_double), c_u64p]),
+    "kid_bench_coverage_count_time": (C.c_int, [C.POINTER(C.c_double)]),
     "kid_synth_db_keys_host": (C.c_int, [C.c_uint64, C.c_int, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p,
                                          C.c_void_p]),
     "kid_synth_db_keys_device": (C.c_int, [C.c_uint64, C.c_int, C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p,
@@ -151,6 +156,7 @@ KID_OPT_MIN_BASE_QUALITY = 3
 KID_OPT_ENTRY_DEPTH = 4
 KID_DB_OPT_MIN_BASE_QUALITY = 1
 KID_SHARED_MAX_SAMPLES = 64
+KID_COVERAGE_MAX_BINS = 1 << 28
 KID_FLAG_U_IS_T = 1
 KID_FLAG_HOST_BUILD = 2
 KID_FLAG_REF_GEOMETRY = 4

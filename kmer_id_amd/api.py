@@ -418,6 +418,15 @@ class KmerDB:
         return _shared_kmers(items, nbytes, info.ntar,
                              lambda ptrs, n, out: self._lib.kid_db_shared_kmers(self._h, ptrs, n, 0, _ptr(out)))
 
+    def seen_coverage(self, items, org, pos, bin_width=1000):
+        """Breadth of coverage per organism (kid_seen_coverage) on this database's device -> COVERAGE_DTYPE[n, n_orgs].  An
+        item is a Sample (its bitmap is exported to the host first) or a uint8 array of seen_bytes bytes; org and pos hold
+        fields 3 and 4 of the probe line of every entry of the database, in the order the builder got them."""
+        info = self.info
+        if np.size(org) != info.n_entries:
+            raise ValueError("org has %d entries, the database has %d" % (np.size(org), info.n_entries))
+        return seen_coverage(org, pos, items, bin_width=bin_width, device=info.device)
+
     def gather_ceiling(self, n_loads=1 << 28, inflight=4, iters=3):
         """Random gather rate over this DB's table: (ms per launch, loads per launch).  inflight 101 / 108: random
         128-byte lines asked for the way the classify kernel asks (64 per load / runs of 8 lanes), 4 loads in flight;
@@ -472,6 +481,98 @@ def shared_kmers_time():
     ms, calls = C.c_double(0), C.c_uint64(0)
     check(_lib.load().kid_shared_kmers_time(C.byref(ms), C.byref(calls)))
     return ms.value, calls.value
+
+
+# kid_coverage: one record per (bitmap, organism) (kid_seen_coverage)
+COVERAGE_DTYPE = np.dtype([(name, np.uint32) for name in ("n_probes", "n_seen", "span_bins", "bins", "bins_seen", "max_gap",
+                                                          "max_bin_seen", "max_bin")])
+
+
+def _coverage_inputs(org, pos, bitmaps, n_orgs):
+    """the arguments of a seen_coverage call -> (org, pos, n_orgs, the bitmaps as host arrays, their pointers)"""
+    org, pos = _as(org, np.uint32).reshape(-1), _as(pos, np.uint32).reshape(-1)
+    if org.size != pos.size:
+        raise ValueError("org has %d entries, pos has %d" % (org.size, pos.size))
+    if n_orgs is None:
+        n_orgs = int(org.max()) + 1 if org.size else 0
+    nbytes = max((org.size + 127) // 128, 1) * 16
+    maps = []
+    for it in bitmaps:
+        a = it.seen_export(0, it.seen_bytes()) if isinstance(it, Sample) else np.ascontiguousarray(it, np.uint8).reshape(-1)
+        if a.size != nbytes:
+            raise ValueError("a bitmap of %d bytes where %d entries have %d" % (a.size, org.size, nbytes))
+        maps.append(a)
+    ptrs = (C.c_void_p * max(len(maps), 1))(*[a.ctypes.data for a in maps])
+    return org, pos, n_orgs, maps, ptrs
+
+
+def seen_coverage(org, pos, bitmaps, bin_width=1000, n_orgs=None, device=0):
+    """Breadth of coverage per organism (kid_seen_coverage): org[n_entries] and pos[n_entries] are fields 3 and 4 of the
+    probe line every entry came from, bitmaps of ((n_entries + 127) // 128) * 16 bytes each (16 for no entries) in the
+    layout of Sample.seen_export -> COVERAGE_DTYPE[n, n_orgs].  n_orgs: the largest org + 1 unless given."""
+    org, pos, n_orgs, maps, ptrs = _coverage_inputs(org, pos, bitmaps, n_orgs)
+    out = np.zeros((len(maps), n_orgs), COVERAGE_DTYPE)
+    check(_lib.load().kid_seen_coverage(device, _ptr(org), _ptr(pos), org.size, n_orgs, bin_width, ptrs, len(maps), _ptr(out)))
+    return out
+
+
+def seen_coverage_bins(org, pos, bitmaps, bin_width=1000, n_orgs=None, device=0):
+    """The per-bin profile behind seen_coverage (kid_seen_coverage_bins) -> (bin_base uint64[n_orgs + 1], probes_per_bin
+    uint32[B], seen_per_bin uint32[n, B]): the bins of organism g are bin_base[g] .. bin_base[g + 1] - 1."""
+    lib = _lib.load()
+    org, pos, n_orgs, maps, ptrs = _coverage_inputs(org, pos, bitmaps, n_orgs)
+    base = np.zeros(n_orgs + 1, np.uint64)
+    n_bins = C.c_uint64(0)
+    check(lib.kid_seen_coverage_bins(device, _ptr(org), _ptr(pos), org.size, n_orgs, bin_width, ptrs, len(maps), _ptr(base), None, None, 0,
+                                     C.byref(n_bins)))
+    B = n_bins.value
+    probes, seen = np.zeros(B, np.uint32), np.zeros((len(maps), B), np.uint32)
+    check(lib.kid_seen_coverage_bins(device, _ptr(org), _ptr(pos), org.size, n_orgs, bin_width, ptrs, len(maps), _ptr(base), _ptr(probes),
+                                     _ptr(seen), B, C.byref(n_bins)))
+    return base, probes, seen
+
+
+def seen_coverage_time():
+    """-> (device ms, calls) of the kernels of the seen_coverage calls of this process since the last query"""
+    ms, calls = C.c_double(0), C.c_uint64(0)
+    check(_lib.load().kid_seen_coverage_time(C.byref(ms), C.byref(calls)))
+    return ms.value, calls.value
+
+
+def read_probe_sites(path, k=30):
+    """(org, pos) as uint32 arrays, one pair per database entry in file order, from a probes file (plain or .gz) whose
+    lines are SEQ,target,org,position,strand,count: a line gives its org and position to each of its entries, one per
+    window of k upper-case ACGT bases.  Plain Python, for users without a front-end; a line that does not parse is
+    skipped, as the loader of the front-ends skips it."""
+    import gzip
+    import re
+    runs = re.compile(rb"[ACGT]+")
+    org, pos = [], []
+    with open(path, "rb") as f:
+        gz = f.read(2) == b"\x1f\x8b"
+    with (gzip.open(path, "rb") if gz else open(path, "rb")) as f:
+        for line in f:
+            if not line.endswith(b"\n"):
+                break  # the unterminated last line is dropped
+            fields = line.replace(b",", b" ").split()
+            if len(fields) < 6:
+                continue
+            try:
+                int(fields[1]), int(fields[5])
+                o, p = int(fields[2]), int(fields[3])
+            except ValueError:
+                continue
+            n = sum(max(len(r) - k + 1, 0) for r in runs.findall(fields[0]))
+            if n == 0:
+                continue
+            if o < 0 or p < 0:
+                raise ValueError("%s: org or position outside 0..2^32-1 in %r" % (path, line[:120]))
+            if o >= 1 << 31 or p >= 1 << 31:
+                continue  # (the loader reads both as int: such a line fails to parse and gives no entry to any front-end)
+            org.append(np.full(n, o, np.uint32))
+            pos.append(np.full(n, p, np.uint32))
+    cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.uint32)  # noqa: E731
+    return cat(org), cat(pos)
 
 
 SEEN_MAGIC = b"KIDSEEN1"

@@ -542,6 +542,47 @@ static void write_seen(kid_sample *s, const Engine &e, const std::string &path)
     }
 }
 
+int read_seen_files(const std::vector<std::string> &paths, long long ntar, unsigned long long k, std::vector<std::vector<uint8_t>> &maps,
+                    SeenHeader &first, std::string &what)
+{
+    auto fail = [&](int code, const std::string &w) { what = w; return code; };
+    const size_t n = paths.size();
+    maps.assign(n, std::vector<uint8_t>());
+    for (size_t f = 0; f < n; f++) {
+        FILE *in = fopen(paths[f].c_str(), "rb");
+        if (!in) return fail(255, "cannot open " + paths[f]);
+        char head[32];
+        SeenHeader h;
+        const bool have_head = fread(head, 1, 32, in) == 32;
+        if (have_head && memcmp(head, kSeenMagic, 8) == 0) {
+            memcpy(&h.n_entries, head + 8, 8);
+            memcpy(&h.ntar, head + 16, 4);
+            memcpy(&h.k, head + 20, 4);
+            memcpy(&h.nbytes, head + 24, 8);
+        }
+        const uint64_t want = h.n_entries < 0xFFFFFFFFull ? (h.n_entries ? (h.n_entries + 127) / 128 * 16 : 16) : 0;
+        bool whole = false;
+        if (have_head && h.nbytes == want && want) {
+            maps[f].resize(want);
+            whole = fread(maps[f].data(), 1, want, in) == want && fgetc(in) == EOF;
+        }
+        fclose(in);
+        if (!have_head) return fail(3, paths[f] + " is truncated: it has no whole header");
+        if (memcmp(head, kSeenMagic, 8) != 0) return fail(3, paths[f] + " is not a seen file (bad magic)");
+        if (h.nbytes != want || !want) return fail(3, paths[f] + ": the size of its bitmap does not fit its number of entries");
+        if (!whole) return fail(3, paths[f] + " is truncated, or has bytes behind its bitmap");
+        if (f == 0) first = h;
+        if (h.n_entries != first.n_entries || h.ntar != first.ntar || h.k != first.k)
+            return fail(3, paths[f] + " was written for another database than " + paths[0] + " (entries, targets or k differ)");
+        if (ntar >= 0 && ((unsigned long long)h.ntar != (unsigned long long)ntar || (unsigned long long)h.k != k))
+            return fail(3, paths[f] + " was written with --ntar " + std::to_string(h.ntar) + " --k " + std::to_string(h.k) +
+                               ", not " + std::to_string(ntar) + " and " + std::to_string(k));
+        if (ntar < 0 && (unsigned long long)h.k != k)
+            return fail(3, paths[f] + " was written with --k " + std::to_string(h.k) + ", not " + std::to_string(k));
+    }
+    return 0;
+}
+
 void SampleOutputs::finish(Engine &e)
 {
     const SidePaths p = side_paths(result_path_);

@@ -207,6 +207,13 @@ struct SeenHeader {
     uint64_t nbytes = 0;
 };
 extern const char kSeenMagic[9];
+// The seen files of a tool that compares them (kmer_shared, kmer_coverage), in the order of `paths`: maps[f] receives the
+// bitmap of file f, `first` the header of the first file.  Every header must fit its file, agree with the first file's
+// (entries, targets, k) and with the tool's own k and, unless ntar is negative, ntar.  Returns 0, or the exit code of the
+// first file that fails -- 255 for one that cannot be opened, 3 for a bad magic, a truncated file, a bitmap whose size
+// does not fit its entries, headers that disagree -- with the line for stderr, without the tool's name, in `what`.
+int read_seen_files(const std::vector<std::string> &paths, long long ntar, unsigned long long k, std::vector<std::vector<uint8_t>> &maps,
+                    SeenHeader &first, std::string &what);
 // For a front-end that takes a sample's outputs back: removes the files beside `result_path` of the options that are on
 // (a sample that never started: one left by an earlier run would stand beside no result) or, with `all`, every one a
 // sample may have written

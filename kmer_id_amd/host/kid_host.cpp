@@ -152,11 +152,13 @@ namespace {
 struct ProbeChunk { // what one block of lines parses to: a worker's own buffers, reused from block to block
     std::vector<uint64_t> keys;
     std::vector<uint32_t> targets;
+    std::vector<uint32_t> orgs, positions; // want_sites: fields 3 and 4 of the line an entry came from
+    bool want_sites = false;
     long long lines_parsed = 0;
 };
 }
 
-static void roll_probe(const char *seq, size_t len, uint32_t target, int k, ProbeChunk &ps)
+static void roll_probe(const char *seq, size_t len, uint32_t target, uint32_t org, uint32_t position, int k, ProbeChunk &ps)
 {
     // process_kmer, :619-661: forward key, upper-case ACGT only, every full window is inserted
     const uint64_t mask = (1ULL << (2 * k)) - 1;
@@ -176,6 +178,10 @@ static void roll_probe(const char *seq, size_t len, uint32_t target, int k, Prob
         if (++cpos == k) {
             ps.keys.push_back(keyF);
             ps.targets.push_back(target);
+            if (ps.want_sites) {
+                ps.orgs.push_back(org);
+                ps.positions.push_back(position);
+            }
             cpos--;
         }
     }
@@ -186,6 +192,8 @@ static void parse_probe_block(const char *text, size_t nbytes, int k, ProbeChunk
 {
     ps.keys.clear();
     ps.targets.clear();
+    ps.orgs.clear();
+    ps.positions.clear();
     ps.lines_parsed = 0;
     std::string tmp, sequence;
     const char *p0 = text, *end = text + nbytes;
@@ -212,7 +220,7 @@ static void parse_probe_block(const char *text, size_t nbytes, int k, ProbeChunk
         if (ok) { p++; ok = (p < e && *p == ','); }
         if (ok) { p++; ok = fast_uint(p, e, count) && p == e; }
         if (ok) {
-            roll_probe(s0, (size_t)(s1 - s0), target, k, ps);
+            roll_probe(s0, (size_t)(s1 - s0), target, org, position, k, ps);
             ps.lines_parsed++;
             continue;
         }
@@ -224,13 +232,16 @@ static void parse_probe_block(const char *text, size_t nbytes, int k, ProbeChunk
         int o2, p2, c2;
         char strand;
         if (ss >> sequence >> t2 >> o2 >> p2 >> strand >> c2) {
-            roll_probe(sequence.data(), sequence.size(), t2, k, ps);
+            // (an int holds nothing above 2^31-1: what does not fit 0..2^32-1 here is a negative value)
+            if (ps.want_sites && (o2 < 0 || p2 < 0))
+                throw Fatal{3, "a probe line whose org or position is outside 0..2^32-1: " + std::string(line, len < 120 ? len : 120)};
+            roll_probe(sequence.data(), sequence.size(), t2, (uint32_t)o2, (uint32_t)p2, k, ps);
             ps.lines_parsed++;
         }
     }
 }
 
-ProbeSet load_probes_gz(const std::string &path, int k, int threads, StartupTiming *timing)
+ProbeSet load_probes_gz(const std::string &path, int k, int threads, StartupTiming *timing, bool want_sites)
 {
     const auto t_begin = std::chrono::steady_clock::now();
     if (threads <= 0) {
@@ -246,6 +257,7 @@ ProbeSet load_probes_gz(const std::string &path, int k, int threads, StartupTimi
     size_t cap = (size_t)1 << 32;
     while (cap >= ((size_t)1 << 20) && !(ps.keys.reserve(cap) && ps.targets.reserve(cap))) cap >>= 1;
     if (cap < ((size_t)1 << 20)) throw Fatal{1, "out of address space for the database entries"};
+    if (want_sites && !(ps.orgs.reserve(cap) && ps.positions.reserve(cap))) throw Fatal{1, "out of address space for the database entries"};
     std::mutex m;
     std::condition_variable cv;
     std::deque<std::pair<size_t, TextBlock>> work;
@@ -256,6 +268,7 @@ ProbeSet load_probes_gz(const std::string &path, int k, int threads, StartupTimi
     Fatal failure{0, ""};
     auto worker = [&]() {
         ProbeChunk out;
+        out.want_sites = want_sites;
         for (;;) {
             std::pair<size_t, TextBlock> job;
             {
@@ -269,7 +282,7 @@ ProbeSet load_probes_gz(const std::string &path, int k, int threads, StartupTimi
             bool bad = false;
             Fatal f{0, ""};
             try { parse_probe_block(job.second.data(), job.second.len, k, out); }
-            catch (const Fatal &e) { bad = true; f = e; out.keys.clear(); out.targets.clear(); out.lines_parsed = 0; }
+            catch (const Fatal &e) { bad = true; f = e; out.keys.clear(); out.targets.clear(); out.orgs.clear(); out.positions.clear(); out.lines_parsed = 0; }
             in.recycle(job.second);
             size_t at;
             bool place;
@@ -290,6 +303,10 @@ ProbeSet load_probes_gz(const std::string &path, int k, int threads, StartupTimi
             if (place && !out.keys.empty()) {
                 memcpy(ps.keys.data() + at, out.keys.data(), out.keys.size() * sizeof(uint64_t));
                 memcpy(ps.targets.data() + at, out.targets.data(), out.targets.size() * sizeof(uint32_t));
+                if (want_sites) {
+                    memcpy(ps.orgs.data() + at, out.orgs.data(), out.orgs.size() * sizeof(uint32_t));
+                    memcpy(ps.positions.data() + at, out.positions.data(), out.positions.size() * sizeof(uint32_t));
+                }
             }
         }
     };
@@ -321,6 +338,10 @@ ProbeSet load_probes_gz(const std::string &path, int k, int threads, StartupTimi
     if (fail_block != (size_t)-1) throw failure; // (the first failure in file order, as the sequential reader would have met it)
     ps.keys.set_size(n_entries);
     ps.targets.set_size(n_entries);
+    if (want_sites) {
+        ps.orgs.set_size(n_entries);
+        ps.positions.set_size(n_entries);
+    }
     ps.lines_parsed = lines_parsed;
     if (timing) {
         timing->inflate_s = in.inflate_seconds();

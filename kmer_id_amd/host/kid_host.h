@@ -75,6 +75,7 @@ template <class T> void HugeVec<T>::release()
 struct ProbeSet {
     HugeVec<uint64_t> keys;    // forward keys in file order (process_kmer, :619-661)
     HugeVec<uint32_t> targets;
+    HugeVec<uint32_t> orgs, positions; // fields 3 and 4 of the line an entry came from: only when load_probes_gz is asked for them (want_sites), else empty
     long long lines_parsed = 0;    // tct, printed as "<n> kmers loaded" (:701,:989)
 };
 // Wall-clock seconds of the start-up phases, for --timing (nk10 prints them to stderr as one JSON line)
@@ -88,7 +89,10 @@ struct StartupTiming {
 };
 // process_kmergz (newkmer_10nx.cpp:663-712).  One thread inflates, `threads` workers parse blocks of whole lines, the
 // entries come out in file order.  Throws Fatal{255} on gz errors / over-long lines.  threads <= 0: one per core, at most 8
-ProbeSet load_probes_gz(const std::string &path, int k, int threads = 0, StartupTiming *timing = nullptr);
+// want_sites: every entry also keeps the org and position of its line (ProbeSet::orgs, positions; a line of more than k
+// bases gives them to each of its entries unchanged); a line whose org or position does not fit 0..2^32-1 throws
+// Fatal{3} with the line in its message.  Without it nothing is reserved or written for them.
+ProbeSet load_probes_gz(const std::string &path, int k, int threads = 0, StartupTiming *timing = nullptr, bool want_sites = false);
 
 // Binary cache of the parsed database: what load_tree + load_probes_gz produce, so that a
 // later run skips the text parse (minutes for 108 M lines).  The cache is tied to the size and

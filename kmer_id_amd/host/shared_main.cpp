@@ -74,37 +74,12 @@ int main(int argc, char **argv)
 
     // ---- the files: header and bitmap of each
     const size_t n = paths.size();
-    std::vector<std::vector<uint8_t>> maps(n);
+    std::vector<std::vector<uint8_t>> maps;
     SeenHeader first;
-    for (size_t f = 0; f < n; f++) {
-        FILE *in = fopen(paths[f].c_str(), "rb");
-        if (!in) return fail(255, "cannot open " + paths[f]);
-        char head[32];
-        SeenHeader h;
-        const bool have_head = fread(head, 1, 32, in) == 32;
-        if (have_head && memcmp(head, kSeenMagic, 8) == 0) {
-            memcpy(&h.n_entries, head + 8, 8);
-            memcpy(&h.ntar, head + 16, 4);
-            memcpy(&h.k, head + 20, 4);
-            memcpy(&h.nbytes, head + 24, 8);
-        }
-        const uint64_t want = h.n_entries < 0xFFFFFFFFull ? (h.n_entries ? (h.n_entries + 127) / 128 * 16 : 16) : 0;
-        bool whole = false;
-        if (have_head && h.nbytes == want && want) {
-            maps[f].resize(want);
-            whole = fread(maps[f].data(), 1, want, in) == want && fgetc(in) == EOF;
-        }
-        fclose(in);
-        if (!have_head) return fail(3, paths[f] + " is truncated: it has no whole header");
-        if (memcmp(head, kSeenMagic, 8) != 0) return fail(3, paths[f] + " is not a seen file (bad magic)");
-        if (h.nbytes != want || !want) return fail(3, paths[f] + ": the size of its bitmap does not fit its number of entries");
-        if (!whole) return fail(3, paths[f] + " is truncated, or has bytes behind its bitmap");
-        if (f == 0) first = h;
-        if (h.n_entries != first.n_entries || h.ntar != first.ntar || h.k != first.k)
-            return fail(3, paths[f] + " was written for another database than " + paths[0] + " (entries, targets or k differ)");
-        if ((unsigned long long)h.ntar != ntar || (unsigned long long)h.k != k)
-            return fail(3, paths[f] + " was written with --ntar " + std::to_string(h.ntar) + " --k " + std::to_string(h.k) +
-                               ", not " + std::to_string(ntar) + " and " + std::to_string(k));
+    {
+        std::string what;
+        const int code = read_seen_files(paths, (long long)ntar, k, maps, first, what);
+        if (code != 0) return fail(code, what);
     }
 
     try {
