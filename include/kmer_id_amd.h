@@ -125,6 +125,10 @@ int kid_sample_begin(kid_db *db, kid_sample **out);
                                 database entry" below); setting 1 again while it is on changes nothing.  value 0 frees the
                                 counters and loses the counts.  Any other value is KID_ERR_ARG.  kid_sample_reset zeroes the
                                 counters and leaves the option on */
+#define KID_OPT_LOW_COMPLEXITY 5 /* value T in 0..1000 (KID_ERR_ARG beyond), 0 = off (the default): the FASTQ blocks handed to
+                                   kid_classify_fastq_async after the call have every base of a low-complexity window read
+                                   as 'N' ("mask low-complexity sequence" below; T = 20 is DUST's usual level).  It stays
+                                   until it is set again; kid_sample_reset does not change it */
 int kid_sample_set_option(kid_sample *s, int option, int value);
 int kid_sample_reset(kid_sample *s);
 void kid_sample_destroy(kid_sample *s);
@@ -239,6 +243,46 @@ int kid_mask_batch(kid_db *db, const uint8_t *bases, const uint8_t *quals, const
  * d_n_masked: nullable; one uint64 that the number of bases masked is ADDED to (it is not reset).                    */
 int kid_mask_batch_device(kid_db *db, void *d_bases, const void *d_quals, const void *d_offsets, uint64_t n_reads,
                           int min_base_quality, void *d_n_masked, void *stream);
+
+/* ---- mask low-complexity sequence ----------------------------------------------------
+ * A poly-A tail, a (CA)n microsatellite or a poly-G run is in every assembled genome and so in every database: one such
+ * 30-mer calls a read, its qualities are fine, and a 40-base repeat gives 11 identical "supporting" hits.  With a
+ * threshold T > 0 every base that lies in a low-complexity window is read as 'N' by everything behind the mask, in the
+ * same way and under the same conditions as a low-quality base above (the device copy of the text, the caller's
+ * untouched, a block's lines in ascending order without overlap while an option is on).
+ * The rule -- a fixed-window, symmetric form of the DUST score, integers only:
+ *   A line is one read's whole sequence s[0, len): the sequence line of a FASTQ record, [offsets[r], offsets[r+1]) in the
+ *   offsets forms; the whole line, whatever its trimmed range.  Lines lying back to back never share a window.
+ *   A byte is a base when the database's lookup takes it as one (ACGTacgt, Uu under KID_FLAG_U_IS_T).  Triplet i is valid
+ *   when bytes i, i + 1, i + 2 are bases, and has the value 16 a + 4 b + c of their codes.
+ *   The window of position p is [lo, hi) = [max(0, p - 32), min(len, p + 32)); l(p) is the number of valid triplets with
+ *   lo <= i and i + 3 <= hi, c_v how many of them have value v, S(p) the sum of c_v (c_v - 1) / 2.
+ *   p is low when l(p) >= 2 and 10 S(p) > T (l(p) - 1).  Every low position whose byte is a base becomes 'N'; nothing else
+ *   is written.  All decisions of a line are taken on the text as it was before this mask wrote anything; where a
+ *   quality option is on as well, the quality mask runs first and this rule sees its 'N's.
+ * A call with the option on returns what the same call with the option off returns on the masked text: start / stop are
+ * unchanged, pos is counted from the read's first byte, n_kmers is smaller (and is the n of the support rule).
+ *   KID_OPT_LOW_COMPLEXITY     the sample's option, above: kid_classify_fastq_async (behind the quality mask, in front of
+ *                              the prepare kernel, on the same stream)
+ *   KID_DB_OPT_LOW_COMPLEXITY  the database's (kid_db_set_option; T in 0..1000, KID_ERR_ARG beyond): every FASTQ form of
+ *                              kid_db_read_hits / _support / _segments / _fragments / _votes.  One call at a time, NOT
+ *                              copied by kid_db_replicate.
+ * With both options off nothing is allocated or launched.                                                           */
+#define KID_DB_OPT_LOW_COMPLEXITY 2
+/* bases masked by KID_OPT_LOW_COMPLEXITY in the sample's FASTQ blocks since kid_sample_begin / kid_sample_reset
+ * (synchronises); bases the quality mask took first are counted there, not here */
+int kid_sample_lowc_bases(kid_sample *s, uint64_t *out);
+/* Host buffers, per read: out_bases (laid out like bases, may equal bases) receives the text of the reads with the masked
+ * bases replaced by 'N'; *n_masked (nullable) their number.  low_complexity = 0 copies the text and reports 0; outside
+ * 0..1000: KID_ERR_ARG.  A record of any length: long ones are spread over many wavefronts.                        */
+int kid_lowc_batch(kid_db *db, const uint8_t *bases, const uint64_t *offsets, uint64_t n_reads, int low_complexity,
+                   uint8_t *out_bases, uint64_t *n_masked);
+/* In place on text resident in HBM, asynchronous on `stream`, in front of kid_classify_batch_device /
+ * kid_db_read_hits_device on the same stream.  d_offsets: uint64[n_reads + 1]; no alignment is asked of the text.
+ * d_n_masked: nullable; one uint64 that the number of bases masked is ADDED to (it is not reset).  The host does not
+ * see the lengths here: every read is one work item, which suits reads and not megabase records.                   */
+int kid_lowc_batch_device(kid_db *db, void *d_bases, const void *d_offsets, uint64_t n_reads, int low_complexity,
+                          void *d_n_masked, void *stream);
 
 /* ---- every read's k-mer hits ------------------------------------------------------
  * What process_read folds (newkmer_10nx.cpp:526-595), handed out instead of folded: for every read, in read-position

@@ -62,6 +62,9 @@ PROTOTYPES = {
     "kid_sample_masked_bases": (C.c_int, [C.c_void_p, c_u64p]),
     "kid_mask_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, c_u64p]),
     "kid_mask_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
+    "kid_sample_lowc_bases": (C.c_int, [C.c_void_p, c_u64p]),
+    "kid_lowc_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, c_u64p]),
+    "kid_lowc_batch_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]),
     "kid_db_read_hits": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_uint64, c_u64p]),
     "kid_db_read_hits_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
@@ -154,7 +157,9 @@ KID_OPT_INPUTS_READY = 1
 KID_OPT_LONG_RECORD_KMERS = 2
 KID_OPT_MIN_BASE_QUALITY = 3
 KID_OPT_ENTRY_DEPTH = 4
+KID_OPT_LOW_COMPLEXITY = 5
 KID_DB_OPT_MIN_BASE_QUALITY = 1
+KID_DB_OPT_LOW_COMPLEXITY = 2
 KID_SHARED_MAX_SAMPLES = 64
 KID_COVERAGE_MAX_BINS = 1 << 28
 KID_FLAG_U_IS_T = 1

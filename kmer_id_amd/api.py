@@ -194,7 +194,7 @@ class KmerDB:
 
     def set_option(self, option, value):
         """kid_db_set_option, e.g. (KID_DB_OPT_MIN_BASE_QUALITY, Q): read_hits_fastq and read_support_fastq read every
-        base of quality below Q as 'N'."""
+        base of quality below Q as 'N'; (KID_DB_OPT_LOW_COMPLEXITY, T): ... every base of a low-complexity window."""
         check(self._lib.kid_db_set_option(self._h, option, value))
 
     def mask_low_quality(self, bases, quals, offsets, q):
@@ -213,6 +213,23 @@ class KmerDB:
         """The same in place on text resident in HBM (raw pointers), asynchronous on `stream`: kid_mask_batch_device.
         d_n_masked: one uint64 in HBM that the number of bases masked is added to (or 0)."""
         check(self._lib.kid_mask_batch_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_quals), C.c_void_p(d_offsets), n_reads, q,
+                                              C.c_void_p(d_n_masked or None), C.c_void_p(stream or None)))
+
+    def mask_low_complexity(self, bases, offsets, t):
+        """Bases that lie in a low-complexity window at threshold t (0..1000; the rule: kmer_id_amd.h, "mask low-complexity
+        sequence") become 'N', read by read (kid_lowc_batch) -> (masked copy of bases, number of bases masked).  t = 0: the
+        text as it is and 0."""
+        bases = _as(bases, np.uint8)
+        offsets = _as(offsets, np.uint64)
+        out = bases.copy()
+        n_masked = C.c_uint64(0)
+        check(self._lib.kid_lowc_batch(self._h, _ptr(bases), _ptr(offsets), offsets.size - 1, t, _ptr(out), C.byref(n_masked)))
+        return out, n_masked.value
+
+    def mask_low_complexity_device(self, d_bases, d_offsets, n_reads, t, d_n_masked=0, stream=0):
+        """The same in place on text resident in HBM (raw pointers), asynchronous on `stream`: kid_lowc_batch_device.
+        d_n_masked: one uint64 in HBM that the number of bases masked is added to (or 0)."""
+        check(self._lib.kid_lowc_batch_device(self._h, C.c_void_p(d_bases), C.c_void_p(d_offsets), n_reads, t,
                                               C.c_void_p(d_n_masked or None), C.c_void_p(stream or None)))
 
     def _read_hits(self, call, n):
@@ -648,6 +665,12 @@ class Sample:
         """-> bases masked under KID_OPT_MIN_BASE_QUALITY since the sample began or was last reset"""
         n = C.c_uint64(0)
         check(self._lib.kid_sample_masked_bases(self._h, C.byref(n)))
+        return n.value
+
+    def low_complexity_bases(self):
+        """-> bases masked under KID_OPT_LOW_COMPLEXITY since the sample began or was last reset"""
+        n = C.c_uint64(0)
+        check(self._lib.kid_sample_lowc_bases(self._h, C.byref(n)))
         return n.value
 
     def classify(self, bases, offsets, start=None, stop=None, want_final=True):

@@ -20,6 +20,7 @@
 #include "kid_support.hip.h"
 #include "kid_segments.hip.h"
 #include "kid_mask.hip.h"
+#include "kid_lowc.hip.h"
 #include "kid_depth.hip.h"
 #include "kid_shared.hip.h"
 #include "kid_coverage.hip.h"
@@ -66,7 +67,8 @@ struct kid_sample {
     uint32_t next_set = 0;
     bool inputs_ready = false;
     int min_base_quality = 0; // KID_OPT_MIN_BASE_QUALITY: FASTQ blocks have their low-quality bases masked behind the upload (kid_mask.hip.h)
-    KidDevBuf masked;         // unsigned long long: bases masked since the last reset
+    KidDevBuf masked;         // unsigned long long [2]: bases masked since the last reset, by quality and ([1]) by low complexity
+    int low_complexity = 0;   // KID_OPT_LOW_COMPLEXITY: ... and their low-complexity bases behind that (kid_lowc.hip.h)
     int64_t long_kmers = 65536; // records of more k-mers than this take the long-record kernels (KID_OPT_LONG_RECORD_KMERS)
     // fixed-layout batches have no descriptors and no prepare kernel: one argument block of their own, rewritten (a
     // one-thread kernel in stream order) only when a launch differs from what the block holds
@@ -101,6 +103,7 @@ struct kid_sample {
         KidDevBuf bases;
         KidDevBuf offsets, start, stop, out; // per read: uint64 (one more), int32, int32, uint32
         KidDevBuf recs; // KidFastqRec: kid_classify_fastq_async, where the host found the lines of the block's records
+        KidDevBuf lowc_plane; // KID_OPT_LOW_COMPLEXITY: the flag plane of a block with a line that is split (kid_lowc.hip.h)
         KidEvent ev_h2d, ev_done, ev_out;
         std::vector<uint64_t> rel; // offsets rebased to the slot (alive until the copy has been issued AND done)
         uint64_t ticket = 0;
@@ -135,7 +138,7 @@ extern "C" int kid_sample_reset(kid_sample *s)
     KID_HIP(hipMemset(s->gcount.p, 0, nt * 8));
     KID_HIP(hipMemset(s->ucount.p, 0, nt * 8));
     KID_HIP(hipMemset(s->stats.p, 0, 256));
-    KID_HIP(hipMemset(s->masked.p, 0, 8));
+    KID_HIP(hipMemset(s->masked.p, 0, 16));
     {   // device-clock stamps of a launch: [30] first workgroup start (min), [31] last end (max); see kid_classify_kernel
         const unsigned long long never = ~0ull;
         KID_HIP(hipMemcpy(s->stats_p() + 30, &never, 8, hipMemcpyHostToDevice));
@@ -176,7 +179,7 @@ extern "C" int kid_sample_begin(kid_db *db, kid_sample **out)
     KID_HIP(s->gcount.alloc(nt * 8));
     KID_HIP(s->ucount.alloc(nt * 8));
     KID_HIP(s->stats.alloc(256));
-    KID_HIP(s->masked.alloc(8));
+    KID_HIP(s->masked.alloc(16));
     KID_HIP(s->seen.alloc(s->seen_words * 4));
     KID_HIP(s->stream.create());
     // the hit log: for the minimizer-localised table (its resolver is the one that logs), bitmaps of up to 1024 pieces
@@ -520,6 +523,11 @@ extern "C" int kid_sample_set_option(kid_sample *s, int option, int value)
         return rc;
     }
     case KID_OPT_ENTRY_DEPTH: return kid_depth_set_option(s, value);
+    case KID_OPT_LOW_COMPLEXITY: {
+        int rc = kid_lowc_check_t(value);
+        if (rc == KID_OK) s->low_complexity = value;
+        return rc;
+    }
     default: return kid_fail(KID_ERR_ARG, "unknown option %d", option);
     }
 }
@@ -779,11 +787,11 @@ extern "C" int kid_classify_fastq_async(kid_sample *s, const uint8_t *text, uint
     if (ticket) *ticket = 0;
     if (n_reads == 0) return KID_OK;
     if (!text || !recs || !out_start || !out_stop) return kid_fail(KID_ERR_ARG, "null argument");
-    const int mask_q = s->min_base_quality;
+    const int mask_q = s->min_base_quality, mask_t = s->low_complexity;
     uint32_t longest = 0;
     int rc = kid_sample_check_open(s);
     if (rc != KID_OK) return rc;
-    rc = kid_check_fastq_block(recs, n_reads, text_nbytes, 0, nullptr, mask_q > 0, &longest);
+    rc = kid_check_fastq_block(recs, n_reads, text_nbytes, 0, nullptr, mask_q > 0 || mask_t > 0, &longest);
     if (rc != KID_OK) return rc;
     rc = kid_use_device(s->db->device);
     if (rc != KID_OK) return rc;
@@ -803,6 +811,12 @@ extern "C" int kid_classify_fastq_async(kid_sample *s, const uint8_t *text, uint
     if (mask_q > 0) {
         rc = kid_mask_launch_fastq(s->db, sl.bases.as<uint8_t>(), sl.recs.as<KidFastqRec>(), n_reads, longest, mask_q,
                                    s->masked.as<unsigned long long>(), cs);
+        if (rc != KID_OK) return rc;
+    }
+    // low-complexity bases -> 'N' behind that, on the text the quality mask left, under the same event
+    if (mask_t > 0) {
+        rc = kid_lowc_launch(s->db, sl.bases.as<uint8_t>(), text_nbytes, sl.recs.as<KidFastqRec>(), nullptr, n_reads, longest, mask_t,
+                             &sl.lowc_plane, s->masked.as<unsigned long long>() + 1, cs);
         if (rc != KID_OK) return rc;
     }
     KidBatch b{};
@@ -972,6 +986,16 @@ extern "C" int kid_sample_masked_bases(kid_sample *s, uint64_t *out)
     if (rc != KID_OK) return rc;
     KID_HIP(hipDeviceSynchronize());
     KID_HIP(hipMemcpy(out, s->masked.p, 8, hipMemcpyDeviceToHost));
+    return KID_OK;
+}
+
+extern "C" int kid_sample_lowc_bases(kid_sample *s, uint64_t *out)
+{
+    if (!s || !out) return kid_fail(KID_ERR_ARG, "null argument");
+    int rc = kid_use_device(s->db->device);
+    if (rc != KID_OK) return rc;
+    KID_HIP(hipDeviceSynchronize());
+    KID_HIP(hipMemcpy(out, s->masked.as<uint64_t>() + 1, 8, hipMemcpyDeviceToHost));
     return KID_OK;
 }
 

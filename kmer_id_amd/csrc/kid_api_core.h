@@ -108,9 +108,9 @@ static int kid_check_offsets_batch(const uint64_t *offsets, const int32_t *start
 }
 
 // ... of a block of FASTQ text with the host's line index.  *max_tiles (null: not wanted) has the records' tiles added:
-// they may share or overlap sequence bytes -- unless `masking` (a min_base_quality option is on: low-quality bases are
-// overwritten in the device copy of the text, kid_mask.hip.h): then the lines must lie in ascending order without
-// overlap, sequence, quality, next sequence, .., as every indexer of a real file leaves them, so that no byte one record
+// they may share or overlap sequence bytes -- unless `masking` (a min_base_quality or low_complexity option is on: bases
+// are overwritten in the device copy of the text, kid_mask.hip.h and kid_lowc.hip.h): then the lines must lie in
+// ascending order without overlap, sequence, quality, next sequence, .., as every indexer of a real file leaves them, so that no byte one record
 // writes is a byte any record's decision reads.  *longest (with `masking`): raised to the longest sequence line.
 // mate: null, or "mate 1, " / "mate 2, " in front of the messages about one block of a call that has two (its caller has
 // checked the size of both together; an absent mate, seq_len = qual_len = 0, has no line to be in order).
@@ -127,7 +127,7 @@ static int kid_check_fastq_block(const kid_fastq_rec *recs, uint64_t n_reads, ui
         if (max_tiles) *max_tiles += c.seq_len / tile + 1;
         if (masking && !(mate && c.seq_len == 0 && c.qual_len == 0)) {
             if (c.seq_off < free_from || (uint64_t)c.seq_off + c.seq_len > c.qual_off)
-                return kid_fail(KID_ERR_ARG, "%srecord %llu: with min_base_quality on, the lines of a block must be in ascending order and "
+                return kid_fail(KID_ERR_ARG, "%srecord %llu: with min_base_quality or low_complexity on, the lines of a block must be in ascending order and "
                                              "must not overlap", pre, (unsigned long long)r);
             free_from = (uint64_t)c.qual_off + c.qual_len;
             if (longest && c.seq_len > *longest) *longest = c.seq_len;

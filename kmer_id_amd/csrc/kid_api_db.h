@@ -21,6 +21,7 @@ struct kid_db {
     std::unique_ptr<struct KidHitsState> hits; // scratch of kid_db_read_hits*, made by the first call (kid_api_hits.h)
     std::mutex hits_mu;
     int min_base_quality = 0; // KID_DB_OPT_MIN_BASE_QUALITY (kid_api_mask.h): read and written under hits_mu; a replica starts at 0
+    int low_complexity = 0;   // KID_DB_OPT_LOW_COMPLEXITY (kid_api_lowc.h): the same rules
     ~kid_db(); // kid_api_hits.h: where KidHitsState is complete
 };
 typedef std::unique_ptr<kid_db, void (*)(kid_db *)> KidDbPtr; // a database under construction

@@ -85,6 +85,7 @@ struct KidHitsState {
     // workgroup of that kernel, zero between calls
     KidDevBuf out_votes, vote_list, vote_n_list, vote_rows;
     KidSpanTimer votes; // the two vote kernels alone
+    KidDevBuf lowc_plane; // KID_DB_OPT_LOW_COMPLEXITY: the flag plane of a staged block with a line that is split (kid_lowc.hip.h)
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
 #define KID_HITS_CTL_WORDS 36u
@@ -130,7 +131,7 @@ struct KidOpenBatch {
     KidBatch b{};                        // the staged copy
     const KidFastqRec *d_recs = nullptr; // FASTQ form: its records (b.start and b.stop are outputs of the prepare kernel then)
     uint64_t max_tiles = 0;              // what the tile arrays are sized for (kid_hits_launch)
-    uint32_t longest = 0;                // FASTQ form under min_base_quality: the longest sequence line, for the mask kernel
+    uint32_t longest = 0;                // FASTQ form under a mask option: the longest sequence line, for the mask kernels
 };
 
 static KidHitsTiles kid_hits_tiles(const KidHitsState *h, const KidBatch &b)
@@ -309,7 +310,8 @@ static int kid_hits_stage_offsets(KidHitsState *h, const uint8_t *bases, const u
     return KID_OK;
 }
 
-// (under KID_DB_OPT_MIN_BASE_QUALITY the staged text is masked here, in front of the hit pass: the caller's is not touched)
+// (under KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY the staged text is masked here, in that order, in front of
+// the hit pass: the caller's is not touched)
 // (text2: a second block that goes right behind the first; the offsets in recs count from the first's first byte)
 static int kid_hits_stage_fastq(const kid_db *db, KidHitsState *h, const uint8_t *text, uint64_t text_nbytes, const uint8_t *text2,
                                 uint64_t nbytes2, const kid_fastq_rec *recs, uint64_t n_reads, uint32_t longest, KidBatch *b,
@@ -325,8 +327,13 @@ static int kid_hits_stage_fastq(const kid_db *db, KidHitsState *h, const uint8_t
     b->stop = h->trim_stop.as<int32_t>();
     b->n = n_reads;
     *d_recs = h->in_recs.as<KidFastqRec>();
-    if (db->min_base_quality > 0)
-        return kid_mask_launch_fastq(db, h->in_bases.as<uint8_t>(), *d_recs, n_reads, longest, db->min_base_quality, nullptr, 0);
+    if (db->min_base_quality > 0) {
+        rc = kid_mask_launch_fastq(db, h->in_bases.as<uint8_t>(), *d_recs, n_reads, longest, db->min_base_quality, nullptr, 0);
+        if (rc != KID_OK) return rc;
+    }
+    if (db->low_complexity > 0)
+        return kid_lowc_launch(db, h->in_bases.as<uint8_t>(), text_nbytes + nbytes2, *d_recs, nullptr, n_reads, longest, db->low_complexity,
+                               &h->lowc_plane, nullptr, 0);
     return KID_OK;
 }
 
@@ -365,13 +372,13 @@ static std::vector<kid_fastq_rec> kid_fastq_interleave(const kid_fastq_rec *recs
 // One block of n_reads records, or (recs2 given) two blocks of n_reads / 2 each, the mates of n_reads / 2 fragments: they
 // are staged as one text, block 2 behind block 1, with one record index in interleaved order (read 2i from block 1,
 // read 2i + 1 from block 2 with its offsets shifted), so that one hit pass takes both.  (The lock comes first:
-// db->min_base_quality, under which a block's lines must be in order.)
+// db->min_base_quality and db->low_complexity, under which a block's lines must be in order.)
 static int kid_hits_open_fastq(KidOpenBatch &ob, kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs,
                                uint64_t n_reads, unsigned settle, KidHitsMoreScratch more_scratch = nullptr, const uint8_t *text2 = nullptr,
                                uint64_t nbytes2 = 0, const kid_fastq_rec *recs2 = nullptr)
 {
     ob.lock = std::unique_lock<std::mutex>(db->hits_mu);
-    const bool masking = db->min_base_quality > 0;
+    const bool masking = db->min_base_quality > 0 || db->low_complexity > 0;
     const uint64_t n_block = recs2 ? n_reads / 2 : n_reads;
     if (!recs2 && (!text || !recs)) return kid_fail(KID_ERR_ARG, "null argument");
     int rc = kid_check_fastq_block(recs, n_block, text_nbytes, KID_HITS_TILE, &ob.max_tiles, masking, &ob.longest, recs2 ? "mate 1, " : nullptr);

@@ -1,10 +1,11 @@
 // kid_api_mask.h -- mask low-quality bases (kid_mask.hip.h): the range check of Q, the two launches of kid_mask_kernel
 // (a FASTQ block with its line index: kid_classify_fastq_async and the FASTQ forms of kid_db_read_hits* /
 // kid_db_read_support* run it on their device copy of the text; bases + quals + offsets: the unit entry points), the
-// database's option, and kid_mask_batch / kid_mask_batch_device.  The sample's option and counter are with the sample
-// (kid_api.hip).
+// database's options (this one and KID_DB_OPT_LOW_COMPLEXITY, kid_api_lowc.h), and kid_mask_batch /
+// kid_mask_batch_device.  The sample's option and counter are with the sample (kid_api.hip).
 #pragma once
 #include "kid_api_db.h"
+#include "kid_api_lowc.h"
 #include "kid_mask.hip.h"
 
 #define KID_MAX_BASE_QUALITY 93 // '~' - 33: the highest quality a FASTQ line can spell
@@ -50,6 +51,13 @@ extern "C" int kid_db_set_option(kid_db *db, int option, int value)
         if (rc != KID_OK) return rc;
         std::lock_guard<std::mutex> lock(db->hits_mu); // (the calls it applies to read it under the same lock)
         db->min_base_quality = value;
+        return KID_OK;
+    }
+    case KID_DB_OPT_LOW_COMPLEXITY: {
+        int rc = kid_lowc_check_t(value);
+        if (rc != KID_OK) return rc;
+        std::lock_guard<std::mutex> lock(db->hits_mu);
+        db->low_complexity = value;
         return KID_OK;
     }
     default: return kid_fail(KID_ERR_ARG, "unknown option %d", option);

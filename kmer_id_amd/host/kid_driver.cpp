@@ -108,17 +108,21 @@ void engine_configure(Engine &e, const SideOptions &side)
         for (kid_db *d : e.dbs) e.fragments.push_back(begin_sample_or_die(d));
     if (side.votes) // (tallied through the database's hit pass too)
         for (kid_db *d : e.dbs) e.votes.push_back(begin_sample_or_die(d));
-    const int q = side.min_base_quality;
-    if (q == 0) return;
-    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
-        for (kid_sample *s : *list) {
-            int rc = kid_sample_set_option(s, KID_OPT_MIN_BASE_QUALITY, q);
+    // the two masks: the sample's option and the database's, each only where it is on
+    const struct { int value, sample_opt, db_opt; } masks[] = {{side.min_base_quality, KID_OPT_MIN_BASE_QUALITY, KID_DB_OPT_MIN_BASE_QUALITY},
+                                                               {side.low_complexity, KID_OPT_LOW_COMPLEXITY, KID_DB_OPT_LOW_COMPLEXITY}};
+    for (const auto &m : masks) {
+        if (m.value == 0) continue;
+        for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident})
+            for (kid_sample *s : *list) {
+                int rc = kid_sample_set_option(s, m.sample_opt, m.value);
+                if (rc != KID_OK) die_kid(rc);
+            }
+        if (!e.owns_dbs) continue; // (a worker: its owner has set it)
+        for (kid_db *d : e.dbs) {
+            int rc = kid_db_set_option(d, m.db_opt, m.value);
             if (rc != KID_OK) die_kid(rc);
         }
-    if (!e.owns_dbs) return; // (a worker: its owner has set it)
-    for (kid_db *d : e.dbs) {
-        int rc = kid_db_set_option(d, KID_DB_OPT_MIN_BASE_QUALITY, q);
-        if (rc != KID_OK) die_kid(rc);
     }
 }
 
@@ -369,6 +373,14 @@ static void read_base_quality(SideOptions &o, const char *prog, const char *opt,
     o.min_base_quality = (int)q;
 }
 
+static void read_low_complexity(SideOptions &o, const char *prog, const char *opt, const char *v)
+{
+    unsigned long long t = 0;
+    size_t at = 0;
+    if (digits_up_to(1000, v, at, t) <= 0 || v[at] != 0) usage_error(prog, opt, "takes a threshold from 0 to 1000");
+    o.low_complexity = (int)t;
+}
+
 static void read_segments(SideOptions &o, const char *prog, const char *opt, const char *v)
 {
     const char *const what = "takes LEN[:STEP], digits only: LEN in 1..2147483647, STEP in 1..LEN with LEN <= 1024 * STEP";
@@ -393,6 +405,7 @@ static const struct {
                     {"--min-hits", 0, read_min_hits, nullptr},
                     {"--confidence", 0, read_confidence, nullptr},
                     {"--min-base-quality", 1, read_base_quality, nullptr},
+                    {"--low-complexity", 1, read_low_complexity, nullptr},
                     {"--segments", 2, read_segments, nullptr},
                     {"--depth", 0, nullptr, &SideOptions::depth},
                     {"--seen", 0, nullptr, &SideOptions::seen},
@@ -600,7 +613,7 @@ void SampleOutputs::finish(Engine &e)
 
 // One call of the kid_db_read_* family on a classified batch (its start / stop / final targets are known) on the batch's
 // device: the FASTQ-block form for a block, else the offsets form; `rest` are the arguments behind the number of reads.
-// (bases: the text of a batch of reads that was classified -- the batch's own, or its masked copy under --min-base-quality)
+// (bases: the text of a batch of reads that was classified -- the batch's own, or its masked copy under --min-base-quality / --low-complexity)
 template <class BlockForm, class OffsetsForm, class... Rest>
 static void read_pass(BlockForm block_form, OffsetsForm offsets_form, kid_db *db, const ReadBatch &b, const uint8_t *bases, Rest... rest)
 {
@@ -693,6 +706,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
     struct InFlight {
         std::unique_ptr<ReadBatch> batch;
         std::vector<uint32_t> final_targ;
+        // --low-complexity on a batch of reads (kid_lowc_batch), and in front of it
         // --min-base-quality on a batch of reads with their qualities (a plain FASTQ file, tokenised and trimmed on the
         // host): the copy of the text with the low-quality bases masked (kid_mask_batch) that is classified in its place --
         // the read saver prints the batch's own text
@@ -810,6 +824,12 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
                     f.masked.resize(f.batch->bases.size());
                     rc = kid_mask_batch(f.db, f.batch->bases.data(), f.batch->quals.data(), f.batch->offsets.data(), nr, e.side.min_base_quality,
                                         f.masked.data(), nullptr);
+                }
+                if (rc == KID_OK && e.side.low_complexity > 0 && !f.batch->bases.empty()) { // (on what the quality mask left; FASTA too)
+                    const bool quality_masked = !f.masked.empty();
+                    f.masked.resize(f.batch->bases.size());
+                    rc = kid_lowc_batch(f.db, quality_masked ? f.masked.data() : f.batch->bases.data(), f.batch->offsets.data(), nr,
+                                        e.side.low_complexity, f.masked.data(), nullptr);
                 }
                 if (rc == KID_OK)
                     rc = kid_classify_batch_async(f.sample, f.bases(), f.batch->offsets.data(), f.batch->start.data(),

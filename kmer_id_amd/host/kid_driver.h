@@ -38,6 +38,11 @@ struct SideOptions {
     // kid_mask_batch before they are classified (run_files).  FASTA input has no qualities: the option is accepted and
     // changes nothing.
     int min_base_quality = 0;
+    // --low-complexity T (digits only, 0..1000; 0 = off, the default; 20 is DUST's usual level): the bases that lie in a
+    // low-complexity window (kmer_id_amd.h, "mask low-complexity sequence") are read as 'N' in the same way
+    // (KID_OPT_LOW_COMPLEXITY / KID_DB_OPT_LOW_COMPLEXITY), behind the quality mask when both are given.  Plain FASTQ and
+    // FASTA input go through kid_lowc_batch into the same masked copy: unlike the quality option, this one applies to FASTA.
+    int low_complexity = 0;
     SegmentsOption segments;
     // --depth (no value): k-mer depth per database entry (KID_OPT_ENTRY_DEPTH), summed up per target in a depth file.  The
     // support pass runs for it under the rule of --min-hits / --confidence when given, else (0, 0).
@@ -54,7 +59,7 @@ struct SideOptions {
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
 // of --segments too) is a usage error: "<prog>: <option> <what>" on stderr and exit code 2 -- of several, the first in
-// the order --min-hits / --confidence, --min-base-quality, --segments.
+// the order --min-hits / --confidence, --min-base-quality / --low-complexity, --segments.
 SideOptions side_options(int argc, char **argv, const char *prog);
 // For a front-end that rejects the words it does not know: the number of value words behind `word` (0 or 1) if it
 // is a side option, else -1
@@ -108,7 +113,7 @@ bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &pare
                  unsigned flags, const std::vector<int> &devices);
 // The side options for an engine that is open: with a rule or --depth one more sample per device (reset, closed and
 // destroyed with the others; --depth switches its depth counters on), under --fragments one more for the fragments, under
-// --votes one more for the vote pass, then --min-base-quality on every sample, the tallied ones included, and on every replica of the database.
+// --votes one more for the vote pass, then --min-base-quality and --low-complexity on every sample, the tallied ones included, and on every replica of the database.
 // A worker of engine_worker() inherits them for its samples.
 void engine_configure(Engine &e, const SideOptions &side);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D

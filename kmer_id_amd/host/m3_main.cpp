@@ -14,6 +14,7 @@
 //   --seen   the seen-bitmap in a seen file (<...>seen.bin beside <...>result.txt), for kmer_shared
 //   --votes   the reads called by root-path votes, whatever the order of their hits (the votes file of kid_driver.h)
 //   --min-base-quality Q   FASTQ bases of quality below Q (0..93; 0 = off) are read as N
+//   --low-complexity T   bases in a low-complexity window at threshold T (0..1000; 0 = off, 20 = DUST's usual level) are read as N
 #include <stdio.h>
 #include <stdlib.h>
 
