@@ -129,6 +129,12 @@ int kid_sample_begin(kid_db *db, kid_sample **out);
                                    kid_classify_fastq_async after the call have every base of a low-complexity window read
                                    as 'N' ("mask low-complexity sequence" below; T = 20 is DUST's usual level).  It stays
                                    until it is set again; kid_sample_reset does not change it */
+#define KID_OPT_LINE_DIGEST 6 /* which front half the pair and duo loops (reads of up to 256 k-mers) run on a GPU-built
+                                minimizer-localised table: 0 = they read the table's line headers, 1 = the 8-byte line digests
+                                of the plane beside the table, 2 = auto (the default): digests until a pass over the hit log
+                                finds the sample's reads full of hits, then headers until kid_sample_reset.  Results are the
+                                same either way; only stats.probes may differ.  Any other value is KID_ERR_ARG.  A table
+                                without a plane (reference geometry, host-built) takes the headers whatever the value */
 int kid_sample_set_option(kid_sample *s, int option, int value);
 int kid_sample_reset(kid_sample *s);
 void kid_sample_destroy(kid_sample *s);

@@ -31,13 +31,21 @@ int kid_synth_reads_device(uint64_t db_seed, uint64_t read_seed, int k, const ui
  * that many independent loads per lane, of which the compiler keeps two 4-byte
  * loads per cell (the round-1 probe: twice the load instructions per line, it tops
  * out at 39 G cells/s where the line probe reaches 49 G lines/s).
+ * inflight = 201 / 208: the shapes of 101 / 108 on the table's digest plane, one 8-byte
+ * load per lane (KID_ERR_ARG for a table without a plane).
  * *ms_out = milliseconds per launch.                                               */
 int kid_bench_gather(struct kid_db *db, uint64_t n_loads, int inflight, int iters, float *ms_out, uint64_t *loads_out);
+
+/* where the table and its digest plane (8 bytes per 128-byte line; none: null and 0) lie in device memory, for
+ * kid_dev_download: tests recompute the plane from the table's headers */
+int kid_bench_db_arrays(struct kid_db *db, const void **table, uint64_t *table_bytes, const void **digest, uint64_t *digest_bytes);
 
 /* which kid_classify_kernel instantiations the sample has launched since it began or was last reset: bit
  * PAIRK*16 | ROWS<<3 | HIST<<2 | MINLOC<<1 | (KFIX == 30) per instantiation (PAIRK 1 pair loop, 2 duo loop, 0 general
  * loops).  A launch is recorded whether or not the kernel finds work: a batch with device-side offsets launches all
- * three loops of its configuration, and the two the batch is not for return at once.                                 */
+ * three loops of its configuration, and the two the batch is not for return at once.  The DIGEST instantiations of
+ * the pair and duo loops (KID_OPT_LINE_DIGEST) have bits of their own: 48 + (PAIRK - 1)*8 + (ROWS<<2 | HIST<<1 |
+ * (KFIX == 30)).                                                                                                      */
 int kid_sample_kernel_variants(struct kid_sample *s, uint64_t *mask);
 
 /* the state of the sample's hit log, for tests that must prove which regime they reached.  Synchronises the device; reads

@@ -134,6 +134,7 @@ PROTOTYPES = {
                                          C.c_uint64, C.c_uint32, C.c_void_p, C.c_int]),
     "kid_sample_kernel_variants": (C.c_int, [C.c_void_p, c_u64p]),
     "kid_sample_log_state": (C.c_int, [C.c_void_p, c_u32p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kid_bench_db_arrays": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), c_u64p, C.POINTER(C.c_void_p), c_u64p]),
     "kid_bench_gather": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_float), c_u64p]),
     "kid_dev_alloc": (C.c_int, [C.c_int, C.c_uint64, c_void_pp]),
     "kid_dev_free": (C.c_int, [C.c_int, C.c_void_p]),
@@ -158,6 +159,7 @@ KID_OPT_LONG_RECORD_KMERS = 2
 KID_OPT_MIN_BASE_QUALITY = 3
 KID_OPT_ENTRY_DEPTH = 4
 KID_OPT_LOW_COMPLEXITY = 5
+KID_OPT_LINE_DIGEST = 6
 KID_DB_OPT_MIN_BASE_QUALITY = 1
 KID_DB_OPT_LOW_COMPLEXITY = 2
 KID_SHARED_MAX_SAMPLES = 64

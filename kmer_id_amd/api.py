@@ -453,6 +453,20 @@ class KmerDB:
         check(self._lib.kid_bench_gather(self._h, n_loads, inflight, iters, C.byref(ms), C.byref(loads)))
         return ms.value, loads.value
 
+    def table_and_digest(self):
+        """-> (table, digest) downloaded: uint32 [cells, 4] and uint32 [lines, 2] (None for a table without a digest
+        plane).  For tests and tools: a full-size table is 16 GiB."""
+        tp, dp, tb, db_ = C.c_void_p(), C.c_void_p(), C.c_uint64(0), C.c_uint64(0)
+        check(self._lib.kid_bench_db_arrays(self._h, C.byref(tp), C.byref(tb), C.byref(dp), C.byref(db_)))
+        dev = self.info.device
+        table = np.empty((tb.value // 16, 4), np.uint32)
+        check(self._lib.kid_dev_download(dev, _ptr(table), tp, tb.value))
+        digest = None
+        if dp.value:
+            digest = np.empty((db_.value // 8, 2), np.uint32)
+            check(self._lib.kid_dev_download(dev, _ptr(digest), dp, db_.value))
+        return table, digest
+
     def sample(self):
         return Sample(self)
 
@@ -772,12 +786,15 @@ class Sample:
         check(self._lib.kid_sample_kernel_time_device(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
-    def kernel_variants(self):
+    def kernel_variants(self, digest=None):
         """-> the kid_classify_kernel instantiations launched since the sample began or was last reset, as a set of
-        (ROWS, HIST, MINLOC, KFIX, PAIRK) tuples (kid_sample_kernel_variants)"""
+        (ROWS, HIST, MINLOC, KFIX, PAIRK) tuples (kid_sample_kernel_variants).  digest=False: only those that read table
+        headers; True: only the DIGEST instantiations of the pair and duo loops (KID_OPT_LINE_DIGEST); None: both."""
         m = C.c_uint64(0)
         check(self._lib.kid_sample_kernel_variants(self._h, C.byref(m)))
-        return {(b >> 3 & 1, b >> 2 & 1, b >> 1 & 1, 30 if b & 1 else 0, b >> 4) for b in range(64) if m.value >> b & 1}
+        hdr = {(b >> 3 & 1, b >> 2 & 1, b >> 1 & 1, 30 if b & 1 else 0, b >> 4) for b in range(48) if m.value >> b & 1}
+        dig = {(b >> 2 & 1, b >> 1 & 1, 1, 30 if b & 1 else 0, 1 + (b >> 3)) for b in range(16) if m.value >> (48 + b) & 1}
+        return hdr | dig if digest is None else dig if digest else hdr
 
     def log_state(self):
         """-> {"passes", "has_log", "logging"}: passes over the hit log queued since the sample began or was last reset,

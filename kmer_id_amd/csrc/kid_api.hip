@@ -92,6 +92,11 @@ struct kid_sample {
     KidDevBuf long_hits, long_tiles;
     bool ended = false; // kid_sample_end* has read the counters and no reset has followed: classify calls and tallies are refused
     uint64_t reads_submitted = 0; // since the last reset: checked against the device's count when results are read
+    // KID_OPT_LINE_DIGEST: 0 the pair and duo loops read table headers, 1 the digest plane, 2 (default) the plane until a
+    // pass over the hit log gives the log up (log_off below: more than 8 log places per read), then headers until the
+    // next reset.  The digest kernels are the faster ones well beyond that rate (profiles/digest/crossover.txt), but
+    // the log's rate is the only signal the host has, and it ends there.
+    int line_digest = 2;
     uint64_t kernel_variants = 0; // since the last reset: one bit per kid_classify_kernel instantiation launched (kid_sample_kernel_variants)
     // the scratch below is one set per sample: batches on different streams are ordered behind each other
     hipStream_t last_stream = nullptr; // (the caller's or ours: not owned)
@@ -201,7 +206,7 @@ extern "C" int kid_sample_begin(kid_db *db, kid_sample **out)
     }
     const KidRareArgs ra{s->gcount.as<unsigned long long>(), s->stats_p(), db->d.line_mask, 0u, 0ull, 0ull, 0, 0u, db->d.rows,
                          s->seen.as<uint32_t>(), nullptr, nullptr, s->seen_log.as<uint32_t>(), s->seen_log_tail.as<uint32_t>(),
-                         s->seen_log_cap, 0u};
+                         s->seen_log_cap, 0u, db->d.table};
     for (kid_sample::Scratch &sc : s->sets) {
         KID_HIP(sc.rare.alloc(sizeof(ra)));
         KID_HIP(hipMemcpy(sc.rare.p, &ra, sizeof(ra), hipMemcpyHostToDevice));
@@ -439,6 +444,8 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
     const bool want_pair = ml && (max_kmers < 0 || max_kmers <= 2 * 64);
     const bool want_duo = ml && (max_kmers < 0 || (max_kmers > 2 * 64 && max_kmers <= 4 * 64));
     const bool want_general = !ml || max_kmers < 0 || max_kmers > 4 * 64;
+    // the pair and duo loops on the digest plane (KID_OPT_LINE_DIGEST), where the table has one
+    const bool digest = ml && db->d.digest != nullptr && (s->line_digest == 1 || (s->line_digest == 2 && !s->log_off));
     KidEvent ev0, ev1;
     if (s->timing) {
         KID_HIP(ev0.create());
@@ -464,15 +471,19 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
         auto launch = [&](auto pk_mode, bool h) {
             constexpr int PK = decltype(pk_mode)::value;
             kid_lift(rows, [&](auto R) { kid_lift(h, [&](auto H) { kid_lift(ml, [&](auto M) { kid_lift(k30, [&](auto K30) {
-                if constexpr (PK == 0 || decltype(M)::value) {
-                    constexpr bool r = decltype(R)::value, hh = decltype(H)::value, m = decltype(M)::value;
+                kid_lift(PK != 0 && digest, [&](auto D) {
+                if constexpr ((PK == 0 || decltype(M)::value) && (!decltype(D)::value || (PK != 0 && decltype(M)::value))) {
+                    constexpr bool r = decltype(R)::value, hh = decltype(H)::value, m = decltype(M)::value, dg = decltype(D)::value;
                     constexpr int KF = decltype(K30)::value ? 30 : 0;
                     const uint32_t hw = hh ? (PK ? hist_words16 : hist_words) : 0u;
-                    s->kernel_variants |= 1ull << (PK * 16 | r << 3 | hh << 2 | m << 1 | (KF == 30));
-                    hipLaunchKernelGGL((kid_classify_kernel<2, r, hh, m, KF, PK>), dim3(grid), dim3(block),
+                    // (the DIGEST instantiations: bits 48..63, see kid_sample_kernel_variants)
+                    s->kernel_variants |= dg ? 1ull << (48 + (PK - 1) * 8 + (r << 2 | hh << 1 | (KF == 30)))
+                                             : 1ull << (PK * 16 | r << 3 | hh << 2 | m << 1 | (KF == 30));
+                    hipLaunchKernelGGL((kid_classify_kernel<2, r, hh, m, KF, PK, dg>), dim3(grid), dim3(block),
                                        (hw + (size_t)wpb * (PK ? KID_PAIR_LDS_WORDS : wave_words)) * 4 + 32, stream, db->d, pk, sd, hw,
                                        pk.desc, rare);
                 }
+                });
             }); }); }); });
         };
         if (want_pair) launch(std::integral_constant<int, 1>{}, hist_pair);
@@ -528,6 +539,10 @@ extern "C" int kid_sample_set_option(kid_sample *s, int option, int value)
         if (rc == KID_OK) s->low_complexity = value;
         return rc;
     }
+    case KID_OPT_LINE_DIGEST:
+        if (value < 0 || value > 2) return kid_fail(KID_ERR_ARG, "KID_OPT_LINE_DIGEST: the value is 0, 1 or 2, not %d", value);
+        s->line_digest = value;
+        return KID_OK;
     default: return kid_fail(KID_ERR_ARG, "unknown option %d", option);
     }
 }

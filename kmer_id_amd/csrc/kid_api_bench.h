@@ -75,9 +75,12 @@ extern "C" int kid_bench_gather(kid_db *db, uint64_t n_loads, int inflight, int 
     const uint64_t lanes = (uint64_t)block * grid;
     // inflight = 101 / 108: random LINES, runs of 1 / 8 lanes on a line, 4 loads in flight (kid_gather_lines_kernel);
     // *loads_out is then the number of distinct line requests
-    const bool by_line = inflight == 101 || inflight == 108 || inflight == 111 || inflight == 121 || inflight == 131; // (1x1: development variants, see the kernel)
+    // inflight = 201 / 208: the same two shapes on the digest plane (8-byte loads; a table without one: KID_ERR_ARG)
+    const bool by_digest = inflight == 201 || inflight == 208;
+    const bool by_line = by_digest || inflight == 101 || inflight == 108 || inflight == 111 || inflight == 121 || inflight == 131; // (1x1: development variants, see the kernel)
     if (!by_line && inflight != 1 && inflight != 2 && inflight != 4 && inflight != 8) return kid_fail(KID_ERR_ARG, "inflight must be 1,2,4 or 8 (or 101, 108: by line)");
     if (by_line && db->d.slot_mask < 7u) return kid_fail(KID_ERR_ARG, "table too small");
+    if (by_digest && !db->d.digest) return kid_fail(KID_ERR_ARG, "the table has no digest plane");
     uint64_t rounds = n_loads / (lanes * (uint64_t)(by_line ? 4 : inflight));
     if (rounds < 1) rounds = 1;
     KidDevBuf sinkb;
@@ -95,6 +98,8 @@ extern "C" int kid_bench_gather(kid_db *db, uint64_t n_loads, int inflight, int 
         case 121: hipLaunchKernelGGL((kid_gather_lines_kernel<1, 2>), dim3(grid), dim3(block), 0, 0, db->d.table, line_mask, rounds, sink); break;
         case 131: hipLaunchKernelGGL((kid_gather_lines_kernel<1, 3>), dim3(grid), dim3(block), 0, 0, db->d.table, line_mask, rounds, sink); break;
         case 108: hipLaunchKernelGGL((kid_gather_lines_kernel<8>), dim3(grid), dim3(block), 0, 0, db->d.table, line_mask, rounds, sink); break;
+        case 201: hipLaunchKernelGGL((kid_gather_digest_kernel<1>), dim3(grid), dim3(block), 0, 0, db->d.digest, line_mask, rounds, sink); break;
+        case 208: hipLaunchKernelGGL((kid_gather_digest_kernel<8>), dim3(grid), dim3(block), 0, 0, db->d.digest, line_mask, rounds, sink); break;
         case 1: hipLaunchKernelGGL((kid_gather_kernel<1>), dim3(grid), dim3(block), 0, 0, db->d.table, db->d.slot_mask, rounds, sink); break;
         case 2: hipLaunchKernelGGL((kid_gather_kernel<2>), dim3(grid), dim3(block), 0, 0, db->d.table, db->d.slot_mask, rounds, sink); break;
         case 4: hipLaunchKernelGGL((kid_gather_kernel<4>), dim3(grid), dim3(block), 0, 0, db->d.table, db->d.slot_mask, rounds, sink); break;
@@ -110,7 +115,18 @@ extern "C" int kid_bench_gather(kid_db *db, uint64_t n_loads, int inflight, int 
     float ms = 0;
     KID_HIP(hipEventElapsedTime(&ms, e0, e1));
     *ms_out = ms / (float)iters;
-    *loads_out = by_line ? rounds * (lanes / (inflight == 108 ? 8 : 1)) * 4 : rounds * lanes * (uint64_t)inflight; // loads (lines) actually asked for per launch
+    *loads_out = by_line ? rounds * (lanes / (inflight == 108 || inflight == 208 ? 8 : 1)) * 4 : rounds * lanes * (uint64_t)inflight; // loads (lines) actually asked for per launch
+    return KID_OK;
+}
+
+// where the table and its digest plane lie in device memory (kid_dev_download reads them): for tests and tools
+extern "C" int kid_bench_db_arrays(struct kid_db *db, const void **table, uint64_t *table_bytes, const void **digest, uint64_t *digest_bytes)
+{
+    if (!db || !table || !table_bytes || !digest || !digest_bytes) return kid_fail(KID_ERR_ARG, "null argument");
+    *table = db->table.p;
+    *table_bytes = db->info.table_bytes;
+    *digest = db->digest.p;
+    *digest_bytes = db->digest.p ? db->info.table_bytes / 16 : 0;
     return KID_OK;
 }
 

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "kid_api_core.h"
+#include "kid_build.hip.h"
 #include "kid_kernels.hip.h"
 
 struct kid_db {
@@ -14,7 +15,8 @@ struct kid_db {
     int num_cu = 0;
     KidDevDb d{}; // what the kernels get: the pointers below and the geometry
     KidDevBuf table, rows, parent, depth;
-    KidDevBuf ord_target;   // uint32: target of entry o as handed to the builder, padded with zeros to a multiple of 128
+    KidDevBuf digest;       // uint2 per table line: the digest plane of a GPU-built minimizer-localised table (kid_common.h)
+    KidDevBuf ord_target;  // uint32: target of entry o as handed to the builder, padded with zeros to a multiple of 128
     uint64_t seen_bits = 0; // entries rounded up to whole 16-byte groups of the seen-bitmap
     KidDevBuf entries_per_target; // unsigned long long [ntar]: made under hits_mu by the first depth spectrum (kid_api_depth.h)
     kid_db_info info{};
@@ -218,9 +220,17 @@ static int kid_db_build_common(const uint64_t *h_keys, const uint32_t *h_targets
             if (occ[1] != 0) return kid_fail(KID_ERR_TARGET, "%llu targets >= ntar", occ[1]);
             n_occupied = occ[0];
         }
+        if (minloc) { // the digest plane, from the finished headers (of an empty table too: all zero)
+            const uint64_t n_lines = nslots >> 3;
+            KID_HIP(db->digest.alloc(n_lines * sizeof(uint2)));
+            hipLaunchKernelGGL(kid_build_digest_kernel, dim3(kid_grid_for(n_lines, KID_BUILD_BLOCK, db->num_cu * 16)), dim3(KID_BUILD_BLOCK), 0, 0,
+                               db->table.as<uint4>(), n_lines, db->digest.as<uint2>());
+            KID_HIP(hipDeviceSynchronize());
+        }
     }
 
     db->d.table = db->table.as<uint4>();
+    db->d.digest = db->digest.as<uint2>();
     db->d.nslots = nslots;
     db->d.slot_mask = (uint32_t)(nslots - 1);
     db->d.max_probes = (uint32_t)max_probes;
@@ -280,6 +290,7 @@ extern "C" int kid_db_replicate(const kid_db *src, int device, kid_db **out)
         return hipMemcpyPeer(dst.p, device, from.p, src->device, nbytes);
     };
     KID_HIP(copy(db->table, src->table, src->info.table_bytes));
+    if (src->digest.p) KID_HIP(copy(db->digest, src->digest, src->info.table_bytes / 16));
     KID_HIP(copy(db->parent, src->parent, sizeof(int32_t) * nt));
     KID_HIP(copy(db->depth, src->depth, sizeof(int32_t) * nt));
     if (src->rows.p) KID_HIP(copy(db->rows, src->rows, sizeof(uint4) * nt));
@@ -288,6 +299,7 @@ extern "C" int kid_db_replicate(const kid_db *src, int device, kid_db **out)
     KID_HIP(hipDeviceSynchronize());
     db->d = src->d;
     db->d.table = db->table.as<uint4>();
+    db->d.digest = db->digest.as<uint2>();
     db->d.rows = db->rows.as<uint4>();
     db->d.parent = db->parent.as<int32_t>();
     db->d.depth = db->depth.as<int32_t>();

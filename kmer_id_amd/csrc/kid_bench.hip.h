@@ -49,6 +49,31 @@ __global__ __launch_bounds__(256) void kid_gather_lines_kernel(const uint4 *tabl
     if (acc == 0x12345678u) sink[0] = acc;
 }
 
+// ... and of the digest plane (kid_common.h): the same random lines, the same runs, one 8-byte load per lane from the
+// line's digest instead of 16 bytes from its header
+template <int RUN>
+__global__ __launch_bounds__(256) void kid_gather_digest_kernel(const uint2 *digest, uint32_t line_mask, uint64_t rounds, uint32_t *sink)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t wave = (blockIdx.x * (uint64_t)blockDim.x + threadIdx.x) >> 6;
+    uint32_t acc = 0;
+    uint64_t ctr = wave * 0x9E3779B97F4A7C15ULL + 12345;
+    for (uint64_t r = 0; r < rounds; r++) {
+        kid_u2 a[4] = {{0, 0}, {0, 0}, {0, 0}, {0, 0}};
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            ctr += 0xD1B54A32D192ED03ULL;
+            const uint32_t line = (uint32_t)kid_fmix64(ctr ^ ((uint64_t)(lane / (uint32_t)RUN) << 48)) & line_mask;
+            const uint2 *p = digest + line;
+            asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(a[u]) : "v"(p) : "memory");
+        }
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]) : : "memory");
+#pragma unroll
+        for (int u = 0; u < 4; u++) acc ^= a[u].x ^ a[u].y;
+    }
+    if (acc == 0x12345678u) sink[0] = acc;
+}
+
 template <int INF>
 __global__ __launch_bounds__(256) void kid_gather_kernel(const uint4 *table, uint32_t slot_mask, uint64_t rounds, uint32_t *sink)
 {

@@ -223,6 +223,19 @@ __global__ __launch_bounds__(KID_BUILD_BLOCK) void kid_build_mark_kernel(uint32_
     kid_build_roll(text, e0, e1, [&](uint64_t, uint64_t kf, uint64_t kr) { table[kid_fmix64(kf < kr ? kf : kr) & cell_mask] = 1; });
 }
 
+// The digest plane of a finished minimizer-localised table (kid_common.h): one thread per line, headers only -- 16 of
+// every 128 bytes asked for, but whole lines fetched: a pass over the table, ~3.4 ms for 16 GiB.  Runs behind
+// kid_build_firstwins_kernel, which leaves the headers as kid_build_insert_kernel wrote them.
+__global__ __launch_bounds__(KID_BUILD_BLOCK) void kid_build_digest_kernel(const uint4 *__restrict__ table, uint64_t n_lines, uint2 *__restrict__ digest)
+{
+    for (uint64_t l = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; l < n_lines; l += (uint64_t)gridDim.x * blockDim.x) {
+        const uint4 h = table[l * KID_LINE_CELLS];
+        uint2 d;
+        kid_digest_of_header(h.x, h.y, h.z, h.w, d.x, d.y);
+        digest[l] = d;
+    }
+}
+
 __global__ void kid_build_entropy_kernel(const uint64_t *__restrict__ keys, uint64_t n, const double *__restrict__ term, double log10_4,
                                          uint8_t *flags)
 {

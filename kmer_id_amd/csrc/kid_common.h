@@ -171,6 +171,52 @@ KID_HD uint32_t kid_key_fp(uint64_t key)
     return f ? f : 1u;
 }
 
+// ---------------------------------------------------------------- the digest plane
+// Beside a GPU-built minimizer-localised table lies a derived array of 8 bytes per 128-byte line (1/16 of the table's
+// bytes: 1 GiB for 2^27 lines, small enough that a good part of it stays in the 256 MiB Infinity Cache), written from
+// the finished headers by kid_build_digest_kernel.  The pair and duo loops read it INSTEAD of the header:
+//   bytes 0..6  kid_digest_fp of the header fingerprints of entries 0..6 (0 = unused slot, as in the header)
+//   byte 7      [3:0] the header's count (0..7, 8 = full and chained), [7:4] the header's 12-bit overflow filter
+//               folded to four bits: nibble bit b is the OR of header filter bits 3b .. 3b + 2
+// The digest's answer is a SUPERSET of the header's: two equal 16-bit fingerprints have equal digest bytes, so every
+// slot the header names as a candidate is named by the digest too, and a key that set filter bit 20 + ((fp * 12) >> 16)
+// finds nibble bit ((fp * 12) >> 16) / 3 = fp >> 14 set, so every chain the header follows the digest follows too.
+// Every candidate is verified against the full key in its cell (line * 8 + 1 + slot; no header is needed to find it),
+// and a chain walk the 12-bit filter would have skipped simply finds nothing: the results are identical to the header
+// path's by construction, only the number of cells read (stats.probes) may differ.  The fingerprint of a tombstone
+// stays, as it does in the header: a false candidate costs a load.
+KID_HD uint32_t kid_digest_fp(uint32_t fp) // fp: kid_key_fp, 1..65535 -> 1..255 (the high byte; 0 is kept for "unused")
+{
+    const uint32_t d = fp >> 8;
+    return d ? d : 1u;
+}
+KID_HD uint32_t kid_digest_ovf_bit(uint32_t fp) { return 28u + (fp >> 14); } // in the digest's high dword
+// the digest {lo, hi} of a line from its header words
+KID_HD void kid_digest_of_header(uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3, uint32_t &lo, uint32_t &hi)
+{
+    const uint32_t f[7] = {h0 & 0xFFFFu, h0 >> 16, h1 & 0xFFFFu, h1 >> 16, h2 & 0xFFFFu, h2 >> 16, h3 & 0xFFFFu};
+    uint32_t b[7];
+    for (int j = 0; j < 7; j++) b[j] = f[j] ? kid_digest_fp(f[j]) : 0u;
+    const uint32_t filt = h3 >> 20;
+    const uint32_t nib = ((filt & 0x007u) ? 1u : 0u) | ((filt & 0x038u) ? 2u : 0u) | ((filt & 0x1C0u) ? 4u : 0u) | ((filt & 0xE00u) ? 8u : 0u);
+    lo = b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24);
+    hi = b[4] | (b[5] << 8) | (b[6] << 16) | (kid_hdr_count(h3) << 24) | (nib << 28);
+}
+KID_HD uint32_t kid_digest_count(uint32_t hi) { return (hi >> 24) & 15u; }
+KID_HD bool kid_digest_continues(uint32_t hi, uint32_t fp)
+{
+    return kid_digest_count(hi) >= KID_HDR_FULL && ((hi >> kid_digest_ovf_bit(fp)) & 1u) != 0;
+}
+// Candidate entries of a digest for fingerprint fp, as a bit set: bit 8j + 7 = entry j (j = 0..3), bit 8j + 6 = entry
+// 4 + j (j = 0..2).  Like kid_hdr_cand a superset (the zero-byte test can flag the byte above a match).
+KID_HD uint32_t kid_digest_cand(uint32_t lo, uint32_t hi, uint32_t fp)
+{
+    const uint32_t rep = kid_digest_fp(fp) * 0x01010101u, one = 0x01010101u, top = 0x80808080u;
+    const uint32_t a = lo ^ rep, b = (hi ^ rep) | 0xFF000000u; // byte 7 = count and filter
+    return (((a - one) & ~a) & top) | ((((b - one) & ~b) & top) >> 1);
+}
+KID_HD uint32_t kid_digest_entry(uint32_t bit) { return (bit >> 3) + ((bit & 1u) ? 0u : 4u); } // bit index -> entry 0..6
+
 // ---------------------------------------------------------------- synthetic data
 KID_HD uint64_t kid_splitmix64(uint64_t x)
 {

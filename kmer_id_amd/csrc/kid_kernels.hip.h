@@ -37,6 +37,10 @@
 // fingerprint false positive, a full line) are queued with their key.  Only while hits are sparse:
 #define KID_EARLY_MAX 4u // ... tiles with at most this many flagged lookups
 #define KID_EARLY_QN 32u // ... while fewer than this many lookups are queued (profiles/r02/clumped_ec.txt)
+// Not in the DIGEST instantiations: there the candidate cell is a line of its own that comes from HBM, not an L2 hit
+// behind the header, and waiting for it in the hot loop costs more than the resolver's second look at the digest --
+// every flagged lookup deferred: 1138-1160 M pairs/s, with the early path 1091, the header kernels 1089
+// (profiles/digest/ab_early_vs_deferred.txt).
 #define KID_GEN_ML_LDS_WORDS (104 + 3 * KID_CQ_CAP + KID_CQ_CAP / 4 + 64) // general loops on the minimizer-localised table: strip, counters, queue, results
 #define KID_CLASSIFY_OCC 8 // waves per SIMD the register allocator must leave room for
 // ... except the duo loop with ancestor rows: at 64 VGPRs it spills, and a spill or copy of a register that an
@@ -87,6 +91,7 @@ struct KidDevDb {
     const int32_t *parent;
     const int32_t *depth;
     int32_t ntar;
+    const uint2 *digest; // minloc, GPU-built: the digest plane, 8 bytes per line (kid_common.h); null: the table has none
 };
 
 struct KidBatch { // what the caller handed over
@@ -174,6 +179,7 @@ struct KidRareArgs {
     uint32_t *seen_log_tail; // their fill counters, 64 bytes apart
     uint32_t seen_log_cap;
     uint32_t pad2;
+    const uint4 *table;      // the DIGEST instantiations keep the plane's pointer in scalar registers, not the table's
 };
 #define KID_LOG_SHARDS 64u      // regions (blockIdx & 63), each with its own fill counter: a resolver chunk costs one fetch-and-add on
                                 // its region's counter, and with 16 hits per read (reads from genomes the database holds) there are
@@ -468,11 +474,11 @@ __global__ void kid_rebase_kernel(KidRareArgs *rare, const KidReadDesc *desc, ui
 //      newkmer_10nx.cpp:588-595);
 //   4. hit cells are marked in the sample's seen-bitmap (ucount, :596-603).
 // gcount is accumulated in an LDS histogram per workgroup and flushed once.
-template <int U>
+template <int U, bool DIGEST = false>
 struct KidGroup {      // a group of U*64 windows between its two halves
     uint64_t key[U];
     uint32_t hlo[U];   // reference geometry: first cell of the probe sequence; minloc: the table line
-    uint4 hd[U];       // minloc: header of that line (in flight)
+    typename std::conditional<DIGEST, uint2, uint4>::type hd[U]; // minloc: header of that line (in flight); DIGEST: its 8-byte digest
     uint32_t fpp;      // minloc: the 16-bit key fingerprints of the U lookups, packed
     bool act[U];
 };
@@ -483,13 +489,22 @@ struct KidGroup {      // a group of U*64 windows between its two halves
 // read as the pair (<= 2*U*64 k-mers), PAIRK = 0 the general loops.  The host launches the one the
 // batch is for when it knows the longest read, else all three: the others return at once.  Separate
 // kernels, because each loop wants all 64 vector registers of an 8-waves-per-SIMD kernel for itself.
-template <int U, bool ROWS, bool HIST, bool MINLOC, int KFIX, int PAIRK>
+// DIGEST (pair and duo loops): a lookup reads the 8-byte digest of its line from the plane beside the table instead of
+// the line's header (kid_common.h has the layout and why the results are the same).  The table pointer then comes from
+// `rare` where a candidate cell or a chained header is fetched, and the plane's takes its scalar registers in the loop.
+template <int U, bool ROWS, bool HIST, bool MINLOC, int KFIX, int PAIRK, bool DIGEST = false>
 __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_ROWS : KID_CLASSIFY_OCC) void kid_classify_kernel(const KidDevDb db, const KidInput b, const KidSampleDev s,
                                                             const uint32_t hist_words,
                                                             const KidReadDesc *__restrict__ const descs,
                                                             const KidRareArgs *__restrict__ const rare)
 {
     static_assert(!PAIRK || (MINLOC && U == 2), "the pair loop exists for the minimizer-localised table, two windows per lane");
+    static_assert(!DIGEST || PAIRK, "the digest plane is read by the pair and duo loops alone");
+    typedef KidGroup<U, DIGEST> Group;
+    auto cells = [&]() -> const uint4 * { // the table, where a rare path needs it
+        if constexpr (DIGEST) return rare->table;
+        else return db.table;
+    };
     if (MINLOC) { // wave-uniform, before anything else
         const uint32_t longest = (uint32_t)rare->batch_max;
         const int mode = longest <= (uint32_t)(U * 64) ? 1 : longest <= (uint32_t)(2 * U * 64) ? 2 : 0;
@@ -551,7 +566,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
 
     // ---- 2, 3a. windows [t0, t0 + U*64) of the staged segment: keys, table line, header loads issued
     auto group_front = [&](const uint32_t *W, const uint32_t sh, const uint32_t nb, const uint32_t segk, const uint32_t t0,
-                           const bool seg_clean, KidGroup<U> &g, uint32_t &n_bad, const bool issue_loads = true,
+                           const bool seg_clean, Group &g, uint32_t &n_bad, const bool issue_loads = true,
                            const uint32_t wcodes = 0, const uint32_t winv = 0) {
         // W == nullptr (pair kernels): no LDS strip; the lanes hold the read's packed words and masks in (wcodes, winv)
         // -- word c of the read in the LW = 4 (pair kernel) or 2 (duo kernel) lanes that loaded its 16 bases, see
@@ -638,19 +653,24 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                 // one 16-byte header per lookup settles every absent key; lanes that share a
                 // minimizer read the same header (one sector for all of them)
                 g.hlo[u] = kid_minloc_line(mz, db.line_shift);
-                g.hd[u] = make_uint4(0, 0, 0, 0);
-                if (issue_loads && g.act[u]) g.hd[u] = kid_load_cell(db.table, g.hlo[u] * KID_LINE_CELLS);
+                if constexpr (DIGEST) g.hd[u] = make_uint2(0, 0); // (the pair and duo loops issue their loads themselves)
+                else {
+                    g.hd[u] = make_uint4(0, 0, 0, 0);
+                    if (issue_loads && g.act[u]) g.hd[u] = kid_load_cell(db.table, g.hlo[u] * KID_LINE_CELLS);
+                }
             }
         }
     };
 
     // ---- 3b, 4, 5. the rest of the probe sequences, seen-bitmap, ordered fold into final_t (vfrow:
     // the ancestor row of final_t, in lanes 0-3)
-    auto group_back = [&](KidGroup<U> &g, uint32_t &final_t, uint32_t &vfrow) {
+    auto group_back = [&](Group &g, uint32_t &final_t, uint32_t &vfrow) {
         uint32_t tgt[U], slot[U];
 #pragma unroll
         for (int u = 0; u < U; u++) { tgt[u] = 0; slot[u] = 0; }
-        if (MINLOC) {
+        if constexpr (DIGEST) {
+            // (the general loops' back half: never reached from the pair and duo loops)
+        } else if (MINLOC) {
             uint32_t mm[U], fp[U];
             bool more = false;
 #pragma unroll
@@ -859,7 +879,9 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
     };
     // i_now: number of the newest queued read (all are within 63 of it); open_tag: a read that may still get
     // entries (general loops, between the groups of a read) -- its run is folded but not committed
-    auto resolve_all = [&](const uint32_t i_now, const uint32_t open_tag) {
+    // (always inlined: left as a call -- the duo loop with rows and without a histogram sits at the inliner's threshold --
+    //  the groups it is handed live in scratch and the loop's scalars in vector registers)
+    auto resolve_all = [&](const uint32_t i_now, const uint32_t open_tag) __attribute__((always_inline)) {
         // (the pair kernel never leaves a read open between calls: its carry lives and dies in here)
         uint32_t ctag = PAIRK == 1 ? 0xFFFFFFFFu : cur_tag, final_t = PAIRK == 1 ? 0u : final_c, vfrow = PAIRK == 1 ? 0u : vfrow_c;
         auto commit_tag = [&](const uint32_t tag, const uint32_t f) {
@@ -881,37 +903,47 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             uint32_t tgt = 0, slot = 0, mu = 0;
             const uint32_t fp = kid_key_fp(((uint64_t)khi << 32) | klo);
             bool fu = false;
+            bool dg = DIGEST; // mu names its entries the digest's way (kid_digest_cand) until a chained line's header replaces it
             if (verified) { tgt = klo; slot = khi; }
             if (valid && !verified) {
-                const uint4 h = kid_load_cell(db.table, ln * KID_LINE_CELLS);
-                mu = kid_hdr_cand(h, fp);
-                fu = kid_hdr_continues(h.w, fp);
+                if constexpr (DIGEST) {
+                    const uint2 h = db.digest[ln];
+                    mu = kid_digest_cand(h.x, h.y, fp);
+                    fu = kid_digest_continues(h.y, fp);
+                } else {
+                    const uint4 h = kid_load_cell(db.table, ln * KID_LINE_CELLS);
+                    mu = kid_hdr_cand(h, fp);
+                    fu = kid_hdr_continues(h.w, fp);
+                }
             }
             { // (cells read: one add for the wave, not one per lane on the same LDS word)
                 const uint64_t cm = __ballot(mu != 0);
                 if (cm && lane == 0) atomicAdd(&WC[3], (uint32_t)__popcll(cm));
             }
             if (mu) { // the first candidate of every entry in one round trip: almost always the key itself
-                const uint32_t idx = ln * KID_LINE_CELLS + 1u + kid_cand_entry((uint32_t)__builtin_ctz(mu));
+                const uint32_t bit = (uint32_t)__builtin_ctz(mu);
+                const uint32_t idx = ln * KID_LINE_CELLS + 1u + (DIGEST ? kid_digest_entry(bit) : kid_cand_entry(bit));
                 mu &= mu - 1;
-                const uint4 c = kid_load_cell(db.table, idx);
+                const uint4 c = kid_load_cell(cells(), idx);
                 if (c.z != 0 && c.x == klo && c.y == khi) { tgt = c.z; slot = c.w - 1u; }
             }
             bool go = valid && !verified && tgt == 0 && (mu != 0 || fu);
             while (go) { // a second candidate (1e-4 of the lookups) or a chained line (1e-5)
                 if (mu) {
-                    const uint32_t j = kid_cand_entry((uint32_t)__builtin_ctz(mu));
+                    const uint32_t bit = (uint32_t)__builtin_ctz(mu);
+                    const uint32_t j = dg ? kid_digest_entry(bit) : kid_cand_entry(bit);
                     mu &= mu - 1;
                     const uint32_t ix = ln * KID_LINE_CELLS + 1u + j;
-                    const uint4 cc = kid_load_cell(db.table, ix);
+                    const uint4 cc = kid_load_cell(cells(), ix);
                     atomicAdd(&WC[3], 1u);
                     if (cc.z != 0 && cc.x == klo && cc.y == khi) { tgt = cc.z; slot = cc.w - 1u; go = false; }
-                } else if (fu) {
+                } else if (fu) { // (a chain is followed along the table's headers, with or without a digest: a 1e-5 event)
                     ln = (ln + 1u) & rare->line_mask;
-                    const uint4 h = kid_load_cell(db.table, ln * KID_LINE_CELLS);
+                    const uint4 h = kid_load_cell(cells(), ln * KID_LINE_CELLS);
                     atomicAdd(&WC[3], 1u);
                     mu = kid_hdr_cand(h, fp);
                     fu = kid_hdr_continues(h.w, fp);
+                    dg = false;
                 } else go = false;
             }
             uint4 row = make_uint4(0, 0, 0, 0);
@@ -1070,7 +1102,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
         __builtin_amdgcn_s_waitcnt(0x0F70); // vmcnt(0), expcnt and lgkmcnt untouched
     };
     // header test of one group of a read; its unsettled lookups go to the queue.  false: there were none
-    auto back_deferred = [&](const KidGroup<U> &g, const uint32_t i) -> bool {
+    auto back_deferred = [&](const Group &g, const uint32_t i) -> bool {
         uint32_t fp[U];
         bool mm[U], more = false;
 #pragma unroll
@@ -1078,7 +1110,8 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             fp[u] = (g.fpp >> (16 * u)) & 0xFFFFu;
             // (a full line: word 3 >= 8 << 16 -- filter bits are only ever set on full lines.  Whether THIS key was
             //  pushed past it is looked at by the resolver: testing the filter bit here costs the hot loop a register)
-            mm[u] = g.act[u] && (kid_hdr_any(g.hd[u], fp[u]) || (g.hd[u].w >> 16) >= KID_HDR_FULL);
+            if constexpr (DIGEST) mm[u] = g.act[u] && (kid_digest_cand(g.hd[u].x, g.hd[u].y, fp[u]) != 0 || kid_digest_count(g.hd[u].y) >= KID_HDR_FULL);
+            else mm[u] = g.act[u] && (kid_hdr_any(g.hd[u], fp[u]) || (g.hd[u].w >> 16) >= KID_HDR_FULL);
             more |= mm[u];
         }
         if (__ballot(more) == 0) return false; // (wave-uniform) ~99 % of the lookups are settled by their header
@@ -1089,8 +1122,9 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             // (only while hits are sparse: with many flagged lookups per tile the resolver runs every few reads, finds the
             //  lines still in the L2, and the wait for the candidate here would cost more than its second fetch --
             //  builder-shaped database, 15.9 hits per read: 2.15 vs 1.92 ms per 1 M pairs, profiles/r02/clumped_ec.txt)
-            const bool early = (uint32_t)__popcll(qm) <= KID_EARLY_MAX && qn < KID_EARLY_QN;
-            const uint32_t cm = (early && mm[u]) ? kid_hdr_cand(g.hd[u], fp[u]) : 0u;
+            const bool early = !DIGEST && (uint32_t)__popcll(qm) <= KID_EARLY_MAX && qn < KID_EARLY_QN;
+            uint32_t cm = 0;
+            if constexpr (!DIGEST) cm = (early && mm[u]) ? kid_hdr_cand(g.hd[u], fp[u]) : 0u;
             { // (cells read: one add for the wave)
                 const uint64_t cmb = __ballot(cm != 0);
                 if (cmb && lane == 0) atomicAdd(&WC[3], (uint32_t)__popcll(cmb));
@@ -1135,7 +1169,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             kid_pack16(make_uint4(raw.x, raw.y, raw.z, raw.w), db.u_is_t, codes, inv);
             const bool seg_clean = stage(WA, codes, inv);
             for (uint32_t t0 = 0; t0 < segk; t0 += U * 64u) {
-                KidGroup<U> g;
+                Group g;
                 group_front(WA, sh, nb, segk, t0, seg_clean, g, n_bad);
                 if (!prefetched) { prefetch(); prefetched = true; }
                 if constexpr (MINLOC) {
@@ -1190,7 +1224,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             kid_pack16(make_uint4(st_raw.x, st_raw.y, st_raw.z, st_raw.w), db.u_is_t, st_codes, st_inv);
             const bool seg_clean = stage(WA, st_codes, st_inv);
             for (uint32_t t0 = 0; t0 < segk; t0 += U * 64u) {
-                KidGroup<U> g;
+                Group g;
                 group_front(WA, sh, nb, segk, t0, seg_clean, g, n_bad);
                 if (!prefetched) { prefetch(); prefetched = true; }
                 if constexpr (MINLOC) {
@@ -1321,11 +1355,21 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             wi = iv;
             return false;
         };
-        auto issue_header = [&](const KidGroup<U> &g, const int u) -> kid_u4 {
-            const uint4 *const p = db.table + (g.act[u] ? g.hlo[u] * KID_LINE_CELLS : 0u);
-            kid_u4 v;
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(v) : "v"(p) : "memory");
+        typedef typename std::conditional<DIGEST, kid_u2, kid_u4>::type Hdr; // what a lookup's first load brings
+        auto issue_header = [&](const Group &g, const int u) -> Hdr {
+            Hdr v;
+            if constexpr (DIGEST) {
+                const uint2 *const p = db.digest + (g.act[u] ? g.hlo[u] : 0u);
+                asm volatile("global_load_dwordx2 %0, %1, off" : "=&v"(v) : "v"(p) : "memory");
+            } else {
+                const uint4 *const p = db.table + (g.act[u] ? g.hlo[u] * KID_LINE_CELLS : 0u);
+                asm volatile("global_load_dwordx4 %0, %1, off" : "=&v"(v) : "v"(p) : "memory");
+            }
             return v;
+        };
+        auto landed = [](const Hdr &v) { // the loaded registers as the group keeps them
+            if constexpr (DIGEST) return make_uint2(v.x, v.y);
+            else return make_uint4(v.x, v.y, v.z, v.w);
         };
         Raw xA{}, xB{};
         if constexpr (PAIRK == 2) {
@@ -1342,7 +1386,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                 const uint32_t nk = (hnC >> 16) & 0x7FFFu;
                 const uint32_t sh = (uint32_t)__builtin_amdgcn_readlane((int)dv_lo, (int)ia) & 15u;
                 const uint32_t nb = nk + (uint32_t)k - 1;
-                KidGroup<U> gA, gB;
+                Group gA, gB;
                 uint32_t bad = 0;
                 if (ia + 2u > 63u) { // (this read's descriptor is in scalars by now)
                     blk = i + 1u;
@@ -1352,19 +1396,19 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                 uint32_t cC, iC;
                 const bool cl = pack_lanes(xC, sh, nk, cC, iC);
                 group_front(nullptr, sh, nb, nk, 0u, cl, gA, bad, false, cC, iC);
-                kid_u4 hA0 = issue_header(gA, 0), hA1 = issue_header(gA, 1);
+                Hdr hA0 = issue_header(gA, 0), hA1 = issue_header(gA, 1);
                 group_front(nullptr, sh, nb, nk, (uint32_t)(U * 64), cl, gB, bad, false, cC, iC);
-                kid_u4 hB0 = issue_header(gB, 0), hB1 = issue_header(gB, 1);
+                Hdr hB0 = issue_header(gB, 0), hB1 = issue_header(gB, 1);
                 issue_words(i + 2u - blk, xC); // this register is used up: the read after the next, two trips ahead
                 n_lookups += nk - bad;
                 asm volatile("s_waitcnt vmcnt(3)" : "+v"(hA0), "+v"(hA1) : : "memory"); // behind: the headers of B, the text just requested
-                gA.hd[0] = make_uint4(hA0.x, hA0.y, hA0.z, hA0.w);
-                gA.hd[1] = make_uint4(hA1.x, hA1.y, hA1.z, hA1.w);
+                gA.hd[0] = landed(hA0);
+                gA.hd[1] = landed(hA1);
                 bool had = back_deferred(gA, i);
                 if (qn >= KID_CQ_FLUSH) resolve_all(i, i & 63u); // the read stays open
                 asm volatile("s_waitcnt vmcnt(1)" : "+v"(hB0), "+v"(hB1) : : "memory"); // behind: the text just requested
-                gB.hd[0] = make_uint4(hB0.x, hB0.y, hB0.z, hB0.w);
-                gB.hd[1] = make_uint4(hB1.x, hB1.y, hB1.z, hB1.w);
+                gB.hd[0] = landed(hB0);
+                gB.hd[1] = landed(hB1);
                 had |= back_deferred(gB, i);
                 if (!had) commit_zero(i);
                 else if (qn >= KID_CQ_FLUSH) resolve_all(i, 0xFFFFFFFFu);
@@ -1423,7 +1467,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             const uint32_t shA = (uint32_t)__builtin_amdgcn_readlane((int)dv_lo, (int)ia) & 15u;
             const uint32_t shB = (uint32_t)__builtin_amdgcn_readlane((int)dv_lo, (int)(ia + 1u)) & 15u;
             const bool realB = ia + 1u < blen; // (a block with an odd number of reads -- the last of a share: B is a phantom of zero k-mers)
-            KidGroup<U> gA, gB;
+            Group gA, gB;
             uint32_t badA = 0, badB = 0;
             // the block's last pair: the next block's descriptors (this pair's are in scalars by now)
             if (ia + 2u >= blen) {
@@ -1438,26 +1482,26 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             uint32_t cA, iA;
             const bool clA = pack_lanes(xA, shA, nkA, cA, iA); // no base of the read resets a window
             group_front(nullptr, shA, nkA + (uint32_t)k - 1, nkA, 0u, clA, gA, badA, false, cA, iA);
-            kid_u4 hA0 = issue_header(gA, 0), hA1 = issue_header(gA, 1);
+            Hdr hA0 = issue_header(gA, 0), hA1 = issue_header(gA, 1);
             issue_words(i + 2u - blk, xA);
 
             asm volatile("s_waitcnt vmcnt(3)" : "+v"(xB) : : "memory"); // behind: headers of A, next text of A
             uint32_t cB, iB;
             const bool clB = pack_lanes(xB, shB, nkB, cB, iB);
             group_front(nullptr, shB, nkB + (uint32_t)k - 1, nkB, 0u, clB, gB, badB, false, cB, iB);
-            kid_u4 hB0 = issue_header(gB, 0), hB1 = issue_header(gB, 1);
+            Hdr hB0 = issue_header(gB, 0), hB1 = issue_header(gB, 1);
             issue_words(i + 3u - blk, xB);
 
             asm volatile("s_waitcnt vmcnt(4)" : "+v"(hA0), "+v"(hA1) : : "memory"); // behind: next text of A, headers and next text of B
-            gA.hd[0] = make_uint4(hA0.x, hA0.y, hA0.z, hA0.w);
-            gA.hd[1] = make_uint4(hA1.x, hA1.y, hA1.z, hA1.w);
+            gA.hd[0] = landed(hA0);
+            gA.hd[1] = landed(hA1);
             n_lookups += nkA - badA;
             if (!back_deferred(gA, i)) commit_zero(i);
             else if (qn >= KID_CQ_FLUSH) resolve_all(i, 0xFFFFFFFFu);
 
             asm volatile("s_waitcnt vmcnt(1)" : "+v"(hB0), "+v"(hB1) : : "memory"); // behind: the next text of B
-            gB.hd[0] = make_uint4(hB0.x, hB0.y, hB0.z, hB0.w);
-            gB.hd[1] = make_uint4(hB1.x, hB1.y, hB1.z, hB1.w);
+            gB.hd[0] = landed(hB0);
+            gB.hd[1] = landed(hB1);
             nreal += realB ? 2u : 1u;
             if (realB) {
                 n_lookups += nkB - badB;

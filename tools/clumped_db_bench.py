@@ -145,6 +145,7 @@ else:
     reads_r = lut[rng.integers(0, 4, (n_reads, L))].astype(np.uint8)
     if CACHE:
         np.savez(CACHE, keys=keys, targets=targets, parent=parent, reads_g=reads_g, reads_r=reads_r, rkeys=rkeys)
+n_launch = int(os.environ.get("DENSE_LAUNCHES", "6"))  # per case
 for name, kk in (("clumped (builder-shaped)", keys), ("random keys", rkeys)):
     db = KmerDB(kk, targets, parent, k=K, log2_slots=log2_slots)
     info = db.info
@@ -154,12 +155,17 @@ for name, kk in (("clumped (builder-shaped)", keys), ("random keys", rkeys)):
     for rname, rd in (("reads from the genomes", reads_g), ("random reads", reads_r)):
         d = torch.from_numpy(np.ascontiguousarray(rd).reshape(-1)).to(dev)
         s = db.sample(); s.set_timing(True)
-        for _ in range(6):
+        if os.environ.get("LINE_DIGEST"):  # KID_OPT_LINE_DIGEST for the samples (unset: the library's default)
+            from kmer_id_amd import KID_OPT_LINE_DIGEST
+            s.set_option(KID_OPT_LINE_DIGEST, int(os.environ["LINE_DIGEST"]))
+        for _ in range(n_launch):
             s.classify_fixed_device(d.data_ptr(), L, n_reads)
+            if os.environ.get("DENSE_SYNC"):  # the host waits for every launch: it then sees what a log pass found
+                torch.cuda.synchronize()
         ms, launches = s.kernel_time()
         st = s.stats()
         print("   %-24s %.3f ms per 1 M pairs, %6.1f G lookups/s, cells per lookup %.4f, hits per read %.2f" % (
-            rname, ms / launches, st["lookups"] / 6 / (ms / launches) / 1e6, st["probes"] / st["lookups"], st["hits"] / st["reads"]), flush=True)
+            rname, ms / launches, st["lookups"] / n_launch / (ms / launches) / 1e6, st["probes"] / st["lookups"], st["hits"] / st["reads"]), flush=True)
         s.close()
         del d
     db.close()

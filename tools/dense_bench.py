@@ -19,7 +19,16 @@ rng = np.random.default_rng(3)
 genomes, keys, targets = _genome_db(parent, 400, 20000, rng)
 db = KmerDB(keys, targets, parent, k=K, log2_slots=int(os.environ.get("LOG2", "26")))
 G = np.stack(genomes)
-for name, frac in (("no hits", 0.0), ("25 % of the reads from the genomes", 0.25), ("all reads from the genomes", 1.0)):
+# DENSE_FRACS: the shares of reads cut from the genomes (the database holds the genomes' forward k-mers: about 60 hits per
+# such read), e.g. 0.25,1.0 for 15 and 60 hits per read; LINE_DIGEST: KID_OPT_LINE_DIGEST for the samples (unset: the
+# library's default, and nothing is asked of a library without it); DENSE_LAUNCHES: launches per case (6); DENSE_SYNC=1:
+# the host waits for every launch, as a caller that reads its results does -- only then does it see what a pass over
+# the hit log found while the case still runs
+n_launch = int(os.environ.get("DENSE_LAUNCHES", "6"))
+cases = (("no hits", 0.0), ("25 % of the reads from the genomes", 0.25), ("all reads from the genomes", 1.0))
+if os.environ.get("DENSE_FRACS"):
+    cases = tuple(("%.1f %% of the reads from the genomes" % (100 * float(f)), float(f)) for f in os.environ["DENSE_FRACS"].split(","))
+for name, frac in cases:
     gi = rng.integers(0, G.shape[0], n); pos = rng.integers(0, G.shape[1] - read_len + 1, n)
     idx = pos[:, None] + np.arange(read_len)[None, :]
     bases = G[gi[:, None], idx]
@@ -27,9 +36,14 @@ for name, frac in (("no hits", 0.0), ("25 % of the reads from the genomes", 0.25
     bases[rnd] = rng.choice(np.frombuffer(b"ACGT", np.uint8), (int(rnd.sum()), read_len))
     d = torch.from_numpy(np.ascontiguousarray(bases).reshape(-1)).cuda()
     s = db.sample(); s.set_timing(True)
-    for _ in range(6):
+    if os.environ.get("LINE_DIGEST"):
+        from kmer_id_amd import KID_OPT_LINE_DIGEST
+        s.set_option(KID_OPT_LINE_DIGEST, int(os.environ["LINE_DIGEST"]))
+    for _ in range(n_launch):
         s.classify_fixed_device(d.data_ptr(), read_len, n)
+        if os.environ.get("DENSE_SYNC"):
+            torch.cuda.synchronize()
     ms, launches = s.kernel_time()
     st = s.stats()
-    print("%-40s %.3f ms per 2 M reads, %.1f G lookups/s, hits per read %.1f, cells per lookup %.3f" % (name, ms / launches, st["lookups"] / 6 / (ms / launches) / 1e6, st["hits"] / st["reads"], st["probes"] / st["lookups"]))
+    print("%-40s %.3f ms per 2 M reads, %.1f G lookups/s, hits per read %.1f, cells per lookup %.3f" % (name, ms / launches, st["lookups"] / n_launch / (ms / launches) / 1e6, st["hits"] / st["reads"], st["probes"] / st["lookups"]))
     s.close()
