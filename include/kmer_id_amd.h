@@ -271,8 +271,8 @@ int kid_mask_batch_device(kid_db *db, void *d_bases, const void *d_quals, const 
  *   KID_OPT_LOW_COMPLEXITY     the sample's option, above: kid_classify_fastq_async (behind the quality mask, in front of
  *                              the prepare kernel, on the same stream)
  *   KID_DB_OPT_LOW_COMPLEXITY  the database's (kid_db_set_option; T in 0..1000, KID_ERR_ARG beyond): every FASTQ form of
- *                              kid_db_read_hits / _support / _segments / _fragments / _votes.  One call at a time, NOT
- *                              copied by kid_db_replicate.
+ *                              kid_db_read_hits / _support / _segments / _fragments / _votes / _fragment_votes.  One
+ *                              call at a time, NOT copied by kid_db_replicate.
  * With both options off nothing is allocated or launched.                                                           */
 #define KID_DB_OPT_LOW_COMPLEXITY 2
 /* bases masked by KID_OPT_LOW_COMPLEXITY in the sample's FASTQ blocks since kid_sample_begin / kid_sample_reset
@@ -482,6 +482,49 @@ int kid_db_read_votes_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbyte
 int kid_db_votes_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
                                   uint32_t min_hits, uint32_t min_permille, void *d_out, void *stream);
 int kid_db_read_votes_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
+
+/* ---- calling fragments by root-path votes -------------------------------------------------
+ * kid_db_read_fragments* calls a pair as one unit but by the left fold, so the call can change when the mates are
+ * exchanged; kid_db_read_votes* is independent of hit order but judges every mate on its own.  These calls vote over the
+ * fragment.  The batch holds 2 F reads interleaved as for kid_db_read_fragments.  With a_1 .. a_p, b_1 .. b_q the hits
+ * of the two mates as kid_db_read_hits reports them and n_1, n_2 their n_kmers:
+ *   multiset     The fragment's hit multiset is {a_1 .. a_p} + {b_1 .. b_q}, with m = p + q.  n = n_1 + n_2 is computed
+ *                in uint32 exactly as kid_fragment.n_kmers is.  An absent or empty mate contributes nothing.
+ *   eight fields call, confident, n_kmers, n_hits, p_best, n_best, s_call and s_confident are exactly the kid_vote record
+ *                above of a read with those m hits and that n, under (min_hits, min_permille).  A target outside
+ *                (0, ntar) is read as the root.
+ *   per mate     call_1 is the vote call of a_1 .. a_p alone and call_2 that of b_1 .. b_q alone.  Each is 0 without a
+ *                hit.  They are what kid_db_read_votes returns as `call` for reads 2i and 2i + 1.
+ * The record is invariant under any permutation of the hits inside each mate; exchanging the two mates exchanges call_1
+ * and call_2 and changes nothing else; with q = 0 the first eight fields are mate 1's kid_vote record except that
+ * n_kmers = n_1 + n_2; when all m hits lie on one root path, call = kid_fragment.final.
+ * On the tree 5 -> 6 -> 8, 5 -> 35 -> 36, X on another lineage (mate 1 | mate 2 -> call, p_best, n_best, call_1, call_2):
+ *   [8] | [36] -> 5, 1, 2, 8, 36        [X, 8] | [6] -> 8, 2, 1, 1, 6 (mate 1 alone is a tie)
+ *   [8] | [X, 6] -> 8, 2, 1, 8, 1 (kid_fragment.final is 6 here)        [] | [6, 8] -> 8, 2, 1, 0, 8
+ * Fragments of more than a few hundred hits in total are settled by a second kernel queued behind the first.         */
+typedef struct kid_fragment_vote {
+    uint32_t call, confident, n_kmers /* n */, n_hits /* m */, p_best, n_best, s_call, s_confident, call_1, call_2;
+} kid_fragment_vote;
+/* The four forms of kid_db_read_fragments*, argument for argument: host buffers (n_reads = 2 F; 40 bytes per fragment
+ * come back), two FASTQ blocks (nbytes1 + nbytes2 below 4 GiB, at most 2^30 - 1 fragments; KID_DB_OPT_MIN_BASE_QUALITY
+ * and KID_DB_OPT_LOW_COMPLEXITY apply as in kid_db_read_fragments_fastq), the kernels alone on an interleaved CSR in
+ * HBM (d_out kid_fragment_vote[n_reads / 2]; asynchronous on `stream`, no tally), and the device time of the
+ * fragment-vote kernels ALONE since the last query.  The error statuses are those of kid_db_read_fragments*, in the same
+ * order: n_reads odd, min_permille > 1000 and null pointers are KID_ERR_ARG; n_reads = 0 returns KID_OK.
+ *   tally      exactly as in kid_db_read_fragments with `confident` as defined here: gcount[confident]++ once per
+ *              counted fragment, under 0 when confident = 0; for fragments with confident > 0 the seen bit of every hit
+ *              of both mates with target > 1, and depth[entry]++ per such hit under KID_OPT_ENTRY_DEPTH.  The FASTQ
+ *              form counts a fragment when at least one mate is kept by process_qual.  kid_sample_stats is NOT updated.
+ * Scratch of its own beside the vote calls': 4 bytes per fragment of the largest batch and one row of 4 * ntar bytes per
+ * compute unit, owned by the kid_db and released by kid_db_destroy.                                                  */
+int kid_db_read_fragment_votes(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                               uint64_t n_reads, uint32_t min_hits, uint32_t min_permille, kid_fragment_vote *out, kid_sample *tally);
+int kid_db_read_fragment_votes_fastq(kid_db *db, const uint8_t *text1, uint64_t nbytes1, const kid_fastq_rec *recs1, const uint8_t *text2,
+                                     uint64_t nbytes2, const kid_fastq_rec *recs2, uint64_t n_fragments, uint32_t min_hits,
+                                     uint32_t min_permille, kid_fragment_vote *out, kid_sample *tally);
+int kid_db_fragment_votes_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
+                                           uint32_t min_hits, uint32_t min_permille, void *d_out, void *stream);
+int kid_db_read_fragment_votes_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *fragments);
 
 /* ---- calling records in segments ------------------------------------------------------
  * kid_db_read_support* gives a record one answer.  A contig that is one species for its first 1.4 Mb and another after

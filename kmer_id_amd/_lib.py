@@ -93,6 +93,13 @@ PROTOTYPES = {
     "kid_db_votes_from_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                                 C.c_void_p, C.c_void_p]),
     "kid_db_read_votes_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
+    "kid_db_read_fragment_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                             C.c_void_p, C.c_void_p]),
+    "kid_db_read_fragment_votes_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                   C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "kid_db_fragment_votes_from_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                         C.c_void_p, C.c_void_p]),
+    "kid_db_read_fragment_votes_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
     "kid_db_read_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
     "kid_db_read_segments_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,

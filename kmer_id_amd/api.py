@@ -101,6 +101,9 @@ FRAGMENT_DTYPE = np.dtype([(name, np.uint32) for name in SUPPORT_DTYPE.names] + 
 VOTE_DTYPE = np.dtype([("call", np.uint32), ("confident", np.uint32), ("n_kmers", np.uint32), ("n_hits", np.uint32),
                        ("p_best", np.uint32), ("n_best", np.uint32), ("s_call", np.uint32), ("s_confident", np.uint32)])
 
+# kid_fragment_vote: one record per fragment (kid_db_read_fragment_votes*); the first eight fields are VOTE_DTYPE's
+FRAGMENT_VOTE_DTYPE = np.dtype([(name, np.uint32) for name in VOTE_DTYPE.names] + [("call_1", np.uint32), ("call_2", np.uint32)])
+
 # kid_segment: one record per segment (kid_db_read_segments*); the six fields behind n_pos are SUPPORT_DTYPE's
 SEGMENT_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in SUPPORT_DTYPE.names])
 
@@ -381,6 +384,46 @@ class KmerDB:
     def read_fragments_time(self):
         """-> (device ms, calls, fragments) of the fragment kernel alone since the last query"""
         return self._time(self._lib.kid_db_read_fragments_time)
+
+    def read_fragment_votes(self, bases, offsets, start=None, stop=None, min_hits=0, min_permille=0, tally=None):
+        """Call mate pairs by root-path votes (kid_db_read_fragment_votes): -> a structured array (FRAGMENT_VOTE_DTYPE:
+        call, confident, n_kmers, n_hits, p_best, n_best, s_call, s_confident, call_1, call_2), one record per fragment.
+        The batch holds 2 F reads in interleaved order, as for read_fragments.  The first eight fields are exactly the
+        read_votes record of a read with the hits of both mates (m = p + q) and n = n_1 + n_2 windows, under (min_hits,
+        min_permille): a pure function of the two mates' hit multisets.  call_1 is the vote call of mate 1's hits alone
+        and call_2 that of mate 2's; each is 0 without a hit.  Exchanging the mates exchanges call_1 and call_2 and
+        changes nothing else.
+        tally: a Sample of this database, counted exactly as read_fragments counts with this `confident`."""
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        out = np.zeros(n // 2, FRAGMENT_VOTE_DTYPE)
+        check(self._lib.kid_db_read_fragment_votes(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
+                                                   _ptr(out), tally._h if tally is not None else None))
+        return out
+
+    def read_fragment_votes_fastq(self, text1, recs1, text2, recs2, min_hits=0, min_permille=0, tally=None):
+        """The same for two blocks of FASTQ text with their line indexes, as read_fragments_fastq: record i of recs1 is
+        mate 1 and record i of recs2 is mate 2; a record with seq_len = 0 and qual_len = 0 is an absent mate.  A fragment
+        is counted when at least one of its mates is kept by process_qual."""
+        text1, recs1, n = _fastq_block(text1, recs1)
+        text2, recs2, n2 = _fastq_block(text2, recs2)
+        if n != n2:
+            raise ValueError("recs1 and recs2 must hold one record per fragment each")
+        out = np.zeros(n, FRAGMENT_VOTE_DTYPE)
+        check(self._lib.kid_db_read_fragment_votes_fastq(self._h, _ptr(text1), text1.size, _ptr(recs1), _ptr(text2), text2.size, _ptr(recs2),
+                                                         n, min_hits, min_permille, _ptr(out), tally._h if tally is not None else None))
+        return out
+
+    def fragment_votes_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
+        """The fragment-vote kernels alone on an interleaved CSR of n_reads = 2 F reads resident in HBM (raw pointers, as
+        kid_db_read_hits_device left it); asynchronous on `stream`: kid_db_fragment_votes_from_hits_device.
+        d_out: kid_fragment_vote[n_reads / 2] (FRAGMENT_VOTE_DTYPE)."""
+        check(self._lib.kid_db_fragment_votes_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
+                                                               C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
+                                                               C.c_void_p(stream or None)))
+
+    def read_fragment_votes_time(self):
+        """-> (device ms, calls, fragments) of the fragment-vote kernels alone since the last query"""
+        return self._time(self._lib.kid_db_read_fragment_votes_time)
 
     def _read_segments(self, call, n):
         """the sizing call, then the call that fills a buffer of exactly that size"""

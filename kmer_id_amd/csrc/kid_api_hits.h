@@ -1,6 +1,6 @@
 // kid_api_hits.h -- every read's k-mer hits: the scratch of a database's hit passes and kid_db_read_hits*.
 // What the other families over the hit pass -- kid_db_read_support* (kid_api_support.h), kid_db_read_fragments*
-// (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h), kid_db_read_votes* (kid_api_votes.h) -- share with kid_db_read_hits* is here once:
+// (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h), kid_db_read_votes* (kid_api_votes.h), kid_db_read_fragment_votes* (kid_api_fragment_votes.h) -- share with kid_db_read_hits* is here once:
 // KidSpanTimer, kid_hits_state (the scratch, free: the timers a family settles), kid_hits_scan (the three-kernel
 // exclusive scan), KidOpenBatch and kid_hits_open_* (a host-buffer batch checked, locked and staged, one function per
 // input form over kid_hits_stage_*), the hit pass into the library's own buffers (kid_hits_host_pass), the checks of
@@ -85,6 +85,10 @@ struct KidHitsState {
     // workgroup of that kernel, zero between calls
     KidDevBuf out_votes, vote_list, vote_n_list, vote_rows;
     KidSpanTimer votes; // the two vote kernels alone
+    // kid_db_read_fragment_votes* (kid_api_fragment_votes.h): the same set once more, of its own (a vote call and a
+    // fragment-vote call queued on two streams never share a list or a row); the list holds fragment indexes
+    KidDevBuf out_fragment_votes, fvote_list, fvote_n_list, fvote_rows;
+    KidSpanTimer fragment_votes; // the two fragment-vote kernels alone
     KidDevBuf lowc_plane; // KID_DB_OPT_LOW_COMPLEXITY: the flag plane of a staged block with a line that is split (kid_lowc.hip.h)
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
@@ -99,7 +103,7 @@ static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensu
 // tiles' scratch behind the pass) -- and of the kernels that read the pass's CSR alone those that `settle` names: a call
 // waits for the timers its family has always waited for, no more (a device-form caller that queues hits -> support on
 // a stream of its own does not block in the next kid_db_read_hits_device).
-enum : unsigned { KID_SETTLE_SUPPORT = 1u, KID_SETTLE_FRAGMENTS = 2u, KID_SETTLE_VOTES = 4u };
+enum : unsigned { KID_SETTLE_SUPPORT = 1u, KID_SETTLE_FRAGMENTS = 2u, KID_SETTLE_VOTES = 4u, KID_SETTLE_FRAGMENT_VOTES = 8u };
 static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
 {
     if (!db->hits) {
@@ -112,6 +116,7 @@ static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
         KID_HIP(h->fragments.create());
         KID_HIP(h->segments.create());
         KID_HIP(h->votes.create());
+        KID_HIP(h->fragment_votes.create());
         db->hits = std::move(h);
     }
     KidHitsState *h = *out = db->hits.get();
@@ -120,6 +125,7 @@ static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
     if (rc == KID_OK && (settle & KID_SETTLE_SUPPORT)) rc = h->support.settle();
     if (rc == KID_OK && (settle & KID_SETTLE_FRAGMENTS)) rc = h->fragments.settle();
     if (rc == KID_OK && (settle & KID_SETTLE_VOTES)) rc = h->votes.settle(); // (its list and rows are one set per kid_db)
+    if (rc == KID_OK && (settle & KID_SETTLE_FRAGMENT_VOTES)) rc = h->fragment_votes.settle(); // (so are this family's)
     return rc;
 }
 

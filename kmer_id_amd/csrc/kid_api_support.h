@@ -2,10 +2,10 @@
 // (kid_support.hip.h) -- and, once, the call path of every family that leaves one record per unit of the batch behind
 // the hit pass (kid_calls_*): the argument checks, the host run with the binding of a tally, the launch between the
 // family's two events, the *_from_hits_device form.  A family is a struct like KidSupportCalls below; the others are
-// KidFragmentCalls (kid_api_fragments.h), whose unit is two reads, and KidVoteCalls (kid_api_votes.h), which queues two
-// kernels through the hook of kid_calls_queue.  The host-buffer forms open their batch with
-// kid_hits_open_* and run the hit pass with kid_hits_host_pass (kid_api_hits.h).  Included behind the sample handle: a
-// tally counts into one.
+// KidFragmentCalls (kid_api_fragments.h), whose unit is two reads, KidVoteCalls (kid_api_votes.h), which queues two
+// kernels through the hook of kid_calls_queue, and KidFragmentVoteCalls (kid_api_fragment_votes.h), which does both.
+// The host-buffer forms open their batch with kid_hits_open_* and run the hit pass with kid_hits_host_pass
+// (kid_api_hits.h).  Included behind the sample handle: a tally counts into one.
 #pragma once
 #include "kid_api_hits.h"
 #include "kid_support.hip.h"

@@ -29,6 +29,8 @@
 //                             The order of the list is not deterministic; nothing read from it depends on that.
 // The row is read and written through agent-scope atomics alone (they bypass the CU's L1, which RMW atomics do not
 // refresh).  The TALLY variants count as kid_support_kernel does, in whichever kernel settles the read.
+// kid_fragment_votes.hip.h calls a mate pair with the same pieces: the climb behind a best set (kid_vote_climb_*) and the
+// stages of the second kernel (kid_vote_big_best / _climb / _clear) are functions of their own for it.
 #pragma once
 #include "kid_support.hip.h"
 
@@ -121,6 +123,34 @@ __device__ __forceinline__ void kid_vote_settle_rows(uint32_t call, const uint4 
     res.s_confident = s.s_confident;
 }
 
+// one lane: S along call's root path over the m hits and the climb -> call, s_call, confident, s_confident (m > 0)
+template <bool ROWS>
+__device__ __forceinline__ void kid_vote_climb_lane(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t call, const uint4 &cr,
+                                                    const KidSupportRule &rule, KidVote &res)
+{
+    if (ROWS) {
+        uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t i = 0; i < m; i++) {
+            const uint32_t t = kid_support_target(db, h[i].target);
+            const uint32_t di = kid_support_common_depth(t, db.rows[t], call, cr);
+#pragma unroll
+            for (int d = 0; d < 9; d++) ge[d] += di >= (uint32_t)d ? 1u : 0u;
+        }
+        kid_vote_settle_rows(call, cr, ge, rule, res);
+    } else {
+        res.call = call;
+        for (uint32_t c = call;;) { // candidates call, parent(call), .., 1: recount under each
+            const int32_t dc = db.depth[c];
+            uint32_t s = 0;
+            for (uint32_t i = 0; i < m; i++) s += kid_support_under(db, kid_support_target(db, h[i].target), c, dc) ? 1u : 0u;
+            if (c == call) res.s_call = s;
+            if (kid_support_passes(s, res.n_kmers, rule)) { res.confident = c; res.s_confident = s; break; }
+            if (c == 1u) break;
+            c = (uint32_t)db.parent[c];
+        }
+    }
+}
+
 // ---- one lane, one read of at most KID_VOTE_LANE_HITS hits
 template <bool ROWS>
 __device__ __forceinline__ void kid_vote_lane(const KidDevDb &db, const KidHit *h, uint32_t m, const KidSupportRule &rule, KidVote &res)
@@ -142,21 +172,37 @@ __device__ __forceinline__ void kid_vote_lane(const KidDevDb &db, const KidHit *
     }
     res.p_best = best;
     res.n_best = nb;
+    kid_vote_climb_lane<ROWS>(db, h, m, call, cr, rule, res);
+}
+
+// the whole wave: the same over m hits (every argument wave-uniform; so is the result)
+template <bool ROWS>
+__device__ __forceinline__ void kid_vote_climb_wave(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t call, const uint4 &cr,
+                                                    const KidSupportRule &rule, uint32_t lane, KidVote &res)
+{
     if (ROWS) {
         uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t i = 0; i < m; i++) {
-            const uint32_t t = kid_support_target(db, h[i].target);
-            const uint32_t di = kid_support_common_depth(t, db.rows[t], call, cr);
+        for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
+            const bool valid = lane < m - c0;
+            uint32_t di = 0;
+            if (valid) {
+                const uint32_t t = kid_support_target(db, h[c0 + lane].target);
+                di = kid_support_common_depth(t, db.rows[t], call, cr);
+            }
 #pragma unroll
-            for (int d = 0; d < 9; d++) ge[d] += di >= (uint32_t)d ? 1u : 0u;
+            for (int d = 0; d < 9; d++) ge[d] += (uint32_t)__popcll(__ballot(valid && di >= (uint32_t)d));
         }
         kid_vote_settle_rows(call, cr, ge, rule, res);
     } else {
         res.call = call;
-        for (uint32_t c = call;;) { // candidates call, parent(call), .., 1: recount under each
+        for (uint32_t c = call;;) {
             const int32_t dc = db.depth[c];
             uint32_t s = 0;
-            for (uint32_t i = 0; i < m; i++) s += kid_support_under(db, kid_support_target(db, h[i].target), c, dc) ? 1u : 0u;
+            for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
+                const bool valid = lane < m - c0;
+                const bool under = valid && kid_support_under(db, kid_support_target(db, h[c0 + lane].target), c, dc);
+                s += (uint32_t)__popcll(__ballot(under));
+            }
             if (c == call) res.s_call = s;
             if (kid_support_passes(s, res.n_kmers, rule)) { res.confident = c; res.s_confident = s; break; }
             if (c == 1u) break;
@@ -198,35 +244,7 @@ __device__ __forceinline__ void kid_vote_wave(const KidDevDb &db, const KidHit *
     kid_vote_wave_merge<ROWS>(db, best, nb, call, cr);
     res.p_best = best;
     res.n_best = nb;
-    if (ROWS) {
-        uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
-            const bool valid = lane < m - c0;
-            uint32_t di = 0;
-            if (valid) {
-                const uint32_t t = kid_support_target(db, h[c0 + lane].target);
-                di = kid_support_common_depth(t, db.rows[t], call, cr);
-            }
-#pragma unroll
-            for (int d = 0; d < 9; d++) ge[d] += (uint32_t)__popcll(__ballot(valid && di >= (uint32_t)d));
-        }
-        kid_vote_settle_rows(call, cr, ge, rule, res);
-    } else {
-        res.call = call;
-        for (uint32_t c = call;;) {
-            const int32_t dc = db.depth[c];
-            uint32_t s = 0;
-            for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
-                const bool valid = lane < m - c0;
-                const bool under = valid && kid_support_under(db, kid_support_target(db, h[c0 + lane].target), c, dc);
-                s += (uint32_t)__popcll(__ballot(under));
-            }
-            if (c == call) res.s_call = s;
-            if (kid_support_passes(s, res.n_kmers, rule)) { res.confident = c; res.s_confident = s; break; }
-            if (c == 1u) break;
-            c = (uint32_t)db.parent[c];
-        }
-    }
+    kid_vote_climb_wave<ROWS>(db, h, m, call, cr, rule, lane, res);
 }
 
 template <bool ROWS, bool TALLY, bool DEPTH>
@@ -319,14 +337,119 @@ __device__ __forceinline__ void kid_vote_block_share(uint32_t *sh, uint32_t v)
     if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = v;
 }
 
+// ---- the stages of kid_vote_big_kernel, each entered by all 256 threads of a workgroup with uniform arguments
+// (sh: uint32[36] of LDS, free on entry and on return; row: the workgroup's, zero on entry to stage 1)
+// 1 w into the row, 2 the maximum of P over the hits, 3 L claimed, counted and LCA-reduced -> (best, nb, call, cr)
+template <bool ROWS>
+__device__ __forceinline__ void kid_vote_big_best(const KidDevDb &db, uint32_t *row, const KidHit *h, uint32_t m, uint32_t *sh, uint32_t &best,
+                                                  uint32_t &nb, uint32_t &call, uint4 &cr)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint4 none = make_uint4(0, 0, 0, 0);
+    // 1: w
+    for (uint32_t i = threadIdx.x; i < m; i += 256u) atomicAdd(row + kid_support_target(db, h[i].target), 1u);
+    kid_vote_sync();
+    // 2: best
+    best = 0;
+    for (uint32_t i = threadIdx.x; i < m; i += 256u) {
+        const uint32_t p = kid_vote_path_sum<ROWS>(db, row, kid_support_target(db, h[i].target));
+        best = p > best ? p : best;
+    }
+    for (int s = 32; s >= 1; s >>= 1) {
+        const uint32_t o = (uint32_t)__shfl_xor((int)best, s);
+        best = o > best ? o : best;
+    }
+    kid_vote_block_share(sh, best);
+    __syncthreads();
+    best = sh[0];
+    for (int w = 1; w < 4; w++) best = sh[w] > best ? sh[w] : best;
+    __syncthreads();
+    // 3: L, each distinct member claimed by the thread that sets its marker
+    uint32_t pb = 0;
+    nb = call = 0;
+    cr = none;
+    for (uint32_t i = threadIdx.x; i < m; i += 256u) {
+        const uint32_t t = kid_support_target(db, h[i].target);
+        if (kid_vote_path_sum<ROWS>(db, row, t) == best && !(atomicOr(row + t, KID_VOTE_MARK) & KID_VOTE_MARK))
+            kid_vote_merge<ROWS>(db, pb, nb, call, cr, best, 1u, t, ROWS ? db.rows[t] : none);
+    }
+    kid_vote_wave_merge<ROWS>(db, pb, nb, call, cr);
+    if (lane == 0) {
+        uint32_t *s6 = sh + wave * 6u;
+        s6[0] = nb; s6[1] = call; s6[2] = cr.x; s6[3] = cr.y; s6[4] = cr.z; s6[5] = cr.w;
+    }
+    __syncthreads();
+    pb = nb = call = 0;
+    cr = none;
+    for (uint32_t w = 0; w < 4; w++) {
+        const uint32_t *s6 = sh + w * 6u;
+        kid_vote_merge<ROWS>(db, pb, nb, call, cr, best, s6[0], s6[1], make_uint4(s6[2], s6[3], s6[4], s6[5]));
+    }
+    __syncthreads();
+}
+
+// 4: S along call's root path, and the climb
+template <bool ROWS>
+__device__ __forceinline__ void kid_vote_big_climb(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t *sh, uint32_t call, const uint4 &cr,
+                                                   const KidSupportRule &rule, KidVote &res)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (ROWS) {
+        uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t c0 = wave * 64u; c0 < m; c0 += 256u) {
+            const bool valid = lane < m - c0;
+            uint32_t di = 0;
+            if (valid) {
+                const uint32_t t = kid_support_target(db, h[c0 + lane].target);
+                di = kid_support_common_depth(t, db.rows[t], call, cr);
+            }
+#pragma unroll
+            for (int d = 0; d < 9; d++) ge[d] += (uint32_t)__popcll(__ballot(valid && di >= (uint32_t)d));
+        }
+        if (lane == 0)
+#pragma unroll
+            for (int d = 0; d < 9; d++) sh[wave * 9u + (uint32_t)d] = ge[d];
+        __syncthreads();
+#pragma unroll
+        for (int d = 0; d < 9; d++) ge[d] = sh[d] + sh[9 + d] + sh[18 + d] + sh[27 + d];
+        __syncthreads();
+        kid_vote_settle_rows(call, cr, ge, rule, res);
+    } else {
+        res.call = call;
+        for (uint32_t c = call;;) {
+            const int32_t dc = db.depth[c];
+            uint32_t s = 0;
+            for (uint32_t c0 = wave * 64u; c0 < m; c0 += 256u) {
+                const bool valid = lane < m - c0;
+                const bool under = valid && kid_support_under(db, kid_support_target(db, h[c0 + lane].target), c, dc);
+                s += (uint32_t)__popcll(__ballot(under));
+            }
+            kid_vote_block_share(sh, s);
+            __syncthreads();
+            s = sh[0] + sh[1] + sh[2] + sh[3];
+            __syncthreads();
+            if (c == call) res.s_call = s;
+            if (kid_support_passes(s, res.n_kmers, rule)) { res.confident = c; res.s_confident = s; break; }
+            if (c == 1u) break;
+            c = (uint32_t)db.parent[c];
+        }
+    }
+}
+
+// 5: the row back to zero for the workgroup's next read (and the next call's)
+__device__ __forceinline__ void kid_vote_big_clear(const KidDevDb &db, uint32_t *row, const KidHit *h, uint32_t m)
+{
+    for (uint32_t i = threadIdx.x; i < m; i += 256u)
+        __hip_atomic_store(row + kid_support_target(db, h[i].target), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    kid_vote_sync();
+}
+
 template <bool ROWS, bool TALLY, bool DEPTH>
 __global__ __launch_bounds__(256) void kid_vote_big_kernel(const KidDevDb db, const uint64_t *hit_offsets, const KidHit *hits,
                                                             const uint32_t *n_kmers, uint64_t n_reads, const KidSupportRule rule,
                                                             KidVote *out /* nullable */, const KidSupportTally tally, const KidVoteBig big)
 {
     __shared__ uint32_t sh[4 * 9]; // per wave: a maximum; (nb, call, its row); the nine ge[d]; a count
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint4 none = make_uint4(0, 0, 0, 0);
     uint32_t *row = big.rows + (uint64_t)blockIdx.x * (uint64_t)db.ntar;
     const uint32_t n_list = *big.n_list;
     for (uint32_t e = blockIdx.x; e < n_list && e < n_reads; e += gridDim.x) {
@@ -334,97 +457,18 @@ __global__ __launch_bounds__(256) void kid_vote_big_kernel(const KidDevDb db, co
         const KidHit *h = hits + hit_offsets[r];
         const uint32_t m = (uint32_t)(hit_offsets[r + 1] - hit_offsets[r]);
         KidVote res = {0u, 0u, n_kmers[r], m, 0u, 0u, 0u, 0u};
-        // 1: w
-        for (uint32_t i = threadIdx.x; i < m; i += 256u) atomicAdd(row + kid_support_target(db, h[i].target), 1u);
-        kid_vote_sync();
-        // 2: best
-        uint32_t best = 0;
-        for (uint32_t i = threadIdx.x; i < m; i += 256u) {
-            const uint32_t p = kid_vote_path_sum<ROWS>(db, row, kid_support_target(db, h[i].target));
-            best = p > best ? p : best;
-        }
-        for (int s = 32; s >= 1; s >>= 1) {
-            const uint32_t o = (uint32_t)__shfl_xor((int)best, s);
-            best = o > best ? o : best;
-        }
-        kid_vote_block_share(sh, best);
-        __syncthreads();
-        best = sh[0];
-        for (int w = 1; w < 4; w++) best = sh[w] > best ? sh[w] : best;
-        __syncthreads();
-        // 3: L, each distinct member claimed by the thread that sets its marker
-        uint32_t nb = 0, call = 0, pb = 0;
-        uint4 cr = none;
-        for (uint32_t i = threadIdx.x; i < m; i += 256u) {
-            const uint32_t t = kid_support_target(db, h[i].target);
-            if (kid_vote_path_sum<ROWS>(db, row, t) == best && !(atomicOr(row + t, KID_VOTE_MARK) & KID_VOTE_MARK))
-                kid_vote_merge<ROWS>(db, pb, nb, call, cr, best, 1u, t, ROWS ? db.rows[t] : none);
-        }
-        kid_vote_wave_merge<ROWS>(db, pb, nb, call, cr);
-        if (lane == 0) {
-            uint32_t *s6 = sh + wave * 6u;
-            s6[0] = nb; s6[1] = call; s6[2] = cr.x; s6[3] = cr.y; s6[4] = cr.z; s6[5] = cr.w;
-        }
-        __syncthreads();
-        pb = nb = call = 0;
-        cr = none;
-        for (uint32_t w = 0; w < 4; w++) {
-            const uint32_t *s6 = sh + w * 6u;
-            kid_vote_merge<ROWS>(db, pb, nb, call, cr, best, s6[0], s6[1], make_uint4(s6[2], s6[3], s6[4], s6[5]));
-        }
-        __syncthreads();
+        uint32_t best, nb, call;
+        uint4 cr;
+        kid_vote_big_best<ROWS>(db, row, h, m, sh, best, nb, call, cr);
         res.p_best = best;
         res.n_best = nb;
-        // 4: S along call's root path, and the climb
-        if (ROWS) {
-            uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-            for (uint32_t c0 = wave * 64u; c0 < m; c0 += 256u) {
-                const bool valid = lane < m - c0;
-                uint32_t di = 0;
-                if (valid) {
-                    const uint32_t t = kid_support_target(db, h[c0 + lane].target);
-                    di = kid_support_common_depth(t, db.rows[t], call, cr);
-                }
-#pragma unroll
-                for (int d = 0; d < 9; d++) ge[d] += (uint32_t)__popcll(__ballot(valid && di >= (uint32_t)d));
-            }
-            if (lane == 0)
-#pragma unroll
-                for (int d = 0; d < 9; d++) sh[wave * 9u + (uint32_t)d] = ge[d];
-            __syncthreads();
-#pragma unroll
-            for (int d = 0; d < 9; d++) ge[d] = sh[d] + sh[9 + d] + sh[18 + d] + sh[27 + d];
-            __syncthreads();
-            kid_vote_settle_rows(call, cr, ge, rule, res);
-        } else {
-            res.call = call;
-            for (uint32_t c = call;;) {
-                const int32_t dc = db.depth[c];
-                uint32_t s = 0;
-                for (uint32_t c0 = wave * 64u; c0 < m; c0 += 256u) {
-                    const bool valid = lane < m - c0;
-                    const bool under = valid && kid_support_under(db, kid_support_target(db, h[c0 + lane].target), c, dc);
-                    s += (uint32_t)__popcll(__ballot(under));
-                }
-                kid_vote_block_share(sh, s);
-                __syncthreads();
-                s = sh[0] + sh[1] + sh[2] + sh[3];
-                __syncthreads();
-                if (c == call) res.s_call = s;
-                if (kid_support_passes(s, res.n_kmers, rule)) { res.confident = c; res.s_confident = s; break; }
-                if (c == 1u) break;
-                c = (uint32_t)db.parent[c];
-            }
-        }
+        kid_vote_big_climb<ROWS>(db, h, m, sh, call, cr, rule, res);
         if (threadIdx.x == 0 && out) out[r] = res;
         if (TALLY && (!tally.fastq_desc || tally.fastq_desc[r].n_kmers > 0)) {
             if (threadIdx.x == 0) atomicAdd(&tally.gcount[res.confident], 1ull);
             if (res.confident > 0)
                 for (uint32_t i = threadIdx.x; i < m; i += 256u) kid_support_tally_hit<DEPTH>(tally, h[i]);
         }
-        // 5: the row back to zero for the workgroup's next read (and the next call's)
-        for (uint32_t i = threadIdx.x; i < m; i += 256u)
-            __hip_atomic_store(row + kid_support_target(db, h[i].target), 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        kid_vote_sync();
+        kid_vote_big_clear(db, row, h, m);
     }
 }

@@ -64,7 +64,7 @@ void load_database(const std::string &tree_path, const std::string &probes_path,
 
 Engine::~Engine()
 {
-    for (const std::vector<kid_sample *> *list : {&samples, &confident, &fragments, &votes})
+    for (const std::vector<kid_sample *> *list : {&samples, &confident, &fragments, &votes, &fragment_votes})
         for (kid_sample *s : *list) kid_sample_destroy(s);
     if (owns_dbs)
         for (kid_db *d : dbs) kid_db_destroy(d);
@@ -108,6 +108,8 @@ void engine_configure(Engine &e, const SideOptions &side)
         for (kid_db *d : e.dbs) e.fragments.push_back(begin_sample_or_die(d));
     if (side.votes) // (tallied through the database's hit pass too)
         for (kid_db *d : e.dbs) e.votes.push_back(begin_sample_or_die(d));
+    if (side.fragment_votes) // (and so are the fragments called by votes)
+        for (kid_db *d : e.dbs) e.fragment_votes.push_back(begin_sample_or_die(d));
     // the two masks: the sample's option and the database's, each only where it is on
     const struct { int value, sample_opt, db_opt; } masks[] = {{side.min_base_quality, KID_OPT_MIN_BASE_QUALITY, KID_DB_OPT_MIN_BASE_QUALITY},
                                                                {side.low_complexity, KID_OPT_LOW_COMPLEXITY, KID_DB_OPT_LOW_COMPLEXITY}};
@@ -142,7 +144,7 @@ std::vector<int> parse_devices(int device, const std::string &list)
 
 void engine_reset(Engine &e)
 {
-    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident, &e.fragments, &e.votes})
+    for (const std::vector<kid_sample *> *list : {&e.samples, &e.confident, &e.fragments, &e.votes, &e.fragment_votes})
         for (kid_sample *s : *list) {
             int rc = kid_sample_reset(s);
             if (rc != KID_OK) die_kid(rc);
@@ -410,7 +412,8 @@ static const struct {
                     {"--depth", 0, nullptr, &SideOptions::depth},
                     {"--seen", 0, nullptr, &SideOptions::seen},
                     {"--fragments", 0, nullptr, &SideOptions::fragments},
-                    {"--votes", 0, nullptr, &SideOptions::votes}};
+                    {"--votes", 0, nullptr, &SideOptions::votes},
+                    {"--fragment-votes", 0, nullptr, &SideOptions::fragment_votes}};
 
 int side_option_values(const char *word)
 {
@@ -444,7 +447,7 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes; };
+struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes, fragment_votes; };
 static SidePaths side_paths(const std::string &r)
 {
     std::string seen = r; // the final "result.txt" becomes "seen.bin"
@@ -452,7 +455,7 @@ static SidePaths side_paths(const std::string &r)
     if (at != std::string::npos) seen.replace(at, 10, "seen.bin");
     else seen += ".seen.bin";
     return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen,
-            sibling_path_for(r, "fragments"), sibling_path_for(r, "votes")};
+            sibling_path_for(r, "fragments"), sibling_path_for(r, "votes"), sibling_path_for(r, "fragment_votes")};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -465,6 +468,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.seen) remove(p.seen.c_str());
     if (all || side.fragments) remove(p.fragments.c_str());
     if (all || side.votes) remove(p.votes.c_str());
+    if (all || side.fragment_votes) remove(p.fragment_votes.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -603,6 +607,7 @@ void SampleOutputs::finish(Engine &e)
     if (side_.support.on) write_counters(e.confident, e.ntar, p.confident);
     if (side_.fragments) write_counters(e.fragments, e.ntar, p.fragments);
     if (side_.votes) write_counters(e.votes, e.ntar, p.votes);
+    if (side_.fragment_votes) write_counters(e.fragment_votes, e.ntar, p.fragment_votes);
     if (side_.depth) write_depth(e.confident, e.ntar, p.depth);
     if (side_.seen) write_seen(side_.support.on ? e.confident[0] : e.samples[0], e, p.seen);
     if (side_.hits) write_lines(p.hits, hits_);
@@ -724,12 +729,14 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
     std::deque<InFlight> q;
     std::vector<long long> handed(count, 0);
     const size_t max_in_flight = 2 * e.samples.size();
-    // --fragments: the blocks of each mate file that are through, in file order, until their records have been paired
+    // --fragments and --fragment-votes: the blocks of each mate file that are through, in file order, until their records have been paired
     struct HeldBlock {
         std::unique_ptr<ReadBatch> batch;
         size_t paired = 0; // records of the block that have been handed on
     };
-    const bool fragments = out.fragments_on() && count == 2 && !e.fragments.empty();
+    const bool by_fold = out.fragments_on() && count == 2 && !e.fragments.empty();
+    const bool by_votes = out.fragment_votes_on() && count == 2 && !e.fragment_votes.empty();
+    const bool fragments = by_fold || by_votes; // (either pairs the records; both are handed the same run of the same blocks)
     std::deque<HeldBlock> held[2];
     unsigned long long mate_records[2] = {0, 0};
     std::vector<kid_fastq_rec> absent;
@@ -756,9 +763,15 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
                 recs[m] = fq ? fq->recs.data() + held[m].front().paired : absent.data();
             }
             const size_t dev = e.next_fragments;
-            e.next_fragments = (e.next_fragments + 1) % e.fragments.size();
-            int rc = kid_db_read_fragments_fastq(e.dbs[dev], text[0], nbytes[0], recs[0], text[1], nbytes[1], recs[1], n, e.side.support.min_hits,
+            e.next_fragments = (e.next_fragments + 1) % e.dbs.size();
+            int rc = KID_OK;
+            if (by_fold)
+                rc = kid_db_read_fragments_fastq(e.dbs[dev], text[0], nbytes[0], recs[0], text[1], nbytes[1], recs[1], n, e.side.support.min_hits,
                                                  e.side.support.min_permille, (kid_fragment *)nullptr, e.fragments[dev]);
+            if (rc == KID_OK && by_votes)
+                rc = kid_db_read_fragment_votes_fastq(e.dbs[dev], text[0], nbytes[0], recs[0], text[1], nbytes[1], recs[1], n,
+                                                      e.side.support.min_hits, e.side.support.min_permille, (kid_fragment_vote *)nullptr,
+                                                      e.fragment_votes[dev]);
             if (rc != KID_OK) die_kid(rc);
             for (int m = 0; m < 2; m++)
                 if (have[m]) held[m].front().paired += n;
@@ -850,8 +863,8 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         pair_up(true);
         if (mate_records[0] != mate_records[1]) {
             const unsigned long long a = mate_records[0], b = mate_records[1];
-            fprintf(stderr, "kmer_id_amd: --fragments: %s: the mate files hold %llu and %llu records: %llu fragments have an absent mate\n",
-                    out.result_path().c_str(), a, b, a > b ? a - b : b - a);
+            fprintf(stderr, "kmer_id_amd: %s: %s: the mate files hold %llu and %llu records: %llu fragments have an absent mate\n",
+                    by_fold ? "--fragments" : "--fragment-votes", out.result_path().c_str(), a, b, a > b ? a - b : b - a);
         }
     }
     long long n = 0;
@@ -899,6 +912,8 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads)
     }
     o.side = side_options(argc, argv, argv[0]);
     if (o.side.fragments) usage_error(argv[0], "--fragments", "is an option of nk10 alone: the inputs of this program are read one file after the other");
+    if (o.side.fragment_votes)
+        usage_error(argv[0], "--fragment-votes", "is an option of nk10 alone: the inputs of this program are read one file after the other");
     return o;
 }
 

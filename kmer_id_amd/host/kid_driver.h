@@ -55,6 +55,9 @@ struct SideOptions {
     // --votes (no value): the reads called by root-path votes (kid_db_read_votes*), whatever the order of their hits, and
     // counted into a votes file
     bool votes = false;
+    // --fragment-votes (no value; nk10 alone, like --fragments): the mate pairs called by root-path votes over both mates'
+    // hits (kid_db_read_fragment_votes_fastq), counted into a fragment_votes file
+    bool fragment_votes = false;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
@@ -81,6 +84,7 @@ struct Engine {
     std::vector<kid_sample *> fragments; // under --fragments: one sample per device that the fragments are tallied into
     size_t next_fragments = 0;           // ... dealt round-robin over the devices
     std::vector<kid_sample *> votes;     // under --votes: one sample per device that the vote pass of every batch tallies into
+    std::vector<kid_sample *> fragment_votes; // under --fragment-votes: one per device for the fragments called by votes (dealt with `fragments`)
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -113,7 +117,7 @@ bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &pare
                  unsigned flags, const std::vector<int> &devices);
 // The side options for an engine that is open: with a rule or --depth one more sample per device (reset, closed and
 // destroyed with the others; --depth switches its depth counters on), under --fragments one more for the fragments, under
-// --votes one more for the vote pass, then --min-base-quality and --low-complexity on every sample, the tallied ones included, and on every replica of the database.
+// --votes one more for the vote pass, under --fragment-votes one more for the fragments called by votes, then --min-base-quality and --low-complexity on every sample, the tallied ones included, and on every replica of the database.
 // A worker of engine_worker() inherits them for its samples.
 void engine_configure(Engine &e, const SideOptions &side);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
@@ -179,6 +183,14 @@ private:
 // --min-hits / --confidence when given, else (0, 0): confident = call; --min-base-quality applies as it does to the
 // confident file.  It does not depend on how the reads were batched, threaded or dealt over devices, and the depth and
 // seen files keep following the samples they follow without it.
+//   --fragment-votes, "fragment_votes" (nk10): a result file in the result file's format, <i>,<fragments>,<unique_kmers>,
+// from the counters of one more sample per device that every fragment is tallied into by
+// kid_db_read_fragment_votes_fastq: the fragments of --fragments (the same pairing of records, the same blocks, absent
+// mates and stderr line -- printed once when both options are given), each called by root-path votes over the hits of both
+// mates, which does not depend on the order of the mates or of their hits.  The rule is that of --min-hits / --confidence
+// when given, else (0, 0); --min-base-quality and --low-complexity apply as they do to the fragments file.  It needs
+// neither --fragments nor --votes, changes nothing they write, and does not depend on how the files were cut into
+// blocks, batched, threaded or dealt over devices.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
 // The batches of files read at the same time interleave: the hit and segment lines are held in memory per file and
 // written in file order by finish() -- what is held is the files themselves (reads without a hit leave nothing),
@@ -190,11 +202,12 @@ public:
     bool hits_on() const { return side_.hits; }
     bool segments_on() const { return side_.segments.on; }
     bool fragments_on() const { return side_.fragments; }
+    bool fragment_votes_on() const { return side_.fragment_votes; }
     const std::string &result_path() const { return result_path_; }
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
-    // confident file, then the fragments file, then the votes file, then the depth file, then the seen file, then the hits file, then the
+    // confident file, then the fragments file, then the votes file, then the fragment_votes file, then the depth file, then the seen file, then the hits file, then the
     // segments file
     void finish(Engine &e);
 private:
@@ -234,10 +247,11 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
 // pass of a batch runs at the same place and tallies into that device's confident sample; with e.side.votes on the vote
 // pass (kid_db_read_votes*) does the same into that device's votes sample.  When its segments file is on, `out` receives
 // the segment lines of every batch under e.side: the segments pass (kid_db_read_segments*) runs at the same place too.
-// With out.fragments_on() and count == 2 the two files are the mates of a sample: the FASTQ blocks of each that are
+// With out.fragments_on() or out.fragment_votes_on() and count == 2 the two files are the mates of a sample: the FASTQ blocks of each that are
 // through wait in a queue until the partner's records have arrived; the longest common run of records is handed to
-// kid_db_read_fragments_fastq with a device's fragment sample as its tally, and a block goes as soon as its last record
-// has: none is held longer than the other file lags.
+// kid_db_read_fragments_fastq with a device's fragment sample as its tally (and, or, to kid_db_read_fragment_votes_fastq
+// with that device's fragment_votes sample: the same run of the same blocks), and a block goes as soon as its last
+// record has: none is held longer than the other file lags.
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, SampleOutputs &out, size_t saver_file = 0,
                     const std::function<void(size_t, long long)> &done = nullptr);
 

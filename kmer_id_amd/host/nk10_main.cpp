@@ -31,6 +31,10 @@
 //                    (kid_driver.h).  Not with --fasta
 //   --votes              also write <prefix>_votes.txt: the result file of the reads called by root-path votes, which do not
 //                    depend on the order of a read's hits, under the rule of --min-hits / --confidence when given (kid_driver.h)
+//   --fragment-votes     also write <prefix>_fragment_votes.txt: the result file of the mate pairs called by root-path votes over
+//                    the hits of both mates -- the fragments of --fragments, a call that does not depend on the order of the
+//                    mates or of their hits -- under the rule of --min-hits / --confidence when given (kid_driver.h).  Not with
+//                    --fasta; needs neither --fragments nor --votes
 //   --block-bytes N      the size of the FASTQ text blocks the files are cut into (8 MiB; at least 32 KiB are taken): no output
 //                    depends on it
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
@@ -126,6 +130,10 @@ int main(int argc, char **argv)
     const SideOptions side = side_options(argc, argv, "nk10"); // (checked, then ignored, with --dry-run; --min-base-quality with --fasta too)
     if (side.fragments && fasta_mode) {
         std::cerr << "nk10: --fragments needs the two FASTQ files of a sample: not with --fasta\n";
+        return 2;
+    }
+    if (side.fragment_votes && fasta_mode) {
+        std::cerr << "nk10: --fragment-votes needs the two FASTQ files of a sample: not with --fasta\n";
         return 2;
     }
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
