@@ -271,8 +271,8 @@ int kid_mask_batch_device(kid_db *db, void *d_bases, const void *d_quals, const 
  *   KID_OPT_LOW_COMPLEXITY     the sample's option, above: kid_classify_fastq_async (behind the quality mask, in front of
  *                              the prepare kernel, on the same stream)
  *   KID_DB_OPT_LOW_COMPLEXITY  the database's (kid_db_set_option; T in 0..1000, KID_ERR_ARG beyond): every FASTQ form of
- *                              kid_db_read_hits / _support / _segments / _fragments / _votes / _fragment_votes.  One
- *                              call at a time, NOT copied by kid_db_replicate.
+ *                              kid_db_read_hits / _support / _segments / _fragments / _votes / _fragment_votes /
+ *                              _segment_votes.  One call at a time, NOT copied by kid_db_replicate.
  * With both options off nothing is allocated or launched.                                                           */
 #define KID_DB_OPT_LOW_COMPLEXITY 2
 /* bases masked by KID_OPT_LOW_COMPLEXITY in the sample's FASTQ blocks since kid_sample_begin / kid_sample_reset
@@ -582,6 +582,48 @@ int kid_db_read_segments_device(kid_db *db, const void *d_bases, uint64_t bases_
 /* Device time of the segment kernels ALONE since the last query (the two scans and the segments kernel; the host forms
  * read the number of segments back in between), their calls and reads; the hit pass is in kid_db_read_hits_time.     */
 int kid_db_read_segments_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
+
+/* ---- calling segments by root-path votes ------------------------------------------------
+ * kid_db_read_segments* calls every segment by the left fold, which depends on the order of the hits: a record and its
+ * reverse complement carry the same hits in opposite order, so a contig assembled on the other strand can get other
+ * segment calls.  These calls cut the record exactly as kid_db_read_segments* does -- seg_len, seg_step and their limits,
+ * P, n_seg, the coverage of segment j, pos and n_pos are those above, and the list is dense -- and call each segment by the
+ * vote rule of kid_db_read_votes*.  The record of a segment:
+ *   pos, n_pos   those of kid_segment
+ *   the rest     the kid_vote record kid_db_read_votes returns under the same (min_hits, min_permille) for that read with
+ *                the range [pos, pos + n_pos + k - 2]: the vote record over the multiset of targets of the read's hits
+ *                with pos in [pos, pos + n_pos), n = the covered positions whose window holds a k-mer.  A target outside
+ *                (0, ntar) is read as the root.  A segment without a hit has call = confident = p_best = n_best =
+ *                s_call = s_confident = 0.
+ * seg_offsets, pos, n_pos, n_kmers and n_hits equal those of kid_db_read_segments for the same arguments.  With seg_len >=
+ * every read's P each read with P > 0 has one segment, whose eight vote fields are its kid_vote record.  When all hits of
+ * a segment lie on one root path, call = kid_segment.final.  For a record with P <= seg_len or (P - seg_len) % seg_step
+ * == 0, segment j of the record is segment n_seg - 1 - j of its reverse complement in n_pos and all eight vote fields.
+ * The calls are pure (no sample, no tally, no atomics on outputs); the output is byte-identical across runs, across any
+ * split of the reads into calls and across the table kinds.  A segment of more than a few hundred hits is settled by a
+ * second kernel queued behind the first; under overlap every hit is visited once per segment that covers it.
+ * The four forms mirror kid_db_read_segments* argument for argument, with the same error statuses in the same order, the
+ * same sizing call (segments = NULL, cap = 0), the same handling of n_reads = 0 and of hits_cap / seg_cap (nothing is
+ * written to d_segments when either is exceeded; the counts and d_seg_offsets are still complete).
+ * KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply to the FASTQ form as they do to
+ * kid_db_read_segments_fastq.  Scratch beside that of kid_db_read_segments*: 40 B per segment (host forms), 24 B per
+ * segment the call can write (the list for the second kernel: the host forms' total, the device form's seg_cap) and the
+ * rows of kid_db_read_votes*.  _time: the device time of the two scans and the two segment-vote kernels ALONE since the
+ * last query, their calls and reads.                                                                                   */
+typedef struct kid_segment_vote {
+    uint32_t pos, n_pos, call, confident, n_kmers, n_hits, p_best, n_best, s_call, s_confident;
+} kid_segment_vote;
+int kid_db_read_segment_votes(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                              uint64_t n_reads, uint32_t seg_len, uint32_t seg_step, uint32_t min_hits, uint32_t min_permille,
+                              uint64_t *seg_offsets, kid_segment_vote *segments, uint64_t cap, uint64_t *n_segments);
+int kid_db_read_segment_votes_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                                    uint32_t seg_len, uint32_t seg_step, uint32_t min_hits, uint32_t min_permille, uint64_t *seg_offsets,
+                                    kid_segment_vote *segments, uint64_t cap, uint64_t *n_segments);
+int kid_db_read_segment_votes_device(kid_db *db, const void *d_bases, uint64_t bases_nbytes, const void *d_offsets, const void *d_start,
+                                     const void *d_stop, uint64_t n_reads, uint32_t seg_len, uint32_t seg_step, uint32_t min_hits,
+                                     uint32_t min_permille, void *d_hits, uint64_t hits_cap, void *d_seg_offsets, void *d_segments,
+                                     uint64_t seg_cap, void *d_n_hits, void *d_n_segments, void *stream);
+int kid_db_read_segment_votes_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
 
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).

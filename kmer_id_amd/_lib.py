@@ -108,6 +108,14 @@ PROTOTYPES = {
                                               C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                               C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "kid_db_read_segments_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
+    "kid_db_read_segment_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
+    "kid_db_read_segment_votes_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
+                                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
+    "kid_db_read_segment_votes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "kid_db_read_segment_votes_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
     "kid_sample_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kid_sample_end_merged": (C.c_int, [c_void_pp, C.c_int, C.c_void_p, C.c_void_p]),
     "kid_sample_stats": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -107,10 +107,14 @@ FRAGMENT_VOTE_DTYPE = np.dtype([(name, np.uint32) for name in VOTE_DTYPE.names] 
 # kid_segment: one record per segment (kid_db_read_segments*); the six fields behind n_pos are SUPPORT_DTYPE's
 SEGMENT_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in SUPPORT_DTYPE.names])
 
+# kid_segment_vote: one record per segment (kid_db_read_segment_votes*); the eight fields behind n_pos are VOTE_DTYPE's
+SEGMENT_VOTE_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in VOTE_DTYPE.names])
+
 
 class ReadSegments:
-    """Every read's segments in read order (kid_db_read_segments*): CSR `offsets` (uint64[n + 1]) over `records`
-    (SEGMENT_DTYPE).  The list is dense: segments without a hit are there, with final = confident = 0."""
+    """Every read's segments in read order (kid_db_read_segments*, kid_db_read_segment_votes*): CSR `offsets`
+    (uint64[n + 1]) over `records` (SEGMENT_DTYPE, SEGMENT_VOTE_DTYPE).  The list is dense: segments without a hit are
+    there, with final = confident = 0 (call = confident = 0)."""
 
     def __init__(self, offsets, records):
         self.offsets = offsets
@@ -425,12 +429,12 @@ class KmerDB:
         """-> (device ms, calls, fragments) of the fragment-vote kernels alone since the last query"""
         return self._time(self._lib.kid_db_read_fragment_votes_time)
 
-    def _read_segments(self, call, n):
+    def _read_segments(self, call, n, dtype=SEGMENT_DTYPE):
         """the sizing call, then the call that fills a buffer of exactly that size"""
         offsets = np.empty(n + 1, np.uint64)
         total = C.c_uint64(0)
         check(call(_ptr(offsets), None, 0, C.byref(total)))
-        records = np.zeros(total.value, SEGMENT_DTYPE)
+        records = np.zeros(total.value, dtype)
         if total.value:
             check(call(_ptr(offsets), _ptr(records), total.value, C.byref(total)))
         return ReadSegments(offsets, records)
@@ -467,6 +471,40 @@ class KmerDB:
     def read_segments_time(self):
         """-> (device ms, calls, reads) of the segment kernels alone since the last query"""
         return self._time(self._lib.kid_db_read_segments_time)
+
+    def read_segment_votes(self, bases, offsets, start=None, stop=None, seg_len=1000, seg_step=None, min_hits=0, min_permille=0):
+        """Call the records of a batch held in host memory in segments by root-path votes (kid_db_read_segment_votes)
+        -> ReadSegments over SEGMENT_VOTE_DTYPE.  The segments are those of read_segments; each is called by the vote
+        rule of read_votes over its own hits, so the call does not depend on their order (nor on the strand the record
+        was assembled on).  Pure: no sample is touched."""
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        step = seg_len if seg_step is None else seg_step
+        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segment_votes(
+            self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n,
+            SEGMENT_VOTE_DTYPE)
+
+    def read_segment_votes_fastq(self, text, recs, seg_len=1000, seg_step=None, min_hits=0, min_permille=0):
+        """The same for a block of FASTQ text with its line index, as read_segments_fastq (a dropped record has no segment;
+        KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply as there)."""
+        text, recs, n = _fastq_block(text, recs)
+        step = seg_len if seg_step is None else seg_step
+        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segment_votes_fastq(
+            self._h, _ptr(text), text.size, _ptr(recs), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n, SEGMENT_VOTE_DTYPE)
+
+    def read_segment_votes_device(self, d_bases, bases_nbytes, d_offsets, n_reads, seg_len, seg_step, d_seg_offsets, d_n_hits, d_n_segments,
+                                  d_start=0, d_stop=0, min_hits=0, min_permille=0, d_hits=0, hits_cap=0, d_segments=0, seg_cap=0, stream=0):
+        """Asynchronous, everything resident in HBM (raw pointers): kid_db_read_segment_votes_device, argument for argument
+        read_segments_device with kid_segment_vote[seg_cap] (SEGMENT_VOTE_DTYPE) at d_segments."""
+        check(self._lib.kid_db_read_segment_votes_device(self._h, C.c_void_p(d_bases), bases_nbytes, C.c_void_p(d_offsets),
+                                                         C.c_void_p(d_start or None), C.c_void_p(d_stop or None), n_reads, seg_len,
+                                                         seg_len if seg_step is None else seg_step, min_hits, min_permille,
+                                                         C.c_void_p(d_hits or None), hits_cap, C.c_void_p(d_seg_offsets),
+                                                         C.c_void_p(d_segments or None), seg_cap, C.c_void_p(d_n_hits),
+                                                         C.c_void_p(d_n_segments), C.c_void_p(stream or None)))
+
+    def read_segment_votes_time(self):
+        """-> (device ms, calls, reads) of the segment scans and segment-vote kernels alone since the last query"""
+        return self._time(self._lib.kid_db_read_segment_votes_time)
 
     def shared_kmers(self, items):
         """K-mers shared between samples (kid_db_shared_kmers) -> int64[n, n, ntar]: [i, j, t] = the database entries of

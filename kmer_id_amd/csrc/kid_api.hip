@@ -1,7 +1,8 @@
 // kid_api.hip -- C ABI (include/kmer_id_amd.h) over the gfx950 kernels: the one translation unit of the library.
 // Here: the sample handle, the pacing of the hit log, kid_launch_classify and the classify entry points -- the launch
 // path a counter profile depends on.  The other areas are the kid_api_*.h files included below (kid_api_support.h
-// at the end: it counts into a sample; kid_api_fragments.h, kid_api_votes.h, kid_api_fragment_votes.h, kid_api_segments.h, kid_api_depth.h, kid_api_shared.h and kid_api_coverage.h behind it).  Host side only:
+// at the end: it counts into a sample; kid_api_fragments.h, kid_api_votes.h, kid_api_fragment_votes.h, kid_api_segments.h,
+// kid_api_segment_votes.h, kid_api_depth.h, kid_api_shared.h and kid_api_coverage.h behind it).  Host side only:
 // handle bookkeeping and launches; no classification work is done on the CPU.
 #include <hip/hip_runtime.h>
 #include <memory>
@@ -1061,6 +1062,7 @@ extern "C" int kid_sample_seen_or(kid_sample *s, uint64_t byte_off, uint64_t nby
 #include "kid_api_votes.h"
 #include "kid_api_fragment_votes.h"
 #include "kid_api_segments.h"
+#include "kid_api_segment_votes.h"
 #include "kid_api_depth.h"
 #include "kid_api_shared.h"
 #include "kid_api_coverage.h"

@@ -1,6 +1,7 @@
 // kid_api_hits.h -- every read's k-mer hits: the scratch of a database's hit passes and kid_db_read_hits*.
 // What the other families over the hit pass -- kid_db_read_support* (kid_api_support.h), kid_db_read_fragments*
-// (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h), kid_db_read_votes* (kid_api_votes.h), kid_db_read_fragment_votes* (kid_api_fragment_votes.h) -- share with kid_db_read_hits* is here once:
+// (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h), kid_db_read_votes* (kid_api_votes.h), kid_db_read_fragment_votes* (kid_api_fragment_votes.h),
+// kid_db_read_segment_votes* (kid_api_segment_votes.h) -- share with kid_db_read_hits* is here once:
 // KidSpanTimer, kid_hits_state (the scratch, free: the timers a family settles), kid_hits_scan (the three-kernel
 // exclusive scan), KidOpenBatch and kid_hits_open_* (a host-buffer batch checked, locked and staged, one function per
 // input form over kid_hits_stage_*), the hit pass into the library's own buffers (kid_hits_host_pass), the checks of
@@ -15,7 +16,8 @@
 // one kid_db run one after the other: a call first waits for the kernels of the call before).  Per batch: 16 B per
 // read (descriptors) + 8 B per read (first tile) + 16 B per tile of 64 windows (mask, first hit) + 8 B per 1024 of
 // either (scan totals); the host-buffer forms add a device copy of their inputs and outputs.  kid_db_read_segments* add
-// 16 B per tile (valid mask, its scan), 8 B per read (first segment) and 32 B per segment (host forms).
+// 16 B per tile (valid mask, its scan), 8 B per read (first segment) and 32 B per segment (host forms);
+// kid_db_read_segment_votes* the same with 40 B per segment, and 24 B per segment the call can write (the second kernel's list).
 // The device time between two events on a stream, added up over the calls since somebody took it
 struct __attribute__((visibility("hidden"))) KidSpanTimer {
     KidEvent ev0, ev1;
@@ -89,6 +91,10 @@ struct KidHitsState {
     // fragment-vote call queued on two streams never share a list or a row); the list holds fragment indexes
     KidDevBuf out_fragment_votes, fvote_list, fvote_n_list, fvote_rows;
     KidSpanTimer fragment_votes; // the two fragment-vote kernels alone
+    // kid_db_read_segment_votes* (kid_api_segment_votes.h): the host forms' records; the segments its first kernel leaves
+    // to the second (24 B per segment the call can write) and their number.  The rows are vote_rows
+    KidDevBuf out_segment_votes, svote_list, svote_n_list;
+    KidSpanTimer segment_votes; // the segment scans and the two segment-vote kernels alone
     KidDevBuf lowc_plane; // KID_DB_OPT_LOW_COMPLEXITY: the flag plane of a staged block with a line that is split (kid_lowc.hip.h)
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
@@ -99,7 +105,7 @@ kid_db::~kid_db() {}
 // a little slack: batches of a file differ slightly in size
 static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensure(nbytes, ((nbytes + nbytes / 8) + 255u) & ~255ull); }
 
-// The scratch, free: the hit pass of the call before, and the segment kernels behind it, are through (they read the
+// The scratch, free: the hit pass of the call before, and the segment and segment-vote kernels behind it, are through (they read the
 // tiles' scratch behind the pass) -- and of the kernels that read the pass's CSR alone those that `settle` names: a call
 // waits for the timers its family has always waited for, no more (a device-form caller that queues hits -> support on
 // a stream of its own does not block in the next kid_db_read_hits_device).
@@ -117,11 +123,13 @@ static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
         KID_HIP(h->segments.create());
         KID_HIP(h->votes.create());
         KID_HIP(h->fragment_votes.create());
+        KID_HIP(h->segment_votes.create());
         db->hits = std::move(h);
     }
     KidHitsState *h = *out = db->hits.get();
     int rc = h->pass.settle();
     if (rc == KID_OK) rc = h->segments.settle();
+    if (rc == KID_OK) rc = h->segment_votes.settle(); // (they read the tiles' scratch too, and vote_rows)
     if (rc == KID_OK && (settle & KID_SETTLE_SUPPORT)) rc = h->support.settle();
     if (rc == KID_OK && (settle & KID_SETTLE_FRAGMENTS)) rc = h->fragments.settle();
     if (rc == KID_OK && (settle & KID_SETTLE_VOTES)) rc = h->votes.settle(); // (its list and rows are one set per kid_db)

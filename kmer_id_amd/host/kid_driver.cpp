@@ -383,7 +383,7 @@ static void read_low_complexity(SideOptions &o, const char *prog, const char *op
     o.low_complexity = (int)t;
 }
 
-static void read_segments(SideOptions &o, const char *prog, const char *opt, const char *v)
+static SegmentsOption parse_segments(const char *prog, const char *opt, const char *v)
 {
     const char *const what = "takes LEN[:STEP], digits only: LEN in 1..2147483647, STEP in 1..LEN with LEN <= 1024 * STEP";
     unsigned long long len = 0, step = 0;
@@ -393,7 +393,12 @@ static void read_segments(SideOptions &o, const char *prog, const char *opt, con
     if (v[at] == ':' && digits_up_to(0x7FFFFFFFull, v, ++at, step) <= 0) usage_error(prog, opt, what);
     if (v[at] != 0) usage_error(prog, opt, what); // (a second colon too)
     if (len < 1 || step < 1 || step > len || len > 1024ull * step) usage_error(prog, opt, what);
-    o.segments = SegmentsOption{true, (uint32_t)len, (uint32_t)step};
+    return SegmentsOption{true, (uint32_t)len, (uint32_t)step};
+}
+static void read_segments(SideOptions &o, const char *prog, const char *opt, const char *v) { o.segments = parse_segments(prog, opt, v); }
+static void read_segment_votes(SideOptions &o, const char *prog, const char *opt, const char *v)
+{
+    o.segment_votes = parse_segments(prog, opt, v);
 }
 
 // The side options: their words, the pass of side_options() that reads each, what reads its value -- or, for a switch,
@@ -409,6 +414,7 @@ static const struct {
                     {"--min-base-quality", 1, read_base_quality, nullptr},
                     {"--low-complexity", 1, read_low_complexity, nullptr},
                     {"--segments", 2, read_segments, nullptr},
+                    {"--segment-votes", 3, read_segment_votes, nullptr},
                     {"--depth", 0, nullptr, &SideOptions::depth},
                     {"--seen", 0, nullptr, &SideOptions::seen},
                     {"--fragments", 0, nullptr, &SideOptions::fragments},
@@ -426,7 +432,7 @@ SideOptions side_options(int argc, char **argv, const char *prog)
 {
     SideOptions o;
     // one pass over the words per step of the order in which malformed options are reported
-    for (int pass = 0; pass < 3; pass++)
+    for (int pass = 0; pass < 4; pass++)
         for (int i = 1; i < argc; i++)
             for (const auto &so : kSideOptions) {
                 if (so.pass != pass || strcmp(argv[i], so.name) != 0) continue;
@@ -447,7 +453,7 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes, fragment_votes; };
+struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes, fragment_votes, segment_votes; };
 static SidePaths side_paths(const std::string &r)
 {
     std::string seen = r; // the final "result.txt" becomes "seen.bin"
@@ -455,7 +461,7 @@ static SidePaths side_paths(const std::string &r)
     if (at != std::string::npos) seen.replace(at, 10, "seen.bin");
     else seen += ".seen.bin";
     return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen,
-            sibling_path_for(r, "fragments"), sibling_path_for(r, "votes"), sibling_path_for(r, "fragment_votes")};
+            sibling_path_for(r, "fragments"), sibling_path_for(r, "votes"), sibling_path_for(r, "fragment_votes"), sibling_path_for(r, "segment_votes")};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -469,6 +475,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.fragments) remove(p.fragments.c_str());
     if (all || side.votes) remove(p.votes.c_str());
     if (all || side.fragment_votes) remove(p.fragment_votes.c_str());
+    if (all || side.segment_votes.on) remove(p.segment_votes.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -612,8 +619,10 @@ void SampleOutputs::finish(Engine &e)
     if (side_.seen) write_seen(side_.support.on ? e.confident[0] : e.samples[0], e, p.seen);
     if (side_.hits) write_lines(p.hits, hits_);
     if (side_.segments.on) write_lines(p.segments, segments_);
+    if (side_.segment_votes.on) write_lines(p.segment_votes, segment_votes_);
     hits_.clear();
     segments_.clear();
+    segment_votes_.clear();
 }
 
 // One call of the kid_db_read_* family on a classified batch (its start / stop / final targets are known) on the batch's
@@ -694,6 +703,37 @@ static void segment_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *base
             const kid_segment &s = segs[i];
             if (s.n_hits == 0) continue;
             n = snprintf(num, sizeof(num), "%s%u:%u:%u:%u:%u:%u", first ? "" : " ", s.pos, s.n_pos, s.n_kmers, s.n_hits, s.final, s.confident);
+            out.append(num, (size_t)n);
+            first = false;
+        }
+        append_header(out, b, r);
+    }
+}
+
+// The segment_votes lines of one classified batch: kid_db_read_segment_votes* under the rule, as segment_lines_of
+static void segment_vote_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, const std::vector<uint32_t> &final_targ,
+                                  const SegmentsOption &o, const SupportRule &rule, std::string &out)
+{
+    const size_t nr = b.size();
+    std::vector<uint64_t> off(nr + 1);
+    const std::vector<kid_segment_vote> segs = read_items<kid_segment_vote>(kid_db_read_segment_votes_fastq, kid_db_read_segment_votes, db, b,
+                                                                            bases, o.seg_len, o.seg_step, rule.min_hits, rule.min_permille,
+                                                                            off.data());
+    if (segs.empty()) return;
+    char num[128];
+    for (size_t r = 0; r < nr; r++) {
+        uint64_t with_hit = 0;
+        for (uint64_t i = off[r]; i < off[r + 1]; i++) with_hit += segs[i].n_hits > 0;
+        if (with_hit == 0) continue;
+        int n = snprintf(num, sizeof(num), "%u\t%d\t%llu\t%llu\t", final_targ[r], b.stop[r] - b.start[r] + 1,
+                         (unsigned long long)(off[r + 1] - off[r]), (unsigned long long)with_hit);
+        out.append(num, (size_t)n);
+        bool first = true;
+        for (uint64_t i = off[r]; i < off[r + 1]; i++) {
+            const kid_segment_vote &s = segs[i];
+            if (s.n_hits == 0) continue;
+            n = snprintf(num, sizeof(num), "%s%u:%u:%u:%u:%u:%u:%u:%u", first ? "" : " ", s.pos, s.n_pos, s.n_kmers, s.n_hits, s.call, s.confident,
+                         s.p_best, s.n_best);
             out.append(num, (size_t)n);
             first = false;
         }
@@ -803,6 +843,11 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             lines.clear();
             segment_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.side.segments, e.side.support, lines);
             out.add_segments(saver_file + f.file, lines);
+        }
+        if (out.segment_votes_on()) {
+            lines.clear();
+            segment_vote_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.side.segment_votes, e.side.support, lines);
+            out.add_segment_votes(saver_file + f.file, lines);
         }
         if (fragments && f.batch->fq) {
             mate_records[f.file] += f.batch->size();

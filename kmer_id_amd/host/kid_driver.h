@@ -58,11 +58,15 @@ struct SideOptions {
     // --fragment-votes (no value; nk10 alone, like --fragments): the mate pairs called by root-path votes over both mates'
     // hits (kid_db_read_fragment_votes_fastq), counted into a fragment_votes file
     bool fragment_votes = false;
+    // --segment-votes LEN[:STEP] (the value grammar of --segments): long records called in segments by root-path votes
+    // (kid_db_read_segment_votes*), into a segment_votes file.  Independent of --segments: both may be given, with
+    // different geometries, and neither changes what the other writes.
+    SegmentsOption segment_votes;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
-// of --segments too) is a usage error: "<prog>: <option> <what>" on stderr and exit code 2 -- of several, the first in
-// the order --min-hits / --confidence, --min-base-quality / --low-complexity, --segments.
+// of --segments or --segment-votes too) is a usage error: "<prog>: <option> <what>" on stderr and exit code 2 -- of several, the first in
+// the order --min-hits / --confidence, --min-base-quality / --low-complexity, --segments, --segment-votes.
 SideOptions side_options(int argc, char **argv, const char *prog);
 // For a front-end that rejects the words it does not know: the number of value words behind `word` (0 or 1) if it
 // is a side option, else -1
@@ -191,10 +195,16 @@ private:
 // when given, else (0, 0); --min-base-quality and --low-complexity apply as they do to the fragments file.  It needs
 // neither --fragments nor --votes, changes nothing they write, and does not depend on how the files were cut into
 // blocks, batched, threaded or dealt over devices.
+//   --segment-votes, "segment_votes": the lines of the segments file, in its order, for the segments of its own LEN[:STEP]
+// called by root-path votes (kid_db_read_segment_votes*), which does not depend on the order of a segment's hits:
+//   <final_targ> <trimmed length> <n_segments> <segments with a hit> <pos>:<n_pos>:<n_kmers>:<n_hits>:<call>:<confident>:<p_best>:<n_best> ... <header>
+// Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0);
+// --min-base-quality and --low-complexity apply as they do to the segments file.  It does not depend on how the reads
+// were batched, threaded or dealt over devices, and needs --segments no more than --segments needs it.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
-// The batches of files read at the same time interleave: the hit and segment lines are held in memory per file and
+// The batches of files read at the same time interleave: the hit, segment and segment_votes lines are held in memory per file and
 // written in file order by finish() -- what is held is the files themselves (reads without a hit leave nothing),
-// nothing else.  One that is not finished (its sample failed) leaves no hits and no segments file.
+// nothing else.  One that is not finished (its sample failed) leaves no hits, no segments and no segment_votes file.
 class SampleOutputs {
 public:
     // removes the files of the options that are on, left there by an earlier run
@@ -203,19 +213,21 @@ public:
     bool segments_on() const { return side_.segments.on; }
     bool fragments_on() const { return side_.fragments; }
     bool fragment_votes_on() const { return side_.fragment_votes; }
+    bool segment_votes_on() const { return side_.segment_votes.on; }
     const std::string &result_path() const { return result_path_; }
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
+    void add_segment_votes(size_t file, const std::string &lines) { add(segment_votes_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
     // confident file, then the fragments file, then the votes file, then the fragment_votes file, then the depth file, then the seen file, then the hits file, then the
-    // segments file
+    // segments file, then the segment_votes file
     void finish(Engine &e);
 private:
     using Lines = std::vector<std::string>; // [file]
     static void add(Lines &to, size_t file, const std::string &lines);
     SideOptions side_;
     std::string result_path_;
-    Lines hits_, segments_;
+    Lines hits_, segments_, segment_votes_;
 };
 // The head of a seen file: the 8 bytes "KIDSEEN1", then these fields, little-endian, 32 bytes in all; nbytes bytes of
 // bitmap follow (the padded size of a database of n_entries: ((n_entries + 127) / 128) * 16, 16 for none)
@@ -246,7 +258,8 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
 // the device that classified it, once its final targets are back.  With e.side.support or e.side.depth on, the support
 // pass of a batch runs at the same place and tallies into that device's confident sample; with e.side.votes on the vote
 // pass (kid_db_read_votes*) does the same into that device's votes sample.  When its segments file is on, `out` receives
-// the segment lines of every batch under e.side: the segments pass (kid_db_read_segments*) runs at the same place too.
+// the segment lines of every batch under e.side: the segments pass (kid_db_read_segments*) runs at the same place too,
+// and so does the segment-votes pass (kid_db_read_segment_votes*) when its segment_votes file is on.
 // With out.fragments_on() or out.fragment_votes_on() and count == 2 the two files are the mates of a sample: the FASTQ blocks of each that are
 // through wait in a queue until the partner's records have arrived; the longest common run of records is handed to
 // kid_db_read_fragments_fastq with a device's fragment sample as its tally (and, or, to kid_db_read_fragment_votes_fastq

@@ -10,6 +10,7 @@
 //   --hits   every read's k-mer hits
 //   --min-hits N  --confidence F   the reads called by k-mer support
 //   --segments LEN[:STEP]   long records called in segments
+//   --segment-votes LEN[:STEP]   long records called in segments by root-path votes (the segment_votes file of kid_driver.h)
 //   --depth   k-mer depth per target (the depth file of kid_driver.h)
 //   --seen   the seen-bitmap in a seen file (<...>seen.bin beside <...>result.txt), for kmer_shared
 //   --votes   the reads called by root-path votes, whatever the order of their hits (the votes file of kid_driver.h)

@@ -21,6 +21,10 @@
 //                    hits and F (a decimal in [0, 1], three fractional digits) of its k-mers, under 0 if none does (kid_driver.h)
 //   --segments LEN[:STEP]   also write <prefix>_segments.txt: every read with a hit called in segments of LEN window
 //                    positions, STEP apart (default LEN; LEN <= 1024 * STEP), under the rule of --min-hits / --confidence (kid_driver.h)
+//   --segment-votes LEN[:STEP]   also write <prefix>_segment_votes.txt: the same segments (of this option's own LEN[:STEP]) called
+//                    by root-path votes, which do not depend on the order of a segment's hits nor on the strand a record was
+//                    assembled on, under the rule of --min-hits / --confidence; needs no --segments and changes nothing it
+//                    writes (kid_driver.h)
 //   --depth              also write <prefix>_depth.txt: per target, the hits on its database k-mers by the reads called (under the
 //                    rule of --min-hits / --confidence when given), how many of them were hit, the quartiles of their depth and
 //                    the largest (kid_driver.h)
