@@ -27,6 +27,35 @@ class KidDbInfo(C.Structure):
     ]
 
 
+_p, _u32, _u64 = C.c_void_p, C.c_uint32, C.c_uint64
+_TIME = (C.c_int, [_p, C.POINTER(C.c_double), c_u64p, c_u64p])  # every kid_db_read_*_time
+
+
+def _unit_family(name, pairs=False):
+    """the four entry points of a family of calls that leaves one record per read, or (pairs: its FASTQ form takes two
+    blocks) per fragment: batch or block, (min_hits, min_permille), out, tally"""
+    rule_out_tally = [_u32, _u32, _p, _p]
+    block = [_p, _u64, _p]
+    return {
+        "kid_db_read_%s" % name: (C.c_int, [_p, _p, _p, _p, _p, _u64] + rule_out_tally),
+        "kid_db_read_%s_fastq" % name: (C.c_int, [_p] + (block + block if pairs else block) + [_u64] + rule_out_tally),
+        "kid_db_%s_from_hits_device" % name: (C.c_int, [_p, _p, _p, _p, _u64] + rule_out_tally),
+        "kid_db_read_%s_time" % name: _TIME,
+    }
+
+
+def _segment_family(name):
+    """the four entry points of a family of segment calls: batch or block, (seg_len, seg_step, min_hits, min_permille),
+    the CSR outputs"""
+    rule = [_u32, _u32, _u32, _u32]
+    return {
+        "kid_db_read_%s" % name: (C.c_int, [_p, _p, _p, _p, _p, _u64] + rule + [_p, _p, _u64, c_u64p]),
+        "kid_db_read_%s_fastq" % name: (C.c_int, [_p, _p, _u64, _p, _u64] + rule + [_p, _p, _u64, c_u64p]),
+        "kid_db_read_%s_device" % name: (C.c_int, [_p, _p, _u64, _p, _p, _p, _u64] + rule + [_p, _u64, _p, _p, _u64, _p, _p, _p]),
+        "kid_db_read_%s_time" % name: _TIME,
+    }
+
+
 # name -> (restype, argtypes); every symbol include/kmer_id_amd.h declares
 PROTOTYPES = {
     "kid_strerror": (C.c_char_p, [C.c_int]),
@@ -71,51 +100,13 @@ PROTOTYPES = {
                                          C.c_void_p, C.c_uint64, c_u64p]),
     "kid_db_read_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
-    "kid_db_read_hits_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
-    "kid_db_read_support": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                      C.c_void_p, C.c_void_p]),
-    "kid_db_read_support_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                            C.c_void_p, C.c_void_p]),
-    "kid_db_support_from_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                  C.c_void_p, C.c_void_p]),
-    "kid_db_read_support_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
-    "kid_db_read_fragments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                        C.c_void_p, C.c_void_p]),
-    "kid_db_read_fragments_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
-                                              C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
-    "kid_db_fragments_from_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                    C.c_void_p, C.c_void_p]),
-    "kid_db_read_fragments_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
-    "kid_db_read_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                    C.c_void_p, C.c_void_p]),
-    "kid_db_read_votes_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                          C.c_void_p, C.c_void_p]),
-    "kid_db_votes_from_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                C.c_void_p, C.c_void_p]),
-    "kid_db_read_votes_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
-    "kid_db_read_fragment_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                             C.c_void_p, C.c_void_p]),
-    "kid_db_read_fragment_votes_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                   C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
-    "kid_db_fragment_votes_from_hits_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                         C.c_void_p, C.c_void_p]),
-    "kid_db_read_fragment_votes_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
-    "kid_db_read_segments": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                       C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
-    "kid_db_read_segments_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                             C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
-    "kid_db_read_segments_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
-                                              C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
-                                              C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "kid_db_read_segments_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
-    "kid_db_read_segment_votes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                            C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
-    "kid_db_read_segment_votes_fastq": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32,
-                                                  C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, c_u64p]),
-    "kid_db_read_segment_votes_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
-                                                   C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
-                                                   C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "kid_db_read_segment_votes_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), c_u64p, c_u64p]),
+    "kid_db_read_hits_time": _TIME,
+    **_unit_family("support"),
+    **_unit_family("fragments", pairs=True),
+    **_unit_family("votes"),
+    **_unit_family("fragment_votes", pairs=True),
+    **_segment_family("segments"),
+    **_segment_family("segment_votes"),
     "kid_sample_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kid_sample_end_merged": (C.c_int, [c_void_pp, C.c_int, C.c_void_p, C.c_void_p]),
     "kid_sample_stats": (C.c_int, [C.c_void_p, C.c_void_p]),

@@ -111,6 +111,13 @@ SEGMENT_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np
 SEGMENT_VOTE_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in VOTE_DTYPE.names])
 
 
+# the families of calls over the hit pass by the name in their entry points: the record, and for those that leave one
+# record per unit the reads of a unit
+_UNIT_FAMILIES = {"support": (SUPPORT_DTYPE, 1), "votes": (VOTE_DTYPE, 1), "fragments": (FRAGMENT_DTYPE, 2),
+                  "fragment_votes": (FRAGMENT_VOTE_DTYPE, 2)}
+_SEGMENT_FAMILIES = {"segments": SEGMENT_DTYPE, "segment_votes": SEGMENT_VOTE_DTYPE}
+
+
 class ReadSegments:
     """Every read's segments in read order (kid_db_read_segments*, kid_db_read_segment_votes*): CSR `offsets`
     (uint64[n + 1]) over `records` (SEGMENT_DTYPE, SEGMENT_VOTE_DTYPE).  The list is dense: segments without a hit are
@@ -282,33 +289,50 @@ class KmerDB:
         """-> (device ms, calls, reads) of the hits kernels since the last query (HIP events around every call)"""
         return self._time(self._lib.kid_db_read_hits_time)
 
+    def _calls_offsets(self, family, bases, offsets, start, stop, min_hits, min_permille, tally):
+        """kid_db_read_<family> over a batch held in host memory -> its records, one per unit"""
+        dtype, unit = _UNIT_FAMILIES[family]
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        out = np.zeros(n // unit, dtype)
+        check(getattr(self._lib, "kid_db_read_" + family)(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits,
+                                                          min_permille, _ptr(out), tally._h if tally is not None else None))
+        return out
+
+    def _calls_fastq(self, family, blocks, min_hits, min_permille, tally):
+        """kid_db_read_<family>_fastq over one block (text, recs) of FASTQ text, or two: the mates -> one record per unit"""
+        blocks = [_fastq_block(text, recs) for text, recs in blocks]
+        n = blocks[0][2]
+        if any(b[2] != n for b in blocks):
+            raise ValueError("recs1 and recs2 must hold one record per fragment each")
+        out = np.zeros(n, _UNIT_FAMILIES[family][0])
+        texts = [a for text, recs, _ in blocks for a in (_ptr(text), text.size, _ptr(recs))]
+        check(getattr(self._lib, "kid_db_read_%s_fastq" % family)(self._h, *texts, n, min_hits, min_permille, _ptr(out),
+                                                                  tally._h if tally is not None else None))
+        return out
+
+    def _from_hits_device(self, family, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits, min_permille, stream):
+        """kid_db_<family>_from_hits_device: a family's kernels alone on a CSR resident in HBM"""
+        check(getattr(self._lib, "kid_db_%s_from_hits_device" % family)(
+            self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None), C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille,
+            C.c_void_p(d_out), C.c_void_p(stream or None)))
+
     def read_support(self, bases, offsets, start=None, stop=None, min_hits=0, min_permille=0, tally=None):
         """Call the reads of a batch held in host memory by k-mer support (kid_db_read_support): -> a structured array
         (SUPPORT_DTYPE: final, confident, n_kmers, n_hits, s_final, s_confident), one record per read.  `confident` is
         the first node on final's root path whose clade holds at least min_hits hits and min_permille / 1000 of the
         read's k-mers, 0 if none does.  tally: a Sample of this database that is counted as if the batch had been
         classified under the rule (gcount[confident]++, seen bits of the hits of reads with confident > 0)."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        out = np.zeros(n, SUPPORT_DTYPE)
-        check(self._lib.kid_db_read_support(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
-                                            _ptr(out), tally._h if tally is not None else None))
-        return out
+        return self._calls_offsets("support", bases, offsets, start, stop, min_hits, min_permille, tally)
 
     def read_support_fastq(self, text, recs, min_hits=0, min_permille=0, tally=None):
         """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
         fails stop - start >= k has no window and no hit, and a tally counts it nowhere."""
-        text, recs, n = _fastq_block(text, recs)
-        out = np.zeros(n, SUPPORT_DTYPE)
-        check(self._lib.kid_db_read_support_fastq(self._h, _ptr(text), text.size, _ptr(recs), n, min_hits, min_permille, _ptr(out),
-                                                  tally._h if tally is not None else None))
-        return out
+        return self._calls_fastq("support", [(text, recs)], min_hits, min_permille, tally)
 
     def support_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
         """The support kernel alone on a CSR resident in HBM (raw pointers, as kid_db_read_hits_device left it);
         asynchronous on `stream`: kid_db_support_from_hits_device.  d_out: kid_support[n_reads] (SUPPORT_DTYPE)."""
-        check(self._lib.kid_db_support_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
-                                                        C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
-                                                        C.c_void_p(stream or None)))
+        self._from_hits_device("support", d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits, min_permille, stream)
 
     def read_support_time(self):
         """-> (device ms, calls, reads) of the support kernel alone since the last query"""
@@ -320,27 +344,17 @@ class KmerDB:
         counts the hits at c or an ancestor of c; `call` is the lowest common ancestor of the hit targets with the largest
         P (n_best of them, P = p_best): a pure function of the multiset of the read's hits, whatever their order.
         `confident` climbs from call under the rule as read_support's climbs from final; tally as there."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        out = np.zeros(n, VOTE_DTYPE)
-        check(self._lib.kid_db_read_votes(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
-                                          _ptr(out), tally._h if tally is not None else None))
-        return out
+        return self._calls_offsets("votes", bases, offsets, start, stop, min_hits, min_permille, tally)
 
     def read_votes_fastq(self, text, recs, min_hits=0, min_permille=0, tally=None):
         """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
         fails stop - start >= k has no window and no hit, and a tally counts it nowhere."""
-        text, recs, n = _fastq_block(text, recs)
-        out = np.zeros(n, VOTE_DTYPE)
-        check(self._lib.kid_db_read_votes_fastq(self._h, _ptr(text), text.size, _ptr(recs), n, min_hits, min_permille, _ptr(out),
-                                                tally._h if tally is not None else None))
-        return out
+        return self._calls_fastq("votes", [(text, recs)], min_hits, min_permille, tally)
 
     def votes_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
         """The vote kernels alone on a CSR resident in HBM (raw pointers, as kid_db_read_hits_device left it);
         asynchronous on `stream`: kid_db_votes_from_hits_device.  d_out: kid_vote[n_reads] (VOTE_DTYPE)."""
-        check(self._lib.kid_db_votes_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
-                                                      C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
-                                                      C.c_void_p(stream or None)))
+        self._from_hits_device("votes", d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits, min_permille, stream)
 
     def read_votes_time(self):
         """-> (device ms, calls, reads) of the vote kernels alone since the last query"""
@@ -357,33 +371,20 @@ class KmerDB:
         tally: a Sample of this database.  A counted fragment adds 1 to gcount[confident]: once per fragment, under 0
         when confident = 0.  When confident > 0, the fragment sets the seen bit of every hit of both mates with
         target > 1 (and under KID_OPT_ENTRY_DEPTH adds 1 to depth[entry] per such hit)."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        out = np.zeros(n // 2, FRAGMENT_DTYPE)
-        check(self._lib.kid_db_read_fragments(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
-                                              _ptr(out), tally._h if tally is not None else None))
-        return out
+        return self._calls_offsets("fragments", bases, offsets, start, stop, min_hits, min_permille, tally)
 
     def read_fragments_fastq(self, text1, recs1, text2, recs2, min_hits=0, min_permille=0, tally=None):
         """The same for two blocks of FASTQ text with their line indexes (uint32[n, 4] each, as Sample.classify_fastq):
         record i of recs1 is mate 1 and record i of recs2 is mate 2.  A record with seq_len = 0 and qual_len = 0 is an
         absent mate.  A fragment is counted when at least one of its mates is kept by process_qual; a dropped mate
         contributes no hit and no window."""
-        text1, recs1, n = _fastq_block(text1, recs1)
-        text2, recs2, n2 = _fastq_block(text2, recs2)
-        if n != n2:
-            raise ValueError("recs1 and recs2 must hold one record per fragment each")
-        out = np.zeros(n, FRAGMENT_DTYPE)
-        check(self._lib.kid_db_read_fragments_fastq(self._h, _ptr(text1), text1.size, _ptr(recs1), _ptr(text2), text2.size, _ptr(recs2), n,
-                                                    min_hits, min_permille, _ptr(out), tally._h if tally is not None else None))
-        return out
+        return self._calls_fastq("fragments", [(text1, recs1), (text2, recs2)], min_hits, min_permille, tally)
 
     def fragments_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
         """The fragment kernel alone on an interleaved CSR of n_reads = 2 F reads resident in HBM (raw pointers, as
         kid_db_read_hits_device left it); asynchronous on `stream`: kid_db_fragments_from_hits_device.
         d_out: kid_fragment[n_reads / 2] (FRAGMENT_DTYPE)."""
-        check(self._lib.kid_db_fragments_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
-                                                          C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
-                                                          C.c_void_p(stream or None)))
+        self._from_hits_device("fragments", d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits, min_permille, stream)
 
     def read_fragments_time(self):
         """-> (device ms, calls, fragments) of the fragment kernel alone since the last query"""
@@ -398,75 +399,77 @@ class KmerDB:
         and call_2 that of mate 2's; each is 0 without a hit.  Exchanging the mates exchanges call_1 and call_2 and
         changes nothing else.
         tally: a Sample of this database, counted exactly as read_fragments counts with this `confident`."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        out = np.zeros(n // 2, FRAGMENT_VOTE_DTYPE)
-        check(self._lib.kid_db_read_fragment_votes(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, min_hits, min_permille,
-                                                   _ptr(out), tally._h if tally is not None else None))
-        return out
+        return self._calls_offsets("fragment_votes", bases, offsets, start, stop, min_hits, min_permille, tally)
 
     def read_fragment_votes_fastq(self, text1, recs1, text2, recs2, min_hits=0, min_permille=0, tally=None):
         """The same for two blocks of FASTQ text with their line indexes, as read_fragments_fastq: record i of recs1 is
         mate 1 and record i of recs2 is mate 2; a record with seq_len = 0 and qual_len = 0 is an absent mate.  A fragment
         is counted when at least one of its mates is kept by process_qual."""
-        text1, recs1, n = _fastq_block(text1, recs1)
-        text2, recs2, n2 = _fastq_block(text2, recs2)
-        if n != n2:
-            raise ValueError("recs1 and recs2 must hold one record per fragment each")
-        out = np.zeros(n, FRAGMENT_VOTE_DTYPE)
-        check(self._lib.kid_db_read_fragment_votes_fastq(self._h, _ptr(text1), text1.size, _ptr(recs1), _ptr(text2), text2.size, _ptr(recs2),
-                                                         n, min_hits, min_permille, _ptr(out), tally._h if tally is not None else None))
-        return out
+        return self._calls_fastq("fragment_votes", [(text1, recs1), (text2, recs2)], min_hits, min_permille, tally)
 
     def fragment_votes_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits=0, min_permille=0, stream=0):
         """The fragment-vote kernels alone on an interleaved CSR of n_reads = 2 F reads resident in HBM (raw pointers, as
         kid_db_read_hits_device left it); asynchronous on `stream`: kid_db_fragment_votes_from_hits_device.
         d_out: kid_fragment_vote[n_reads / 2] (FRAGMENT_VOTE_DTYPE)."""
-        check(self._lib.kid_db_fragment_votes_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
-                                                               C.c_void_p(d_n_kmers), n_reads, min_hits, min_permille, C.c_void_p(d_out),
-                                                               C.c_void_p(stream or None)))
+        self._from_hits_device("fragment_votes", d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, min_hits, min_permille, stream)
 
     def read_fragment_votes_time(self):
         """-> (device ms, calls, fragments) of the fragment-vote kernels alone since the last query"""
         return self._time(self._lib.kid_db_read_fragment_votes_time)
 
-    def _read_segments(self, call, n, dtype=SEGMENT_DTYPE):
-        """the sizing call, then the call that fills a buffer of exactly that size"""
+    def _read_segments(self, family, n, call):
+        """the sizing call, then the call that fills a buffer of exactly that size: call(offsets, records, cap, total)"""
         offsets = np.empty(n + 1, np.uint64)
         total = C.c_uint64(0)
         check(call(_ptr(offsets), None, 0, C.byref(total)))
-        records = np.zeros(total.value, dtype)
+        records = np.zeros(total.value, _SEGMENT_FAMILIES[family])
         if total.value:
             check(call(_ptr(offsets), _ptr(records), total.value, C.byref(total)))
         return ReadSegments(offsets, records)
+
+    def _segments_offsets(self, family, bases, offsets, start, stop, seg_len, seg_step, min_hits, min_permille):
+        """kid_db_read_<family> over a batch held in host memory"""
+        fn = getattr(self._lib, "kid_db_read_" + family)
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        step = seg_len if seg_step is None else seg_step
+        return self._read_segments(family, n, lambda o, s, cap, tot: fn(
+            self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, seg_len, step, min_hits, min_permille, o, s, cap, tot))
+
+    def _segments_fastq(self, family, text, recs, seg_len, seg_step, min_hits, min_permille):
+        """kid_db_read_<family>_fastq over a block of FASTQ text"""
+        fn = getattr(self._lib, "kid_db_read_%s_fastq" % family)
+        text, recs, n = _fastq_block(text, recs)
+        step = seg_len if seg_step is None else seg_step
+        return self._read_segments(family, n, lambda o, s, cap, tot: fn(
+            self._h, _ptr(text), text.size, _ptr(recs), n, seg_len, step, min_hits, min_permille, o, s, cap, tot))
+
+    def _segments_device(self, family, d_bases, bases_nbytes, d_offsets, n_reads, seg_len, seg_step, d_seg_offsets, d_n_hits, d_n_segments,
+                         d_start, d_stop, min_hits, min_permille, d_hits, hits_cap, d_segments, seg_cap, stream):
+        """kid_db_read_<family>_device: everything resident in HBM"""
+        check(getattr(self._lib, "kid_db_read_%s_device" % family)(
+            self._h, C.c_void_p(d_bases), bases_nbytes, C.c_void_p(d_offsets), C.c_void_p(d_start or None), C.c_void_p(d_stop or None),
+            n_reads, seg_len, seg_len if seg_step is None else seg_step, min_hits, min_permille, C.c_void_p(d_hits or None), hits_cap,
+            C.c_void_p(d_seg_offsets), C.c_void_p(d_segments or None), seg_cap, C.c_void_p(d_n_hits), C.c_void_p(d_n_segments),
+            C.c_void_p(stream or None)))
 
     def read_segments(self, bases, offsets, start=None, stop=None, seg_len=1000, seg_step=None, min_hits=0, min_permille=0):
         """Call the records of a batch held in host memory in segments (kid_db_read_segments) -> ReadSegments.  A read
         with P window positions is cut into segments of seg_len positions, seg_step apart (None: seg_len; seg_len <=
         1024 * seg_step); each is called by its own hits under (min_hits, min_permille) as read_support calls a whole
         read.  `pos` is counted from the first byte of the read.  Pure: no sample is touched."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        step = seg_len if seg_step is None else seg_step
-        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segments(
-            self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n)
+        return self._segments_offsets("segments", bases, offsets, start, stop, seg_len, seg_step, min_hits, min_permille)
 
     def read_segments_fastq(self, text, recs, seg_len=1000, seg_step=None, min_hits=0, min_permille=0):
         """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
         fails stop - start >= k has no segment; KID_DB_OPT_MIN_BASE_QUALITY applies as in read_hits_fastq."""
-        text, recs, n = _fastq_block(text, recs)
-        step = seg_len if seg_step is None else seg_step
-        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segments_fastq(
-            self._h, _ptr(text), text.size, _ptr(recs), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n)
+        return self._segments_fastq("segments", text, recs, seg_len, seg_step, min_hits, min_permille)
 
     def read_segments_device(self, d_bases, bases_nbytes, d_offsets, n_reads, seg_len, seg_step, d_seg_offsets, d_n_hits, d_n_segments,
                              d_start=0, d_stop=0, min_hits=0, min_permille=0, d_hits=0, hits_cap=0, d_segments=0, seg_cap=0, stream=0):
         """Asynchronous, everything resident in HBM (raw pointers): kid_db_read_segments_device.  d_hits / hits_cap is the
         caller's scratch for the hits; no segment is written when the hits or the segments exceed their cap."""
-        check(self._lib.kid_db_read_segments_device(self._h, C.c_void_p(d_bases), bases_nbytes, C.c_void_p(d_offsets),
-                                                    C.c_void_p(d_start or None), C.c_void_p(d_stop or None), n_reads, seg_len,
-                                                    seg_len if seg_step is None else seg_step, min_hits, min_permille,
-                                                    C.c_void_p(d_hits or None), hits_cap, C.c_void_p(d_seg_offsets),
-                                                    C.c_void_p(d_segments or None), seg_cap, C.c_void_p(d_n_hits),
-                                                    C.c_void_p(d_n_segments), C.c_void_p(stream or None)))
+        self._segments_device("segments", d_bases, bases_nbytes, d_offsets, n_reads, seg_len, seg_step, d_seg_offsets, d_n_hits, d_n_segments,
+                              d_start, d_stop, min_hits, min_permille, d_hits, hits_cap, d_segments, seg_cap, stream)
 
     def read_segments_time(self):
         """-> (device ms, calls, reads) of the segment kernels alone since the last query"""
@@ -477,30 +480,19 @@ class KmerDB:
         -> ReadSegments over SEGMENT_VOTE_DTYPE.  The segments are those of read_segments; each is called by the vote
         rule of read_votes over its own hits, so the call does not depend on their order (nor on the strand the record
         was assembled on).  Pure: no sample is touched."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        step = seg_len if seg_step is None else seg_step
-        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segment_votes(
-            self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n,
-            SEGMENT_VOTE_DTYPE)
+        return self._segments_offsets("segment_votes", bases, offsets, start, stop, seg_len, seg_step, min_hits, min_permille)
 
     def read_segment_votes_fastq(self, text, recs, seg_len=1000, seg_step=None, min_hits=0, min_permille=0):
         """The same for a block of FASTQ text with its line index, as read_segments_fastq (a dropped record has no segment;
         KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply as there)."""
-        text, recs, n = _fastq_block(text, recs)
-        step = seg_len if seg_step is None else seg_step
-        return self._read_segments(lambda o, s, cap, tot: self._lib.kid_db_read_segment_votes_fastq(
-            self._h, _ptr(text), text.size, _ptr(recs), n, seg_len, step, min_hits, min_permille, o, s, cap, tot), n, SEGMENT_VOTE_DTYPE)
+        return self._segments_fastq("segment_votes", text, recs, seg_len, seg_step, min_hits, min_permille)
 
     def read_segment_votes_device(self, d_bases, bases_nbytes, d_offsets, n_reads, seg_len, seg_step, d_seg_offsets, d_n_hits, d_n_segments,
                                   d_start=0, d_stop=0, min_hits=0, min_permille=0, d_hits=0, hits_cap=0, d_segments=0, seg_cap=0, stream=0):
         """Asynchronous, everything resident in HBM (raw pointers): kid_db_read_segment_votes_device, argument for argument
         read_segments_device with kid_segment_vote[seg_cap] (SEGMENT_VOTE_DTYPE) at d_segments."""
-        check(self._lib.kid_db_read_segment_votes_device(self._h, C.c_void_p(d_bases), bases_nbytes, C.c_void_p(d_offsets),
-                                                         C.c_void_p(d_start or None), C.c_void_p(d_stop or None), n_reads, seg_len,
-                                                         seg_len if seg_step is None else seg_step, min_hits, min_permille,
-                                                         C.c_void_p(d_hits or None), hits_cap, C.c_void_p(d_seg_offsets),
-                                                         C.c_void_p(d_segments or None), seg_cap, C.c_void_p(d_n_hits),
-                                                         C.c_void_p(d_n_segments), C.c_void_p(stream or None)))
+        self._segments_device("segment_votes", d_bases, bases_nbytes, d_offsets, n_reads, seg_len, seg_step, d_seg_offsets, d_n_hits, d_n_segments,
+                              d_start, d_stop, min_hits, min_permille, d_hits, hits_cap, d_segments, seg_cap, stream)
 
     def read_segment_votes_time(self):
         """-> (device ms, calls, reads) of the segment scans and segment-vote kernels alone since the last query"""

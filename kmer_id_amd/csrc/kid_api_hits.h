@@ -2,10 +2,11 @@
 // What the other families over the hit pass -- kid_db_read_support* (kid_api_support.h), kid_db_read_fragments*
 // (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h), kid_db_read_votes* (kid_api_votes.h), kid_db_read_fragment_votes* (kid_api_fragment_votes.h),
 // kid_db_read_segment_votes* (kid_api_segment_votes.h) -- share with kid_db_read_hits* is here once:
-// KidSpanTimer, kid_hits_state (the scratch, free: the timers a family settles), kid_hits_scan (the three-kernel
-// exclusive scan), KidOpenBatch and kid_hits_open_* (a host-buffer batch checked, locked and staged, one function per
-// input form over kid_hits_stage_*), the hit pass into the library's own buffers (kid_hits_host_pass), the checks of
-// a CSR output.
+// KidSpanTimer, KidFamily and KidFamilyState (a family's id, and its share of the state under that id), KidVoteScratch
+// and kid_vote_scratch_bind (the scratch of a vote family's second kernel), kid_hits_state (the scratch, free: the
+// timers a family settles), kid_hits_scan (the three-kernel exclusive scan), KidOpenBatch and kid_hits_open_* (a
+// host-buffer batch checked, locked and staged, one function per input form over kid_hits_stage_*), the hit pass into
+// the library's own buffers (kid_hits_host_pass), the checks of a CSR output.
 #pragma once
 #include "kid_api_db.h"
 #include "kid_api_mask.h"
@@ -62,6 +63,36 @@ struct __attribute__((visibility("hidden"))) KidSpanTimer {
     }
 };
 
+// The families of calls over the hit pass (the files named on top).  A family's struct (KidSupportCalls, ..) names its id;
+// KidHitsState::family[id] is its share of the state, bit kid_settle(id) its timer in the mask of kid_hits_state.
+enum KidFamily : int {
+    KID_FAM_PASS = -1, // (kid_hits_take_time: the hit pass, which is not a family)
+    KID_FAM_SEGMENTS,
+    KID_FAM_SEGMENT_VOTES,
+    KID_FAM_SUPPORT,
+    KID_FAM_FRAGMENTS,
+    KID_FAM_VOTES,
+    KID_FAM_FRAGMENT_VOTES,
+    KID_FAM_COUNT
+};
+constexpr unsigned kid_settle(KidFamily f) { return 1u << f; }
+// What every call waits for beside the pass, whatever its family: the segment and segment-vote kernels read the tiles'
+// scratch behind the pass (and the segment-vote kernels the vote family's rows).
+constexpr unsigned KID_SETTLE_ALWAYS = kid_settle(KID_FAM_SEGMENTS) | kid_settle(KID_FAM_SEGMENT_VOTES);
+
+struct KidFamilyState {
+    KidDevBuf out;      // the host forms' records
+    KidSpanTimer timer; // the family's kernels alone, behind the pass
+};
+
+// What the second kernel of a vote family works on: the units its first kernel leaves to it (with more than
+// KID_VOTE_WAVE_HITS hits) and their number (one word), one row uint32[ntar] per workgroup (num_cu of them), zero between
+// calls.  One set per family and kid_db: a family's settle mask names whoever may still be using the set it binds.
+struct KidVoteScratch {
+    KidDevBuf list, n_list, own_rows;
+    KidDevBuf *rows = &own_rows; // (the segment-vote family's: the vote family's, KidHitsState())
+};
+
 struct KidHitsState {
     KidDevBuf desc, tile_off, rsum, tile_mask, tile_hit_off, tsum, trim_start, trim_stop;          // every form
     KidDevBuf in_bases, in_offsets, in_start, in_stop, in_recs, out_offsets, out_nk, out_hits;      // host-buffer forms
@@ -71,31 +102,20 @@ struct KidHitsState {
     // then a KidRareArgs (the prepare kernels announce the batch's longest read there; nobody reads it)
     KidDevBuf ctl_buf;
     uint32_t seq = 0;
-    KidDevBuf out_support; // kid_db_read_support* (kid_api_support.h): the host forms' records
-    KidSpanTimer pass;     // the hit pass of every call, a kid_db_read_support* host call's included
-    KidSpanTimer support;  // the support kernel alone
-    KidDevBuf out_fragments; // kid_db_read_fragments* (kid_api_fragments.h): the host forms' records
-    KidSpanTimer fragments;  // the fragment kernel alone
-    // kid_db_read_segments* (kid_api_segments.h): per tile the mask of its lanes that hold a k-mer and their scan (the hit
-    // pass stores the mask while want_valid is set: the buffer is sized for the batch then), [0] the batch's segments and
-    // [1] its valid windows, the host forms' offsets and records
-    KidDevBuf tile_valid, tile_valid_off, seg_ctl, out_seg_offsets, out_segments;
+    KidSpanTimer pass; // the hit pass of every call, a family's host call's included
+    KidFamilyState family[KID_FAM_COUNT];
+    // kid_db_read_segments*, kid_db_read_segment_votes* (kid_api_segments.h): per tile the mask of its lanes that hold a
+    // k-mer and their scan (the hit pass stores the mask while want_valid is set: the buffer is sized for the batch then),
+    // [0] the batch's segments and [1] its valid windows, the host forms' offsets
+    KidDevBuf tile_valid, tile_valid_off, seg_ctl, out_seg_offsets;
     bool want_valid = false;
-    KidSpanTimer segments; // the segment kernels alone
-    // kid_db_read_votes* (kid_api_votes.h): the host forms' records; the reads kid_vote_kernel leaves to
-    // kid_vote_big_kernel (uint32 per read of the largest batch) and their number (one word); one row uint32[ntar] per
-    // workgroup of that kernel, zero between calls
-    KidDevBuf out_votes, vote_list, vote_n_list, vote_rows;
-    KidSpanTimer votes; // the two vote kernels alone
-    // kid_db_read_fragment_votes* (kid_api_fragment_votes.h): the same set once more, of its own (a vote call and a
-    // fragment-vote call queued on two streams never share a list or a row); the list holds fragment indexes
-    KidDevBuf out_fragment_votes, fvote_list, fvote_n_list, fvote_rows;
-    KidSpanTimer fragment_votes; // the two fragment-vote kernels alone
-    // kid_db_read_segment_votes* (kid_api_segment_votes.h): the host forms' records; the segments its first kernel leaves
-    // to the second (24 B per segment the call can write) and their number.  The rows are vote_rows
-    KidDevBuf out_segment_votes, svote_list, svote_n_list;
-    KidSpanTimer segment_votes; // the segment scans and the two segment-vote kernels alone
+    // kid_db_read_votes* (a list of uint32 per read of the largest batch), kid_db_read_fragment_votes* (the same set once
+    // more, of its own: a vote call and a fragment-vote call queued on two streams never share a list or a row; the list
+    // holds fragment indexes), kid_db_read_segment_votes* (a list of 24 B per segment the call can write, and the vote
+    // family's rows)
+    KidVoteScratch vote_big, fragment_vote_big, segment_vote_big;
     KidDevBuf lowc_plane; // KID_DB_OPT_LOW_COMPLEXITY: the flag plane of a staged block with a line that is split (kid_lowc.hip.h)
+    KidHitsState() { segment_vote_big.rows = &vote_big.own_rows; }
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }
 };
 #define KID_HITS_CTL_WORDS 36u
@@ -105,11 +125,25 @@ kid_db::~kid_db() {}
 // a little slack: batches of a file differ slightly in size
 static hipError_t kid_hits_ensure(KidDevBuf &b, uint64_t nbytes) { return b.ensure(nbytes, ((nbytes + nbytes / 8) + 255u) & ~255ull); }
 
-// The scratch, free: the hit pass of the call before, and the segment and segment-vote kernels behind it, are through (they read the
-// tiles' scratch behind the pass) -- and of the kernels that read the pass's CSR alone those that `settle` names: a call
-// waits for the timers its family has always waited for, no more (a device-form caller that queues hits -> support on
-// a stream of its own does not block in the next kid_db_read_hits_device).
-enum : unsigned { KID_SETTLE_SUPPORT = 1u, KID_SETTLE_FRAGMENTS = 2u, KID_SETTLE_VOTES = 4u, KID_SETTLE_FRAGMENT_VOTES = 8u };
+// The units of a batch bound to a vote scratch on `stream`: a list of list_nbytes, the rows grown to num_cu * ntar words
+// (the kernels leave them zero: only new ones are zeroed), no unit on the list.
+static int kid_vote_scratch_bind(const kid_db *db, KidVoteScratch &s, uint64_t list_nbytes, hipStream_t stream)
+{
+    const size_t rows_nbytes = (size_t)db->num_cu * (size_t)db->d.ntar * 4u;
+    KID_HIP(kid_hits_ensure(s.list, list_nbytes));
+    if (!s.n_list.p) KID_HIP(s.n_list.alloc(4));
+    if (rows_nbytes > s.rows->cap) {
+        KID_HIP(s.rows->alloc(rows_nbytes));
+        KID_HIP(hipMemsetAsync(s.rows->p, 0, rows_nbytes, stream));
+    }
+    KID_HIP(hipMemsetAsync(s.n_list.p, 0, 4, stream));
+    return KID_OK;
+}
+
+// The scratch, free: the hit pass of the call before and the kernels of KID_SETTLE_ALWAYS are through -- and of the
+// kernels that read the pass's CSR alone those that `settle` names: a call waits for the timers its family has always
+// waited for, no more (a device-form caller that queues hits -> support on a stream of its own does not block in the
+// next kid_db_read_hits_device).
 static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
 {
     if (!db->hits) {
@@ -118,22 +152,13 @@ static int kid_hits_state(kid_db *db, unsigned settle, KidHitsState **out)
         KID_HIP(h->ctl_buf.alloc(nb));
         KID_HIP(hipMemset(h->ctl(), 0, nb));
         KID_HIP(h->pass.create());
-        KID_HIP(h->support.create());
-        KID_HIP(h->fragments.create());
-        KID_HIP(h->segments.create());
-        KID_HIP(h->votes.create());
-        KID_HIP(h->fragment_votes.create());
-        KID_HIP(h->segment_votes.create());
+        for (KidFamilyState &f : h->family) KID_HIP(f.timer.create());
         db->hits = std::move(h);
     }
     KidHitsState *h = *out = db->hits.get();
     int rc = h->pass.settle();
-    if (rc == KID_OK) rc = h->segments.settle();
-    if (rc == KID_OK) rc = h->segment_votes.settle(); // (they read the tiles' scratch too, and vote_rows)
-    if (rc == KID_OK && (settle & KID_SETTLE_SUPPORT)) rc = h->support.settle();
-    if (rc == KID_OK && (settle & KID_SETTLE_FRAGMENTS)) rc = h->fragments.settle();
-    if (rc == KID_OK && (settle & KID_SETTLE_VOTES)) rc = h->votes.settle(); // (its list and rows are one set per kid_db)
-    if (rc == KID_OK && (settle & KID_SETTLE_FRAGMENT_VOTES)) rc = h->fragment_votes.settle(); // (so are this family's)
+    for (unsigned f = 0; f < KID_FAM_COUNT && rc == KID_OK; f++)
+        if ((settle | KID_SETTLE_ALWAYS) >> f & 1u) rc = h->family[f].timer.settle();
     return rc;
 }
 
@@ -478,9 +503,9 @@ extern "C" int kid_db_read_hits_device(kid_db *db, const void *d_bases, uint64_t
     return h->pass.end(st, n_reads);
 }
 
-// kid_db_read_hits_time / kid_db_read_support_time: one of the state's timers, settled and taken; check: report what
-// the prepare kernels refused since the last query as well
-static int kid_hits_take_time(kid_db *db, KidSpanTimer KidHitsState::*timer, bool check, double *device_ms, uint64_t *calls, uint64_t *reads)
+// kid_db_read_hits_time and every family's *_time: the timer of the pass or of a family, settled and taken; the pass's
+// query reports what the prepare kernels refused since the last query as well
+static int kid_hits_take_time(kid_db *db, KidFamily f, double *device_ms, uint64_t *calls, uint64_t *reads)
 {
     if (!db) return kid_fail(KID_ERR_ARG, "null argument");
     if (device_ms) *device_ms = 0;
@@ -491,12 +516,13 @@ static int kid_hits_take_time(kid_db *db, KidSpanTimer KidHitsState::*timer, boo
     if (!h) return KID_OK;
     int rc = kid_use_device(db->device);
     if (rc != KID_OK) return rc;
-    if ((rc = (h->*timer).settle()) != KID_OK) return rc;
-    (h->*timer).take(device_ms, calls, reads);
-    return check ? kid_hits_check(h) : KID_OK;
+    KidSpanTimer &timer = f == KID_FAM_PASS ? h->pass : h->family[f].timer;
+    if ((rc = timer.settle()) != KID_OK) return rc;
+    timer.take(device_ms, calls, reads);
+    return f == KID_FAM_PASS ? kid_hits_check(h) : KID_OK;
 }
 
 extern "C" int kid_db_read_hits_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads)
 {
-    return kid_hits_take_time(db, &KidHitsState::pass, true, device_ms, calls, reads);
+    return kid_hits_take_time(db, KID_FAM_PASS, device_ms, calls, reads);
 }

@@ -3,11 +3,11 @@
 // and the two kernels of kid_segment_votes.hip.h.  The family is KidSegmentVoteCalls on the three forms of
 // kid_api_segments.h (kid_segment_calls_*), so the quartet is kid_db_read_segments* argument for argument, check for
 // check; its launch binds the scratch and queues the two kernels behind each other.  The kernels run between the two
-// events of the timer `segment_votes`; like the segment kernels they read the tiles' scratch behind the pass, so every
-// later call on the database waits for them (kid_hits_state).  The scratch:
+// events of the family's timer; like the segment kernels they read the tiles' scratch behind the pass, so every
+// later call on the database waits for them (KID_SETTLE_ALWAYS).  The scratch is KidHitsState::segment_vote_big:
 // the list of segments with more than KID_VOTE_WAVE_HITS hits (24 B per segment the call can write: the host forms know
-// the total, the device form has seg_cap) and its length are the family's own; the rows are KidHitsState::vote_rows,
-// the vote family's -- a call settles KID_SETTLE_SUPPORT | KID_SETTLE_VOTES before it binds them, and a vote call waits
+// the total, the device form has seg_cap) and its length are the family's own; the rows are the vote family's
+// (vote_big.own_rows) -- a call settles the support and vote timers before it binds them, and a vote call waits
 // for this family's timer as every call does.  Included behind kid_api_segments.h and kid_api_votes.h.
 #pragma once
 #include "kid_api_segments.h"
@@ -18,27 +18,20 @@ static_assert(sizeof(kid_segment_vote) == sizeof(KidSegmentVote) && sizeof(KidSe
 
 struct KidSegmentVoteCalls {
     typedef KidSegmentVote Rec;
-    static constexpr unsigned settle = KID_SETTLE_SUPPORT | KID_SETTLE_VOTES;
-    static constexpr KidDevBuf KidHitsState::*out = &KidHitsState::out_segment_votes;
-    static constexpr KidSpanTimer KidHitsState::*timer = &KidHitsState::segment_votes;
+    static constexpr KidFamily id = KID_FAM_SEGMENT_VOTES;
+    static constexpr unsigned settle = kid_settle(KID_FAM_SUPPORT) | kid_settle(KID_FAM_VOTES);
     // a.seg_cap: the segments the call can write, which the list is sized for
     static int launch(kid_db *db, KidHitsState *h, const KidSegmentsIn &a, KidSegGeom g, KidSupportRule rule, KidSegmentVote *d_segments,
                       hipStream_t stream)
     {
-        const unsigned big_grid = (unsigned)db->num_cu;
-        const size_t rows_nbytes = (size_t)big_grid * (size_t)db->d.ntar * 4u;
-        KID_HIP(kid_hits_ensure(h->svote_list, a.seg_cap * sizeof(KidSegmentVoteEntry)));
-        if (!h->svote_n_list.p) KID_HIP(h->svote_n_list.alloc(4));
-        if (rows_nbytes > h->vote_rows.cap) { // (the kernels leave it zero)
-            KID_HIP(h->vote_rows.alloc(rows_nbytes));
-            KID_HIP(hipMemsetAsync(h->vote_rows.p, 0, rows_nbytes, stream));
-        }
-        const KidSegmentVoteBig big{h->svote_list.as<KidSegmentVoteEntry>(), h->svote_n_list.as<uint32_t>(), h->vote_rows.as<uint32_t>(), a.seg_cap};
-        KID_HIP(hipMemsetAsync(big.n_list, 0, 4, stream));
+        KidVoteScratch &s = h->segment_vote_big;
+        const int rc = kid_vote_scratch_bind(db, s, a.seg_cap * sizeof(KidSegmentVoteEntry), stream);
+        if (rc != KID_OK) return rc;
+        const KidSegmentVoteBig big{s.list.as<KidSegmentVoteEntry>(), s.n_list.as<uint32_t>(), s.rows->as<uint32_t>(), a.seg_cap};
         const dim3 grid(kid_grid_for(a.seg_cap, 256, db->num_cu * 8)), block(256);
         kid_lift(db->d.rows != nullptr, [&](auto rows) {
             hipLaunchKernelGGL((kid_segment_votes_kernel<decltype(rows)::value>), grid, block, 0, stream, db->d, a, g, rule, d_segments, big);
-            hipLaunchKernelGGL((kid_segment_votes_big_kernel<decltype(rows)::value>), dim3(big_grid), block, 0, stream, db->d, a, g, rule,
+            hipLaunchKernelGGL((kid_segment_votes_big_kernel<decltype(rows)::value>), dim3(db->num_cu), block, 0, stream, db->d, a, g, rule,
                                d_segments, big);
         });
         return KID_OK;
@@ -73,5 +66,5 @@ extern "C" int kid_db_read_segment_votes_device(kid_db *db, const void *d_bases,
 
 extern "C" int kid_db_read_segment_votes_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads)
 {
-    return kid_hits_take_time(db, &KidHitsState::segment_votes, false, device_ms, calls, reads);
+    return kid_hits_take_time(db, KidSegmentVoteCalls::id, device_ms, calls, reads);
 }

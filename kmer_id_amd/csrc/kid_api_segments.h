@@ -4,8 +4,8 @@
 // (kid_hits_open_*, kid_hits_host_pass with every hit filled in); the device form runs kid_hits_launch into the caller's
 // hit buffer.  While one of these calls runs, the hit pass also leaves the tiles' valid masks (KidHitsState::want_valid,
 // sized by kid_segments_size).  The segment kernels -- segments per read and their scan, the scan of the valid masks
-// (both kid_hits_scan), kid_segments_kernel -- follow the pass on its stream and have the third KidSpanTimer of the
-// state.  A call settles the pass, segments and support timers, not the fragments one.
+// (both kid_hits_scan), kid_segments_kernel -- follow the pass on its stream and have the KidSpanTimer of the family's
+// KidFamilyState.  A call settles the pass, what every call waits for (KID_SETTLE_ALWAYS) and the support timer.
 #pragma once
 #include "kid_api_support.h"
 #include "kid_segments.hip.h"
@@ -56,15 +56,14 @@ static int kid_segments_launch_scans(kid_db *db, KidHitsState *h, uint64_t n, ui
 
 // A family of segment calls -- KidSegmentCalls here, KidSegmentVoteCalls in kid_api_segment_votes.h -- is a struct with
 //   Rec      its device record (= the C ABI's)
+//   id       its KidFamilyState in KidHitsState: the host forms' records, the timer of its kernels
 //   settle   the timers it waits for before the scratch is its own (kid_hits_state)
-//   out      the host forms' records in KidHitsState, `timer` its KidSpanTimer there
 //   launch   its kernels behind the scans over the batch `a` on `stream`, the grid sized for a.seg_cap segments
 // and kid_segment_calls_* below are its three forms, once: the checks, the hit pass, the scans, the launch, the downloads.
 struct KidSegmentCalls {
     typedef KidSegment Rec;
-    static constexpr unsigned settle = KID_SETTLE_SUPPORT;
-    static constexpr KidDevBuf KidHitsState::*out = &KidHitsState::out_segments;
-    static constexpr KidSpanTimer KidHitsState::*timer = &KidHitsState::segments;
+    static constexpr KidFamily id = KID_FAM_SEGMENTS;
+    static constexpr unsigned settle = kid_settle(KID_FAM_SUPPORT);
     static int launch(kid_db *db, KidHitsState *, const KidSegmentsIn &a, KidSegGeom g, KidSupportRule rule, KidSegment *d_segments,
                       hipStream_t stream)
     {
@@ -110,8 +109,8 @@ static int kid_segment_calls_host_run(kid_db *db, const KidOpenBatch &ob, KidSeg
 {
     typedef typename F::Rec Rec;
     KidHitsState *h = ob.h;
-    KidSpanTimer &timer = h->*F::timer;
-    KidDevBuf &d_out = h->*F::out;
+    KidSpanTimer &timer = h->family[F::id].timer;
+    KidDevBuf &d_out = h->family[F::id].out;
     const KidWantValid valid(h);
     const uint64_t n = ob.b.n, limit = segments ? cap : 0;
     uint64_t n_hits = 0, total = 0;
@@ -191,7 +190,7 @@ static int kid_segment_calls_device(kid_db *db, const void *d_bases, uint64_t ba
     if ((rc = kid_hits_state(db, F::settle, &h)) != KID_OK) return rc;
     if ((rc = kid_segments_size(h, max_tiles)) != KID_OK) return rc;
     KidWantValid valid(h);
-    KidSpanTimer &timer = h->*F::timer;
+    KidSpanTimer &timer = h->family[F::id].timer;
     KID_HIP(kid_hits_ensure(h->out_offsets, (n_reads + 1) * 8)); // (the hit pass wants a place for its CSR offsets)
     rc = kid_hits_launch(db, h, b, nullptr, max_tiles, h->out_offsets.as<uint64_t>(), nullptr, (KidHit *)d_hits, hits_cap, (uint64_t *)d_n_hits, st, true);
     if (rc != KID_OK) return rc;
@@ -236,5 +235,5 @@ extern "C" int kid_db_read_segments_device(kid_db *db, const void *d_bases, uint
 
 extern "C" int kid_db_read_segments_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads)
 {
-    return kid_hits_take_time(db, &KidHitsState::segments, false, device_ms, calls, reads);
+    return kid_hits_take_time(db, KidSegmentCalls::id, device_ms, calls, reads);
 }

@@ -1,23 +1,34 @@
 // kid_api_support.h -- call reads by k-mer support: kid_db_read_support* over the hit pass and kid_support_kernel
 // (kid_support.hip.h) -- and, once, the call path of every family that leaves one record per unit of the batch behind
 // the hit pass (kid_calls_*): the argument checks, the host run with the binding of a tally, the launch between the
-// family's two events, the *_from_hits_device form.  A family is a struct like KidSupportCalls below; the others are
-// KidFragmentCalls (kid_api_fragments.h), whose unit is two reads, KidVoteCalls (kid_api_votes.h), which queues two
-// kernels through the hook of kid_calls_queue, and KidFragmentVoteCalls (kid_api_fragment_votes.h), which does both.
+// family's two events, and the four forms (kid_calls_offsets, _fastq, _fastq_pairs, _from_hits_device) that the
+// families' extern "C" functions forward to.  A family is a struct like KidSupportCalls below; the others are
+// KidFragmentCalls (kid_api_fragments.h), whose unit is two reads, KidVoteCalls (kid_api_votes.h), which has a second
+// kernel over a KidVoteScratch, and KidFragmentVoteCalls (kid_api_fragment_votes.h), which has both.
 // The host-buffer forms open their batch with kid_hits_open_* and run the hit pass with kid_hits_host_pass
 // (kid_api_hits.h).  Included behind the sample handle: a tally counts into one.
 #pragma once
 #include "kid_api_hits.h"
 #include "kid_support.hip.h"
+#include "kid_votes.hip.h"
 
 static_assert(sizeof(kid_support) == sizeof(KidSupport), "kid_support is the device record");
 
+// A family of these calls is a struct with
+//   Rec            its device record (= the C ABI's)
+//   id             its KidFamilyState in KidHitsState: the host forms' records, the timer of its kernels
+//   unit_reads     the reads of the batch that one record is about
+//   needs_sink     whether a call with neither `out` nor `tally` is refused
+//   settle         the timers it waits for before the scratch is its own (kid_hits_state)
+//   kernel()       its kernel over the units of a batch, and where it has a second one for the units with many hits:
+//   big            the KidVoteScratch of KidHitsState the two share (the others: null), big_kernel() the second
 struct KidSupportCalls {
     typedef KidSupport Rec;
+    static constexpr KidFamily id = KID_FAM_SUPPORT;
     static constexpr uint64_t unit_reads = 1;
-    static constexpr unsigned settle = KID_SETTLE_SUPPORT;
-    static constexpr KidDevBuf KidHitsState::*out = &KidHitsState::out_support;     // the host forms' records
-    static constexpr KidSpanTimer KidHitsState::*timer = &KidHitsState::support;    // the kernel alone
+    static constexpr bool needs_sink = false;
+    static constexpr unsigned settle = kid_settle(KID_FAM_SUPPORT);
+    static constexpr KidVoteScratch KidHitsState::*big = nullptr;
     template <bool ROWS, bool TALLY, bool DEPTH> static constexpr auto kernel() { return &kid_support_kernel<ROWS, TALLY, DEPTH>; }
 };
 
@@ -36,7 +47,8 @@ static int kid_support_check_tally(const kid_db *db, const kid_sample *tally)
 }
 
 // what every form of a family refuses first, in the order callers see
-template <class F> static int kid_calls_check_args(const kid_db *db, uint64_t n_reads, uint32_t min_permille, const kid_sample *tally)
+template <class F>
+static int kid_calls_check_args(const kid_db *db, uint64_t n_reads, uint32_t min_permille, const void *out, const kid_sample *tally)
 {
     if (!db) return kid_fail(KID_ERR_ARG, "null argument");
     int rc = kid_support_check_rule(min_permille);
@@ -45,23 +57,25 @@ template <class F> static int kid_calls_check_args(const kid_db *db, uint64_t n_
     if (rc != KID_OK) return rc;
     if (n_reads % F::unit_reads)
         return kid_fail(KID_ERR_ARG, "n_reads = %llu is odd: a batch of fragments holds two reads each", (unsigned long long)n_reads);
+    if (F::needs_sink && n_reads && !out && !tally) return kid_fail(KID_ERR_ARG, "null argument");
     return KID_OK;
 }
 
-// What a family queues between its timer's two events.  A family without a hook: its kernel() over the grid.  The
-// optional hook: a static F::queue<ROWS, TALLY, DEPTH>(db, h, grid, stream, the kernel's arguments...) -> status, in
-// which the family binds scratch of its own to the batch and queues what it needs (KidVoteCalls: a second kernel
-// behind the first).  The first overload is the better match and drops out where F has no such member.
+// What a family queues between its timer's two events: its kernel over the grid, and where it has a second kernel, the
+// scratch bound to the batch of n units, both kernels with the scratch as their last argument, the second over one
+// workgroup per row: it reads the list's length on the device, there is no host round trip.
 template <class F, bool ROWS, bool TALLY, bool DEPTH, class... A>
-static auto kid_calls_queue(int, kid_db *db, KidHitsState *h, dim3 grid, hipStream_t stream, A... a)
-    -> decltype(F::template queue<ROWS, TALLY, DEPTH>(db, h, grid, stream, a...))
+static int kid_calls_queue(kid_db *db, KidHitsState *h, dim3 grid, hipStream_t stream, uint64_t n, A... a)
 {
-    return F::template queue<ROWS, TALLY, DEPTH>(db, h, grid, stream, a...);
-}
-template <class F, bool ROWS, bool TALLY, bool DEPTH, class... A>
-static int kid_calls_queue(long, kid_db *, KidHitsState *, dim3 grid, hipStream_t stream, A... a)
-{
-    hipLaunchKernelGGL((F::template kernel<ROWS, TALLY, DEPTH>()), grid, dim3(256), 0, stream, a...);
+    if constexpr (F::big != nullptr) {
+        KidVoteScratch &s = h->*F::big;
+        const int rc = kid_vote_scratch_bind(db, s, n * 4u, stream);
+        if (rc != KID_OK) return rc;
+        const KidVoteBig big{s.list.as<uint32_t>(), s.n_list.as<uint32_t>(), s.rows->as<uint32_t>()};
+        hipLaunchKernelGGL((F::template kernel<ROWS, TALLY, DEPTH>()), grid, dim3(256), 0, stream, a..., big);
+        hipLaunchKernelGGL((F::template big_kernel<ROWS, TALLY, DEPTH>()), dim3(db->num_cu), dim3(256), 0, stream, a..., big);
+    } else
+        hipLaunchKernelGGL((F::template kernel<ROWS, TALLY, DEPTH>()), grid, dim3(256), 0, stream, a...);
     return KID_OK;
 }
 
@@ -71,7 +85,7 @@ static int kid_calls_launch(kid_db *db, KidHitsState *h, const uint64_t *d_hit_o
                             uint64_t n, KidSupportRule rule, typename F::Rec *d_out, const KidSupportTally *t, hipStream_t stream)
 {
     const dim3 grid(kid_grid_for(n, 256, db->num_cu * 8));
-    KidSpanTimer &timer = h->*F::timer;
+    KidSpanTimer &timer = h->family[F::id].timer;
     int rc = timer.begin(stream);
     if (rc != KID_OK) return rc;
     kid_lift(db->d.rows != nullptr, [&](auto rows) {
@@ -79,7 +93,7 @@ static int kid_calls_launch(kid_db *db, KidHitsState *h, const uint64_t *d_hit_o
             kid_lift(t != nullptr && t->depth != nullptr, [&](auto depth) { // the depth form exists for a tally alone
                 if constexpr (decltype(tally)::value || !decltype(depth)::value)
                     rc = kid_calls_queue<F, decltype(rows)::value, decltype(tally)::value, decltype(depth)::value>(
-                        0, db, h, grid, stream, db->d, d_hit_offsets, d_hits, d_n_kmers, n, rule, d_out, t ? *t : KidSupportTally{});
+                        db, h, grid, stream, n, db->d, d_hit_offsets, d_hits, d_n_kmers, n, rule, d_out, t ? *t : KidSupportTally{});
             });
         });
     });
@@ -95,11 +109,11 @@ template <class F>
 static int kid_calls_host_run(kid_db *db, const KidOpenBatch &ob, KidSupportRule rule, void *out, kid_sample *tally)
 {
     KidHitsState *h = ob.h;
-    const KidDevBuf &d_out = h->*F::out;
+    KidDevBuf &d_out = h->family[F::id].out;
     const uint64_t n = ob.b.n / F::unit_reads, out_nbytes = n * sizeof(typename F::Rec);
     uint64_t total = 0;
     int rc;
-    if (out) KID_HIP(kid_hits_ensure(h->*F::out, out_nbytes));
+    if (out) KID_HIP(kid_hits_ensure(d_out, out_nbytes));
     if ((rc = kid_hits_host_pass(db, ob, KID_HITS_NO_LIMIT, &total)) != KID_OK) return rc;
     // what the prepare kernels refuse (a range outside its read, a short quality line) is refused before anything is counted
     if ((rc = kid_hits_check(h)) != KID_OK) return rc;
@@ -121,12 +135,55 @@ static int kid_calls_host_run(kid_db *db, const KidOpenBatch &ob, KidSupportRule
     return KID_OK;
 }
 
+// The forms of a family, once; every one checks with kid_calls_check_args first.  A batch of reads in host memory:
+template <class F>
+static int kid_calls_offsets(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                             uint64_t n_reads, uint32_t min_hits, uint32_t min_permille, void *out, kid_sample *tally)
+{
+    int rc = kid_calls_check_args<F>(db, n_reads, min_permille, out, tally);
+    if (rc != KID_OK || n_reads == 0) return rc;
+    KidOpenBatch ob;
+    if ((rc = kid_hits_open_offsets(ob, db, bases, offsets, start, stop, n_reads, F::settle)) != KID_OK) return rc;
+    return kid_calls_host_run<F>(db, ob, KidSupportRule{min_hits, min_permille}, out, tally);
+}
+
+// a block of FASTQ text with its line index
+template <class F>
+static int kid_calls_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                           uint32_t min_hits, uint32_t min_permille, void *out, kid_sample *tally)
+{
+    int rc = kid_calls_check_args<F>(db, n_reads, min_permille, out, tally);
+    if (rc != KID_OK || n_reads == 0) return rc;
+    KidOpenBatch ob;
+    if ((rc = kid_hits_open_fastq(ob, db, text, text_nbytes, recs, n_reads, F::settle)) != KID_OK) return rc;
+    return kid_calls_host_run<F>(db, ob, KidSupportRule{min_hits, min_permille}, out, tally);
+}
+
+// two blocks of FASTQ text, the mates of n_fragments fragments (a family whose unit is two reads)
+template <class F>
+static int kid_calls_fastq_pairs(kid_db *db, const uint8_t *text1, uint64_t nbytes1, const kid_fastq_rec *recs1, const uint8_t *text2,
+                                 uint64_t nbytes2, const kid_fastq_rec *recs2, uint64_t n_fragments, uint32_t min_hits, uint32_t min_permille,
+                                 void *out, kid_sample *tally)
+{
+    static_assert(F::unit_reads == 2, "a pair of blocks holds fragments");
+    if (n_fragments > 0x3FFFFFFFull) return kid_fail(KID_ERR_ARG, "at most 2^30-1 fragments per batch");
+    int rc = kid_calls_check_args<F>(db, 2 * n_fragments, min_permille, out, tally);
+    if (rc != KID_OK || n_fragments == 0) return rc;
+    if (!recs1 || !recs2 || (!text1 && nbytes1) || (!text2 && nbytes2)) return kid_fail(KID_ERR_ARG, "null argument");
+    // one staged text: the shifted offsets of block 2 are 32-bit like every kid_fastq_rec
+    if (nbytes1 + nbytes2 < nbytes1 || nbytes1 + nbytes2 >= 0xFFFFFFFFull) return kid_fail(KID_ERR_ARG, "two FASTQ blocks of 4 GiB or more together");
+    KidOpenBatch ob;
+    rc = kid_hits_open_fastq(ob, db, text1, nbytes1, recs1, 2 * n_fragments, F::settle, nullptr, text2, nbytes2, recs2);
+    if (rc != KID_OK) return rc;
+    return kid_calls_host_run<F>(db, ob, KidSupportRule{min_hits, min_permille}, out, tally);
+}
+
 // the family's kernel over a hit CSR in device memory (the caller's, or what kid_db_read_hits_device left)
 template <class F>
 static int kid_calls_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
                                       uint32_t min_hits, uint32_t min_permille, void *d_out, void *stream)
 {
-    int rc = kid_calls_check_args<F>(db, n_reads, min_permille, nullptr);
+    int rc = kid_calls_check_args<F>(db, n_reads, min_permille, d_out, nullptr);
     if (rc != KID_OK) return rc;
     if (n_reads && (!d_hit_offsets || !d_n_kmers || !d_out)) return kid_fail(KID_ERR_ARG, "null argument");
     if ((rc = kid_use_device(db->device)) != KID_OK) return rc;
@@ -142,21 +199,13 @@ static int kid_calls_from_hits_device(kid_db *db, const void *d_hit_offsets, con
 extern "C" int kid_db_read_support(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
                                    uint64_t n_reads, uint32_t min_hits, uint32_t min_permille, kid_support *out, kid_sample *tally)
 {
-    int rc = kid_calls_check_args<KidSupportCalls>(db, n_reads, min_permille, tally);
-    if (rc != KID_OK || n_reads == 0) return rc;
-    KidOpenBatch ob;
-    if ((rc = kid_hits_open_offsets(ob, db, bases, offsets, start, stop, n_reads, KidSupportCalls::settle)) != KID_OK) return rc;
-    return kid_calls_host_run<KidSupportCalls>(db, ob, KidSupportRule{min_hits, min_permille}, out, tally);
+    return kid_calls_offsets<KidSupportCalls>(db, bases, offsets, start, stop, n_reads, min_hits, min_permille, out, tally);
 }
 
 extern "C" int kid_db_read_support_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
                                          uint32_t min_hits, uint32_t min_permille, kid_support *out, kid_sample *tally)
 {
-    int rc = kid_calls_check_args<KidSupportCalls>(db, n_reads, min_permille, tally);
-    if (rc != KID_OK || n_reads == 0) return rc;
-    KidOpenBatch ob;
-    if ((rc = kid_hits_open_fastq(ob, db, text, text_nbytes, recs, n_reads, KidSupportCalls::settle)) != KID_OK) return rc;
-    return kid_calls_host_run<KidSupportCalls>(db, ob, KidSupportRule{min_hits, min_permille}, out, tally);
+    return kid_calls_fastq<KidSupportCalls>(db, text, text_nbytes, recs, n_reads, min_hits, min_permille, out, tally);
 }
 
 extern "C" int kid_db_support_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
@@ -167,5 +216,5 @@ extern "C" int kid_db_support_from_hits_device(kid_db *db, const void *d_hit_off
 
 extern "C" int kid_db_read_support_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads)
 {
-    return kid_hits_take_time(db, &KidHitsState::support, false, device_ms, calls, reads);
+    return kid_hits_take_time(db, KidSupportCalls::id, device_ms, calls, reads);
 }

@@ -21,21 +21,19 @@ KID_VOTE_WAVE_HITS); every read draws one of six shapes (SHAPES) and its n_kmers
 32-bit product says it is.  Reads 2i and 2i + 1 are the mates of fragment i.  pos and entry count up: nothing here tallies.
 """
 import functools
-import os
-import re
 
 import numpy as np
 
-from helpers import ROOT, oracle_db
+from helpers import oracle_db
+from read_calls import header_constant
 from read_fragments_model import FRAGMENT_DTYPE, fragment_csr
 from read_hits_model import HitModel, Hits
 from read_support_cases import random_keys
 from read_support_model import SupportModel
 from read_votes_model import VoteModel
 
-_HEADER = open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_votes.hip.h")).read()
-LANE_HITS = int(re.search(r"#define\s+KID_VOTE_LANE_HITS\s+(\d+)u", _HEADER).group(1))
-WAVE_HITS = int(re.search(r"#define\s+KID_VOTE_WAVE_HITS\s+(\d+)u", _HEADER).group(1))
+LANE_HITS = header_constant("kid_votes.hip.h", "KID_VOTE_LANE_HITS")
+WAVE_HITS = header_constant("kid_votes.hip.h", "KID_VOTE_WAVE_HITS")
 
 TREES = {"rows8": (300, 8), "climb9": (300, 9), "flat": (201, 1), "wide_rows": (65536, 4), "wide_climb": (65537, 4)}
 M_VALUES = [0, 1, 2, LANE_HITS - 1, LANE_HITS, LANE_HITS + 1, 63, 64, 65, 127, 128, 129, WAVE_HITS - 1, WAVE_HITS, WAVE_HITS + 1,

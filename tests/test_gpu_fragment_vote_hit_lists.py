@@ -11,6 +11,7 @@ import pytest
 import hit_list_cases as hc
 from helpers import DeviceCsr
 from kmer_id_amd import FRAGMENT_VOTE_DTYPE, VOTE_DTYPE, KidError, KmerDB, _lib
+from read_calls import same_records
 from read_fragment_votes_model import FragmentVoteModel, exchanged, exchanged_records
 from read_hits_model import Hits
 
@@ -19,13 +20,6 @@ pytestmark = pytest.mark.gpu
 WIDE_RULES = [(0, 0), (0, 1000)]
 PQ = [(0, 0), (8, 0), (0, 8), (4, 4), (5, 4), (8, 1), (64, 0), (63, 2), (256, 256), (512, 0), (0, 512), (257, 256), (512, 1), (1, 600), (600, 1),
       (600, 600)]
-
-
-def same_records(got, exp, what):
-    assert got.dtype == FRAGMENT_VOTE_DTYPE and got.dtype.itemsize == 40 and got.shape == exp.shape, what
-    for f in exp.dtype.names:
-        bad = np.flatnonzero(got[f] != exp[f])
-        assert bad.size == 0, "%s: fragment %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got[bad[0]], exp[bad[0]])
 
 
 def call(db, d, d_out, rule, first=0, n=None, stream=0):
@@ -80,7 +74,7 @@ def test_all_ten_fields_equal_the_model(dbs, name):
     with csr(c.hits) as d:
         for rule in (WIDE_RULES if name.startswith("wide") else hc.RULES):
             got = run(db, d, rule)
-            same_records(got, fvm.batch_anc(c.hits, rule, c.plain.calls), "%s, rule %s" % (name, rule))
+            same_records(got, fvm.batch_anc(c.hits, rule, c.plain.calls), FRAGMENT_VOTE_DTYPE, "%s, rule %s" % (name, rule))
             votes = run_votes(db, d, rule)  # GPU against GPU: the per-mate calls are the reads' vote calls
             assert np.array_equal(got["call_1"], votes["call"][0::2]) and np.array_equal(got["call_2"], votes["call"][1::2]), (name, rule)
 
@@ -89,7 +83,7 @@ def test_targets_outside_the_tree_are_read_as_the_root(dbs):
     c, db, fvm = hc.case("rows8"), dbs("rows8"), model("rows8")
     raw, exp = c.out_of_range
     with csr(raw) as d:
-        same_records(run(db, d, (2, 25)), fvm.batch_anc(exp.hits, (2, 25), exp.calls), "out of range")
+        same_records(run(db, d, (2, 25)), fvm.batch_anc(exp.hits, (2, 25), exp.calls), FRAGMENT_VOTE_DTYPE, "out of range")
 
 
 # ------------------------------------------------------------------ 2. work-split edges: the three regimes in one wave
@@ -123,7 +117,7 @@ def test_work_split_edges(dbs, name):
         hits = edge_list(name, nf)
         with csr(hits) as d:
             for rule in [(0, 0), (2, 25)]:
-                same_records(run(db, d, rule), fvm.batch_anc(hits, rule), "%s, %d fragments, rule %s" % (name, nf, rule))
+                same_records(run(db, d, rule), fvm.batch_anc(hits, rule), FRAGMENT_VOTE_DTYPE, "%s, %d fragments, rule %s" % (name, nf, rule))
     whole = edge_list(name, 16)
     for f in (3, 7, 15):  # F = 1: a lane's, a wave's and a workgroup's fragment, each a batch of its own
         lo, hi = int(whole.offsets[2 * f]), int(whole.offsets[2 * f + 2])
@@ -131,7 +125,7 @@ def test_work_split_edges(dbs, name):
                    whole.entry[lo:hi])
         with csr(one) as d:
             for rule in [(0, 0), (2, 25)]:
-                same_records(run(db, d, rule), fvm.batch_anc(one, rule), "%s, fragment %d alone, rule %s" % (name, f, rule))
+                same_records(run(db, d, rule), fvm.batch_anc(one, rule), FRAGMENT_VOTE_DTYPE, "%s, fragment %d alone, rule %s" % (name, f, rule))
 
 
 # ------------------------------------------------------------------ 3. shuffles and exchanges
@@ -149,7 +143,7 @@ def test_shuffles_change_nothing_and_exchanges_the_last_two_columns(dbs, name):
             got = run(db, d, rule)
         assert got.tobytes() == exchanged_records(plain).tobytes(), (name, rule)
         assert (plain["call_1"] != plain["call_2"]).any()
-        same_records(got, fvm.batch_anc(ex, rule), "%s, exchanged, rule %s" % (name, rule))
+        same_records(got, fvm.batch_anc(ex, rule), FRAGMENT_VOTE_DTYPE, "%s, exchanged, rule %s" % (name, rule))
 
 
 # ------------------------------------------------------------------ 4. splits
@@ -183,7 +177,7 @@ def test_more_big_fragments_than_workgroups_and_clean_rows_behind_them(dbs):
     assert torch.cuda.get_device_properties(0).multi_processor_count < 300  # one workgroup per compute unit takes the list
     for hits, what in ((a, "300 big fragments"), (b, "a second call on other hits"), (c.hits, "a third on the lists")):
         with csr(hits) as d:
-            same_records(run(db, d, (2, 25)), fvm.batch_anc(hits, (2, 25)), what)
+            same_records(run(db, d, (2, 25)), fvm.batch_anc(hits, (2, 25)), FRAGMENT_VOTE_DTYPE, what)
 
 
 # ------------------------------------------------------------------ 6. a vote call and a fragment-vote call on two streams
@@ -215,7 +209,7 @@ def test_a_vote_call_and_a_fragment_vote_call_on_two_streams(dbs, first):
         got_v, got_f = da.records(out_v, da.n, VOTE_DTYPE), db_.records(out_f, db_.n // 2, FRAGMENT_VOTE_DTYPE)
         for f in exp_votes.dtype.names:
             assert np.array_equal(got_v[f], exp_votes[f]), (first, f)
-        same_records(got_f, exp_frag, "%s first" % first)
+        same_records(got_f, exp_frag, FRAGMENT_VOTE_DTYPE, "%s first" % first)
         ms, calls, frags = db.read_fragment_votes_time()
         assert (calls, frags) == (1, 300) and ms > 0
 

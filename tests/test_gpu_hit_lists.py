@@ -13,19 +13,13 @@ import read_support_cases as sc
 from helpers import DeviceCsr, concat_reads
 from kmer_id_amd import FRAGMENT_DTYPE, VOTE_DTYPE, KmerDB, _lib
 from kmer_id_amd.api import SUPPORT_DTYPE
+from read_calls import same_records
 
 pytestmark = pytest.mark.gpu
 
 FAMILIES = {"support": (SUPPORT_DTYPE, 1), "fragments": (FRAGMENT_DTYPE, 2), "votes": (VOTE_DTYPE, 1)}  # the record, reads per record
 WIDE_RULES = [(0, 0), (0, 1000)]
 CUTS = [0, 65, 130, hc.N_READS]
-
-
-def same_records(got, exp, what):
-    assert got.dtype == exp.dtype and got.shape == exp.shape, what
-    for f in exp.dtype.names:
-        bad = np.flatnonzero(got[f] != exp[f])
-        assert bad.size == 0, "%s: record %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got[bad[0]], exp[bad[0]])
 
 
 def call(db, family, d, d_out, rule, first=0, n=None, stream=0):
@@ -70,7 +64,8 @@ def test_every_family_equals_its_model(dbs, name, variant):
     with DeviceCsr(hits.offsets, hc.raw_hits(hits), hits.n_kmers) as d:
         for family in FAMILIES:
             for rule in rules:
-                same_records(run(db, family, d, rule), getattr(exp, family)(rule), "%s, %s, %s, rule %s" % (name, variant, family, rule))
+                same_records(run(db, family, d, rule), getattr(exp, family)(rule), FAMILIES[family][0],
+                             "%s, %s, %s, rule %s" % (name, variant, family, rule))
 
 
 # ------------------------------------------------------------------ 2. splits
@@ -80,7 +75,7 @@ def test_three_calls_give_the_bytes_of_one(dbs, name):
     with DeviceCsr(c.hits.offsets, hc.raw_hits(c.hits), c.hits.n_kmers) as d:
         for family, (dtype, unit) in FAMILIES.items():
             whole = run(db, family, d, rule)
-            same_records(whole, getattr(c.plain, family)(rule), "%s, %s, one call" % (name, family))
+            same_records(whole, getattr(c.plain, family)(rule), FAMILIES[family][0], "%s, %s, one call" % (name, family))
             d_out = d.out(d.n // unit, dtype)
             cuts = [x + x % unit for x in CUTS]  # (a batch of fragments is cut between two pairs: 66 reads, 130 = 65 fragments)
             for a, b in zip(cuts[:-1], cuts[1:]):
@@ -100,8 +95,8 @@ def test_votes_survive_a_shuffle_of_every_reads_hits_and_finals_do_not(dbs, name
         with DeviceCsr(sh.offsets, hc.raw_hits(sh), sh.n_kmers) as d:
             votes_sh, support_sh = run(db, "votes", d, rule), run(db, "support", d, rule)
         assert votes_sh.tobytes() == votes.tobytes(), (name, rule)
-        same_records(votes_sh, c.plain.votes(rule), "%s, shuffled, rule %s" % (name, rule))
-        same_records(support_sh, sh_exp.support(rule), "%s, shuffled, support, rule %s" % (name, rule))
+        same_records(votes_sh, c.plain.votes(rule), VOTE_DTYPE, "%s, shuffled, rule %s" % (name, rule))
+        same_records(support_sh, sh_exp.support(rule), SUPPORT_DTYPE, "%s, shuffled, support, rule %s" % (name, rule))
         assert (support_sh["final"] != support["final"]).any()  # ... which `final` does not survive
 
 
@@ -140,7 +135,7 @@ def test_vote_calls_on_two_streams_do_not_share_scratch_in_flight(dbs, race, fir
         dev = {"A": da, "B": db_}
         if first == "A":  # what the second kernel costs on list A alone: for the log, outside the race
             db.read_votes_time()
-            same_records(run(db, "votes", da, rule), race["exp_A"], "A alone")
+            same_records(run(db, "votes", da, rule), race["exp_A"], VOTE_DTYPE, "A alone")
             print("votes(A) alone: read_votes_time = %s" % (db.read_votes_time(),))
         out = {name: d.out(d.n, VOTE_DTYPE) for name, d in dev.items()}
         out_support = db_.out(db_.n, SUPPORT_DTYPE)
@@ -151,9 +146,9 @@ def test_vote_calls_on_two_streams_do_not_share_scratch_in_flight(dbs, race, fir
         call(db, "support", db_, out_support, rule, stream=s2.cuda_stream)
         host = db.read_votes(race["bases"], race["off"], min_hits=rule[0], min_permille=rule[1])
         _lib.check(da.lib.kid_dev_sync(0))
-        same_records(da.records(out["A"], da.n, VOTE_DTYPE), race["exp_A"], "A, %s first" % first)
-        same_records(db_.records(out["B"], db_.n, VOTE_DTYPE), race["exp_B"], "B, %s first" % first)
-        same_records(db_.records(out_support, db_.n, SUPPORT_DTYPE), race["exp_support_B"], "support(B), %s first" % first)
-        same_records(host, race["exp_host"], "host form, %s first" % first)
+        same_records(da.records(out["A"], da.n, VOTE_DTYPE), race["exp_A"], VOTE_DTYPE, "A, %s first" % first)
+        same_records(db_.records(out["B"], db_.n, VOTE_DTYPE), race["exp_B"], VOTE_DTYPE, "B, %s first" % first)
+        same_records(db_.records(out_support, db_.n, SUPPORT_DTYPE), race["exp_support_B"], SUPPORT_DTYPE, "support(B), %s first" % first)
+        same_records(host, race["exp_host"], VOTE_DTYPE, "host form, %s first" % first)
         ms, calls, reads = db.read_votes_time()
         assert (calls, reads) == (3, 2000 + hc.N_READS + n_host) and ms > 0

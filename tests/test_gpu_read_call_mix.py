@@ -19,7 +19,12 @@ families in three forms, each at least twice; in the first 49 a segments call in
 another family, in the last 7 a vote call directly in front of and behind a call of each other family; the same batch
 sizes; every other host and FASTQ call of support, fragments and votes tallies into the one sample, the mirror counting a
 vote call with the vote record's `confident`.  After every call all five *_time queries report exactly that call; at the
-end kid_sample_end equals the mirror."""
+end kid_sample_end equals the mirror.
+
+test_vote_families_alternate_on_one_scratch: the three families with a second kernel -- votes, fragment votes, segment
+votes -- alternate twice on one kid_db.  Each binds a list, a counter and rows through the same function; the segment
+votes bind the rows of the votes.  Every batch holds one unit for the second kernel (KID_VOTE_WAVE_HITS + 1 hits) and one for
+a lane; the records equal those of the same call on a database that has seen no other call."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -28,9 +33,10 @@ import pytest
 import read_fragments_cases as fc
 import read_support_cases as sc
 from helpers import DeviceBatch, concat_reads, fastq_block, oracle_db
-from hit_list_cases import WAVE_HITS
-from kmer_id_amd import FRAGMENT_DTYPE, VOTE_DTYPE, KmerDB, _lib
+from hit_list_cases import LANE_HITS, WAVE_HITS
+from kmer_id_amd import FRAGMENT_DTYPE, FRAGMENT_VOTE_DTYPE, SEGMENT_VOTE_DTYPE, VOTE_DTYPE, KmerDB, _lib
 from kmer_id_amd.api import SEGMENT_DTYPE, SUPPORT_DTYPE
+from read_calls import genome_world, same_records
 from read_depth_model import depth_of
 from read_fragments_model import FragmentModel, fragment_csr
 from read_hits_model import HitModel, Hits, trim_ranges, windows
@@ -169,13 +175,6 @@ def same_csr(what, got_off, got_nk, got_hits, exp):
         assert np.array_equal(got_hits[:, j], getattr(exp, f)), "%s: %s" % (what, f)
 
 
-def same_records(what, got, exp, dtype):
-    assert got.dtype == dtype and got.shape == exp.shape, what
-    for f in dtype.names:
-        bad = np.flatnonzero(got[f] != exp[f])
-        assert bad.size == 0, "%s: record %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got[bad[0]], exp[bad[0]])
-
-
 class Mix:
     """the calls; each compares what it got and returns {family: (calls, units)}: what the timers must have seen of it"""
 
@@ -229,7 +228,7 @@ class Mix:
     # ---- support
     def support_host(self, what, a, n, rule, seg, tally):
         got = self.db.read_support(*self.offsets(a, n), min_hits=rule[0], min_permille=rule[1], tally=self.t if tally else None)
-        same_records(what, got, self.p.plain.rec[rule][a:a + n], SUPPORT_DTYPE)
+        same_records(got, self.p.plain.rec[rule][a:a + n], SUPPORT_DTYPE, what)
         if tally:
             self.m.tally(np.arange(a, a + n), rule)
             self.tallied(what)
@@ -239,7 +238,7 @@ class Mix:
         text, recs = self.block(range(a, a + n))
         got = self.db.read_support_fastq(text, recs, min_hits=rule[0], min_permille=rule[1], tally=self.t if tally else None)
         exp = self.p.fastq.rec[rule][a:a + n]
-        same_records(what, got, exp, SUPPORT_DTYPE)
+        same_records(got, exp, SUPPORT_DTYPE, what)
         if tally:
             self.m.count(self.p.fastq.sub(a, n), exp, self.p.keep[a:a + n])
             self.tallied(what)
@@ -253,14 +252,14 @@ class Mix:
             d_out = d.dev(n * 24, np.full(n * 6, 0xA5A5A5A5, np.uint32))
             self.db.support_from_hits_device(d.d_ho.value, d.d_hits.value, d.d_nk.value, n, d_out.value, min_hits=rule[0], min_permille=rule[1])
             _lib.check(d.lib.kid_dev_sync(0))
-            same_records(what, d.down(d_out, np.uint32, n * 6).view(SUPPORT_DTYPE), self.p.plain.rec[rule][a:a + n], SUPPORT_DTYPE)
+            same_records(d.down(d_out, np.uint32, n * 6).view(SUPPORT_DTYPE), self.p.plain.rec[rule][a:a + n], SUPPORT_DTYPE, what)
         return {"hits": (1, n), "support": (1, n)}
 
     # ---- votes (a VotePool's facts)
     def votes_host(self, what, a, n, rule, seg, tally):
         got = self.db.read_votes(*self.offsets(a, n), min_hits=rule[0], min_permille=rule[1], tally=self.t if tally else None)
         exp = self.p.plain.votes[rule][a:a + n]
-        same_records(what, got, exp, VOTE_DTYPE)
+        same_records(got, exp, VOTE_DTYPE, what)
         if tally:
             self.m.count(self.p.plain.sub(a, n), exp, np.ones(n, bool))
             self.tallied(what)
@@ -270,7 +269,7 @@ class Mix:
         text, recs = self.block(range(a, a + n))
         got = self.db.read_votes_fastq(text, recs, min_hits=rule[0], min_permille=rule[1], tally=self.t if tally else None)
         exp = self.p.fastq.votes[rule][a:a + n]
-        same_records(what, got, exp, VOTE_DTYPE)
+        same_records(got, exp, VOTE_DTYPE, what)
         if tally:
             self.m.count(self.p.fastq.sub(a, n), exp, self.p.keep[a:a + n])
             self.tallied(what)
@@ -284,7 +283,7 @@ class Mix:
             d_out = d.dev(n * 32, np.full(n * 8, 0xA5A5A5A5, np.uint32))
             self.db.votes_from_hits_device(d.d_ho.value, d.d_hits.value, d.d_nk.value, n, d_out.value, min_hits=rule[0], min_permille=rule[1])
             _lib.check(d.lib.kid_dev_sync(0))
-            same_records(what, d.down(d_out, np.uint32, n * 8).view(VOTE_DTYPE), self.p.plain.votes[rule][a:a + n], VOTE_DTYPE)
+            same_records(d.down(d_out, np.uint32, n * 8).view(VOTE_DTYPE), self.p.plain.votes[rule][a:a + n], VOTE_DTYPE, what)
         return {"hits": (1, n), "votes": (1, n)}
 
     # ---- fragments (n: reads, even)
@@ -292,7 +291,7 @@ class Mix:
         hits = self.p.plain.sub(a, n)
         exp = self.p.fm.batch(hits, rule)
         got = self.db.read_fragments(*self.offsets(a, n), min_hits=rule[0], min_permille=rule[1], tally=self.t if tally else None)
-        same_records(what, got, exp, FRAGMENT_DTYPE)
+        same_records(got, exp, FRAGMENT_DTYPE, what)
         if tally:
             self.m.count(fragment_csr(hits), exp, np.ones(n // 2, bool))
             self.tallied(what)
@@ -303,7 +302,7 @@ class Mix:
         exp = self.p.fm.batch(hits, rule)
         (t1, r1), (t2, r2) = self.block(range(a, a + n, 2)), self.block(range(a + 1, a + n, 2))
         got = self.db.read_fragments_fastq(t1, r1, t2, r2, min_hits=rule[0], min_permille=rule[1], tally=self.t if tally else None)
-        same_records(what, got, exp, FRAGMENT_DTYPE)
+        same_records(got, exp, FRAGMENT_DTYPE, what)
         if tally:
             keep = self.p.keep[a:a + n]
             self.m.count(fragment_csr(hits), exp, keep[0::2] | keep[1::2])  # counted when at least one mate is kept
@@ -318,13 +317,13 @@ class Mix:
             d_out = d.dev(n * 16, np.full(n * 4, 0xA5A5A5A5, np.uint32))
             self.db.fragments_from_hits_device(d.d_ho.value, d.d_hits.value, d.d_nk.value, n, d_out.value, min_hits=rule[0], min_permille=rule[1])
             _lib.check(d.lib.kid_dev_sync(0))
-            same_records(what, d.down(d_out, np.uint32, n * 4).view(FRAGMENT_DTYPE), self.p.fm.batch(hits, rule), FRAGMENT_DTYPE)
+            same_records(d.down(d_out, np.uint32, n * 4).view(FRAGMENT_DTYPE), self.p.fm.batch(hits, rule), FRAGMENT_DTYPE, what)
         return {"hits": (1, n), "fragments": (1, n // 2)}
 
     # ---- segments
     def same_segments(self, what, got, exp, n):
         assert got.offsets.dtype == np.uint64 and np.array_equal(got.offsets, exp[0]), what
-        same_records(what, got.records, exp[1], SEGMENT_DTYPE)
+        same_records(got.records, exp[1], SEGMENT_DTYPE, what)
         c = 1 + (exp[1].size > 0)
         return {"hits": (c, c * n), "segments": (c, c * n)}
 
@@ -357,7 +356,7 @@ class Mix:
             assert (int(d.down(d.d_tot, np.uint64, 1)[0]), int(d.down(d_ns, np.uint64, 1)[0])) == (n_hits, n_seg), what
             assert np.array_equal(d.down(d_so, np.uint64, n + 1), exp[0]), what
             out = d.down(d_seg, np.uint32, canary.size)
-            same_records(what, out[:n_seg * 8].view(SEGMENT_DTYPE), exp[1], SEGMENT_DTYPE)
+            same_records(out[:n_seg * 8].view(SEGMENT_DTYPE), exp[1], SEGMENT_DTYPE, what)
             assert np.all(out[n_seg * 8:] == 0xA5A5A5A5), what
         return {"hits": (1, n), "segments": (1, n)}
 
@@ -476,4 +475,37 @@ def test_mixed_calls_with_votes_share_one_state(vote_pool):
     g, u = t.end()
     assert np.array_equal(g, mix.m.gcount) and np.array_equal(u, mix.m.ucount()) and int(g.sum()) > 0
     t.close()
+    db.close()
+
+
+def test_vote_families_alternate_on_one_scratch():
+    parent, spine, sibs = sc.chain_taxonomy(12)  # 26 nodes
+    g, keys, tg = genome_world(np.random.default_rng(513), spine + sibs, 1300, 1)
+    big, small = WAVE_HITS + 1, LANE_HITS  # hits of a stretch of the genome: its windows
+    cut = lambda p, h: g[p:p + h + K - 1]  # noqa: E731
+
+    def batches(p):
+        """-> {family: (the call's arguments, the hits its two units must have)}, from the genome at p on"""
+        reads = concat_reads([cut(p, big), cut(p + 600, small)])
+        mates = concat_reads([cut(p, 300), cut(p + 300, big - 300), cut(p + 600, small // 2), cut(p + 650, small - small // 2)])
+        return {"votes": (reads, {}), "fragment_votes": (mates, {}), "segment_votes": (reads, {"seg_len": big})}
+
+    def call(db, family, args):
+        (bases, off), kw = args
+        got = getattr(db, "read_" + family)(bases, off, min_hits=2, min_permille=25, **kw)
+        return (got.offsets, got.records) if family == "segment_votes" else (None, got)
+
+    dtypes = {"votes": VOTE_DTYPE, "fragment_votes": FRAGMENT_VOTE_DTYPE, "segment_votes": SEGMENT_VOTE_DTYPE}
+    plan = [(family, args) for p in (0, 40) for family, args in batches(p).items()]
+    exp = []
+    for family, args in plan:  # each call on a database of its own
+        fresh = KmerDB(keys, tg, parent, k=K, log2_slots=12)
+        exp.append(call(fresh, family, args))
+        fresh.close()
+        assert exp[-1][1]["n_hits"].tolist() == [big, small], family  # one unit for the second kernel, one for a lane
+    db = KmerDB(keys, tg, parent, k=K, log2_slots=12)
+    for i, (family, args) in enumerate(plan):
+        off, rec = call(db, family, args)
+        assert off is None or np.array_equal(off, exp[i][0]), (i, family)
+        same_records(rec, exp[i][1], dtypes[family], "call %d: %s" % (i, family))
     db.close()

@@ -1,42 +1,36 @@
 """k-mer depth per database entry (KID_OPT_ENTRY_DEPTH): the counters a tally leaves, their spectrum, the export / add
 pair and the merged form, against the independent model of tests/read_depth_model.py and against the sample's own seen
 bitmap and ucount.  Every comparison is exact: integers."""
-import os
-import re
 
 import numpy as np
 import pytest
 
+import read_calls
 import read_depth_model as dm
 import read_support_cases as sc
-from helpers import ROOT, concat_reads, fastq_block, oracle_db
-from kmer_id_amd import (KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KID_OPT_ENTRY_DEPTH, KidError, KmerDB,
-                         depth_spectrum_merged, end_merged)
-from read_hits_model import HitModel, trim_ranges, windows
-from read_support_model import RULES, SupportModel
+from helpers import concat_reads, fastq_block
+from kmer_id_amd import KID_DB_OPT_MIN_BASE_QUALITY, KID_OPT_ENTRY_DEPTH, KmerDB, depth_spectrum_merged, end_merged
+from read_calls import KINDS, header_constant, seen_bits, status
+from read_hits_model import trim_ranges, windows
+from read_support_model import RULES
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"minloc": 0, "ref_geometry": KID_FLAG_REF_GEOMETRY, "host_build": KID_FLAG_HOST_BUILD}
-LANE_HITS = int(re.search(r"#define\s+KID_SUPPORT_LANE_HITS\s+(\d+)u", open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_support.hip.h")).read()).group(1))
+LANE_HITS = header_constant("kid_support.hip.h", "KID_SUPPORT_LANE_HITS")
 MAXD = dm.DEPTH_MAX
 
 
-class World:
+class World(read_calls.World):
     """a database, its model, a batch of reads and, per rule, the model's records and depth: computed once"""
 
     def __init__(self, parent, keys, targets, bases, off, log2_slots, rules):
-        self.parent, self.keys, self.targets, self.bases, self.off, self.log2_slots = parent, keys, targets, bases, off, log2_slots
-        self.hm = HitModel(oracle_db(parent, keys, targets, log2_slots), keys, targets, 30)
-        self.model = SupportModel(self.hm, parent)
+        super().__init__(parent, keys, targets, bases, off, log2_slots)
+        self.model = self.sm
         self.hits = self.hm.batch(bases, off)
         self.finals = self.model.finals(self.hits)
         self.counted = np.ones(self.finals.size, bool)
         self.rec = {rule: self.model.batch_identity(self.hits, rule, self.finals) for rule in rules}
         self.depth = {rule: dm.depth_of(self.hits, self.rec[rule], self.counted, keys.size) for rule in rules}
-
-    def db(self, flags=0):
-        return KmerDB(self.keys, self.targets, self.parent, k=30, log2_slots=self.log2_slots, flags=flags)
 
     def spectrum(self, depth, bins):
         return dm.spectrum_of(depth, self.targets, self.parent.size, bins)
@@ -53,16 +47,6 @@ def same_spectrum(got, exp, what=""):
         assert g.dtype == e.dtype and g.shape == e.shape, "%s: %s" % (what, name)
         bad = np.argwhere(g != e)
         assert bad.size == 0, "%s: %s%s: got %d, the model %d" % (what, name, tuple(bad[0]), int(g[tuple(bad[0])]), int(e[tuple(bad[0])]))
-
-
-def seen_bits(s, n_entries):
-    return np.unpackbits(s.seen_export(0, s.seen_bytes()), bitorder="little")[:n_entries].astype(bool)
-
-
-def status(f):
-    with pytest.raises(KidError) as e:
-        f()
-    return e.value.status
 
 
 @pytest.fixture(scope="module")

@@ -7,9 +7,11 @@ import pytest
 
 import read_depth_model as dm
 import read_fragments_cases as fc
-import test_gpu_read_fragments as rf
+import read_calls
+import read_support_cases as sc
 from helpers import DeviceBatch, fastq_block
-from kmer_id_amd import (FRAGMENT_VOTE_DTYPE, KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_REF_GEOMETRY, KID_OPT_ENTRY_DEPTH, KidError, KmerDB, _lib)
+from kmer_id_amd import FRAGMENT_VOTE_DTYPE, KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_REF_GEOMETRY, KID_OPT_ENTRY_DEPTH, KmerDB, _lib
+from read_calls import ends_equal, fastq_model, fastq_world, same_records, status
 from read_fragment_votes_model import FragmentVoteModel
 from read_fragments_model import fragment_csr
 from read_votes_model import VoteModel
@@ -19,26 +21,13 @@ pytestmark = pytest.mark.gpu
 RULES = [(0, 0), (2, 25), (3, 0)]
 
 
-def same_records(got, exp, what=""):
-    assert got.dtype == FRAGMENT_VOTE_DTYPE and got.dtype.itemsize == 40 and got.shape == exp.shape, what
-    for f in FRAGMENT_VOTE_DTYPE.names:
-        bad = np.flatnonzero(got[f] != exp[f])
-        assert bad.size == 0, "%s: fragment %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got[bad[0]], exp[bad[0]])
-
-
-def status(f):
-    with pytest.raises(KidError) as e:
-        f()
-    return e.value.status
-
-
 @pytest.fixture(scope="module")
 def world():
     """the fragments of tests/read_fragments_cases.py: a few hundred ragged mates, some empty, the hand-built pairs"""
-    parent, cum, keys, targets = rf.sc.database()
+    parent, cum, keys, targets = sc.database()
     bases, off, where = fc.fragments(parent, cum, keys, targets)
-    w = rf.World(parent, keys, targets, bases, off, 20, rules=[])
-    w.where, w.cum = where, cum
+    w = read_calls.World(parent, keys, targets, bases, off, 20)
+    w.where, w.cum, w.hits, w.nf = where, cum, w.hm.batch(bases, off), (off.size - 1) // 2
     w.fvm = FragmentVoteModel(VoteModel(w.sm))
     w.vexp = {rule: w.fvm.batch_anc(w.hits, rule) for rule in RULES}
     return w
@@ -61,7 +50,8 @@ def test_all_ten_fields_equal_the_model(world, flags):
     assert ((per[0::2] == 0) & (per[1::2] > 0)).any() and ((per[0::2] > 0) & (per[1::2] == 0)).any() and ((per[0::2] + per[1::2]) == 0).any()
     d = world.db(flags)
     for rule, exp in world.vexp.items():
-        same_records(d.read_fragment_votes(world.bases, world.off, min_hits=rule[0], min_permille=rule[1]), exp, "flags %d rule %s" % (flags, rule))
+        same_records(d.read_fragment_votes(world.bases, world.off, min_hits=rule[0], min_permille=rule[1]), exp, FRAGMENT_VOTE_DTYPE,
+                     "flags %d rule %s" % (flags, rule))
     d.close()
 
 
@@ -84,8 +74,8 @@ def test_records_do_not_depend_on_the_split_into_calls(world, db):
 # ------------------------------------------------------------------ 2. the FASTQ form: dropped records, absent mates
 @pytest.mark.parametrize("q", [0, 20])
 def test_fastq_form(world, db, q):
-    n, (s1, q1, t1, r1), (s2, q2, t2, r2) = rf.fastq_world(world)
-    hits, keep1, keep2 = rf.fastq_model(world, (s1, q1), (s2, q2), q)
+    n, (s1, q1, t1, r1), (s2, q2, t2, r2) = fastq_world(world)
+    hits, keep1, keep2 = fastq_model(world, (s1, q1), (s2, q2), q)
     assert (keep1 & ~keep2).sum() >= 20 and (~keep1 & keep2).sum() >= 20 and (~keep1 & ~keep2).sum() >= 20
     assert tuple(r2[9 + 200, [1, 3]]) == (0, 0)  # an absent mate
     counted = keep1 | keep2
@@ -95,9 +85,9 @@ def test_fastq_form(world, db, q):
             exp = world.fvm.batch_anc(hits, rule)
             t = db.sample()
             got = db.read_fragment_votes_fastq(t1, r1[5:5 + n], t2, r2[9:9 + n], min_hits=rule[0], min_permille=rule[1], tally=t)
-            same_records(got, exp, "q %d rule %s" % (q, rule))
+            same_records(got, exp, FRAGMENT_VOTE_DTYPE, "q %d rule %s" % (q, rule))
             g, u = t.end()
-            assert rf.ends_equal((g, u), world.fvm.tally(hits, exp, counted, world.targets)), (q, rule)
+            assert ends_equal((g, u), world.fvm.tally(hits, exp, counted, world.targets)), (q, rule)
             assert int(g.sum()) == int(counted.sum()) < n  # a fragment with both mates dropped is counted nowhere
             t.close()
     finally:
@@ -110,15 +100,15 @@ def test_tally_equals_the_model_and_adds_to_a_classified_sample(world, db):
     t = db.sample()
     rec = db.read_fragment_votes(world.bases, world.off, min_hits=2, min_permille=25, tally=t)
     exp = world.vexp[(2, 25)]
-    same_records(rec, exp)
+    same_records(rec, exp, FRAGMENT_VOTE_DTYPE)
     g, u = world.fvm.tally(world.hits, exp, counted, world.targets)
     assert int(g.sum()) == world.nf and int(g[0]) > int((exp["call"] == 0).sum())  # once per fragment; the rule un-calls some
     before = t.stats()
-    assert rf.ends_equal(t.end(), (g, u))
+    assert ends_equal(t.end(), (g, u))
     assert before == {"reads": 0, "lookups": 0, "probes": 0, "hits": 0}  # kid_sample_stats is not updated
     t.reset()
     db.read_fragment_votes(world.bases, world.off, tally=t, min_hits=3)  # out is what the Python form always asks for; a reset sample counts from nothing
-    assert rf.ends_equal(t.end(), world.fvm.tally(world.hits, world.vexp[(3, 0)], counted, world.targets))
+    assert ends_equal(t.end(), world.fvm.tally(world.hits, world.vexp[(3, 0)], counted, world.targets))
     # classify and this tally in one sample: the reads and the fragments add up, and under (0, 0) both see the same k-mers
     t.reset()
     t.classify(world.bases, world.off)
@@ -158,8 +148,8 @@ def test_device_form_on_what_read_hits_device_left(world, db):
         db.fragment_votes_from_hits_device(d.d_ho.value, d.d_hits.value, d.d_nk.value, n, d_out.value, min_hits=2, min_permille=25)
         _lib.check(d.lib.kid_dev_sync(0))
         got = d.down(d_out, np.uint32, nf * 10).view(FRAGMENT_VOTE_DTYPE)
-        same_records(got, host, "device form")
-        same_records(got, world.vexp[(2, 25)], "device form vs model")
+        same_records(got, host, FRAGMENT_VOTE_DTYPE, "device form")
+        same_records(got, world.vexp[(2, 25)], FRAGMENT_VOTE_DTYPE, "device form vs model")
     ms, calls, frags = db.read_fragment_votes_time()
     assert calls == 2 and frags == 2 * nf and ms > 0
     assert db.read_fragment_votes_time() == (0.0, 0, 0)
@@ -226,8 +216,8 @@ def test_tally_of_fragments_settled_by_every_regime(world, depth):
     combos = [(0, 0), (3, 4), (8, 0), (40, 30), (300, 300), (600, 0), (0, 600), (512, 1), (2, 2), (257, 256)]
     rng = np.random.default_rng(2020)
     parent = world.parent
-    x = next(int(t) for t in world.targets if t > 1 and rf.sc.top_level(parent, int(t)) != 5)
-    g = rng.choice(rf.sc.ACGT, 4000).tobytes()
+    x = next(int(t) for t in world.targets if t > 1 and sc.top_level(parent, int(t)) != 5)
+    g = rng.choice(sc.ACGT, 4000).tobytes()
     keys, _ = windows(g, 0, len(g) - 1, 30)
     tg = np.array([8, 6, 5, 36, 35, 8, 1, x], np.uint32)[rng.integers(0, 8, keys.size)]
 
@@ -251,7 +241,8 @@ def test_tally_of_fragments_settled_by_every_regime(world, depth):
     for rule in [(0, 0), (200, 0), (2, 900)]:
         exp = fvm.batch_anc(hits, rule)
         t.reset()
-        same_records(d.read_fragment_votes(bases, off, min_hits=rule[0], min_permille=rule[1], tally=t), exp, "depth %d rule %s" % (depth, rule))
+        same_records(d.read_fragment_votes(bases, off, min_hits=rule[0], min_permille=rule[1], tally=t), exp, FRAGMENT_VOTE_DTYPE,
+                     "depth %d rule %s" % (depth, rule))
         if depth:
             want = dm.depth_of(fragment_csr(hits), exp, counted, keys.size)
             got = t.entry_depth()
@@ -259,7 +250,7 @@ def test_tally_of_fragments_settled_by_every_regime(world, depth):
             assert bad.size == 0, "rule %s: entry %d: got %d, the model %d" % (rule, bad[0], got[bad[0]], want[bad[0]])
         g_u = fvm.tally(hits, exp, counted, tg)
         assert int(g_u[0].sum()) == len(combos)
-        assert rf.ends_equal(t.end(), g_u), (depth, rule)
+        assert ends_equal(t.end(), g_u), (depth, rule)
     assert len({int(c) for c in fvm.batch_anc(hits, (200, 0))["confident"]}) > 1  # the rule un-calls the small fragments alone
     t.close()
     d.close()

@@ -1,67 +1,43 @@
 """kid_db_read_fragments* (mate pairs called as one fragment) against the independent model of
 tests/read_fragments_model.py, against the classify and read-support paths of the same library, and against its own
 contract.  Every comparison is exact: integers and bytes."""
-import os
-import re
 
 import numpy as np
 import pytest
 
+import read_calls
 import read_depth_model as dm
 import read_fragments_cases as fc
 import read_support_cases as sc
-from base_quality_cases import np_mask
-from helpers import ROOT, DeviceBatch, concat_reads, fastq_block, oracle_db
-from kmer_id_amd import (FRAGMENT_DTYPE, KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KID_OPT_ENTRY_DEPTH,
-                         KID_OPT_MIN_BASE_QUALITY, KidError, KmerDB, _lib)
+from helpers import DeviceBatch, concat_reads, fastq_block, oracle_db
+from kmer_id_amd import (FRAGMENT_DTYPE, KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_REF_GEOMETRY, KID_OPT_ENTRY_DEPTH, KID_OPT_MIN_BASE_QUALITY, KmerDB,
+                         _lib)
+from read_calls import KINDS, ends_equal, fastq_model, fastq_world, header_constant, same_records, status
 from read_fragments_model import FragmentModel, fragment_csr, interleave
-from read_hits_model import HitModel, trim_ranges, windows
+from read_hits_model import HitModel, windows
 from read_support_model import SupportModel
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"minloc": 0, "ref_geometry": KID_FLAG_REF_GEOMETRY, "host_build": KID_FLAG_HOST_BUILD}
 FIELDS = FRAGMENT_DTYPE.names
 SUPPORT_FIELDS = FIELDS[:6]
-LANE_HITS = int(re.search(r"#define\s+KID_SUPPORT_LANE_HITS\s+(\d+)u", open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_support.hip.h")).read()).group(1))
+LANE_HITS = header_constant("kid_support.hip.h", "KID_SUPPORT_LANE_HITS")
 
 
-def same_records(got, exp, what=""):
-    assert got.dtype == FRAGMENT_DTYPE and got.dtype.itemsize == 32 and got.shape == exp.shape, what
-    for f in FIELDS:
-        bad = np.flatnonzero(got[f] != exp[f])
-        assert bad.size == 0, "%s: fragment %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got[bad[0]], exp[bad[0]])
-
-
-def ends_equal(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
-def status(f):
-    with pytest.raises(KidError) as e:
-        f()
-    return e.value.status
-
-
-class World:
+class World(read_calls.World):
     """a database, its models, a batch of 2 F interleaved reads and the model's records for every rule: computed once"""
 
     def __init__(self, parent, keys, targets, bases, off, log2_slots, rules=fc.RULES):
-        self.parent, self.keys, self.targets, self.bases, self.off, self.log2_slots = parent, keys, targets, bases, off, log2_slots
-        self.odb = oracle_db(parent, keys, targets, log2_slots)
-        self.hm = HitModel(self.odb, keys, targets, 30)
-        self.sm = SupportModel(self.hm, parent)
+        super().__init__(parent, keys, targets, bases, off, log2_slots)
         self.fm = FragmentModel(self.sm)
         self.hits = self.hm.batch(bases, off)
         self.exp = {rule: self.fm.batch(self.hits, rule) for rule in rules}
         self.nf = (off.size - 1) // 2
 
-    def db(self, flags=0):
-        return KmerDB(self.keys, self.targets, self.parent, k=30, log2_slots=self.log2_slots, flags=flags)
-
     def check(self, db, what=""):
         for rule, exp in self.exp.items():
-            same_records(db.read_fragments(self.bases, self.off, min_hits=rule[0], min_permille=rule[1]), exp, "%s rule %s" % (what, rule))
+            same_records(db.read_fragments(self.bases, self.off, min_hits=rule[0], min_permille=rule[1]), exp, FRAGMENT_DTYPE,
+                         "%s rule %s" % (what, rule))
 
 
 @pytest.fixture(scope="module")
@@ -122,7 +98,7 @@ def test_work_split_edges(world):
         assert [(int(per[2 * j]), int(per[2 * j + 1])) for j in at] == combos[i:i + 4]  # from the model, before the library is asked
         assert int(per.sum()) == sum(p + q for p, q in combos[i:i + 4])  # the fragments between have no hit
         for rule in fc.RULES:
-            same_records(d.read_fragments(bases, off, min_hits=rule[0], min_permille=rule[1]), fm.batch(hits, rule),
+            same_records(d.read_fragments(bases, off, min_hits=rule[0], min_permille=rule[1]), fm.batch(hits, rule), FRAGMENT_DTYPE,
                          "batch %d rule %s" % (i // 4, rule))
     d.close()
 
@@ -193,51 +169,6 @@ def test_records_repeat_and_do_not_depend_on_the_split_into_calls(world, db):
 
 
 # ------------------------------------------------------------------ 6. the FASTQ form
-def fastq_world(world):
-    """two blocks of n + 5 and n + 9 records: fragment i is record 5 + i of block 1 and record 9 + i of block 2"""
-    from kmer_id_amd import synth
-    n, length = 400, 150
-    bases, _ = sc.cases.synth_reads(world.cum, world.parent, 2 * n + 14, length)
-    quals = [q.tobytes() for q in synth.qualities(2 * n + 14, length)]
-    seqs = [bases[i * length:(i + 1) * length].tobytes() for i in range(2 * n + 14)]
-    s1, q1, s2, q2 = seqs[:n + 5], quals[:n + 5], seqs[n + 5:], quals[n + 5:]
-    raw = bytes(world.bases)
-    for j, name in enumerate(sorted(world.where)):  # the hand-built fragments, qualities that trim nothing
-        f = world.where[name]
-        a, b = raw[int(world.off[2 * f]):int(world.off[2 * f + 1])], raw[int(world.off[2 * f + 1]):int(world.off[2 * f + 2])]
-        s1[5 + 20 + j], q1[5 + 20 + j], s2[9 + 20 + j], q2[9 + 20 + j] = a, b"I" * len(a), b, b"I" * len(b)
-    for i in range(0, 60, 3):  # dropped by quality: mate 1 only, mate 2 only, both
-        q1[5 + 100 + i] = b"!" * length
-        q2[9 + 100 + i + 1] = b"!" * length
-        q1[5 + 100 + i + 2] = q2[9 + 100 + i + 2] = b"!" * length
-    s2[9 + 200], q2[9 + 200] = b"", b""  # an absent mate (its lines are empty)
-    for i in range(210, 230):  # low-quality bases inside reads that are kept: KID_DB_OPT_MIN_BASE_QUALITY changes their hits
-        for q in (q1, q2):
-            row = bytearray(q[9 + i])
-            row[40:44] = b"++++"
-            row[90] = ord("2")
-            q[9 + i] = bytes(row)
-    t1, r1 = fastq_block(s1, q1, eol=b"\r\n", blank_every=5)
-    t2, r2 = fastq_block(s2, q2, eol=b"\n", blank_every=3)
-    return n, (s1[5:], q1[5:], t1, r1), (s2[9:], q2[9:], t2, r2)
-
-
-def fastq_model(world, mate1, mate2, q):
-    """-> (hits of the 2 n interleaved reads under their trimmed ranges, counted)"""
-    per = []
-    for seqs, quals in (mate1, mate2):
-        start, stop, keep = trim_ranges(quals, [len(s) for s in seqs], 30)
-        start[~keep], stop[~keep] = 0, -1  # a dropped mate contributes no hit and no window
-        if q:
-            seqs = [np_mask(np.frombuffer(s, np.uint8), np.frombuffer(ql, np.uint8)[:len(s)], q)[0].tobytes() if k else s
-                    for s, ql, k in zip(seqs, quals, keep)]
-        per.append((seqs, start, stop, keep))
-    bases, off = concat_reads(interleave(per[0][0], per[1][0]))
-    start, stop = np.zeros(off.size - 1, np.int32), np.zeros(off.size - 1, np.int32)
-    start[0::2], start[1::2], stop[0::2], stop[1::2] = per[0][1], per[1][1], per[0][2], per[1][2]
-    return world.hm.batch(bases, off, start, stop), per[0][3], per[1][3]
-
-
 @pytest.mark.parametrize("q", [0, 20])
 def test_fastq_form(world, db, q):
     n, (s1, q1, t1, r1), (s2, q2, t2, r2) = fastq_world(world)
@@ -254,7 +185,7 @@ def test_fastq_form(world, db, q):
             exp = world.fm.batch(hits, rule)
             t = db.sample()
             got = db.read_fragments_fastq(t1, r1[5:5 + n], t2, r2[9:9 + n], min_hits=rule[0], min_permille=rule[1], tally=t)
-            same_records(got, exp, "q %d rule %s" % (q, rule))
+            same_records(got, exp, FRAGMENT_DTYPE, "q %d rule %s" % (q, rule))
             g, u = t.end()
             assert ends_equal((g, u), world.fm.tally(hits, exp, counted, world.targets)), (q, rule)
             assert int(g.sum()) == int(counted.sum()) < n
@@ -275,7 +206,7 @@ def test_tally_under_rule_2_25_equals_the_model(world, db):
     t = db.sample()
     rec = db.read_fragments(world.bases, world.off, min_hits=2, min_permille=25, tally=t)
     exp = world.exp[(2, 25)]
-    same_records(rec, exp)
+    same_records(rec, exp, FRAGMENT_DTYPE)
     counted = np.ones(world.nf, bool)
     g, u = world.fm.tally(world.hits, exp, counted, world.targets)
     assert int(g.sum()) == world.nf and int(g[0]) > int((exp["final"] == 0).sum())  # once per fragment; the rule un-calls some
@@ -323,8 +254,8 @@ def test_device_form_equals_host_form(world, db):
         db.fragments_from_hits_device(d.d_ho.value, d.d_hits.value, d.d_nk.value, n, d_out.value, min_hits=2, min_permille=25)
         _lib.check(d.lib.kid_dev_sync(0))
         got = d.down(d_out, np.uint32, nf * 8).view(FRAGMENT_DTYPE)
-        same_records(got, host, "device form")
-        same_records(got, world.exp[(2, 25)], "device form vs model")
+        same_records(got, host, FRAGMENT_DTYPE, "device form")
+        same_records(got, world.exp[(2, 25)], FRAGMENT_DTYPE, "device form vs model")
         # the same batch in three calls (offsets stay absolute: the hits pointer is the same)
         d_out3 = d.dev(nf * 32, np.full(nf * 8, 0xA5A5A5A5, np.uint32))
         cuts = [0, nf // 3, nf // 3 + 65, nf]

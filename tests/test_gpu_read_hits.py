@@ -9,11 +9,11 @@ import pytest
 import read_hits_cases as cases
 from helpers import DeviceBatch, concat_reads, fastq_block, ob, oracle_db
 from kmer_id_amd import KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KID_FLAG_U_IS_T, KidError, KmerDB, _lib, synth
+from read_calls import KINDS
 from read_hits_model import HitModel, trim_ranges, windows
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"minloc": 0, "ref_geometry": KID_FLAG_REF_GEOMETRY, "host_build": KID_FLAG_HOST_BUILD}
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 
 

@@ -2,44 +2,31 @@
 tests/read_segment_votes_model.py (its direct form), against kid_db_read_segments and kid_db_read_votes of the same
 library, and against its own contract.  Every comparison is exact: integers."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import read_calls
 import read_support_cases as sc
 from base_quality_cases import hit_reads, mask_block
-from helpers import ROOT, DeviceBatch, concat_reads, fastq_block, oracle_db
-from kmer_id_amd import (FRAGMENT_VOTE_DTYPE, KID_DB_OPT_LOW_COMPLEXITY, KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY,
-                         SEGMENT_VOTE_DTYPE, VOTE_DTYPE, KidError, KmerDB, _lib)
+from helpers import DeviceBatch, concat_reads, fastq_block, oracle_db
+from kmer_id_amd import (FRAGMENT_VOTE_DTYPE, KID_DB_OPT_LOW_COMPLEXITY, KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_REF_GEOMETRY, SEGMENT_VOTE_DTYPE,
+                         VOTE_DTYPE, KmerDB, _lib)
 from low_complexity_model import mask_block as lowc_mask_block
+from read_calls import KINDS, RC_SETTINGS, genome_world, header_constant, mirrored, same_segments, status, strand_world
 from read_fragment_votes_model import FragmentVoteModel
 from read_hits_model import HitModel, trim_ranges
 from read_segment_votes_model import VOTE_FIELDS, SegmentVoteModel
 from read_support_model import SupportModel
-from test_gpu_read_segments import genome_world
-from test_read_segment_votes_model import RC_SETTINGS, mirrored, strand_world
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"minloc": 0, "ref_geometry": KID_FLAG_REF_GEOMETRY, "host_build": KID_FLAG_HOST_BUILD}
 SETTINGS = [(1, 1), (63, 63), (64, 64), (65, 13), (100, 50), (121, 121), (10 ** 6, 10 ** 6)]
 RULES = [(0, 0), (2, 25)]
 GEOMETRY = ("pos", "n_pos", "n_kmers", "n_hits")
-_VOTES_H = open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_votes.hip.h")).read()
-LANE = int(re.search(r"#define\s+KID_VOTE_LANE_HITS\s+(\d+)u", _VOTES_H).group(1))
-WAVE = int(re.search(r"#define\s+KID_VOTE_WAVE_HITS\s+(\d+)u", _VOTES_H).group(1))
+LANE = header_constant("kid_votes.hip.h", "KID_VOTE_LANE_HITS")
+WAVE = header_constant("kid_votes.hip.h", "KID_VOTE_WAVE_HITS")
 CANARY = 0xA5A5A5A5
-
-
-def same_segments(got, exp, what=""):
-    """got: ReadSegments; exp: (offsets, records) of the model"""
-    assert got.offsets.dtype == np.uint64 and np.array_equal(got.offsets, exp[0]), what
-    assert got.records.dtype == SEGMENT_VOTE_DTYPE and got.records.shape == exp[1].shape, what
-    for f in SEGMENT_VOTE_DTYPE.names:
-        bad = np.flatnonzero(got.records[f] != exp[1][f])
-        assert bad.size == 0, "%s: segment %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got.records[bad[0]], exp[1][bad[0]])
 
 
 def call(db, bases, off, seg, rule, start=None, stop=None):
@@ -52,14 +39,11 @@ def regimes(rec):
     return int(((m > 0) & (m <= LANE)).sum()), int(((m > LANE) & (m <= WAVE)).sum()), int((m > WAVE).sum())
 
 
-class World:
+class World(read_calls.World):
     """a database, its models and a batch of reads; the model's segments per (setting, rule) are computed once"""
 
     def __init__(self, parent, keys, targets, bases, off, log2_slots, start=None, stop=None):
-        self.parent, self.keys, self.targets, self.bases, self.off, self.log2_slots = parent, keys, targets, bases, off, log2_slots
-        self.odb = oracle_db(parent, keys, targets, log2_slots)
-        self.hm = HitModel(self.odb, keys, targets, 30)
-        self.sm = SupportModel(self.hm, parent)
+        super().__init__(parent, keys, targets, bases, off, log2_slots)
         self.seg = SegmentVoteModel(self.sm, bases, off, start, stop)
         self.start, self.stop = start, stop
         self._exp = {}
@@ -69,13 +53,11 @@ class World:
             self._exp[(seg, rule)] = self.seg.direct(seg[0], seg[1], rule)
         return self._exp[(seg, rule)]
 
-    def db(self, flags=0):
-        return KmerDB(self.keys, self.targets, self.parent, k=30, log2_slots=self.log2_slots, flags=flags)
-
     def check(self, db, settings, rules, what=""):
         for seg in settings:
             for rule in rules:
-                same_segments(call(db, self.bases, self.off, seg, rule, self.start, self.stop), self.exp(seg, rule), "%s %s rule %s" % (what, seg, rule))
+                same_segments(call(db, self.bases, self.off, seg, rule, self.start, self.stop), self.exp(seg, rule), SEGMENT_VOTE_DTYPE,
+                              "%s %s rule %s" % (what, seg, rule))
 
 
 @pytest.fixture(scope="module")
@@ -145,7 +127,7 @@ def test_tile_edges(world):
                     for rule in [(0, 0), (2, 25)]:
                         exp = model.direct(seg_len, seg_step, rule)
                         what = "P %d %s %d:%d %s" % (P, copy, seg_len, seg_step, rule)
-                        same_segments(call(d, bases, off, (seg_len, seg_step), rule), exp, what)
+                        same_segments(call(d, bases, off, (seg_len, seg_step), rule), exp, SEGMENT_VOTE_DTYPE, what)
                         rec = exp[1]
                         assert int(exp[0][1]) * 2 == rec.size == int(exp[0][4]) and exp[0][1] == exp[0][2] == exp[0][3], what
                         if copy == "plain":
@@ -185,7 +167,7 @@ def test_regime_edges(world):
             assert exp[1].size >= 130 and [int(exp[0][j]) for j in (0, 63, 64)] == [0, 63, 64]
             assert [int(exp[1]["n_hits"][int(exp[0][j])]) for j in sorted(at)] == [at[j] for j in sorted(at)]
             assert int(exp[1]["n_hits"][1:63].sum()) == 0
-            same_segments(call(d, bases, off, (2000, 2000), rule), exp, "batch %d rule %s" % (i, rule))
+            same_segments(call(d, bases, off, (2000, 2000), rule), exp, SEGMENT_VOTE_DTYPE, "batch %d rule %s" % (i, rule))
         seen |= set(at.values())
     assert seen == set(counts)
     # (b) the same counts as segments INSIDE one record: a stretch of h hits and a hit-free spacer fill 1600 bases each,
@@ -198,7 +180,7 @@ def test_regime_edges(world):
         exp = model.direct(1600, 1600, rule)
         rec = exp[1][int(exp[0][1]):int(exp[0][2])]
         assert rec["n_hits"].tolist() == counts and regimes(rec) == (2, 6, 2)
-        same_segments(call(d, bases, off, (1600, 1600), rule), exp, "one record rule %s" % (rule,))
+        same_segments(call(d, bases, off, (1600, 1600), rule), exp, SEGMENT_VOTE_DTYPE, "one record rule %s" % (rule,))
     # (c) overlap: about a hundred segments of more than WAVE hits that share hits, all the workgroup kernel's
     bases, off = concat_reads([spacer(100), spacer(700) + dense(700) + spacer(700), spacer(100)])
     model = SegmentVoteModel(sm, bases, off)
@@ -207,7 +189,7 @@ def test_regime_edges(world):
         exp = model.direct(seg[0], seg[1], rule)
         lane, wave, big = regimes(exp[1])
         assert big >= 100 and wave >= 100 and lane >= 8, (lane, wave, big)
-        same_segments(call(d, bases, off, seg, rule), exp, "overlap rule %s" % (rule,))
+        same_segments(call(d, bases, off, seg, rule), exp, SEGMENT_VOTE_DTYPE, "overlap rule %s" % (rule,))
     # no read at all; reads without a window only
     empty = d.read_segment_votes(np.zeros(0, np.uint8), np.zeros(1, np.uint64), seg_len=5)
     assert empty.records.size == 0 and empty.records.dtype == SEGMENT_VOTE_DTYPE and empty.offsets.tolist() == [0]
@@ -245,7 +227,7 @@ def test_reverse_complement(world):
     for seg in RC_SETTINGS:
         for rule in RULES:
             got = call(d, bases, off, seg, rule)
-            same_segments(got, w.exp(seg, rule), "strands %s %s" % (seg, rule))
+            same_segments(got, w.exp(seg, rule), SEGMENT_VOTE_DTYPE, "strands %s %s" % (seg, rule))
             a, b = mirrored(got.offsets, got.records, (seg, rule))
             for f in VOTE_FIELDS:
                 assert np.array_equal(a[f], b[f]), (seg, rule, f)
@@ -321,7 +303,7 @@ def test_fastq_form(world, db):
 
     for seg, rule in [((40, 20), (0, 0)), ((64, 64), (2, 25)), ((10 ** 6, 10 ** 6), (2, 25))]:
         got = fq(text, seg, rule)
-        same_segments(got, expect(seqs, seg, rule), "fastq %s %s" % (seg, rule))
+        same_segments(got, expect(seqs, seg, rule), SEGMENT_VOTE_DTYPE, "fastq %s %s" % (seg, rule))
         per = np.diff(got.offsets.astype(np.int64))
         assert not per[~keep].any() and np.all(per[keep] >= 1)  # a dropped record has no segment
         assert np.array_equal(got.records["pos"][got.offsets[:-1][keep].astype(np.int64)], start[keep])
@@ -337,7 +319,7 @@ def test_fastq_form(world, db):
         finally:
             db.set_option(option, 0)
         mseqs = [masked[int(r[0]):int(r[0] + r[1])].tobytes() for r in recs]
-        same_segments(on, expect(mseqs, seg, rule), "masked %d" % option)
+        same_segments(on, expect(mseqs, seg, rule), SEGMENT_VOTE_DTYPE, "masked %d" % option)
         off_masked = fq(masked, seg, rule)
         assert on.records.tobytes() == off_masked.records.tobytes() and on.records.tobytes() != plain.records.tobytes(), option
         assert np.array_equal(on.offsets, plain.offsets)  # (the ranges come from the quality line alone)
@@ -443,7 +425,7 @@ def test_two_streams_share_the_rows_with_the_vote_families(world):
         got_f = b.down(d_frag, np.uint32, (n // 2 + 2) * 10)
         assert got_f[:(n // 2) * 10].view(FRAGMENT_VOTE_DTYPE).tobytes() == exp_frag.tobytes() and np.all(got_f[(n // 2) * 10:] == CANARY)
     # and the host form behind them, on rows that must be zero again
-    same_segments(call(d, bases, off, segs[0], rule), exp[0], "host form behind the streams")
+    same_segments(call(d, bases, off, segs[0], rule), exp[0], SEGMENT_VOTE_DTYPE, "host form behind the streams")
     assert VOTE_DTYPE.itemsize == 32
     d.close()
 
@@ -451,11 +433,6 @@ def test_two_streams_share_the_rows_with_the_vote_families(world):
 # ------------------------------------------------------------------ 9. errors
 def test_error_statuses(world, db):
     bases, off = world.bases[:int(world.off[600])], world.off[:601]
-
-    def status(f):
-        with pytest.raises(KidError) as e:
-            f()
-        return e.value.status
 
     for seg_len, seg_step in [(0, 1), (10, 0), (10, 11), (2048, 1), (0, 0)]:
         assert status(lambda: db.read_segment_votes(bases, off, seg_len=seg_len, seg_step=seg_step)) == -1, (seg_len, seg_step)
@@ -539,7 +516,7 @@ def test_sizing_splits_and_repeats(world, db):
     ok = lens > 0
     b2, o2 = concat_reads([bases[int(off[r]):int(off[r + 1])].tobytes() for r in np.flatnonzero(ok)])
     model = SegmentVoteModel(world.sm, b2, o2, start[ok], stop[ok])
-    same_segments(call(db, b2, o2, (40, 20), (2, 25), start[ok], stop[ok]), model.direct(40, 20, (2, 25)), "trimmed")
+    same_segments(call(db, b2, o2, (40, 20), (2, 25), start[ok], stop[ok]), model.direct(40, 20, (2, 25)), SEGMENT_VOTE_DTYPE, "trimmed")
 
 
 # ------------------------------------------------------------------ 11. the timer

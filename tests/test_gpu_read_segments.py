@@ -2,50 +2,37 @@
 (its direct form), against kid_db_read_support of the same library, and against its own contract.  Every comparison is
 exact: integers."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import read_calls
 import read_support_cases as sc
 from base_quality_cases import hit_reads, mask_block
-from helpers import ROOT, DeviceBatch, concat_reads, fastq_block, oracle_db
-from kmer_id_amd import KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KidError, KmerDB, _lib
+from helpers import DeviceBatch, concat_reads, fastq_block, oracle_db
+from kmer_id_amd import KID_DB_OPT_MIN_BASE_QUALITY, KID_FLAG_REF_GEOMETRY, KmerDB, _lib
 from kmer_id_amd.api import SEGMENT_DTYPE, SUPPORT_DTYPE
-from read_hits_model import HitModel, trim_ranges, windows
+from read_calls import KINDS, genome_world, header_constant, same_segments, status
+from read_hits_model import HitModel, trim_ranges
 from read_segments_model import SegmentModel
 from read_support_model import SupportModel
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"minloc": 0, "ref_geometry": KID_FLAG_REF_GEOMETRY, "host_build": KID_FLAG_HOST_BUILD}
 SETTINGS = [(1, 1), (63, 63), (64, 64), (65, 13), (100, 50), (121, 121), (10 ** 6, 10 ** 6)]
 RULES = [(0, 0), (2, 25)]
-LANE_HITS = int(re.search(r"#define\s+KID_SUPPORT_LANE_HITS\s+(\d+)u", open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_support.hip.h")).read()).group(1))
-
-
-def same_segments(got, exp, what=""):
-    """got: ReadSegments; exp: (offsets, records) of the model"""
-    assert got.offsets.dtype == np.uint64 and np.array_equal(got.offsets, exp[0]), what
-    assert got.records.dtype == SEGMENT_DTYPE and got.records.shape == exp[1].shape, what
-    for f in SEGMENT_DTYPE.names:
-        bad = np.flatnonzero(got.records[f] != exp[1][f])
-        assert bad.size == 0, "%s: segment %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got.records[bad[0]], exp[1][bad[0]])
+LANE_HITS = header_constant("kid_support.hip.h", "KID_SUPPORT_LANE_HITS")
 
 
 def call(db, bases, off, seg, rule, start=None, stop=None):
     return db.read_segments(bases, off, start, stop, seg_len=seg[0], seg_step=seg[1], min_hits=rule[0], min_permille=rule[1])
 
 
-class World:
+class World(read_calls.World):
     """a database, its models and a batch of reads; the model's segments per (setting, rule) are computed once"""
 
     def __init__(self, parent, keys, targets, bases, off, log2_slots, start=None, stop=None):
-        self.parent, self.keys, self.targets, self.bases, self.off, self.log2_slots = parent, keys, targets, bases, off, log2_slots
-        self.odb = oracle_db(parent, keys, targets, log2_slots)
-        self.hm = HitModel(self.odb, keys, targets, 30)
-        self.sm = SupportModel(self.hm, parent)
+        super().__init__(parent, keys, targets, bases, off, log2_slots)
         self.seg = SegmentModel(self.sm, bases, off, start, stop)
         self.start, self.stop = start, stop
         self._exp = {}
@@ -55,13 +42,11 @@ class World:
             self._exp[(seg, rule)] = self.seg.direct(seg[0], seg[1], rule)
         return self._exp[(seg, rule)]
 
-    def db(self, flags=0):
-        return KmerDB(self.keys, self.targets, self.parent, k=30, log2_slots=self.log2_slots, flags=flags)
-
     def check(self, db, settings, rules, what=""):
         for seg in settings:
             for rule in rules:
-                same_segments(call(db, self.bases, self.off, seg, rule, self.start, self.stop), self.exp(seg, rule), "%s %s rule %s" % (what, seg, rule))
+                same_segments(call(db, self.bases, self.off, seg, rule, self.start, self.stop), self.exp(seg, rule), SEGMENT_DTYPE,
+                              "%s %s rule %s" % (what, seg, rule))
 
 
 @pytest.fixture(scope="module")
@@ -101,15 +86,6 @@ def test_segments_equal_the_model(world, kind):
 
 
 # ------------------------------------------------------------------ 2. tile edges
-def genome_world(rng, lineage, genome_len, every):
-    """a database of every `every`-th window of a random genome under targets drawn from `lineage`"""
-    g = rng.choice(sc.ACGT, genome_len).tobytes()
-    keys, _ = windows(g, 0, genome_len - 1, 30)
-    keys = keys[::every]
-    tg = np.array(lineage, np.uint32)[rng.integers(0, len(lineage), keys.size)]
-    return g, keys, tg
-
-
 def test_tile_edges(world):
     rng = np.random.default_rng(6464)
     parent = world.parent
@@ -134,7 +110,7 @@ def test_tile_edges(world):
                     for rule in [(0, 0), (2, 25)]:
                         exp = model.direct(seg_len, seg_step, rule)
                         what = "P %d %s %d:%d %s" % (P, copy, seg_len, seg_step, rule)
-                        same_segments(call(d, bases, off, (seg_len, seg_step), rule), exp, what)
+                        same_segments(call(d, bases, off, (seg_len, seg_step), rule), exp, SEGMENT_DTYPE, what)
                         rec = exp[1]
                         assert int(exp[0][1]) * 2 == rec.size == int(exp[0][4]) and exp[0][1] == exp[0][2] == exp[0][3], what
                         if copy == "plain":
@@ -172,7 +148,7 @@ def test_work_split(world):
             assert exp[1].size >= 130 and [int(exp[0][j]) for j in (0, 63, 64)] == [0, 63, 64]
             assert [int(exp[1]["n_hits"][j]) for j in (0, 63, 64)] == [counts[i], counts[(i + 1) % 7], counts[(i + 2) % 7]]
             assert int(exp[1]["n_hits"][1:63].sum()) == 0
-            same_segments(call(d, bases, off, (300, 300), rule), exp, "batch %d rule %s" % (i, rule))
+            same_segments(call(d, bases, off, (300, 300), rule), exp, SEGMENT_DTYPE, "batch %d rule %s" % (i, rule))
     # the same counts as segments INSIDE one record: stretches of the genome between hit-free spacers of 300 bases
     parts = []
     for h in counts:
@@ -182,7 +158,7 @@ def test_work_split(world):
     for seg in [(64, 64), (229, 1), (300, 150)]:
         for rule in [(0, 0), (3, 0), (2, 25)]:
             exp = model.direct(seg[0], seg[1], rule)
-            same_segments(call(d, bases, off, seg, rule), exp, "one record %s rule %s" % (seg, rule))
+            same_segments(call(d, bases, off, seg, rule), exp, SEGMENT_DTYPE, "one record %s rule %s" % (seg, rule))
     assert int(model.direct(229, 1, (0, 0))[1]["n_hits"].max()) >= 200
     # no read at all; reads without a window only
     empty = d.read_segments(np.zeros(0, np.uint8), np.zeros(1, np.uint64), seg_len=5)
@@ -225,7 +201,7 @@ def test_a_chimera(world):
     d = w.db()
     for rule in [(0, 0), (0, 600)]:
         got = call(d, bases, off, (500, 250), rule)
-        same_segments(got, w.exp((500, 250), rule), "chimera %s" % (rule,))
+        same_segments(got, w.exp((500, 250), rule), SEGMENT_DTYPE, "chimera %s" % (rule,))
         rec = got.of(1)
         assert rec.size == 23 and int(rec["pos"][-1] + rec["n_pos"][-1]) == 6000 - 29
         left = rec[rec["pos"] + rec["n_pos"] + 29 <= 3000]   # every window inside the first genome
@@ -290,7 +266,7 @@ def test_fastq_form(world, db):
 
     for seg, rule in [((40, 20), (0, 0)), ((64, 64), (2, 25)), ((10 ** 6, 10 ** 6), (2, 25))]:
         got = db.read_segments_fastq(text, recs, seg_len=seg[0], seg_step=seg[1], min_hits=rule[0], min_permille=rule[1])
-        same_segments(got, expect(seqs, seg, rule), "fastq %s %s" % (seg, rule))
+        same_segments(got, expect(seqs, seg, rule), SEGMENT_DTYPE, "fastq %s %s" % (seg, rule))
         per = np.diff(got.offsets.astype(np.int64))
         assert not per[~keep].any() and np.all(per[keep] >= 1)  # a dropped record has no segment
         assert np.array_equal(got.records["pos"][got.offsets[:-1][keep].astype(np.int64)], start[keep])
@@ -304,7 +280,7 @@ def test_fastq_form(world, db):
         on = db.read_segments_fastq(text, recs, seg_len=40, seg_step=20, min_hits=2, min_permille=25)
     finally:
         db.set_option(KID_DB_OPT_MIN_BASE_QUALITY, 0)
-    same_segments(on, expect(mseqs, (40, 20), (2, 25)), "masked")
+    same_segments(on, expect(mseqs, (40, 20), (2, 25)), SEGMENT_DTYPE, "masked")
     off_masked = db.read_segments_fastq(masked, recs, seg_len=40, seg_step=20, min_hits=2, min_permille=25)
     assert on.records.tobytes() == off_masked.records.tobytes() and on.records.tobytes() != plain.records.tobytes()
     assert np.array_equal(on.offsets, plain.offsets)  # (the ranges come from the quality line alone)
@@ -345,7 +321,7 @@ def test_sizing_splits_and_repeats(world, db):
     sel = np.flatnonzero(ok)
     b2, o2 = concat_reads([bases[int(off[r]):int(off[r + 1])].tobytes() for r in sel])
     model = SegmentModel(world.sm, b2, o2, start[ok], stop[ok])
-    same_segments(call(db, b2, o2, (40, 20), (2, 25), start[ok], stop[ok]), model.direct(40, 20, (2, 25)), "trimmed")
+    same_segments(call(db, b2, o2, (40, 20), (2, 25), start[ok], stop[ok]), model.direct(40, 20, (2, 25)), SEGMENT_DTYPE, "trimmed")
 
 
 # ------------------------------------------------------------------ 9. the device form, the timer
@@ -395,11 +371,6 @@ def test_device_form_and_time(world, db):
 # ------------------------------------------------------------------ 10. errors
 def test_error_statuses(world, db):
     bases, off = world.bases[:int(world.off[600])], world.off[:601]
-
-    def status(f):
-        with pytest.raises(KidError) as e:
-            f()
-        return e.value.status
 
     for seg_len, seg_step in [(0, 1), (10, 0), (10, 11), (2048, 1), (0, 0)]:
         assert status(lambda: db.read_segments(bases, off, seg_len=seg_len, seg_step=seg_step)) == -1, (seg_len, seg_step)

@@ -1,51 +1,39 @@
 """kid_db_read_support* (reads called by k-mer support) against the independent model of tests/read_support_model.py,
 against the classify path of the same library, and against its own contract.  Every comparison is exact: integers."""
-import os
-import re
 
 import numpy as np
 import pytest
 
+import read_calls
 import read_support_cases as sc
-from helpers import ROOT, DeviceBatch, concat_reads, fastq_block, oracle_db
-from kmer_id_amd import KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KidError, KmerDB, _lib, end_merged
+from helpers import DeviceBatch, concat_reads, fastq_block, oracle_db
+from kmer_id_amd import KID_FLAG_REF_GEOMETRY, KmerDB, _lib, end_merged
 from kmer_id_amd.api import SUPPORT_DTYPE
-from read_hits_model import HitModel, trim_ranges, windows
+from read_calls import KINDS, ends_equal, genome_world, header_constant, same_records, status
+from read_hits_model import HitModel, trim_ranges
 from read_support_model import RULES, SupportModel
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"minloc": 0, "ref_geometry": KID_FLAG_REF_GEOMETRY, "host_build": KID_FLAG_HOST_BUILD}
 FIELDS = SUPPORT_DTYPE.names
-LANE_HITS = int(re.search(r"#define\s+KID_SUPPORT_LANE_HITS\s+(\d+)u", open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_support.hip.h")).read()).group(1))
+LANE_HITS = header_constant("kid_support.hip.h", "KID_SUPPORT_LANE_HITS")
 
 
-def same_records(got, exp, what=""):
-    assert got.dtype == SUPPORT_DTYPE and got.shape == exp.shape, what
-    for f in FIELDS:
-        bad = np.flatnonzero(got[f] != exp[f])
-        assert bad.size == 0, "%s: read %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got[bad[0]], exp[bad[0]])
-
-
-class World:
+class World(read_calls.World):
     """a database, its model, a batch of reads and the model's records for every rule of the grid: computed once"""
 
     def __init__(self, parent, keys, targets, bases, off, log2_slots, rules=RULES):
-        self.parent, self.keys, self.targets, self.bases, self.off, self.log2_slots = parent, keys, targets, bases, off, log2_slots
-        self.odb = oracle_db(parent, keys, targets, log2_slots)
-        self.hm = HitModel(self.odb, keys, targets, 30)
-        self.model = SupportModel(self.hm, parent)
+        super().__init__(parent, keys, targets, bases, off, log2_slots)
+        self.model = self.sm
         self.hits = self.hm.batch(bases, off)
         self.finals = self.model.finals(self.hits)
         self.exp = {rule: self.model.batch_identity(self.hits, rule, self.finals) for rule in rules}
 
-    def db(self, flags=0):
-        return KmerDB(self.keys, self.targets, self.parent, k=30, log2_slots=self.log2_slots, flags=flags)
-
     def check(self, db, what=""):
         """every rule's records equal the model's, and `final` equals kid_classify_batch's per-read output"""
         for rule, exp in self.exp.items():
-            same_records(db.read_support(self.bases, self.off, min_hits=rule[0], min_permille=rule[1]), exp, "%s rule %s" % (what, rule))
+            same_records(db.read_support(self.bases, self.off, min_hits=rule[0], min_permille=rule[1]), exp, SUPPORT_DTYPE,
+                         "%s rule %s" % (what, rule))
         s = db.sample()
         assert np.array_equal(s.classify(self.bases, self.off), self.finals), what
         s.close()
@@ -96,16 +84,6 @@ def test_records_repeat_byte_for_byte(world, db):
 
 
 # ------------------------------------------------------------------ 2. work-split edges
-def genome_world(rng, lineage, genome_len, every):
-    """a database of every `every`-th window of a random genome under targets drawn from `lineage`; a read that is a
-    stretch of the genome has a run of consecutive database k-mers"""
-    g = rng.choice(sc.ACGT, genome_len).tobytes()
-    keys, _ = windows(g, 0, genome_len - 1, 30)
-    keys = keys[::every]
-    tg = np.array(lineage, np.uint32)[rng.integers(0, len(lineage), keys.size)]
-    return g, keys, tg
-
-
 def test_work_split_edges(world):
     rng = np.random.default_rng(64)
     parent = world.parent
@@ -136,7 +114,7 @@ def test_work_split_edges(world):
         assert [int(per[j]) for j in (0, 63, 64)] == [counts[i], counts[(i + 1) % 7], counts[(i + 2) % 7]] and int(per[1]) == 0
         finals = model.finals(hits)
         for rule in rules:
-            same_records(d.read_support(bases, off, min_hits=rule[0], min_permille=rule[1]), model.batch_identity(hits, rule, finals),
+            same_records(d.read_support(bases, off, min_hits=rule[0], min_permille=rule[1]), model.batch_identity(hits, rule, finals), SUPPORT_DTYPE,
                          "batch %d rule %s" % (i, rule))
         s = d.sample()
         assert np.array_equal(s.classify(bases, off), finals)
@@ -195,10 +173,6 @@ def test_hand_built_trees(depth):
 
 
 # ------------------------------------------------------------------ 5. tally
-def ends_equal(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
 def adversarial(world):
     n = 600  # the first 600 reads of the world are the adversarial ones: 0 .. 300 bytes, whole-read ranges
     return world.bases[:int(world.off[n])], world.off[:n + 1]
@@ -210,7 +184,7 @@ def test_tally_under_rule_00_equals_classifying(world, db):
     s, t = db.sample(), db.sample()
     s.classify(bases, off)
     rec = db.read_support(bases, off, tally=t)
-    same_records(rec, world.exp[(0, 0)][:600])
+    same_records(rec, world.exp[(0, 0)][:600], SUPPORT_DTYPE)
     g, u = t.end()
     assert ends_equal((g, u), s.end()) and int(g.sum()) == 600 and int(u.sum()) > 100
     s.close(), t.close()
@@ -261,7 +235,7 @@ def test_tally_under_rule_2_25_equals_the_model(world, db):
     t = db.sample()
     rec = db.read_support(world.bases, world.off, min_hits=2, min_permille=25, tally=t)
     exp = world.exp[(2, 25)]
-    same_records(rec, exp)
+    same_records(rec, exp, SUPPORT_DTYPE)
     g, u = world.model.tally(world.hits, exp, np.ones(exp.size, bool), world.targets)
     assert int(g[0]) > int((world.finals == 0).sum())  # the rule un-calls reads
     before = t.stats()
@@ -287,8 +261,8 @@ def test_device_form_equals_host_form(world, db):
         db.support_from_hits_device(d.d_ho.value, d.d_hits.value, d.d_nk.value, n, d_out.value, min_hits=2, min_permille=25)
         _lib.check(d.lib.kid_dev_sync(0))
         got = d.down(d_out, np.uint32, n * 6).view(SUPPORT_DTYPE)
-        same_records(got, host, "device form")
-        same_records(got, world.exp[(2, 25)], "device form vs model")
+        same_records(got, host, SUPPORT_DTYPE, "device form")
+        same_records(got, world.exp[(2, 25)], SUPPORT_DTYPE, "device form vs model")
         # the same batch in three calls (offsets stay absolute: the hits pointer is the same)
         d_out3 = d.dev(n * 24, np.full(n * 6, 0xA5A5A5A5, np.uint32))
         cuts = [0, n // 3, n // 3 + 65, n]
@@ -305,11 +279,6 @@ def test_device_form_equals_host_form(world, db):
 # ------------------------------------------------------------------ 7. errors
 def test_error_statuses(world, db):
     bases, off = adversarial(world)
-
-    def status(f):
-        with pytest.raises(KidError) as e:
-            f()
-        return e.value.status
 
     assert status(lambda: db.read_support(bases, off, min_permille=1001)) == -1
     assert db.read_support(bases, off, min_permille=1000).size == 600

@@ -1,64 +1,42 @@
 """kid_db_read_votes* (reads called by root-path votes) against the independent model of tests/read_votes_model.py and
 against its own contract: a record that does not depend on the order of a read's hits.  Every comparison is exact."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
+import read_calls
 import read_depth_model as dm
 import read_support_cases as sc
 import read_votes_cases as vc
-from helpers import ROOT, DeviceBatch, concat_reads, fastq_block, oracle_db
-from kmer_id_amd import KID_FLAG_HOST_BUILD, KID_FLAG_REF_GEOMETRY, KID_OPT_ENTRY_DEPTH, VOTE_DTYPE, KidError, KmerDB, _lib
+from helpers import DeviceBatch, concat_reads, fastq_block, oracle_db
+from kmer_id_amd import KID_FLAG_REF_GEOMETRY, KID_OPT_ENTRY_DEPTH, VOTE_DTYPE, KmerDB, _lib
+from read_calls import KINDS, ends_equal, header_constant, same_records, seen_bits, status
 from read_hits_model import HitModel, Hits, trim_ranges, windows
 from read_support_model import RULES, SupportModel
 from read_votes_model import VoteModel
 
 pytestmark = pytest.mark.gpu
 
-KINDS = {"minloc": 0, "ref_geometry": KID_FLAG_REF_GEOMETRY, "host_build": KID_FLAG_HOST_BUILD}
 FIELDS = VOTE_DTYPE.names
-_HEADER = open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_votes.hip.h")).read()
-LANE_HITS = int(re.search(r"#define\s+KID_VOTE_LANE_HITS\s+(\d+)u", _HEADER).group(1))
-WAVE_HITS = int(re.search(r"#define\s+KID_VOTE_WAVE_HITS\s+(\d+)u", _HEADER).group(1))
+LANE_HITS = header_constant("kid_votes.hip.h", "KID_VOTE_LANE_HITS")
+WAVE_HITS = header_constant("kid_votes.hip.h", "KID_VOTE_WAVE_HITS")
 EDGE_RULES = [(0, 0), (3, 0), (2, 25), (0, 1000)]
 
 
-def same_records(got, exp, what=""):
-    assert got.dtype == VOTE_DTYPE and got.shape == exp.shape, what
-    for f in FIELDS:
-        bad = np.flatnonzero(got[f] != exp[f])
-        assert bad.size == 0, "%s: read %d: %s: got %s, the model %s" % (what, int(bad[0]), f, got[bad[0]], exp[bad[0]])
-
-
-def ends_equal(a, b):
-    return np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
-
-
-def seen_bits(s, n_entries):
-    return np.unpackbits(s.seen_export(0, s.seen_bytes()), bitorder="little")[:n_entries].astype(bool)
-
-
-class World:
+class World(read_calls.World):
     """a database, its models, a batch of reads and the model's records for every rule of the grid: computed once"""
 
     def __init__(self, parent, keys, targets, bases, off, log2_slots, rules=RULES):
-        self.parent, self.keys, self.targets, self.bases, self.off, self.log2_slots = parent, keys, targets, bases, off, log2_slots
-        self.hm = HitModel(oracle_db(parent, keys, targets, log2_slots), keys, targets, 30)
-        self.sm = SupportModel(self.hm, parent)
+        super().__init__(parent, keys, targets, bases, off, log2_slots)
         self.vm = VoteModel(self.sm)
         self.hits = self.hm.batch(bases, off)
         calls = self.vm.calls_anc(self.hits)
         self.exp = {rule: self.vm.batch_anc(self.hits, rule, calls) for rule in rules}
 
-    def db(self, flags=0):
-        return KmerDB(self.keys, self.targets, self.parent, k=30, log2_slots=self.log2_slots, flags=flags)
-
     def check(self, db, what=""):
         for rule, exp in self.exp.items():
-            same_records(db.read_votes(self.bases, self.off, min_hits=rule[0], min_permille=rule[1]), exp, "%s rule %s" % (what, rule))
+            same_records(db.read_votes(self.bases, self.off, min_hits=rule[0], min_permille=rule[1]), exp, VOTE_DTYPE, "%s rule %s" % (what, rule))
 
 
 @pytest.fixture(scope="module")
@@ -167,7 +145,7 @@ class Dense:
 
     def check(self, bases, off, exp, what):
         for rule, e in exp.items():
-            same_records(self.db.read_votes(bases, off, min_hits=rule[0], min_permille=rule[1]), e, "%s rule %s" % (what, rule))
+            same_records(self.db.read_votes(bases, off, min_hits=rule[0], min_permille=rule[1]), e, VOTE_DTYPE, "%s rule %s" % (what, rule))
 
 
 @pytest.fixture(scope="module")
@@ -245,7 +223,7 @@ def test_splits_of_a_batch_into_calls_give_the_same_bytes(dense):
         batch[slot] = dense.read(h)
     bases, off = concat_reads(batch)
     whole = dense.db.read_votes(bases, off, min_hits=2, min_permille=25)
-    same_records(whole, dense.model(bases, off, [(2, 25)])[1][(2, 25)], "whole")
+    same_records(whole, dense.model(bases, off, [(2, 25)])[1][(2, 25)], VOTE_DTYPE, "whole")
     for step in (1, 63, 65):
         parts = [dense.db.read_votes(bases, off[a:a + step + 1], min_hits=2, min_permille=25) for a in range(0, 130, step)]
         assert np.concatenate(parts).tobytes() == whole.tobytes(), step
@@ -271,7 +249,7 @@ def test_tally_equals_the_model_applied_to_the_vote_records(world, db, dense):
     for rule in [(0, 0), (2, 25)]:
         s = depth_sample(db)
         rec = db.read_votes(world.bases, world.off, min_hits=rule[0], min_permille=rule[1], tally=s)
-        same_records(rec, world.exp[rule])
+        same_records(rec, world.exp[rule], VOTE_DTYPE)
         g, _ = check_tally(s, world.sm, world.hits, world.exp[rule], np.ones(rec.size, bool), world.targets, world.keys.size, "rule %s" % (rule,))
         assert int(g.sum()) == rec.size
         s.close()
@@ -284,7 +262,7 @@ def test_tally_equals_the_model_applied_to_the_vote_records(world, db, dense):
     assert len({int(e["confident"][63]) for e in exp.values()}) >= 2
     for rule, e in exp.items():
         s = depth_sample(dense.db)
-        same_records(dense.db.read_votes(bases, off, min_hits=rule[0], min_permille=rule[1], tally=s), e)
+        same_records(dense.db.read_votes(bases, off, min_hits=rule[0], min_permille=rule[1], tally=s), e, VOTE_DTYPE)
         check_tally(s, dense.sm, hits, e, np.ones(e.size, bool), dense.tg, dense.keys.size, "dense rule %s" % (rule,))
         s.close()
 
@@ -306,7 +284,7 @@ def test_tally_of_a_fastq_block_with_dropped_records(world, db):
     exp = world.vm.batch_anc(hits, (2, 0))
     s = depth_sample(db)
     got = db.read_votes_fastq(text, recs, min_hits=2, tally=s)
-    same_records(got, exp, "fastq")
+    same_records(got, exp, VOTE_DTYPE, "fastq")
     assert np.all(got["n_kmers"][~keep] == 0)
     g, _ = check_tally(s, world.sm, hits, exp, keep, world.targets, world.keys.size, "fastq")
     assert int(g.sum()) == int(keep.sum())  # a dropped record is counted nowhere
@@ -332,11 +310,6 @@ def test_classify_and_vote_tallies_mix_in_one_sample(world, db):
 def test_error_statuses(world, db):
     n = 600
     bases, off = world.bases[:int(world.off[n])], world.off[:n + 1]
-
-    def status(f):
-        with pytest.raises(KidError) as e:
-            f()
-        return e.value.status
 
     assert status(lambda: db.read_votes(bases, off, min_permille=1001)) == -1
     assert db.read_votes(bases, off, min_permille=1000).size == n
@@ -376,8 +349,8 @@ def test_device_form_on_what_read_hits_device_left(world, db):
         db.votes_from_hits_device(d.d_ho.value, d.d_hits.value, d.d_nk.value, n, d_out.value, min_hits=2, min_permille=25)
         _lib.check(d.lib.kid_dev_sync(0))
         got = d.down(d_out, np.uint32, n * 8).view(VOTE_DTYPE)
-        same_records(got, host, "device form")
-        same_records(got, world.exp[(2, 25)], "device form vs model")
+        same_records(got, host, VOTE_DTYPE, "device form")
+        same_records(got, world.exp[(2, 25)], VOTE_DTYPE, "device form vs model")
         # the same batch in three calls (offsets stay absolute: the hits pointer is the same)
         d_out3 = d.dev(n * 32, np.full(n * 8, 0xA5A5A5A5, np.uint32))
         cuts = [0, n // 3, n // 3 + 65, n]
@@ -401,5 +374,5 @@ def test_device_form_on_what_read_hits_device_left(world, db):
         tg = world.hits.target.copy()
         tg[h0], tg[h0 + 1] = 1, 1
         patched = Hits(world.hits.offsets, world.hits.n_kmers, world.hits.pos, tg, world.hits.entry)
-        same_records(got, world.vm.batch_anc(patched, (0, 0)), "targets out of range")
+        same_records(got, world.vm.batch_anc(patched, (0, 0)), VOTE_DTYPE, "targets out of range")
         assert (int(got[r]["call"]), int(got[r]["p_best"]), int(got[r]["n_best"])) == (6, 3, 1)

@@ -4,22 +4,20 @@ of a word, a tile and a workgroup's span, for entries in (org, pos) order and un
 runs of one bin across those edges, organisms of 0 .. 3000 bins and 70 000 organisms, a bin of 70 000 seen entries, the
 bin widths at their extremes, 1 .. 64 bitmaps, a live sample; the argument errors write nothing."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import seen_coverage_model as cm
 import shared_kmers_model as sm
-from helpers import ROOT, small_db
+from helpers import small_db
 from kmer_id_amd import COVERAGE_DTYPE, KidError, KmerDB, _lib, seen_coverage, seen_coverage_bins, synth
+from read_calls import header_constant
 
 pytestmark = pytest.mark.gpu
 
-SRC = open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_coverage.hip.h")).read()
-TILE = int(re.search(r"#define\s+KID_COV_TILE\s+(\d+)u", SRC).group(1))
-SPAN = TILE * int(re.search(r"#define\s+KID_COV_MIN_SPAN\s+(\d+)u", SRC).group(1))  # entries a workgroup takes at least
+TILE = header_constant("kid_coverage.hip.h", "KID_COV_TILE")
+SPAN = TILE * header_constant("kid_coverage.hip.h", "KID_COV_MIN_SPAN")  # entries a workgroup takes at least
 
 
 def same_records(got, exp, what):

@@ -3,22 +3,20 @@ tests/shared_kmers_model.py: exact equality of int64[n, n, ntar] for the entry c
 the kernel's words, quads, tiles and spans, for bitmaps that are empty, full (padding bits included), sparse and dense,
 for 1 .. 64 bitmaps in host and in device memory, through both forms; two real samples; the argument errors."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import shared_kmers_model as sm
-from helpers import ROOT, oracle_db, small_db
+from helpers import oracle_db, small_db
 from kmer_id_amd import KidError, KmerDB, _lib, shared_kmers, synth
+from read_calls import header_constant
 
 pytestmark = pytest.mark.gpu
 
 NTAR = 12
-SRC = open(os.path.join(ROOT, "kmer_id_amd", "csrc", "kid_shared.hip.h")).read()
-TILE = int(re.search(r"#define\s+KID_SHARED_TILE\s+(\d+)u", SRC).group(1))
-SPAN = TILE * int(re.search(r"#define\s+KID_SHARED_MIN_SPAN\s+(\d+)u", SRC).group(1))  # entries a workgroup takes at least
+TILE = header_constant("kid_shared.hip.h", "KID_SHARED_TILE")
+SPAN = TILE * header_constant("kid_shared.hip.h", "KID_SHARED_MIN_SPAN")  # entries a workgroup takes at least
 SIZES = [1, 31, 32, 33, 127, 128, 129, 2047, 2048, 2049, 4097, SPAN - 1, SPAN, SPAN + 1, 70001]
 
 

@@ -8,41 +8,13 @@ import pytest
 
 import read_support_cases as sc
 from helpers import concat_reads, oracle_db
-from read_hits_model import HitModel, windows
+from read_calls import RC_SETTINGS, mirrored, strand_world
+from read_hits_model import HitModel
 from read_segment_votes_model import VOTE_FIELDS, SegmentVoteModel, segment_votes_line
 from read_segments_model import SegmentModel
 from read_support_model import SupportModel
 
 SETTINGS = [(63, 63), (64, 64), (65, 13), (100, 50), (121, 121), (10 ** 6, 10 ** 6)]
-RC_SETTINGS = [(100, 50), (500, 250), (2000, 2000)]
-COMPLEMENT = bytes.maketrans(b"ACGTN", b"TGCAN")
-
-
-def revcomp(seq):
-    return bytes(seq).translate(COMPLEMENT)[::-1]
-
-
-def strand_world(parent, targets_of_world, rng=None):
-    """the 2029-base genome world: every window of a random genome under targets drawn from [8, 6, 5, 36, 35, 8, 6, X]
-    (X on another lineage), the genome as one record (P = 2000) and its reverse complement as a second
-    -> keys, targets, bases, offsets"""
-    rng = rng or np.random.default_rng(2029)
-    x = next(int(t) for t in targets_of_world if t > 1 and sc.top_level(parent, int(t)) != 5)
-    g = rng.choice(sc.ACGT, 2029).tobytes()
-    keys, _ = windows(g, 0, len(g) - 1, 30)
-    tg = np.array([8, 6, 5, 36, 35, 8, 6, x], np.uint32)[rng.integers(0, 8, keys.size)]
-    bases, off = concat_reads([g, revcomp(g)])
-    return keys, tg, bases, off
-
-
-def mirrored(off, rec, what=""):
-    """the records of read 0 against those of read 1, its reverse complement: segment j is segment n_seg - 1 - j there"""
-    a, b = rec[int(off[0]):int(off[1])], rec[int(off[1]):int(off[2])][::-1]
-    assert a.size == b.size and a.size > 0, what
-    assert np.array_equal(a["n_pos"], b["n_pos"]), what
-    P = int(a["pos"][-1] + a["n_pos"][-1])  # (start = 0)
-    assert np.array_equal(a["pos"].astype(np.int64), P - b["pos"].astype(np.int64) - b["n_pos"].astype(np.int64)), what
-    return a, b
 
 
 @pytest.fixture(scope="module")
