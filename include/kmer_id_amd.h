@@ -625,6 +625,60 @@ int kid_db_read_segment_votes_device(kid_db *db, const void *d_bases, uint64_t b
                                      uint64_t seg_cap, void *d_n_hits, void *d_n_segments, void *stream);
 int kid_db_read_segment_votes_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
 
+/* ---- placing reads on a genome by colinear hits --------------------------------------------
+ * Every call above uses a hit's target alone.  A hit also says where on which genome its probe lies: a line of the
+ * probes file is SEQ,target,org,position,strand,count.  The hits of a read that is a stretch of genome g lie on one
+ * diagonal -- position - pos is the same for all of them when the read is forward, position + pos when it is reverse --
+ * and spurious hits, hits in repeats and the two halves of a chimeric read do not.  These calls find, per read, the
+ * diagonal most hits agree on.  Integers only; targets play no role.
+ * Sites: two host arrays uint32[n_entries] in the numbering of kid_hit.entry (what load_probes_gz(.., want_sites) and
+ * read_probe_sites yield): org[o] < 2^24 = KID_LOCI_MAX_ORGS and pos[o] < 2^31, n_entries the database's own; anything
+ * else is KID_ERR_ARG and changes nothing.  org = pos = NULL with n_entries = 0 frees the sites; a second call replaces
+ * them.  8 bytes of HBM per entry, owned by the kid_db; NOT copied by kid_db_replicate.  Synchronises the device.       */
+#define KID_LOCI_MAX_ORGS (1u << 24)
+#define KID_LOCI_MAX_HITS 4096u
+int kid_db_set_sites(kid_db *db, const uint32_t *org, const uint32_t *pos, uint64_t n_entries);
+/* For one read let h_1 .. h_m be its hits as kid_db_read_hits reports them, n its n_kmers and W >= 1 the diagonal bin
+ * width diag_bin.
+ *   participants  the first min(m, KID_LOCI_MAX_HITS) hits in list order; of these a hit with entry >= n_entries (possible
+ *                 in the from-hits form alone) is ignored: it counts in n_hits and nowhere else.  Hits with target 1 or
+ *                 a target outside (0, ntar) take part like any other.
+ *   keys          participant i with g = org[entry_i], x = pos[entry_i], r = pos_i has the forward key
+ *                 (g, 0, floor((x - r) / W)) and the reverse key (g, 1, (x + r) / W): 64-bit signed arithmetic, floor
+ *                 toward minus infinity.  c(key) is the number of participants that have the key.
+ *   best key      the largest c; ties go to strand 0 before strand 1, then the lowest g, then the lowest diagonal.  The
+ *                 chain is the set of participants with the best key.
+ *   org, strand   those of the best key;  n_chain its c
+ *   n_org         the participants with g = org, on whatever diagonal
+ *   n_other       the largest c(key) over keys with g != org, 0 when there is none: the evidence for a chimera
+ *   n_hits        m: all hits, those beyond KID_LOCI_MAX_HITS and the ignored ones included;  n_kmers = n
+ *   pos_first, pos_last  the smallest and largest pos in the chain
+ *   entry_first   the entry of the chain hit at pos_first (the lowest if several share that pos): the chain lies at genome
+ *                 coordinate pos[entry_first] at read position pos_first
+ * Without a participant every field but n_hits and n_kmers is 0; n_chain = 0 says so.  With one, n_chain = 1 and strand = 0
+ * by the tie order: the strand then carries no information.
+ * For m <= KID_LOCI_MAX_HITS the record is a pure function of the multiset of (pos, entry) and of n: the same under any
+ * permutation of the hits, byte-identical across runs, splits of a batch into calls and table kinds.  No atomics on
+ * outputs; reads of more than a few hundred hits are settled by a second kernel queued behind the first.
+ * There is no rule, no tally and no sample: a locus is not a count.                                                   */
+typedef struct kid_locus {
+    uint32_t org, strand, n_chain, n_org, n_other, n_hits /* m */, n_kmers, pos_first, pos_last, entry_first;
+} kid_locus;
+/* The forms of kid_db_read_support* with diag_bin in the place of the rule and without a tally: host buffers (40 bytes per
+ * read come back), a FASTQ block (KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply as in
+ * kid_db_read_hits_fastq), the kernels alone on a CSR in HBM (d_out: kid_locus[n_reads]; asynchronous on `stream`), and the
+ * device time of the loci kernels ALONE since the last query.  Errors and the one-call-at-a-time rule are theirs, in the
+ * same order, with diag_bin = 0 KID_ERR_ARG where they refuse a rule, and a database without sites KID_ERR_STATE (nothing
+ * is allocated or launched) behind the check of n_reads; out = NULL with reads is KID_ERR_ARG; n_reads = 0 returns KID_OK
+ * and launches nothing.  Scratch beside the hit pass's: 4 bytes per read of the largest batch.                        */
+int kid_db_read_loci(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                     uint64_t n_reads, uint32_t diag_bin, kid_locus *out);
+int kid_db_read_loci_fastq(kid_db *db, const uint8_t *text, uint64_t text_nbytes, const kid_fastq_rec *recs, uint64_t n_reads,
+                           uint32_t diag_bin, kid_locus *out);
+int kid_db_loci_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
+                                 uint32_t diag_bin, void *d_out, void *stream);
+int kid_db_read_loci_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
+
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).
  * Synchronises the sample's outstanding work first.  The sample has ended then:

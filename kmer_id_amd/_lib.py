@@ -56,6 +56,17 @@ def _segment_family(name):
     }
 
 
+def _loci_family():
+    """kid_db_set_sites and the four entry points of kid_db_read_loci*: batch or block, diag_bin, out"""
+    return {
+        "kid_db_set_sites": (C.c_int, [_p, _p, _p, _u64]),
+        "kid_db_read_loci": (C.c_int, [_p, _p, _p, _p, _p, _u64, _u32, _p]),
+        "kid_db_read_loci_fastq": (C.c_int, [_p, _p, _u64, _p, _u64, _u32, _p]),
+        "kid_db_loci_from_hits_device": (C.c_int, [_p, _p, _p, _p, _u64, _u32, _p, _p]),
+        "kid_db_read_loci_time": _TIME,
+    }
+
+
 # name -> (restype, argtypes); every symbol include/kmer_id_amd.h declares
 PROTOTYPES = {
     "kid_strerror": (C.c_char_p, [C.c_int]),
@@ -107,6 +118,7 @@ PROTOTYPES = {
     **_unit_family("fragment_votes", pairs=True),
     **_segment_family("segments"),
     **_segment_family("segment_votes"),
+    **_loci_family(),
     "kid_sample_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kid_sample_end_merged": (C.c_int, [c_void_pp, C.c_int, C.c_void_p, C.c_void_p]),
     "kid_sample_stats": (C.c_int, [C.c_void_p, C.c_void_p]),
@@ -168,6 +180,8 @@ KID_OPT_LOW_COMPLEXITY = 5
 KID_OPT_LINE_DIGEST = 6
 KID_DB_OPT_MIN_BASE_QUALITY = 1
 KID_DB_OPT_LOW_COMPLEXITY = 2
+KID_LOCI_MAX_ORGS = 1 << 24
+KID_LOCI_MAX_HITS = 4096
 KID_SHARED_MAX_SAMPLES = 64
 KID_COVERAGE_MAX_BINS = 1 << 28
 KID_FLAG_U_IS_T = 1

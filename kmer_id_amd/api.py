@@ -110,6 +110,10 @@ SEGMENT_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np
 # kid_segment_vote: one record per segment (kid_db_read_segment_votes*); the eight fields behind n_pos are VOTE_DTYPE's
 SEGMENT_VOTE_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(name, np.uint32) for name in VOTE_DTYPE.names])
 
+# kid_locus: one record per read (kid_db_read_loci*)
+LOCUS_DTYPE = np.dtype([(name, np.uint32) for name in ("org", "strand", "n_chain", "n_org", "n_other", "n_hits", "n_kmers", "pos_first",
+                                                       "pos_last", "entry_first")])
+
 
 # the families of calls over the hit pass by the name in their entry points: the record, and for those that leave one
 # record per unit the reads of a unit
@@ -497,6 +501,51 @@ class KmerDB:
     def read_segment_votes_time(self):
         """-> (device ms, calls, reads) of the segment scans and segment-vote kernels alone since the last query"""
         return self._time(self._lib.kid_db_read_segment_votes_time)
+
+    def set_sites(self, org, pos):
+        """Give the database its sites (kid_db_set_sites): org and pos hold fields 3 and 4 of the probe line of every entry,
+        in the order the builder got them (what read_probe_sites yields); org < 2^24, pos < 2^31.  A second call replaces
+        them; a replica starts without."""
+        org = _as(org, np.uint32)
+        pos = _as(pos, np.uint32)
+        if org.shape != pos.shape or org.ndim != 1:
+            raise ValueError("org and pos must be 1-D arrays of equal length")
+        check(self._lib.kid_db_set_sites(self._h, _ptr(org), _ptr(pos), org.size))
+
+    def clear_sites(self):
+        """Free the sites: every read_loci call is KID_ERR_STATE until set_sites."""
+        check(self._lib.kid_db_set_sites(self._h, None, None, 0))
+
+    def read_loci(self, bases, offsets, start=None, stop=None, diag_bin=1):
+        """Place the reads of a batch held in host memory by colinear hits (kid_db_read_loci): -> a structured array
+        (LOCUS_DTYPE: org, strand, n_chain, n_org, n_other, n_hits, n_kmers, pos_first, pos_last, entry_first), one record
+        per read.  A hit at read position r on entry e has the forward key (org[e], 0, floor((pos[e] - r) / diag_bin)) and
+        the reverse key (org[e], 1, (pos[e] + r) / diag_bin); the chain is the set of hits with the most common key
+        (ties: strand 0, then the lowest org, then the lowest diagonal), n_other the most common key's count on another
+        org.  The chain lies at genome coordinate pos[entry_first] at read position pos_first."""
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        out = np.zeros(n, LOCUS_DTYPE)
+        check(self._lib.kid_db_read_loci(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, diag_bin, _ptr(out)))
+        return out
+
+    def read_loci_fastq(self, text, recs, diag_bin=1):
+        """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
+        fails stop - start >= k has no window and no hit; KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply
+        as in read_hits_fastq."""
+        text, recs, n = _fastq_block(text, recs)
+        out = np.zeros(n, LOCUS_DTYPE)
+        check(self._lib.kid_db_read_loci_fastq(self._h, _ptr(text), text.size, _ptr(recs), n, diag_bin, _ptr(out)))
+        return out
+
+    def loci_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, diag_bin=1, stream=0):
+        """The loci kernels alone on a CSR resident in HBM (raw pointers, as kid_db_read_hits_device left it); asynchronous
+        on `stream`: kid_db_loci_from_hits_device.  d_out: kid_locus[n_reads] (LOCUS_DTYPE)."""
+        check(self._lib.kid_db_loci_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None), C.c_void_p(d_n_kmers),
+                                                     n_reads, diag_bin, C.c_void_p(d_out), C.c_void_p(stream or None)))
+
+    def read_loci_time(self):
+        """-> (device ms, calls, reads) of the loci kernels alone since the last query"""
+        return self._time(self._lib.kid_db_read_loci_time)
 
     def shared_kmers(self, items):
         """K-mers shared between samples (kid_db_shared_kmers) -> int64[n, n, ntar]: [i, j, t] = the database entries of

@@ -24,6 +24,7 @@ struct kid_db {
     std::mutex hits_mu;
     int min_base_quality = 0; // KID_DB_OPT_MIN_BASE_QUALITY (kid_api_mask.h): read and written under hits_mu; a replica starts at 0
     int low_complexity = 0;   // KID_DB_OPT_LOW_COMPLEXITY (kid_api_lowc.h): the same rules
+    KidDevBuf site_org, site_pos; // uint32 per entry: kid_db_set_sites (kid_api_loci.h), under hits_mu; a replica starts without
     ~kid_db(); // kid_api_hits.h: where KidHitsState is complete
 };
 typedef std::unique_ptr<kid_db, void (*)(kid_db *)> KidDbPtr; // a database under construction

@@ -1,7 +1,7 @@
 // kid_api_hits.h -- every read's k-mer hits: the scratch of a database's hit passes and kid_db_read_hits*.
 // What the other families over the hit pass -- kid_db_read_support* (kid_api_support.h), kid_db_read_fragments*
 // (kid_api_fragments.h), kid_db_read_segments* (kid_api_segments.h), kid_db_read_votes* (kid_api_votes.h), kid_db_read_fragment_votes* (kid_api_fragment_votes.h),
-// kid_db_read_segment_votes* (kid_api_segment_votes.h) -- share with kid_db_read_hits* is here once:
+// kid_db_read_segment_votes* (kid_api_segment_votes.h), kid_db_read_loci* (kid_api_loci.h) -- share with kid_db_read_hits* is here once:
 // KidSpanTimer, KidFamily and KidFamilyState (a family's id, and its share of the state under that id), KidVoteScratch
 // and kid_vote_scratch_bind (the scratch of a vote family's second kernel), kid_hits_state (the scratch, free: the
 // timers a family settles), kid_hits_scan (the three-kernel exclusive scan), KidOpenBatch and kid_hits_open_* (a
@@ -73,6 +73,7 @@ enum KidFamily : int {
     KID_FAM_FRAGMENTS,
     KID_FAM_VOTES,
     KID_FAM_FRAGMENT_VOTES,
+    KID_FAM_LOCI,
     KID_FAM_COUNT
 };
 constexpr unsigned kid_settle(KidFamily f) { return 1u << f; }
@@ -114,6 +115,7 @@ struct KidHitsState {
     // holds fragment indexes), kid_db_read_segment_votes* (a list of 24 B per segment the call can write, and the vote
     // family's rows)
     KidVoteScratch vote_big, fragment_vote_big, segment_vote_big;
+    KidDevBuf loci_list, loci_n_list; // kid_db_read_loci* (kid_api_loci.h): the reads of the second kernel (uint32 per read), their number
     KidDevBuf lowc_plane; // KID_DB_OPT_LOW_COMPLEXITY: the flag plane of a staged block with a line that is split (kid_lowc.hip.h)
     KidHitsState() { segment_vote_big.rows = &vote_big.own_rows; }
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }

@@ -1,0 +1,353 @@
+// kid_loci.hip.h -- place reads on a genome by colinear hits (kid_db_read_loci*): one record per read from the hits of a
+// batch and the sites of the database (org and pos per entry, kid_db_set_sites), a pure function of the MULTISET of a
+// read's (pos, entry) pairs; targets play no role.
+// Input: the CSR of kid_hits.hip.h and the windows looked up per read, as for kid_support.hip.h.  For one read with hits
+// h_1 .. h_m, n windows and the diagonal bin W >= 1:
+//   participants the first min(m, KID_LOCI_MAX_HITS) hits whose entry < n_entries
+//   keys         of a participant with g = org[entry], x = pos[entry], r = its pos in the read:
+//                forward (g, 0, floor((x - r) / W)), reverse (g, 1, (x + r) / W); 64-bit, floor toward minus infinity
+//   c(key)       the participants that have the key
+//   best key     the largest c; ties: strand 0 first, then the lowest g, then the lowest diagonal.  The chain: the
+//                participants with that key
+//   record       org and strand of the best key, n_chain = its c, n_org = participants with g = org, n_other = the
+//                largest c over keys of another g (0: none), n_hits = m, n_kmers = n, pos_first / pos_last = the smallest
+//                and largest read position in the chain, entry_first = the entry of the chain hit at pos_first (the lowest
+//                if several share it).  No participant: everything but n_hits and n_kmers is 0
+// A key is one 64-bit word, strand << 58 | g << 34 | diagonal (g < 2^24; the forward diagonal biased by 2^32: x - r is
+// at least -(2^32 - 1), and both stay below 2^34), so the tie order is the order of the words.
+//
+// What a set of keys comes to is a KidLociTop: the best (c, key) and the largest c among keys of another g, with that g.
+// Two of them merge (kid_loci_top_merge); the merge is associative, commutative and idempotent in what the record takes
+// from it, so lanes, waves and strands may be folded in any order and a key may be offered more than once.
+//
+// Three regimes by the read's hits m, all giving the same record:
+//   m <= KID_LOCI_LANE_HITS   a lane takes the read: its keys in registers, c by pairwise tests
+//   m <= KID_LOCI_WAVE_HITS   the whole wave: 64 candidate hits per tile, every lane's two keys against the keys of all m
+//                             hits (computed 64 at a time and handed round by readlane); the lanes' tops merged by a butterfly
+//   more                      kid_loci_kernel appends the read's index to a device list and writes nothing for it;
+//                             kid_loci_big_kernel, queued behind it, takes the list with one workgroup per read: the forward
+//                             keys of the participants sorted in LDS (bitonic, 32 KiB), every run's length found by a binary
+//                             search from its first element, then the same for the reverse keys; the threads' tops merged
+//                             through LDS.  The order of the list is not deterministic; nothing read from it depends on that.
+// Behind the best key every regime passes over the participants once more for n_org and the chain's ends.
+// No atomics but the list's counter; nothing is written outside `out`, the list and its counter.
+#pragma once
+#include "kid_hits.hip.h"
+
+#define KID_LOCI_LANE_HITS 8u    // a read with more hits than this is taken by the whole wave
+#define KID_LOCI_WAVE_HITS 256u  // ... and one with more than this by a workgroup of kid_loci_big_kernel
+#define KID_LOCI_MAX_HITS 4096u  // the hits of a read that take part (= include/kmer_id_amd.h)
+#define KID_LOCI_NO_KEY (~0ull)  // the keys of a hit that takes no part: equal to no participant's
+
+struct KidLocus { // = kid_locus (include/kmer_id_amd.h)
+    uint32_t org, strand, n_chain, n_org, n_other, n_hits, n_kmers, pos_first, pos_last, entry_first;
+};
+struct KidLociSites {
+    const uint32_t *org, *pos; // per entry: org < 2^24, pos < 2^31 (kid_db_set_sites checks)
+    uint64_t n_entries;
+    uint32_t diag_bin; // W >= 1
+};
+struct KidLociBig { // the reads left to kid_loci_big_kernel
+    uint32_t *list;   // uint32[n_reads]
+    uint32_t *n_list; // their number: zeroed in front of kid_loci_kernel
+};
+struct KidLociTop {
+    uint64_t key;    // the best key so far (c > 0)
+    uint32_t c;      // its count; 0: no key yet
+    uint32_t c2, g2; // the largest count among keys of another org than the best key's, and that org (c2 > 0)
+};
+struct KidLociEnds { // of the chain, and n_org
+    unsigned long long first; // min of pos << 32 | entry over the chain
+    uint32_t last, n_org;
+};
+
+__device__ __forceinline__ uint32_t kid_loci_key_org(uint64_t key) { return (uint32_t)(key >> 34) & 0xFFFFFFu; }
+
+// the two keys of a hit; KID_LOCI_NO_KEY twice when its entry is none of the database's (the CSR may be the caller's)
+__device__ __forceinline__ void kid_loci_keys(const KidLociSites &s, const KidHit &h, uint64_t &fk, uint64_t &rk)
+{
+    fk = rk = KID_LOCI_NO_KEY;
+    if ((uint64_t)h.entry >= s.n_entries) return;
+    const uint64_t g = s.org[h.entry] & 0xFFFFFFu, w = s.diag_bin;
+    const int64_t x = (int64_t)s.pos[h.entry], r = (int64_t)h.pos;
+    int64_t df = x - r;
+    uint64_t dr = (uint64_t)(x + r);
+    if (w != 1) {
+        df = df >= 0 ? (int64_t)((uint64_t)df / w) : -(int64_t)(((uint64_t)(-df) + w - 1) / w);
+        dr /= w;
+    }
+    fk = g << 34 | (uint64_t)(df + (1ll << 32));
+    rk = 1ull << 58 | g << 34 | dr;
+}
+
+__device__ __forceinline__ KidLociTop kid_loci_top_empty()
+{
+    KidLociTop t = {KID_LOCI_NO_KEY, 0u, 0u, 0u};
+    return t;
+}
+
+// a := what the keys behind a and those behind b come to together
+__device__ __forceinline__ void kid_loci_top_merge(KidLociTop &a, const KidLociTop &b)
+{
+    const uint32_t cc[4] = {a.c, a.c2, b.c, b.c2};
+    const uint32_t gg[4] = {kid_loci_key_org(a.key), a.g2, kid_loci_key_org(b.key), b.g2};
+    if (b.c > a.c || (b.c == a.c && b.key < a.key)) { a.key = b.key; a.c = b.c; }
+    const uint32_t g = kid_loci_key_org(a.key);
+    a.c2 = a.g2 = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+        if (gg[i] != g && cc[i] > a.c2) { a.c2 = cc[i]; a.g2 = gg[i]; }
+}
+
+__device__ __forceinline__ void kid_loci_top_add(KidLociTop &a, uint64_t key, uint32_t c)
+{
+    const KidLociTop b = {key, c, 0u, 0u};
+    kid_loci_top_merge(a, b);
+}
+
+// the tops of a wave's lanes -> one, the same in every lane
+__device__ __forceinline__ void kid_loci_top_wave(KidLociTop &t)
+{
+    for (int s = 32; s >= 1; s >>= 1) {
+        KidLociTop o;
+        o.key = (uint64_t)__shfl_xor((unsigned long long)t.key, s);
+        o.c = (uint32_t)__shfl_xor((int)t.c, s);
+        o.c2 = (uint32_t)__shfl_xor((int)t.c2, s);
+        o.g2 = (uint32_t)__shfl_xor((int)t.g2, s);
+        kid_loci_top_merge(t, o);
+    }
+    // (lanes may differ in g2 where two orgs tie for c2, which nobody reads behind this: one copy for all)
+    t.key = (uint64_t)__shfl((unsigned long long)t.key, 0);
+    t.c = (uint32_t)__builtin_amdgcn_readlane((int)t.c, 0);
+    t.c2 = (uint32_t)__builtin_amdgcn_readlane((int)t.c2, 0);
+    t.g2 = (uint32_t)__builtin_amdgcn_readlane((int)t.g2, 0);
+}
+
+__device__ __forceinline__ KidLociEnds kid_loci_ends_empty()
+{
+    KidLociEnds e = {~0ull, 0u, 0u};
+    return e;
+}
+
+// one participant (fk != KID_LOCI_NO_KEY) into the ends of the chain of `best`
+__device__ __forceinline__ void kid_loci_ends_add(KidLociEnds &e, uint64_t best, uint64_t fk, uint64_t rk, const KidHit &h)
+{
+    e.n_org += kid_loci_key_org(fk) == kid_loci_key_org(best) ? 1u : 0u;
+    if ((best >> 58 ? rk : fk) == best) {
+        const unsigned long long p = (unsigned long long)h.pos << 32 | h.entry;
+        e.first = p < e.first ? p : e.first;
+        e.last = h.pos > e.last ? h.pos : e.last;
+    }
+}
+
+__device__ __forceinline__ void kid_loci_ends_merge(KidLociEnds &e, unsigned long long first, uint32_t last, uint32_t n_org)
+{
+    e.first = first < e.first ? first : e.first;
+    e.last = last > e.last ? last : e.last;
+    e.n_org += n_org;
+}
+
+__device__ __forceinline__ void kid_loci_ends_wave(KidLociEnds &e)
+{
+    for (int s = 32; s >= 1; s >>= 1)
+        kid_loci_ends_merge(e, __shfl_xor(e.first, s), (uint32_t)__shfl_xor((int)e.last, s), (uint32_t)__shfl_xor((int)e.n_org, s));
+}
+
+// top (c > 0) and the ends of its chain -> the record's first five fields and its last three
+__device__ __forceinline__ void kid_loci_settle(const KidLociTop &t, const KidLociEnds &e, KidLocus &res)
+{
+    res.org = kid_loci_key_org(t.key);
+    res.strand = (uint32_t)(t.key >> 58) & 1u;
+    res.n_chain = t.c;
+    res.n_org = e.n_org;
+    res.n_other = t.c2;
+    res.pos_first = (uint32_t)(e.first >> 32);
+    res.pos_last = e.last;
+    res.entry_first = (uint32_t)e.first;
+}
+
+// ---- one lane, one read of 1 .. KID_LOCI_LANE_HITS hits
+__device__ __forceinline__ void kid_loci_lane(const KidLociSites &s, const KidHit *h, uint32_t m, KidLocus &res)
+{
+    uint64_t fk[KID_LOCI_LANE_HITS], rk[KID_LOCI_LANE_HITS];
+#pragma unroll
+    for (uint32_t i = 0; i < KID_LOCI_LANE_HITS; i++) {
+        fk[i] = rk[i] = KID_LOCI_NO_KEY;
+        if (i < m) kid_loci_keys(s, h[i], fk[i], rk[i]);
+    }
+    KidLociTop top = kid_loci_top_empty();
+#pragma unroll
+    for (uint32_t i = 0; i < KID_LOCI_LANE_HITS; i++) {
+        if (fk[i] == KID_LOCI_NO_KEY) continue;
+        uint32_t cf = 0, cr = 0;
+#pragma unroll
+        for (uint32_t j = 0; j < KID_LOCI_LANE_HITS; j++) {
+            cf += fk[j] == fk[i] ? 1u : 0u;
+            cr += rk[j] == rk[i] ? 1u : 0u;
+        }
+        kid_loci_top_add(top, fk[i], cf);
+        kid_loci_top_add(top, rk[i], cr);
+    }
+    if (top.c == 0) return;
+    KidLociEnds e = kid_loci_ends_empty();
+#pragma unroll
+    for (uint32_t i = 0; i < KID_LOCI_LANE_HITS; i++)
+        if (fk[i] != KID_LOCI_NO_KEY) kid_loci_ends_add(e, top.key, fk[i], rk[i], h[i]);
+    kid_loci_settle(top, e, res);
+}
+
+__device__ __forceinline__ uint64_t kid_loci_readlane(uint64_t v, uint32_t j)
+{
+    return (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, (int)j) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), (int)j) << 32;
+}
+
+// ---- the whole wave, one read of at most KID_LOCI_WAVE_HITS hits (every argument wave-uniform; so is the result)
+__device__ __forceinline__ void kid_loci_wave(const KidLociSites &s, const KidHit *h, uint32_t m, uint32_t lane, KidLocus &res)
+{
+    KidLociTop top = kid_loci_top_empty();
+    for (uint32_t c0 = 0; c0 < m; c0 += 64u) { // a tile of 64 candidate hits, one per lane
+        uint64_t fk = KID_LOCI_NO_KEY, rk = KID_LOCI_NO_KEY;
+        if (lane < m - c0) kid_loci_keys(s, h[c0 + lane], fk, rk);
+        uint32_t cf = 0, cr = 0;
+        for (uint32_t j0 = 0; j0 < m; j0 += 64u) { // against all m hits, 64 at a time
+            const uint32_t nj = m - j0 < 64u ? m - j0 : 64u;
+            uint64_t fj = fk, rj = rk;
+            if (j0 != c0) {
+                fj = rj = KID_LOCI_NO_KEY;
+                if (lane < nj) kid_loci_keys(s, h[j0 + lane], fj, rj);
+            }
+            for (uint32_t q = 0; q < nj; q++) {
+                cf += kid_loci_readlane(fj, q) == fk ? 1u : 0u;
+                cr += kid_loci_readlane(rj, q) == rk ? 1u : 0u;
+            }
+        }
+        if (fk != KID_LOCI_NO_KEY) {
+            kid_loci_top_add(top, fk, cf);
+            kid_loci_top_add(top, rk, cr);
+        }
+    }
+    kid_loci_top_wave(top);
+    if (top.c == 0) return;
+    KidLociEnds e = kid_loci_ends_empty();
+    for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
+        if (lane < m - c0) {
+            uint64_t fk, rk;
+            kid_loci_keys(s, h[c0 + lane], fk, rk);
+            if (fk != KID_LOCI_NO_KEY) kid_loci_ends_add(e, top.key, fk, rk, h[c0 + lane]);
+        }
+    }
+    kid_loci_ends_wave(e);
+    kid_loci_settle(top, e, res);
+}
+
+__global__ __launch_bounds__(256) void kid_loci_kernel(const uint64_t *hit_offsets, const KidHit *hits, const uint32_t *n_kmers,
+                                                        uint64_t n_reads, const KidLociSites sites, KidLocus *out, const KidLociBig big)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
+    for (uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; r0 < n_reads; r0 += n_waves * 64u) {
+        const uint64_t r = r0 + lane;
+        const bool have = r < n_reads;
+        uint64_t h0 = 0;
+        KidLocus res = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        if (have) {
+            h0 = hit_offsets[r];
+            res.n_hits = (uint32_t)(hit_offsets[r + 1] - h0);
+            res.n_kmers = n_kmers[r];
+        }
+        const uint32_t m = res.n_hits;
+        const bool later = m > KID_LOCI_WAVE_HITS; // kid_loci_big_kernel's: nothing is written for it here
+        if (later) big.list[atomicAdd(big.n_list, 1u)] = (uint32_t)r;
+        if (m > 0 && m <= KID_LOCI_LANE_HITS) kid_loci_lane(sites, hits + h0, m, res);
+        uint64_t wide = __ballot(m > KID_LOCI_LANE_HITS && !later);
+        while (wide) { // the reads of the 64 with more hits: the whole wave, one after the other
+            const int j = __builtin_ctzll(wide);
+            wide &= wide - 1ull;
+            const KidHit *wh = hits + (uint64_t)__shfl((unsigned long long)h0, j);
+            const uint32_t wm = (uint32_t)__builtin_amdgcn_readlane((int)m, j);
+            KidLocus w = {0u, 0u, 0u, 0u, 0u, wm, (uint32_t)__builtin_amdgcn_readlane((int)res.n_kmers, j), 0u, 0u, 0u};
+            kid_loci_wave(sites, wh, wm, lane, w);
+            if (lane == (uint32_t)j) res = w;
+        }
+        if (have && !later) out[r] = res;
+    }
+}
+
+// ------------------------------------------------------------------ reads of more than KID_LOCI_WAVE_HITS hits
+// keys[0, n2) of LDS ascending: n2 a power of two, at least 512; entered and left by all 256 threads
+__device__ __forceinline__ void kid_loci_sort(uint64_t *keys, uint32_t n2)
+{
+    for (uint32_t k = 2; k <= n2; k <<= 1)
+        for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+            for (uint32_t t = threadIdx.x; t < n2 / 2u; t += 256u) {
+                const uint32_t i = ((t & ~(j - 1u)) << 1) | (t & (j - 1u)), l = i | j;
+                const uint64_t a = keys[i], b = keys[l];
+                if ((a > b) == ((i & k) == 0u)) { keys[i] = b; keys[l] = a; }
+            }
+            __syncthreads();
+        }
+}
+
+// (the arguments of kid_loci_kernel; the list is at most n_reads long by construction, so that number is not looked at)
+__global__ __launch_bounds__(256) void kid_loci_big_kernel(const uint64_t *hit_offsets, const KidHit *hits, const uint32_t *n_kmers,
+                                                            uint64_t /* n_reads */, const KidLociSites sites, KidLocus *out, const KidLociBig big)
+{
+    __shared__ uint64_t keys[KID_LOCI_MAX_HITS];
+    __shared__ KidLociTop sh_top[4];
+    __shared__ KidLociEnds sh_ends[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t n_list = *big.n_list;
+    for (uint32_t e = blockIdx.x; e < n_list; e += gridDim.x) {
+        const uint32_t r = big.list[e];
+        const KidHit *h = hits + hit_offsets[r];
+        const uint32_t m = (uint32_t)(hit_offsets[r + 1] - hit_offsets[r]);
+        const uint32_t p = m < KID_LOCI_MAX_HITS ? m : KID_LOCI_MAX_HITS;
+        uint32_t n2 = 512u;
+        while (n2 < p) n2 <<= 1; // (at most KID_LOCI_MAX_HITS)
+        KidLociTop top = kid_loci_top_empty();
+        for (uint32_t strand = 0; strand < 2u; strand++) {
+            for (uint32_t i = threadIdx.x; i < n2; i += 256u) {
+                uint64_t fk = KID_LOCI_NO_KEY, rk = KID_LOCI_NO_KEY;
+                if (i < p) kid_loci_keys(sites, h[i], fk, rk);
+                keys[i] = strand ? rk : fk;
+            }
+            __syncthreads();
+            kid_loci_sort(keys, n2);
+            for (uint32_t i = threadIdx.x; i < p; i += 256u) { // the first element of a run finds its end
+                const uint64_t k = keys[i];
+                if (k == KID_LOCI_NO_KEY || (i > 0 && keys[i - 1] == k)) continue;
+                uint32_t lo = i + 1u, hi = n2;
+                while (lo < hi) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (keys[mid] <= k) lo = mid + 1u;
+                    else hi = mid;
+                }
+                kid_loci_top_add(top, k, lo - i);
+            }
+            __syncthreads(); // (the keys are overwritten next)
+        }
+        kid_loci_top_wave(top);
+        if (lane == 0) sh_top[wave] = top;
+        __syncthreads();
+        top = sh_top[0];
+        for (uint32_t w = 1; w < 4u; w++) kid_loci_top_merge(top, sh_top[w]);
+        KidLocus res = {0u, 0u, 0u, 0u, 0u, m, n_kmers[r], 0u, 0u, 0u};
+        if (top.c != 0) { // (uniform)
+            KidLociEnds ends = kid_loci_ends_empty();
+            for (uint32_t i = threadIdx.x; i < p; i += 256u) {
+                uint64_t fk, rk;
+                kid_loci_keys(sites, h[i], fk, rk);
+                if (fk != KID_LOCI_NO_KEY) kid_loci_ends_add(ends, top.key, fk, rk, h[i]);
+            }
+            kid_loci_ends_wave(ends);
+            if (lane == 0) sh_ends[wave] = ends;
+            __syncthreads();
+            ends = sh_ends[0];
+            for (uint32_t w = 1; w < 4u; w++) kid_loci_ends_merge(ends, sh_ends[w].first, sh_ends[w].last, sh_ends[w].n_org);
+            kid_loci_settle(top, ends, res);
+        }
+        if (threadIdx.x == 0) out[r] = res;
+        __syncthreads(); // (sh_top and sh_ends are written again for the next read)
+    }
+}

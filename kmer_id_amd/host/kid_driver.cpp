@@ -38,17 +38,23 @@ static double seconds_since(const std::chrono::steady_clock::time_point &t0)
 
 void load_database(const std::string &tree_path, const std::string &probes_path, const std::string &cache_path, int k, int ntar,
                    std::vector<int32_t> &parent, ProbeSet &ps, bool *from_cache, int threads, StartupTiming *timing,
-                   std::thread *cache_writer)
+                   std::thread *cache_writer, bool want_sites)
 {
     if (from_cache) *from_cache = false;
     const auto t0 = std::chrono::steady_clock::now();
     if (!cache_path.empty() && load_db_cache(cache_path, tree_path, probes_path, k, ntar, parent, ps)) {
         if (from_cache) *from_cache = true;
         if (timing) timing->cache_read_s = seconds_since(t0);
+        if (want_sites) { // the cache holds no sites: the text is read for them alone
+            ProbeSet text = load_probes_gz(probes_path, k, threads, timing, true);
+            if (text.orgs.size() != ps.keys.size()) throw Fatal{3, probes_path + " has another number of entries than the database cache " + cache_path};
+            ps.orgs = std::move(text.orgs);
+            ps.positions = std::move(text.positions);
+        }
         return;
     }
     parent = load_tree(tree_path, ntar);
-    ps = load_probes_gz(probes_path, k, threads, timing);
+    ps = load_probes_gz(probes_path, k, threads, timing, want_sites);
     if (cache_path.empty()) return;
     // the cache is written beside the upload and the table build when the caller can wait for it later (it must: `ps`
     // and `parent` are read until the writer is joined)
@@ -88,6 +94,7 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner)
     e->k = owner.k;
     e->batch_reads = owner.batch_reads;
     e->batch_bases = owner.batch_bases;
+    e->site_pos = owner.site_pos;
     for (kid_db *d : e->dbs) e->samples.push_back(begin_sample_or_die(d));
     e->sample = e->samples[0];
     engine_configure(*e, owner.side);
@@ -175,6 +182,11 @@ bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &pare
         if (rc != KID_OK) die_kid(rc);
         e.dbs.push_back(r);
         e.samples.push_back(begin_sample_or_die(r));
+    }
+    if (ps.orgs.size() == ps.keys.size() && ps.positions.size() == ps.keys.size() && ps.keys.size() > 0) { // loaded with sites: --loci
+        for (kid_db *d : e.dbs)
+            if ((rc = kid_db_set_sites(d, ps.orgs.data(), ps.positions.data(), ps.keys.size())) != KID_OK) die_kid(rc);
+        e.site_pos = std::make_shared<const std::vector<uint32_t>>(ps.positions.data(), ps.positions.data() + ps.positions.size());
     }
     return true;
 }
@@ -401,6 +413,14 @@ static void read_segment_votes(SideOptions &o, const char *prog, const char *opt
     o.segment_votes = parse_segments(prog, opt, v);
 }
 
+static void read_loci(SideOptions &o, const char *prog, const char *opt, const char *v)
+{
+    unsigned long long w = 0;
+    size_t at = 0;
+    if (digits_up_to(0x7FFFFFFFull, v, at, w) <= 0 || v[at] != 0 || w < 1) usage_error(prog, opt, "takes W, digits only: 1..2147483647");
+    o.loci = LociOption{true, (uint32_t)w};
+}
+
 // The side options: their words, the pass of side_options() that reads each, what reads its value -- or, for a switch,
 // which takes none, the flag it sets
 static const struct {
@@ -415,6 +435,7 @@ static const struct {
                     {"--low-complexity", 1, read_low_complexity, nullptr},
                     {"--segments", 2, read_segments, nullptr},
                     {"--segment-votes", 3, read_segment_votes, nullptr},
+                    {"--loci", 4, read_loci, nullptr},
                     {"--depth", 0, nullptr, &SideOptions::depth},
                     {"--seen", 0, nullptr, &SideOptions::seen},
                     {"--fragments", 0, nullptr, &SideOptions::fragments},
@@ -432,7 +453,7 @@ SideOptions side_options(int argc, char **argv, const char *prog)
 {
     SideOptions o;
     // one pass over the words per step of the order in which malformed options are reported
-    for (int pass = 0; pass < 4; pass++)
+    for (int pass = 0; pass < 5; pass++)
         for (int i = 1; i < argc; i++)
             for (const auto &so : kSideOptions) {
                 if (so.pass != pass || strcmp(argv[i], so.name) != 0) continue;
@@ -453,7 +474,7 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes, fragment_votes, segment_votes; };
+struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes, fragment_votes, segment_votes, loci; };
 static SidePaths side_paths(const std::string &r)
 {
     std::string seen = r; // the final "result.txt" becomes "seen.bin"
@@ -461,7 +482,8 @@ static SidePaths side_paths(const std::string &r)
     if (at != std::string::npos) seen.replace(at, 10, "seen.bin");
     else seen += ".seen.bin";
     return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen,
-            sibling_path_for(r, "fragments"), sibling_path_for(r, "votes"), sibling_path_for(r, "fragment_votes"), sibling_path_for(r, "segment_votes")};
+            sibling_path_for(r, "fragments"), sibling_path_for(r, "votes"), sibling_path_for(r, "fragment_votes"), sibling_path_for(r, "segment_votes"),
+            sibling_path_for(r, "loci")};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -476,6 +498,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.votes) remove(p.votes.c_str());
     if (all || side.fragment_votes) remove(p.fragment_votes.c_str());
     if (all || side.segment_votes.on) remove(p.segment_votes.c_str());
+    if (all || side.loci.on) remove(p.loci.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -620,9 +643,11 @@ void SampleOutputs::finish(Engine &e)
     if (side_.hits) write_lines(p.hits, hits_);
     if (side_.segments.on) write_lines(p.segments, segments_);
     if (side_.segment_votes.on) write_lines(p.segment_votes, segment_votes_);
+    if (side_.loci.on) write_lines(p.loci, loci_);
     hits_.clear();
     segments_.clear();
     segment_votes_.clear();
+    loci_.clear();
 }
 
 // One call of the kid_db_read_* family on a classified batch (its start / stop / final targets are known) on the batch's
@@ -741,6 +766,26 @@ static void segment_vote_lines_of(kid_db *db, const ReadBatch &b, const uint8_t 
     }
 }
 
+// The loci lines of one classified batch: kid_db_read_loci* with diag_bin = W; site_pos: the position of every entry's probe
+static void loci_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, const std::vector<uint32_t> &final_targ, int k, uint32_t diag_bin,
+                          const std::vector<uint32_t> &site_pos, std::string &out)
+{
+    const size_t nr = b.size();
+    std::vector<kid_locus> loci(nr);
+    read_pass(kid_db_read_loci_fastq, kid_db_read_loci, db, b, bases, diag_bin, loci.data());
+    char num[192];
+    for (size_t r = 0; r < nr; r++) {
+        const kid_locus &l = loci[r];
+        if (l.n_hits == 0) continue;
+        if (b.fq && !(b.stop[r] - b.start[r] >= k)) continue; // (dropped by process_qual: it has no hits anyway)
+        const uint32_t at = l.n_chain && l.entry_first < site_pos.size() ? site_pos[l.entry_first] : 0u;
+        const int n = snprintf(num, sizeof(num), "%u\t%d\t%u\t%u\t%u:%u:%u:%u:%u:%u:%u:%u", final_targ[r], b.stop[r] - b.start[r] + 1, l.n_kmers,
+                               l.n_hits, l.org, l.strand, l.n_chain, l.n_org, l.n_other, l.pos_first, l.pos_last, at);
+        out.append(num, (size_t)n);
+        append_header(out, b, r);
+    }
+}
+
 long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadSaver &saver, SampleOutputs &out, size_t saver_file,
                     const std::function<void(size_t, long long)> &done)
 {
@@ -848,6 +893,11 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             lines.clear();
             segment_vote_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.side.segment_votes, e.side.support, lines);
             out.add_segment_votes(saver_file + f.file, lines);
+        }
+        if (out.loci_on() && e.site_pos) {
+            lines.clear();
+            loci_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.k, e.side.loci.diag_bin, *e.site_pos, lines);
+            out.add_loci(saver_file + f.file, lines);
         }
         if (fragments && f.batch->fq) {
             mate_records[f.file] += f.batch->size();

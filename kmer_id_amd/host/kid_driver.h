@@ -27,6 +27,12 @@ struct SegmentsOption {
     bool on = false;
     uint32_t seg_len = 0, seg_step = 0;
 };
+// --loci W: place reads on a genome by colinear hits (kid_db_read_loci*).  Digits only; W, the diagonal bin width, in
+// 1..2147483647.
+struct LociOption {
+    bool on = false;
+    uint32_t diag_bin = 0;
+};
 struct SideOptions {
     bool hits = false;   // --hits: every read's k-mer hits
     SupportRule support;
@@ -62,11 +68,14 @@ struct SideOptions {
     // (kid_db_read_segment_votes*), into a segment_votes file.  Independent of --segments: both may be given, with
     // different geometries, and neither changes what the other writes.
     SegmentsOption segment_votes;
+    // --loci W: every read with a hit placed on a genome by its colinear hits, into a loci file.  The probes are loaded
+    // with their sites (load_database's want_sites) and every replica of the database gets them (engine_open).
+    LociOption loci;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
 // of --segments or --segment-votes too) is a usage error: "<prog>: <option> <what>" on stderr and exit code 2 -- of several, the first in
-// the order --min-hits / --confidence, --min-base-quality / --low-complexity, --segments, --segment-votes.
+// the order --min-hits / --confidence, --min-base-quality / --low-complexity, --segments, --segment-votes, --loci.
 SideOptions side_options(int argc, char **argv, const char *prog);
 // For a front-end that rejects the words it does not know: the number of value words behind `word` (0 or 1) if it
 // is a side option, else -1
@@ -89,6 +98,9 @@ struct Engine {
     size_t next_fragments = 0;           // ... dealt round-robin over the devices
     std::vector<kid_sample *> votes;     // under --votes: one sample per device that the vote pass of every batch tallies into
     std::vector<kid_sample *> fragment_votes; // under --fragment-votes: one per device for the fragments called by votes (dealt with `fragments`)
+    // under --loci: the position of every entry's probe (the host's copy of what the replicas got in engine_open: the loci
+    // file prints pos[entry_first]); a worker shares its owner's
+    std::shared_ptr<const std::vector<uint32_t>> site_pos;
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -110,12 +122,15 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner);
 // (and the cache is written for the next run).  `from_cache` reports which way it went.
 // `threads`: parse workers of the probes text (0: one per core, at most 8).  `cache_writer`: if given, a cache that has
 // to be (re)written is written on that thread -- join it before `parent` / `ps` go away.
+// `want_sites` (--loci): ps.orgs / ps.positions are filled as well.  The cache does not hold them and its format does not
+// change: behind a valid cache the probes text is still read once, for the sites alone (its entries must be the cache's).
 void load_database(const std::string &tree_path, const std::string &probes_path, const std::string &cache_path, int k, int ntar,
                    std::vector<int32_t> &parent, ProbeSet &ps, bool *from_cache = nullptr, int threads = 0,
-                   StartupTiming *timing = nullptr, std::thread *cache_writer = nullptr);
+                   StartupTiming *timing = nullptr, std::thread *cache_writer = nullptr, bool want_sites = false);
 
 // Hashtable + Tree1 onto the GPU(s) of parse_devices(): the table is built on the first device and replicated into the
-// others.  Returns false after printing the reference's "out of memory in table " (newkmer_10nx.cpp:256-260: the caller
+// others.  A ProbeSet with sites (--loci): every replica gets them (kid_db_set_sites) and e.site_pos a copy of the
+// positions.  Returns false after printing the reference's "out of memory in table " (newkmer_10nx.cpp:256-260: the caller
 // exits with 1).
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
@@ -201,10 +216,15 @@ private:
 // Only the segments with a hit are listed.  The rule is that of --min-hits / --confidence when given, else (0, 0);
 // --min-base-quality and --low-complexity apply as they do to the segments file.  It does not depend on how the reads
 // were batched, threaded or dealt over devices, and needs --segments no more than --segments needs it.
+//   --loci W, "loci": one line per read that was handed to process_read and has at least one k-mer hit, in the order of
+// the hits file, tab-separated, the header line last (kid_db_read_loci* with diag_bin = W on the batch's device):
+//   <final_targ> <trimmed length> <n_kmers> <n_hits> <org>:<strand>:<n_chain>:<n_org>:<n_other>:<pos_first>:<pos_last>:<pos[entry_first]> <header>
+// --min-base-quality and --low-complexity apply as they do to the hits file.  It does not depend on how the reads were
+// batched, threaded or dealt over devices.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
-// The batches of files read at the same time interleave: the hit, segment and segment_votes lines are held in memory per file and
+// The batches of files read at the same time interleave: the hit, segment, segment_votes and loci lines are held in memory per file and
 // written in file order by finish() -- what is held is the files themselves (reads without a hit leave nothing),
-// nothing else.  One that is not finished (its sample failed) leaves no hits, no segments and no segment_votes file.
+// nothing else.  One that is not finished (its sample failed) leaves no hits, no segments, no segment_votes and no loci file.
 class SampleOutputs {
 public:
     // removes the files of the options that are on, left there by an earlier run
@@ -214,20 +234,22 @@ public:
     bool fragments_on() const { return side_.fragments; }
     bool fragment_votes_on() const { return side_.fragment_votes; }
     bool segment_votes_on() const { return side_.segment_votes.on; }
+    bool loci_on() const { return side_.loci.on; }
     const std::string &result_path() const { return result_path_; }
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
     void add_segment_votes(size_t file, const std::string &lines) { add(segment_votes_, file, lines); }
+    void add_loci(size_t file, const std::string &lines) { add(loci_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
     // confident file, then the fragments file, then the votes file, then the fragment_votes file, then the depth file, then the seen file, then the hits file, then the
-    // segments file, then the segment_votes file
+    // segments file, then the segment_votes file, then the loci file
     void finish(Engine &e);
 private:
     using Lines = std::vector<std::string>; // [file]
     static void add(Lines &to, size_t file, const std::string &lines);
     SideOptions side_;
     std::string result_path_;
-    Lines hits_, segments_, segment_votes_;
+    Lines hits_, segments_, segment_votes_, loci_;
 };
 // The head of a seen file: the 8 bytes "KIDSEEN1", then these fields, little-endian, 32 bytes in all; nbytes bytes of
 // bitmap follow (the padded size of a database of n_entries: ((n_entries + 127) / 128) * 16, 16 for none)

@@ -25,6 +25,8 @@
 //                    by root-path votes, which do not depend on the order of a segment's hits nor on the strand a record was
 //                    assembled on, under the rule of --min-hits / --confidence; needs no --segments and changes nothing it
 //                    writes (kid_driver.h)
+//   --loci W             also write <prefix>_loci.txt: every read with a hit placed on a genome by its colinear hits, the diagonal
+//                    bin W wide (digits only, 1..2147483647); the probes are loaded with their sites (kid_driver.h)
 //   --depth              also write <prefix>_depth.txt: per target, the hits on its database k-mers by the reads called (under the
 //                    rule of --min-hits / --confidence when given), how many of them were hit, the quartiles of their depth and
 //                    the largest (kid_driver.h)
@@ -177,7 +179,7 @@ int main(int argc, char **argv)
                 if (kid_host_alloc(warm_device, 4096, &p) == KID_OK) kid_host_free(p);
             });
         }
-        load_database(tpath, pname, db_cache, k, ntar, parent, ps, &from_cache, threads, &tm, &cache_writer);
+        load_database(tpath, pname, db_cache, k, ntar, parent, ps, &from_cache, threads, &tm, &cache_writer, side.loci.on && dry_run.empty());
         const double t_db_loaded = since_start();
         double t_gpu_ready = -1, t_first_file = -1;
         size_t n_entries = ps.keys.size(), n_devices = 0;
