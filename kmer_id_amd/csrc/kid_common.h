@@ -179,18 +179,22 @@ KID_HD uint32_t kid_key_fp(uint64_t key)
 //   byte 7      [3:0] the header's count (0..7, 8 = full and chained), [7:4] the header's 12-bit overflow filter
 //               folded to four bits: nibble bit b is the OR of header filter bits 3b .. 3b + 2
 // The digest's answer is a SUPERSET of the header's: two equal 16-bit fingerprints have equal digest bytes, so every
-// slot the header names as a candidate is named by the digest too, and a key that set filter bit 20 + ((fp * 12) >> 16)
-// finds nibble bit ((fp * 12) >> 16) / 3 = fp >> 14 set, so every chain the header follows the digest follows too.
-// Every candidate is verified against the full key in its cell (line * 8 + 1 + slot; no header is needed to find it),
-// and a chain walk the 12-bit filter would have skipped simply finds nothing: the results are identical to the header
-// path's by construction, only the number of cells read (stats.probes) may differ.  The fingerprint of a tombstone
-// stays, as it does in the header: a false candidate costs a load.
+// slot the header names as a candidate is named by the digest too, and the loops flag every lookup on a full line, so
+// every chain the header follows is looked at.  (The nibble would narrow that to the keys whose filter bit
+// 20 + ((fp * 12) >> 16) falls into a set nibble bit, ((fp * 12) >> 16) / 3 = fp >> 14; no kernel reads it since the
+// resolver has the header's own 12 bits, but the plane's format is fixed -- tests/test_gpu_line_digest.py -- and keeps it.)
+// The digest only decides WHETHER a lookup is looked at again: a lookup it flags is settled by the resolver from the
+// header of its table line (the 16-bit fingerprints, the count, the 12-bit filter) and the candidate cells that header
+// names, each verified against the full key (line * 8 + 1 + slot) -- the header lies in the same 128-byte line as the
+// cells, so it comes with the request the first cell would have made.  A lookup the digest does not flag has no
+// candidate in the header either and no chain to follow: the results are identical to the header path's by
+// construction; a false flag of the 8-bit fingerprints or of a full line costs the resolver one header, no cell.  The
+// fingerprint of a tombstone stays, as it does in the header: a false candidate costs a load.
 KID_HD uint32_t kid_digest_fp(uint32_t fp) // fp: kid_key_fp, 1..65535 -> 1..255 (the high byte; 0 is kept for "unused")
 {
     const uint32_t d = fp >> 8;
     return d ? d : 1u;
 }
-KID_HD uint32_t kid_digest_ovf_bit(uint32_t fp) { return 28u + (fp >> 14); } // in the digest's high dword
 // the digest {lo, hi} of a line from its header words
 KID_HD void kid_digest_of_header(uint32_t h0, uint32_t h1, uint32_t h2, uint32_t h3, uint32_t &lo, uint32_t &hi)
 {
@@ -203,19 +207,15 @@ KID_HD void kid_digest_of_header(uint32_t h0, uint32_t h1, uint32_t h2, uint32_t
     hi = b[4] | (b[5] << 8) | (b[6] << 16) | (kid_hdr_count(h3) << 24) | (nib << 28);
 }
 KID_HD uint32_t kid_digest_count(uint32_t hi) { return (hi >> 24) & 15u; }
-KID_HD bool kid_digest_continues(uint32_t hi, uint32_t fp)
-{
-    return kid_digest_count(hi) >= KID_HDR_FULL && ((hi >> kid_digest_ovf_bit(fp)) & 1u) != 0;
-}
 // Candidate entries of a digest for fingerprint fp, as a bit set: bit 8j + 7 = entry j (j = 0..3), bit 8j + 6 = entry
-// 4 + j (j = 0..2).  Like kid_hdr_cand a superset (the zero-byte test can flag the byte above a match).
+// 4 + j (j = 0..2).  Like kid_hdr_cand a superset (the zero-byte test can flag the byte above a match).  Only "any bit
+// set" is used: which entries they are the resolver takes from the header.
 KID_HD uint32_t kid_digest_cand(uint32_t lo, uint32_t hi, uint32_t fp)
 {
     const uint32_t rep = kid_digest_fp(fp) * 0x01010101u, one = 0x01010101u, top = 0x80808080u;
     const uint32_t a = lo ^ rep, b = (hi ^ rep) | 0xFF000000u; // byte 7 = count and filter
     return (((a - one) & ~a) & top) | ((((b - one) & ~b) & top) >> 1);
 }
-KID_HD uint32_t kid_digest_entry(uint32_t bit) { return (bit >> 3) + ((bit & 1u) ? 0u : 4u); } // bit index -> entry 0..6
 
 // ---------------------------------------------------------------- synthetic data
 KID_HD uint64_t kid_splitmix64(uint64_t x)

@@ -37,10 +37,12 @@
 // fingerprint false positive, a full line) are queued with their key.  Only while hits are sparse:
 #define KID_EARLY_MAX 4u // ... tiles with at most this many flagged lookups
 #define KID_EARLY_QN 32u // ... while fewer than this many lookups are queued (profiles/r02/clumped_ec.txt)
-// Not in the DIGEST instantiations: there the candidate cell is a line of its own that comes from HBM, not an L2 hit
-// behind the header, and waiting for it in the hot loop costs more than the resolver's second look at the digest --
-// every flagged lookup deferred: 1138-1160 M pairs/s, with the early path 1091, the header kernels 1089
-// (profiles/digest/ab_early_vs_deferred.txt).
+// Not in the DIGEST instantiations: their hot loop has brought in a plane line, not the table line, so the candidate
+// cell would come from HBM, not from L2 behind a header, and waiting for it in the hot loop costs more than deferring
+// every flagged lookup: 1138-1160 M pairs/s, with the early path 1091, the header kernels 1089
+// (profiles/digest/ab_early_vs_deferred.txt).  The resolver then settles a flagged lookup from its table line alone:
+// the header (cell 0, the one HBM request) and the candidate cell behind it in the same 128 bytes -- the digest is not
+// read a second time (profiles/resolver_header/).
 #define KID_GEN_ML_LDS_WORDS (104 + 3 * KID_CQ_CAP + KID_CQ_CAP / 4 + 64) // general loops on the minimizer-localised table: strip, counters, queue, results
 #define KID_CLASSIFY_OCC 8 // waves per SIMD the register allocator must leave room for
 // ... except the duo loop with ancestor rows: at 64 VGPRs it spills, and a spill or copy of a register that an
@@ -898,23 +900,19 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             if (valid) { klo = CQ_klo[base + lane]; khi = CQ_khi[base + lane]; ln = CQ_lw[base + lane]; tag = CQ_tag[base + lane]; }
             const bool verified = (tag & 0x80u) != 0; // {target, entry ordinal} fetched when the header came in
             tag &= 63u;
-            // the header once more (the queue keeps only the line: working out the candidates at
-            // queueing time would cost the hot loop ~45 instructions per read with a match)
+            // the header (the queue keeps only the line: working out the candidates at queueing time would cost the hot
+            // loop ~45 instructions per read with a match).  Header kernels: once more, usually still in L2.  DIGEST: for
+            // the first time -- the hot loop flagged the lookup on the digest's 8-bit fingerprints, and the header's 16-bit
+            // ones, count and 12-bit filter decide here; it arrives with the 128-byte line the candidate cell lies in, so a
+            // flagged lookup costs one table line, and a false flag of the digest no cell load at all
             uint32_t tgt = 0, slot = 0, mu = 0;
             const uint32_t fp = kid_key_fp(((uint64_t)khi << 32) | klo);
             bool fu = false;
-            bool dg = DIGEST; // mu names its entries the digest's way (kid_digest_cand) until a chained line's header replaces it
             if (verified) { tgt = klo; slot = khi; }
             if (valid && !verified) {
-                if constexpr (DIGEST) {
-                    const uint2 h = db.digest[ln];
-                    mu = kid_digest_cand(h.x, h.y, fp);
-                    fu = kid_digest_continues(h.y, fp);
-                } else {
-                    const uint4 h = kid_load_cell(db.table, ln * KID_LINE_CELLS);
-                    mu = kid_hdr_cand(h, fp);
-                    fu = kid_hdr_continues(h.w, fp);
-                }
+                const uint4 h = kid_load_cell(cells(), ln * KID_LINE_CELLS);
+                mu = kid_hdr_cand(h, fp);
+                fu = kid_hdr_continues(h.w, fp);
             }
             { // (cells read: one add for the wave, not one per lane on the same LDS word)
                 const uint64_t cm = __ballot(mu != 0);
@@ -922,7 +920,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             }
             if (mu) { // the first candidate of every entry in one round trip: almost always the key itself
                 const uint32_t bit = (uint32_t)__builtin_ctz(mu);
-                const uint32_t idx = ln * KID_LINE_CELLS + 1u + (DIGEST ? kid_digest_entry(bit) : kid_cand_entry(bit));
+                const uint32_t idx = ln * KID_LINE_CELLS + 1u + kid_cand_entry(bit);
                 mu &= mu - 1;
                 const uint4 c = kid_load_cell(cells(), idx);
                 if (c.z != 0 && c.x == klo && c.y == khi) { tgt = c.z; slot = c.w - 1u; }
@@ -931,7 +929,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             while (go) { // a second candidate (1e-4 of the lookups) or a chained line (1e-5)
                 if (mu) {
                     const uint32_t bit = (uint32_t)__builtin_ctz(mu);
-                    const uint32_t j = dg ? kid_digest_entry(bit) : kid_cand_entry(bit);
+                    const uint32_t j = kid_cand_entry(bit);
                     mu &= mu - 1;
                     const uint32_t ix = ln * KID_LINE_CELLS + 1u + j;
                     const uint4 cc = kid_load_cell(cells(), ix);
@@ -943,7 +941,6 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                     atomicAdd(&WC[3], 1u);
                     mu = kid_hdr_cand(h, fp);
                     fu = kid_hdr_continues(h.w, fp);
-                    dg = false;
                 } else go = false;
             }
             uint4 row = make_uint4(0, 0, 0, 0);
