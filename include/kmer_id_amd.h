@@ -679,6 +679,77 @@ int kid_db_loci_from_hits_device(kid_db *db, const void *d_hit_offsets, const vo
                                  uint32_t diag_bin, void *d_out, void *stream);
 int kid_db_read_loci_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
 
+/* ---- placed reads piled up per genome bin ---------------------------------------------------
+ * kid_locus records added up: how many placed reads cover each stretch of each genome.  Integers only.
+ * Geometry.  A pileup belongs to one kid_db that has sites and to a bin width W >= 1; its geometry is that of
+ *   kid_seen_coverage for the same W (see below), so the two profiles line up bin for bin:
+ *   n_orgs = the largest org of the sites + 1;  span_bins[g] = 1 + max(pos[o] / W) over the entries of organism g, 0 when
+ *   it has none;  bin_base = the exclusive scan of span_bins;  B = their sum.  B > KID_COVERAGE_MAX_BINS is KID_ERR_ARG,
+ *   before anything of B elements is allocated.
+ * Counters.  Two uint32 per bin, starts[g][b] and depth[g][b], zero after creation and after kid_pileup_reset; two uint64
+ *   beside them, n_records (records handed in) and n_placed.  The per-bin counters are exact while a pileup has placed
+ *   fewer than 2^32 records; beyond that they are taken modulo 2^32.
+ * Placing.  One call adds a list of records under min_chain >= 1 and min_margin >= 0.  A record L is placed when
+ *   L.n_chain >= min_chain,  (L.n_chain >= L.n_other ? L.n_chain - L.n_other : 0) >= min_margin,  L.strand <= 1,
+ *   L.entry_first < n_entries  and  L.org == org[L.entry_first] (which implies span_bins[L.org] >= 1); otherwise it changes
+ *   nothing.  Records kid_db_read_loci* produced with n_chain >= 1 always satisfy the last three; the device form may be
+ *   handed anything.
+ * What a placed record adds (64-bit signed arithmetic).  a = pos[L.entry_first];  d = L.pos_last >= L.pos_first ?
+ *   L.pos_last - L.pos_first : 0;  k the database's k-mer length.  Forward (strand 0): lo = a, hi = a + d + k - 1.  Reverse
+ *   (strand 1): lo = max(0, a - d), hi = a + k - 1.  With g = L.org: b_lo = min(lo / W, span_bins[g] - 1) and b_hi =
+ *   min(hi / W, span_bins[g] - 1).  The record adds 1 to starts[g][b_lo] and 1 to depth[g][b] for every b in b_lo..b_hi.
+ *   With diag_bin = 1 the interval [lo, hi] is exactly the genome interval covered by the chain's k-mers.
+ * The pileup is a pure function of the multiset of placed records: it does not depend on the order of the records, the
+ *   split into calls or the stream, is byte-identical across runs, and the pileup of a union is the element-wise sum of
+ *   the pileups of the parts.
+ * Summary.  One kid_pileup_rec per organism:
+ *   n_placed        the sum of starts over the organism's bins         span_bins  as above
+ *   bins_covered    bins with depth >= 1
+ *   max_gap         the longest run of consecutive bins 0..span_bins-1 with depth = 0 (span_bins when nothing is placed)
+ *   max_depth, max_depth_bin    the largest depth and the lowest bin that reaches it (0 when nothing is placed)
+ *   max_starts, max_starts_bin  the same for starts
+ *   reserved        0                                                   depth_sum  the sum of depth over the bins
+ *   An organism without entries has an all-zero record.  The record is 48 bytes: nine uint32, four bytes of padding (zero)
+ *   that align the uint64, and depth_sum.
+ * Worked case.  W = 100, k = 30, organism 3 with entries at positions 0, 100, 250, 990: span_bins = 10.  Under
+ *   (min_chain, min_margin) = (2, 1):  forward, entry_first at pos 100, pos_first 10, pos_last 130, n_chain 5, n_other 0:
+ *   [lo, hi] = [100, 249], bins 1..2;  reverse, entry_first at pos 250, pos_first 0, pos_last 120, n_chain 3, n_other 2:
+ *   [130, 279], bins 1..2;  forward, entry_first at pos 990, pos_last - pos_first = 100, n_chain 2, n_other 2: the margin is 0,
+ *   not placed.  The third once more under (2, 0): [990, 1119], both ends clamp to bin 9.  Then
+ *   starts = [0,2,0,0,0,0,0,0,0,1], depth = [0,2,2,0,0,0,0,0,0,1], record 3, 10, 3, 6, 2, 1, 2, 1, 0, depth_sum 5.
+ * Storage.  depth is kept as a step array of B + n_orgs uint32: organism g owns the span_bins[g] + 1 slots from
+ *   bin_base[g] + g on, a record adds +1 at slot b_lo and -1 (wrap-around) at slot b_hi + 1, and depth is the running sum.
+ *   kid_pileup_export and kid_pileup_merge move (starts, steps): both are linear, merge adds element-wise.
+ * Lifetime.  The database must outlive the pileup.  A pileup's geometry is that of the sites in force when it was made:
+ *   after a later kid_db_set_sites (the clearing form included) kid_pileup_add* return KID_ERR_STATE, while summary, bins,
+ *   export, counts and reset keep working on what it holds (it keeps the old site arrays alive; nothing freed is read).
+ *   After kid_db_destroy of its database a pileup may only be passed to kid_pileup_destroy.
+ * Calls.  A null pointer is KID_ERR_ARG.  kid_pileup_create: bin_width = 0 KID_ERR_ARG, then a database without sites
+ *   KID_ERR_STATE (nothing allocated or launched), then B over the cap KID_ERR_ARG.  kid_pileup_add*: min_chain = 0
+ *   KID_ERR_ARG, a stale pileup KID_ERR_STATE, n = 0 KID_OK with nothing launched.  kid_pileup_add_device (d_loci:
+ *   kid_locus[n] in HBM) is asynchronous on `stream`; every reading call (counts, summary, bins, export, time) first waits
+ *   for the pileup's own queued adds.  kid_pileup_bins with starts = depth = NULL and cap = 0 is the sizing call (bin_base
+ *   alone is written; B is bin_base[n_orgs]); one array without the other, or cap < B, is KID_ERR_ARG and nothing is
+ *   written.  kid_pileup_time: device time of the add kernels alone since the last query.  Calls on one pileup from
+ *   several threads are serialised.                                                                                   */
+typedef struct kid_pileup kid_pileup;
+typedef struct kid_pileup_rec {
+    uint32_t n_placed, span_bins, bins_covered, max_gap, max_depth, max_depth_bin, max_starts, max_starts_bin, reserved;
+    uint64_t depth_sum; /* at offset 40 */
+} kid_pileup_rec;
+int kid_pileup_create(kid_db *db, uint32_t bin_width, kid_pileup **out);
+int kid_pileup_destroy(kid_pileup *p);
+int kid_pileup_info(kid_pileup *p, uint32_t *n_orgs, uint64_t *n_bins, uint32_t *bin_width);
+int kid_pileup_reset(kid_pileup *p);
+int kid_pileup_add(kid_pileup *p, const kid_locus *loci, uint64_t n, uint32_t min_chain, uint32_t min_margin);
+int kid_pileup_add_device(kid_pileup *p, const void *d_loci, uint64_t n, uint32_t min_chain, uint32_t min_margin, void *stream);
+int kid_pileup_counts(kid_pileup *p, uint64_t *n_records, uint64_t *n_placed);
+int kid_pileup_summary(kid_pileup *p, kid_pileup_rec *out /* [n_orgs] */);
+int kid_pileup_bins(kid_pileup *p, uint64_t *bin_base /* [n_orgs + 1] */, uint32_t *starts, uint32_t *depth, uint64_t cap);
+int kid_pileup_export(kid_pileup *p, uint32_t *starts /* [B] */, uint32_t *steps /* [B + n_orgs] */);
+int kid_pileup_merge(kid_pileup *p, const uint32_t *starts, const uint32_t *steps, uint64_t n_records, uint64_t n_placed);
+int kid_pileup_time(kid_pileup *p, double *device_ms, uint64_t *calls, uint64_t *records);
+
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).
  * Synchronises the sample's outstanding work first.  The sample has ended then:

@@ -67,6 +67,25 @@ def _loci_family():
     }
 
 
+def _pileup_family():
+    """the kid_pileup_* entry points: a handle over a database's sites and a bin width"""
+    dp = C.POINTER(C.c_double)
+    return {
+        "kid_pileup_create": (C.c_int, [_p, _u32, c_void_pp]),
+        "kid_pileup_destroy": (C.c_int, [_p]),
+        "kid_pileup_info": (C.c_int, [_p, c_u32p, c_u64p, c_u32p]),
+        "kid_pileup_reset": (C.c_int, [_p]),
+        "kid_pileup_add": (C.c_int, [_p, _p, _u64, _u32, _u32]),
+        "kid_pileup_add_device": (C.c_int, [_p, _p, _u64, _u32, _u32, _p]),
+        "kid_pileup_counts": (C.c_int, [_p, c_u64p, c_u64p]),
+        "kid_pileup_summary": (C.c_int, [_p, _p]),
+        "kid_pileup_bins": (C.c_int, [_p, _p, _p, _p, _u64]),
+        "kid_pileup_export": (C.c_int, [_p, _p, _p]),
+        "kid_pileup_merge": (C.c_int, [_p, _p, _p, _u64, _u64]),
+        "kid_pileup_time": (C.c_int, [_p, dp, c_u64p, c_u64p]),
+    }
+
+
 # name -> (restype, argtypes); every symbol include/kmer_id_amd.h declares
 PROTOTYPES = {
     "kid_strerror": (C.c_char_p, [C.c_int]),
@@ -119,6 +138,7 @@ PROTOTYPES = {
     **_segment_family("segments"),
     **_segment_family("segment_votes"),
     **_loci_family(),
+    **_pileup_family(),
     "kid_sample_end": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "kid_sample_end_merged": (C.c_int, [c_void_pp, C.c_int, C.c_void_p, C.c_void_p]),
     "kid_sample_stats": (C.c_int, [C.c_void_p, C.c_void_p]),

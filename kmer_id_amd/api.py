@@ -113,6 +113,10 @@ SEGMENT_VOTE_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(nam
 # kid_locus: one record per read (kid_db_read_loci*)
 LOCUS_DTYPE = np.dtype([(name, np.uint32) for name in ("org", "strand", "n_chain", "n_org", "n_other", "n_hits", "n_kmers", "pos_first",
                                                        "pos_last", "entry_first")])
+# kid_pileup_rec: one record per organism (kid_pileup_summary): nine uint32, four bytes of padding, depth_sum at offset 40
+PILEUP_FIELDS = ("n_placed", "span_bins", "bins_covered", "max_gap", "max_depth", "max_depth_bin", "max_starts", "max_starts_bin", "reserved")
+PILEUP_DTYPE = np.dtype({"names": PILEUP_FIELDS + ("depth_sum",), "formats": [np.uint32] * 9 + [np.uint64],
+                         "offsets": [4 * i for i in range(9)] + [40], "itemsize": 48})
 
 
 # the families of calls over the hit pass by the name in their entry points: the record, and for those that leave one
@@ -547,6 +551,11 @@ class KmerDB:
         """-> (device ms, calls, reads) of the loci kernels alone since the last query"""
         return self._time(self._lib.kid_db_read_loci_time)
 
+    def pileup(self, bin_width=1000):
+        """A pileup of placed reads per genome bin over this database's sites (kid_pileup_create): -> Pileup.  The
+        database must outlive it."""
+        return Pileup(self, bin_width)
+
     def shared_kmers(self, items):
         """K-mers shared between samples (kid_db_shared_kmers) -> int64[n, n, ntar]: [i, j, t] = the database entries of
         target t that items i and j both have a bit for; the diagonal is an item's own bits per target (a sample's
@@ -596,6 +605,94 @@ class KmerDB:
         if getattr(self, "_h", None):
             self._lib.kid_db_destroy(self._h)
             self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Pileup:
+    """Placed reads piled up per genome bin (kid_pileup_*): two uint32 counters per bin of bin_width bases, `starts` and
+    `depth`, in the geometry of seen_coverage for the same bin width.  add() takes LOCUS_DTYPE records as read_loci
+    returns them; a record is placed when n_chain >= min_chain, n_chain - n_other (0 when negative) >= min_margin, strand
+    <= 1, entry_first < n_entries and org == org[entry_first].  With a = pos[entry_first], d = max(pos_last - pos_first, 0):
+    forward lo = a, hi = a + d + k - 1; reverse lo = max(0, a - d), hi = a + k - 1; b_lo and b_hi are lo / W and hi / W
+    clamped to span_bins - 1; the record adds 1 to starts[b_lo] and 1 to depth[b] for b in b_lo..b_hi.  The result does not
+    depend on the order of the records, the split into calls or the stream.  A context manager; the database must outlive it."""
+
+    def __init__(self, db, bin_width=1000):
+        self._lib = db._lib
+        self._h = None
+        h = C.c_void_p()
+        check(self._lib.kid_pileup_create(db._h, bin_width, C.byref(h)))
+        self._h = h
+        n_orgs, n_bins, w = C.c_uint32(0), C.c_uint64(0), C.c_uint32(0)
+        check(self._lib.kid_pileup_info(self._h, C.byref(n_orgs), C.byref(n_bins), C.byref(w)))
+        self.n_orgs, self.n_bins, self.bin_width = n_orgs.value, n_bins.value, w.value
+
+    def add(self, loci, min_chain=2, min_margin=1):
+        """Add LOCUS_DTYPE records held in host memory (kid_pileup_add)."""
+        loci = np.ascontiguousarray(loci, LOCUS_DTYPE)
+        check(self._lib.kid_pileup_add(self._h, _ptr(loci), loci.size, min_chain, min_margin))
+
+    def add_device(self, ptr, n, min_chain=2, min_margin=1, stream=0):
+        """Add n kid_locus records resident in HBM (a raw pointer); asynchronous on `stream`: kid_pileup_add_device."""
+        check(self._lib.kid_pileup_add_device(self._h, C.c_void_p(ptr or None), n, min_chain, min_margin, C.c_void_p(stream or None)))
+
+    def counts(self):
+        """-> (records handed in, records placed)"""
+        a, b = C.c_uint64(0), C.c_uint64(0)
+        check(self._lib.kid_pileup_counts(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def summary(self):
+        """-> PILEUP_DTYPE[n_orgs]: n_placed, span_bins, bins_covered, max_gap, max_depth, max_depth_bin, max_starts,
+        max_starts_bin, reserved, depth_sum"""
+        out = np.zeros(self.n_orgs, PILEUP_DTYPE)
+        check(self._lib.kid_pileup_summary(self._h, _ptr(out)))
+        return out
+
+    def bins(self):
+        """-> (bin_base uint64[n_orgs + 1], starts uint32[B], depth uint32[B]): organism g's bins lie at bin_base[g]"""
+        base = np.zeros(self.n_orgs + 1, np.uint64)
+        starts, depth = np.zeros(self.n_bins, np.uint32), np.zeros(self.n_bins, np.uint32)
+        check(self._lib.kid_pileup_bins(self._h, _ptr(base), _ptr(starts), _ptr(depth), self.n_bins))
+        return base, starts, depth
+
+    def export(self):
+        """-> (starts uint32[B], steps uint32[B + n_orgs]): what merge() of another pileup of the same geometry takes"""
+        starts, steps = np.zeros(self.n_bins, np.uint32), np.zeros(self.n_bins + self.n_orgs, np.uint32)
+        check(self._lib.kid_pileup_export(self._h, _ptr(starts), _ptr(steps)))
+        return starts, steps
+
+    def merge(self, starts, steps, n_records, n_placed):
+        """Add the export of another pileup of the same geometry, element-wise with wrap-around (kid_pileup_merge)."""
+        starts, steps = _as(starts, np.uint32), _as(steps, np.uint32)
+        if starts.shape != (self.n_bins,) or steps.shape != (self.n_bins + self.n_orgs,):
+            raise ValueError("starts and steps must have %d and %d elements" % (self.n_bins, self.n_bins + self.n_orgs))
+        check(self._lib.kid_pileup_merge(self._h, _ptr(starts), _ptr(steps), n_records, n_placed))
+
+    def reset(self):
+        check(self._lib.kid_pileup_reset(self._h))
+
+    def time(self):
+        """-> (device ms, calls, records) of the add kernels alone since the last query"""
+        ms, calls, records = C.c_double(0), C.c_uint64(0), C.c_uint64(0)
+        check(self._lib.kid_pileup_time(self._h, C.byref(ms), C.byref(calls), C.byref(records)))
+        return ms.value, calls.value, records.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.kid_pileup_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
     def __del__(self):
         try:

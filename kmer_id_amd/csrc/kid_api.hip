@@ -2,7 +2,7 @@
 // Here: the sample handle, the pacing of the hit log, kid_launch_classify and the classify entry points -- the launch
 // path a counter profile depends on.  The other areas are the kid_api_*.h files included below (kid_api_support.h
 // at the end: it counts into a sample; kid_api_fragments.h, kid_api_votes.h, kid_api_fragment_votes.h, kid_api_segments.h,
-// kid_api_segment_votes.h, kid_api_loci.h, kid_api_depth.h, kid_api_shared.h and kid_api_coverage.h behind it).  Host side only:
+// kid_api_segment_votes.h, kid_api_loci.h, kid_api_pileup.h, kid_api_depth.h, kid_api_shared.h and kid_api_coverage.h behind it).  Host side only:
 // handle bookkeeping and launches; no classification work is done on the CPU.
 #include <hip/hip_runtime.h>
 #include <memory>
@@ -26,6 +26,7 @@
 #include "kid_shared.hip.h"
 #include "kid_coverage.hip.h"
 #include "kid_loci.hip.h"
+#include "kid_pileup.hip.h"
 #include "kid_api_core.h"
 #include "kid_api_db.h"
 #include "kid_api_mask.h"
@@ -1065,6 +1066,7 @@ extern "C" int kid_sample_seen_or(kid_sample *s, uint64_t byte_off, uint64_t nby
 #include "kid_api_segments.h"
 #include "kid_api_segment_votes.h"
 #include "kid_api_loci.h"
+#include "kid_api_pileup.h"
 #include "kid_api_depth.h"
 #include "kid_api_shared.h"
 #include "kid_api_coverage.h"

@@ -10,6 +10,13 @@
 #include "kid_build.hip.h"
 #include "kid_kernels.hip.h"
 
+// the sites of a database's entries (kid_db_set_sites, kid_api_loci.h): shared with the pileups made from them
+// (kid_api_pileup.h), which keep the arrays they were made for alive behind a second kid_db_set_sites or kid_db_destroy
+struct KidSites {
+    KidDevBuf org, pos;  // uint32 per entry
+    uint32_t n_orgs = 0; // the largest org + 1
+};
+
 struct kid_db {
     int device = 0;
     int num_cu = 0;
@@ -24,7 +31,8 @@ struct kid_db {
     std::mutex hits_mu;
     int min_base_quality = 0; // KID_DB_OPT_MIN_BASE_QUALITY (kid_api_mask.h): read and written under hits_mu; a replica starts at 0
     int low_complexity = 0;   // KID_DB_OPT_LOW_COMPLEXITY (kid_api_lowc.h): the same rules
-    KidDevBuf site_org, site_pos; // uint32 per entry: kid_db_set_sites (kid_api_loci.h), under hits_mu; a replica starts without
+    std::shared_ptr<KidSites> sites; // kid_db_set_sites (kid_api_loci.h), under hits_mu; a replica starts without
+    uint64_t sites_gen = 0;          // bumped by every kid_db_set_sites that takes effect, the clearing form included
     ~kid_db(); // kid_api_hits.h: where KidHitsState is complete
 };
 typedef std::unique_ptr<kid_db, void (*)(kid_db *)> KidDbPtr; // a database under construction

@@ -16,6 +16,7 @@ extern "C" int kid_db_set_sites(kid_db *db, const uint32_t *org, const uint32_t 
 {
     if (!db) return kid_fail(KID_ERR_ARG, "null argument");
     const bool clear = !org && !pos && n_entries == 0;
+    uint32_t n_orgs = 0;
     if (!clear) {
         if (!org || !pos) return kid_fail(KID_ERR_ARG, "null argument");
         if (n_entries != db->info.n_entries)
@@ -24,27 +25,30 @@ extern "C" int kid_db_set_sites(kid_db *db, const uint32_t *org, const uint32_t 
         for (uint64_t o = 0; o < n_entries; o++) {
             if (org[o] >= KID_LOCI_MAX_ORGS) return kid_fail(KID_ERR_ARG, "entry %llu: org = %u is 2^24 or more", (unsigned long long)o, org[o]);
             if (pos[o] >> 31) return kid_fail(KID_ERR_ARG, "entry %llu: pos = %u is 2^31 or more", (unsigned long long)o, pos[o]);
+            n_orgs = org[o] >= n_orgs ? org[o] + 1u : n_orgs;
         }
     }
     int rc = kid_use_device(db->device);
     if (rc != KID_OK) return rc;
     std::lock_guard<std::mutex> lock(db->hits_mu);
-    KidDevBuf d_org, d_pos;
+    std::shared_ptr<KidSites> sites;
     if (!clear) { // (the old sites stay in force unless both copies arrive)
-        KID_HIP(d_org.alloc(n_entries * 4));
-        KID_HIP(d_pos.alloc(n_entries * 4));
-        KID_HIP(hipMemcpy(d_org.p, org, n_entries * 4, hipMemcpyHostToDevice));
-        KID_HIP(hipMemcpy(d_pos.p, pos, n_entries * 4, hipMemcpyHostToDevice));
+        sites = std::make_shared<KidSites>();
+        sites->n_orgs = n_orgs;
+        KID_HIP(sites->org.alloc(n_entries * 4));
+        KID_HIP(sites->pos.alloc(n_entries * 4));
+        KID_HIP(hipMemcpy(sites->org.p, org, n_entries * 4, hipMemcpyHostToDevice));
+        KID_HIP(hipMemcpy(sites->pos.p, pos, n_entries * 4, hipMemcpyHostToDevice));
     }
     KID_HIP(hipDeviceSynchronize()); // no kernel of a device-form call still reads the sites that go
-    db->site_org = std::move(d_org);
-    db->site_pos = std::move(d_pos);
+    db->sites = std::move(sites);    // (a pileup made from the old ones keeps them: kid_api_pileup.h)
+    db->sites_gen++;
     return KID_OK;
 }
 
 static int kid_loci_check_sites(kid_db *db)
 {
-    if (!db->site_org.p) return kid_fail(KID_ERR_STATE, "the database has no sites (kid_db_set_sites)");
+    if (!db->sites) return kid_fail(KID_ERR_STATE, "the database has no sites (kid_db_set_sites)");
     return KID_OK;
 }
 
@@ -71,7 +75,7 @@ static int kid_loci_launch(kid_db *db, KidHitsState *h, const uint64_t *d_hit_of
     if (rc != KID_OK) return rc;
     KID_HIP(kid_hits_ensure(h->loci_list, n * 4u));
     if (!h->loci_n_list.p) KID_HIP(h->loci_n_list.alloc(4));
-    const KidLociSites sites{db->site_org.as<uint32_t>(), db->site_pos.as<uint32_t>(), db->info.n_entries, diag_bin};
+    const KidLociSites sites{db->sites->org.as<uint32_t>(), db->sites->pos.as<uint32_t>(), db->info.n_entries, diag_bin};
     const KidLociBig big{h->loci_list.as<uint32_t>(), h->loci_n_list.as<uint32_t>()};
     KidSpanTimer &timer = h->family[KID_FAM_LOCI].timer;
     if ((rc = timer.begin(stream)) != KID_OK) return rc;

@@ -72,6 +72,7 @@ Engine::~Engine()
 {
     for (const std::vector<kid_sample *> *list : {&samples, &confident, &fragments, &votes, &fragment_votes})
         for (kid_sample *s : *list) kid_sample_destroy(s);
+    for (kid_pileup *p : pileups) kid_pileup_destroy(p); // (before their databases)
     if (owns_dbs)
         for (kid_db *d : dbs) kid_db_destroy(d);
 }
@@ -117,6 +118,13 @@ void engine_configure(Engine &e, const SideOptions &side)
         for (kid_db *d : e.dbs) e.votes.push_back(begin_sample_or_die(d));
     if (side.fragment_votes) // (and so are the fragments called by votes)
         for (kid_db *d : e.dbs) e.fragment_votes.push_back(begin_sample_or_die(d));
+    if (side.pileup.on && e.site_pos) // (the databases have their sites: engine_open)
+        for (kid_db *d : e.dbs) {
+            kid_pileup *p = nullptr;
+            int rc = kid_pileup_create(d, side.pileup.bin_width, &p);
+            if (rc != KID_OK) die_kid(rc);
+            e.pileups.push_back(p);
+        }
     // the two masks: the sample's option and the database's, each only where it is on
     const struct { int value, sample_opt, db_opt; } masks[] = {{side.min_base_quality, KID_OPT_MIN_BASE_QUALITY, KID_DB_OPT_MIN_BASE_QUALITY},
                                                                {side.low_complexity, KID_OPT_LOW_COMPLEXITY, KID_DB_OPT_LOW_COMPLEXITY}};
@@ -156,6 +164,10 @@ void engine_reset(Engine &e)
             int rc = kid_sample_reset(s);
             if (rc != KID_OK) die_kid(rc);
         }
+    for (kid_pileup *p : e.pileups) {
+        int rc = kid_pileup_reset(p);
+        if (rc != KID_OK) die_kid(rc);
+    }
     e.next_sample = 0;
     e.next_fragments = 0;
 }
@@ -421,6 +433,19 @@ static void read_loci(SideOptions &o, const char *prog, const char *opt, const c
     o.loci = LociOption{true, (uint32_t)w};
 }
 
+static void read_pileup(SideOptions &o, const char *prog, const char *opt, const char *v)
+{
+    const char *const what = "takes W[:MIN_CHAIN[:MIN_MARGIN]], digits only: W in 1..2147483647, MIN_CHAIN in 1..4096, MIN_MARGIN in 0..4096";
+    unsigned long long w = 0, chain = 2, margin = 1;
+    size_t at = 0;
+    if (digits_up_to(0x7FFFFFFFull, v, at, w) <= 0) usage_error(prog, opt, what); // (an empty part too)
+    if (v[at] == ':' && digits_up_to(4096, v, ++at, chain) <= 0) usage_error(prog, opt, what);
+    if (v[at] == ':' && digits_up_to(4096, v, ++at, margin) <= 0) usage_error(prog, opt, what);
+    if (v[at] != 0) usage_error(prog, opt, what); // (a fourth part too)
+    if (w < 1 || chain < 1) usage_error(prog, opt, what);
+    o.pileup = PileupOption{true, (uint32_t)w, (uint32_t)chain, (uint32_t)margin};
+}
+
 // The side options: their words, the pass of side_options() that reads each, what reads its value -- or, for a switch,
 // which takes none, the flag it sets
 static const struct {
@@ -436,6 +461,7 @@ static const struct {
                     {"--segments", 2, read_segments, nullptr},
                     {"--segment-votes", 3, read_segment_votes, nullptr},
                     {"--loci", 4, read_loci, nullptr},
+                    {"--pileup", 5, read_pileup, nullptr},
                     {"--depth", 0, nullptr, &SideOptions::depth},
                     {"--seen", 0, nullptr, &SideOptions::seen},
                     {"--fragments", 0, nullptr, &SideOptions::fragments},
@@ -453,7 +479,7 @@ SideOptions side_options(int argc, char **argv, const char *prog)
 {
     SideOptions o;
     // one pass over the words per step of the order in which malformed options are reported
-    for (int pass = 0; pass < 5; pass++)
+    for (int pass = 0; pass < 6; pass++)
         for (int i = 1; i < argc; i++)
             for (const auto &so : kSideOptions) {
                 if (so.pass != pass || strcmp(argv[i], so.name) != 0) continue;
@@ -474,7 +500,7 @@ static std::string sibling_path_for(const std::string &result_path, const char *
 }
 
 // The side files beside a result file: the one place that has their names
-struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes, fragment_votes, segment_votes, loci; };
+struct SidePaths { std::string hits, confident, segments, depth, seen, fragments, votes, fragment_votes, segment_votes, loci, pileup; };
 static SidePaths side_paths(const std::string &r)
 {
     std::string seen = r; // the final "result.txt" becomes "seen.bin"
@@ -483,7 +509,7 @@ static SidePaths side_paths(const std::string &r)
     else seen += ".seen.bin";
     return {sibling_path_for(r, "hits"), sibling_path_for(r, "confident"), sibling_path_for(r, "segments"), sibling_path_for(r, "depth"), seen,
             sibling_path_for(r, "fragments"), sibling_path_for(r, "votes"), sibling_path_for(r, "fragment_votes"), sibling_path_for(r, "segment_votes"),
-            sibling_path_for(r, "loci")};
+            sibling_path_for(r, "loci"), sibling_path_for(r, "pileup")};
 }
 
 void remove_side_files(const std::string &result_path, const SideOptions &side, bool all)
@@ -499,6 +525,7 @@ void remove_side_files(const std::string &result_path, const SideOptions &side, 
     if (all || side.fragment_votes) remove(p.fragment_votes.c_str());
     if (all || side.segment_votes.on) remove(p.segment_votes.c_str());
     if (all || side.loci.on) remove(p.loci.c_str());
+    if (all || side.pileup.on) remove(p.pileup.c_str());
 }
 
 SampleOutputs::SampleOutputs(const std::string &result_path, const SideOptions &side) : side_(side), result_path_(result_path)
@@ -630,6 +657,43 @@ int read_seen_files(const std::vector<std::string> &paths, long long ntar, unsig
     return 0;
 }
 
+// The pileups of a sample (one per device: the others are merged into the first) -> the head line and one line per
+// organism with a placed read
+static void write_pileup(std::vector<kid_pileup *> &pileups, const PileupOption &o, const std::string &path)
+{
+    kid_pileup *all = pileups[0];
+    uint32_t n_orgs = 0;
+    uint64_t n_bins = 0;
+    int rc = kid_pileup_info(all, &n_orgs, &n_bins, nullptr);
+    if (rc != KID_OK) die_kid(rc);
+    if (pileups.size() > 1) {
+        std::vector<uint32_t> starts((size_t)n_bins + 1), steps((size_t)n_bins + n_orgs + 1);
+        for (size_t i = 1; i < pileups.size(); i++) {
+            uint64_t n_records = 0, n_placed = 0;
+            if ((rc = kid_pileup_export(pileups[i], starts.data(), steps.data())) != KID_OK) die_kid(rc);
+            if ((rc = kid_pileup_counts(pileups[i], &n_records, &n_placed)) != KID_OK) die_kid(rc);
+            if ((rc = kid_pileup_merge(all, starts.data(), steps.data(), n_records, n_placed)) != KID_OK) die_kid(rc);
+        }
+    }
+    uint64_t n_records = 0, n_placed = 0;
+    std::vector<kid_pileup_rec> recs((size_t)n_orgs + 1);
+    if ((rc = kid_pileup_counts(all, &n_records, &n_placed)) != KID_OK) die_kid(rc);
+    if ((rc = kid_pileup_summary(all, recs.data())) != KID_OK) die_kid(rc);
+    std::string text;
+    char line[256];
+    int n = snprintf(line, sizeof(line), "#%llu,%llu,%u,%u,%u\n", (unsigned long long)n_records, (unsigned long long)n_placed, o.bin_width,
+                     o.min_chain, o.min_margin);
+    text.append(line, (size_t)n);
+    for (uint32_t g = 0; g < n_orgs; g++) {
+        const kid_pileup_rec &r = recs[g];
+        if (r.n_placed == 0) continue;
+        n = snprintf(line, sizeof(line), "%u,%u,%u,%u,%u,%u,%u,%u,%u,%llu\n", g, r.n_placed, r.span_bins, r.bins_covered, r.max_gap, r.max_depth,
+                     r.max_depth_bin, r.max_starts, r.max_starts_bin, (unsigned long long)r.depth_sum);
+        text.append(line, (size_t)n);
+    }
+    write_lines(path, std::vector<std::string>(1, text));
+}
+
 void SampleOutputs::finish(Engine &e)
 {
     const SidePaths p = side_paths(result_path_);
@@ -644,6 +708,7 @@ void SampleOutputs::finish(Engine &e)
     if (side_.segments.on) write_lines(p.segments, segments_);
     if (side_.segment_votes.on) write_lines(p.segment_votes, segment_votes_);
     if (side_.loci.on) write_lines(p.loci, loci_);
+    if (side_.pileup.on && !e.pileups.empty()) write_pileup(e.pileups, side_.pileup, p.pileup);
     hits_.clear();
     segments_.clear();
     segment_votes_.clear();
@@ -766,13 +831,18 @@ static void segment_vote_lines_of(kid_db *db, const ReadBatch &b, const uint8_t 
     }
 }
 
-// The loci lines of one classified batch: kid_db_read_loci* with diag_bin = W; site_pos: the position of every entry's probe
-static void loci_lines_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, const std::vector<uint32_t> &final_targ, int k, uint32_t diag_bin,
+// The loci records of one classified batch: kid_db_read_loci* with diag_bin = W
+static void loci_of(kid_db *db, const ReadBatch &b, const uint8_t *bases, uint32_t diag_bin, std::vector<kid_locus> &loci)
+{
+    loci.resize(b.size());
+    read_pass(kid_db_read_loci_fastq, kid_db_read_loci, db, b, bases, diag_bin, loci.data());
+}
+
+// ... and their lines; site_pos: the position of every entry's probe
+static void loci_lines_of(const std::vector<kid_locus> &loci, const ReadBatch &b, const std::vector<uint32_t> &final_targ, int k,
                           const std::vector<uint32_t> &site_pos, std::string &out)
 {
     const size_t nr = b.size();
-    std::vector<kid_locus> loci(nr);
-    read_pass(kid_db_read_loci_fastq, kid_db_read_loci, db, b, bases, diag_bin, loci.data());
     char num[192];
     for (size_t r = 0; r < nr; r++) {
         const kid_locus &l = loci[r];
@@ -808,8 +878,10 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         kid_db *db = nullptr;
         kid_sample *confident = nullptr;
         kid_sample *votes = nullptr;
+        kid_pileup *pileup = nullptr;
         size_t file = 0;
     };
+    std::vector<kid_locus> loci;
     std::string lines;
     std::deque<InFlight> q;
     std::vector<long long> handed(count, 0);
@@ -894,10 +966,23 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             segment_vote_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.side.segment_votes, e.side.support, lines);
             out.add_segment_votes(saver_file + f.file, lines);
         }
-        if (out.loci_on() && e.site_pos) {
-            lines.clear();
-            loci_lines_of(f.db, *f.batch, f.bases(), f.final_targ, e.k, e.side.loci.diag_bin, *e.site_pos, lines);
-            out.add_loci(saver_file + f.file, lines);
+        if ((out.loci_on() || f.pileup) && e.site_pos) { // one loci pass feeds both: --loci's diagonal bin when given, else 1
+            loci_of(f.db, *f.batch, f.bases(), out.loci_on() ? e.side.loci.diag_bin : 1u, loci);
+            if (out.loci_on()) {
+                lines.clear();
+                loci_lines_of(loci, *f.batch, f.final_targ, e.k, *e.site_pos, lines);
+                out.add_loci(saver_file + f.file, lines);
+            }
+            if (f.pileup) {
+                if (f.batch->fq) { // (the records process_qual drops were never handed to process_read: they have no hit, and do not count)
+                    size_t kept = 0;
+                    for (size_t r = 0; r < loci.size(); r++)
+                        if (f.batch->stop[r] - f.batch->start[r] >= e.k) loci[kept++] = loci[r];
+                    loci.resize(kept);
+                }
+                int rc = kid_pileup_add(f.pileup, loci.data(), loci.size(), e.side.pileup.min_chain, e.side.pileup.min_margin);
+                if (rc != KID_OK) die_kid(rc);
+            }
         }
         if (fragments && f.batch->fq) {
             mate_records[f.file] += f.batch->size();
@@ -920,6 +1005,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
             f.db = e.dbs[e.next_sample];
             f.confident = e.confident.empty() ? nullptr : e.confident[e.next_sample];
             f.votes = e.votes.empty() ? nullptr : e.votes[e.next_sample];
+            f.pileup = out.pileup_on() && !e.pileups.empty() ? e.pileups[e.next_sample] : nullptr;
             e.next_sample = (e.next_sample + 1) % e.samples.size();
             int rc;
             const auto t_sub = std::chrono::steady_clock::now();

@@ -33,6 +33,12 @@ struct LociOption {
     bool on = false;
     uint32_t diag_bin = 0;
 };
+// --pileup W[:MIN_CHAIN[:MIN_MARGIN]]: pile the placed reads up per genome bin (kid_pileup_*).  Digits only; W, the bin
+// width, in 1..2147483647; MIN_CHAIN in 1..4096, default 2; MIN_MARGIN in 0..4096, default 1.
+struct PileupOption {
+    bool on = false;
+    uint32_t bin_width = 0, min_chain = 2, min_margin = 1;
+};
 struct SideOptions {
     bool hits = false;   // --hits: every read's k-mer hits
     SupportRule support;
@@ -71,11 +77,15 @@ struct SideOptions {
     // --loci W: every read with a hit placed on a genome by its colinear hits, into a loci file.  The probes are loaded
     // with their sites (load_database's want_sites) and every replica of the database gets them (engine_open).
     LociOption loci;
+    // --pileup W[:MIN_CHAIN[:MIN_MARGIN]]: the loci records of every batch piled up per genome bin of W bases, summed up per
+    // organism in a pileup file.  It loads the sites as --loci does and runs the loci pass where --loci runs it, with
+    // --loci's diagonal bin when that is given, else 1: with both options one loci pass per batch feeds both files.
+    PileupOption pileup;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
-// of --segments or --segment-votes too) is a usage error: "<prog>: <option> <what>" on stderr and exit code 2 -- of several, the first in
-// the order --min-hits / --confidence, --min-base-quality / --low-complexity, --segments, --segment-votes, --loci.
+// of --segments or --segment-votes, a fourth part of --pileup too) is a usage error: "<prog>: <option> <what>" on stderr and exit code 2 -- of several, the first in
+// the order --min-hits / --confidence, --min-base-quality / --low-complexity, --segments, --segment-votes, --loci, --pileup.
 SideOptions side_options(int argc, char **argv, const char *prog);
 // For a front-end that rejects the words it does not know: the number of value words behind `word` (0 or 1) if it
 // is a side option, else -1
@@ -101,6 +111,8 @@ struct Engine {
     // under --loci: the position of every entry's probe (the host's copy of what the replicas got in engine_open: the loci
     // file prints pos[entry_first]); a worker shares its owner's
     std::shared_ptr<const std::vector<uint32_t>> site_pos;
+    // under --pileup: one pileup per device (engine_configure), reset with the samples, merged into [0] when a sample is closed
+    std::vector<kid_pileup *> pileups;
     int ntar = 0, k = 30;
     size_t batch_reads = 1 << 20;
     size_t batch_bases = 256u << 20;
@@ -122,21 +134,21 @@ std::unique_ptr<Engine> engine_worker(const Engine &owner);
 // (and the cache is written for the next run).  `from_cache` reports which way it went.
 // `threads`: parse workers of the probes text (0: one per core, at most 8).  `cache_writer`: if given, a cache that has
 // to be (re)written is written on that thread -- join it before `parent` / `ps` go away.
-// `want_sites` (--loci): ps.orgs / ps.positions are filled as well.  The cache does not hold them and its format does not
+// `want_sites` (--loci, --pileup): ps.orgs / ps.positions are filled as well.  The cache does not hold them and its format does not
 // change: behind a valid cache the probes text is still read once, for the sites alone (its entries must be the cache's).
 void load_database(const std::string &tree_path, const std::string &probes_path, const std::string &cache_path, int k, int ntar,
                    std::vector<int32_t> &parent, ProbeSet &ps, bool *from_cache = nullptr, int threads = 0,
                    StartupTiming *timing = nullptr, std::thread *cache_writer = nullptr, bool want_sites = false);
 
 // Hashtable + Tree1 onto the GPU(s) of parse_devices(): the table is built on the first device and replicated into the
-// others.  A ProbeSet with sites (--loci): every replica gets them (kid_db_set_sites) and e.site_pos a copy of the
+// others.  A ProbeSet with sites (--loci, --pileup): every replica gets them (kid_db_set_sites) and e.site_pos a copy of the
 // positions.  Returns false after printing the reference's "out of memory in table " (newkmer_10nx.cpp:256-260: the caller
 // exits with 1).
 bool engine_open(Engine &e, const ProbeSet &ps, const std::vector<int32_t> &parent, int k, int log2_slots, int max_probes,
                  unsigned flags, const std::vector<int> &devices);
 // The side options for an engine that is open: with a rule or --depth one more sample per device (reset, closed and
 // destroyed with the others; --depth switches its depth counters on), under --fragments one more for the fragments, under
-// --votes one more for the vote pass, under --fragment-votes one more for the fragments called by votes, then --min-base-quality and --low-complexity on every sample, the tallied ones included, and on every replica of the database.
+// --votes one more for the vote pass, under --fragment-votes one more for the fragments called by votes, under --pileup one pileup per device (the sites are there: engine_open), then --min-base-quality and --low-complexity on every sample, the tallied ones included, and on every replica of the database.
 // A worker of engine_worker() inherits them for its samples.
 void engine_configure(Engine &e, const SideOptions &side);
 // --device D / --devices A,B,... ("0,1,2,3"; a device may be named twice): the list when there is one, else D
@@ -221,6 +233,13 @@ private:
 //   <final_targ> <trimmed length> <n_kmers> <n_hits> <org>:<strand>:<n_chain>:<n_org>:<n_other>:<pos_first>:<pos_last>:<pos[entry_first]> <header>
 // --min-base-quality and --low-complexity apply as they do to the hits file.  It does not depend on how the reads were
 // batched, threaded or dealt over devices.
+//   --pileup W[:MIN_CHAIN[:MIN_MARGIN]], "pileup": the loci records of every batch (diag_bin = --loci's W when given, else 1)
+// added to the batch's device's pileup of bin width W under (MIN_CHAIN, MIN_MARGIN); at the sample's end the devices'
+// pileups are merged (kid_pileup_export, kid_pileup_merge) and summed up per organism.  Integers only:
+//   #<n_records>,<n_placed>,<W>,<MIN_CHAIN>,<MIN_MARGIN>
+//   <org>,<n_placed>,<span_bins>,<bins_covered>,<max_gap>,<max_depth>,<max_depth_bin>,<max_starts>,<max_starts_bin>,<depth_sum>
+// n_records the reads that were handed to process_read, and one line for every organism with n_placed >= 1, in ascending order.  --min-base-quality and --low-complexity apply as they
+// do to the loci file.  It does not depend on how the reads were batched, threaded or dealt over devices.
 // Nothing else changes under any of them: the result and reads files and stdout are what they are without.
 // The batches of files read at the same time interleave: the hit, segment, segment_votes and loci lines are held in memory per file and
 // written in file order by finish() -- what is held is the files themselves (reads without a hit leave nothing),
@@ -235,6 +254,7 @@ public:
     bool fragment_votes_on() const { return side_.fragment_votes; }
     bool segment_votes_on() const { return side_.segment_votes.on; }
     bool loci_on() const { return side_.loci.on; }
+    bool pileup_on() const { return side_.pileup.on; }
     const std::string &result_path() const { return result_path_; }
     void add_hits(size_t file, const std::string &lines) { add(hits_, file, lines); }
     void add_segments(size_t file, const std::string &lines) { add(segments_, file, lines); }
@@ -242,7 +262,7 @@ public:
     void add_loci(size_t file, const std::string &lines) { add(loci_, file, lines); }
     // gcount / ucount of the sample -> "<i>,<g>,<u>" lines in the result file, those of the tallied sample(s) -> the
     // confident file, then the fragments file, then the votes file, then the fragment_votes file, then the depth file, then the seen file, then the hits file, then the
-    // segments file, then the segment_votes file, then the loci file
+    // segments file, then the segment_votes file, then the loci file, then the pileup file
     void finish(Engine &e);
 private:
     using Lines = std::vector<std::string>; // [file]

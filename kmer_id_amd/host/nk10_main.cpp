@@ -27,6 +27,9 @@
 //                    writes (kid_driver.h)
 //   --loci W             also write <prefix>_loci.txt: every read with a hit placed on a genome by its colinear hits, the diagonal
 //                    bin W wide (digits only, 1..2147483647); the probes are loaded with their sites (kid_driver.h)
+//   --pileup W[:MIN_CHAIN[:MIN_MARGIN]]   also write <prefix>_pileup.txt: the placed reads piled up per genome bin of W bases
+//                    and summed up per organism, a read placed when its chain has MIN_CHAIN (2) hits and MIN_MARGIN (1) more
+//                    than the best chain on another organism; the loci pass is --loci's when given (kid_driver.h)
 //   --depth              also write <prefix>_depth.txt: per target, the hits on its database k-mers by the reads called (under the
 //                    rule of --min-hits / --confidence when given), how many of them were hit, the quartiles of their depth and
 //                    the largest (kid_driver.h)
@@ -179,7 +182,7 @@ int main(int argc, char **argv)
                 if (kid_host_alloc(warm_device, 4096, &p) == KID_OK) kid_host_free(p);
             });
         }
-        load_database(tpath, pname, db_cache, k, ntar, parent, ps, &from_cache, threads, &tm, &cache_writer, side.loci.on && dry_run.empty());
+        load_database(tpath, pname, db_cache, k, ntar, parent, ps, &from_cache, threads, &tm, &cache_writer, (side.loci.on || side.pileup.on) && dry_run.empty());
         const double t_db_loaded = since_start();
         double t_gpu_ready = -1, t_first_file = -1;
         size_t n_entries = ps.keys.size(), n_devices = 0;

@@ -14,6 +14,7 @@
 //   --segments LEN[:STEP]   long records called in segments
 //   --segment-votes LEN[:STEP]   long records called in segments by root-path votes (the segment_votes file of kid_driver.h)
 //   --loci W   every read with a hit placed on a genome by its colinear hits (the loci file of kid_driver.h)
+//   --pileup W[:MIN_CHAIN[:MIN_MARGIN]]   the placed reads piled up per genome bin (the pileup file of kid_driver.h)
 //   --depth   k-mer depth per target (the depth file of kid_driver.h)
 //   --seen   the seen-bitmap in a seen file (<...>seen.bin beside <...>result.txt), for kmer_shared
 //   --votes   the reads called by root-path votes, whatever the order of their hits (the votes file of kid_driver.h)
@@ -61,7 +62,7 @@ int main(int argc, char **argv)
         std::vector<int32_t> parent;
         ProbeSet ps;
         set_inflate_threads(opt.threads >= 6 ? opt.threads / 2 : 1); // (gzip inputs: pieces inflated side by side when there are threads for it)
-        load_database(tname, pname, opt.db_cache, k, num_targ, parent, ps, nullptr, 0, nullptr, nullptr, opt.side.loci.on && opt.dry_run.empty());
+        load_database(tname, pname, opt.db_cache, k, num_targ, parent, ps, nullptr, 0, nullptr, nullptr, (opt.side.loci.on || opt.side.pileup.on) && opt.dry_run.empty());
         std::cout << "tree loaded" << std::endl;
         std::cout << ps.lines_parsed << " kmers loaded" << std::endl;
 
