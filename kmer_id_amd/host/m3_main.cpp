@@ -6,7 +6,7 @@
 // What reaches the kernel: lookups give up after MAXREPROBE = 16 probes (:42,:232), so the table is
 // built sequentially on the host with the reference's exact cell geometry (results depend on it).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
-// and the side options (SideOptions, kid_driver.h), whose files stand beside DIR/result.txt (SampleOutputs):
+// and the side options (SideOptions, kid_side.h), whose files stand beside DIR/result.txt (SampleOutputs):
 //   --hits   every read's k-mer hits
 //   --min-hits N  --confidence F   the reads called by k-mer support
 //   --segments LEN[:STEP]   long records called in segments

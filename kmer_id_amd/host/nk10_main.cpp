@@ -15,42 +15,42 @@
 //                    <prefix><r1 suffix> per sample, read by process_fa (:877-913), no R2 file
 //   --db-cache FILE  binary cache of the parsed database: read if valid, (re)written otherwise
 //   --samples-in-flight N (threads / 2)  samples read and classified at the same time, each with its own counters on the GPU
-//   --hits               also write <prefix>_hits.txt: every read's k-mer hits (kid_driver.h)
+//   --hits               also write <prefix>_hits.txt: every read's k-mer hits (kid_side.h)
 //   --min-hits N  --confidence F   also write <prefix>_confident.txt, the result file of the reads called by k-mer support:
 //                    a read counts under the first node of its target's root path whose clade holds at least N of its k-mer
-//                    hits and F (a decimal in [0, 1], three fractional digits) of its k-mers, under 0 if none does (kid_driver.h)
+//                    hits and F (a decimal in [0, 1], three fractional digits) of its k-mers, under 0 if none does (kid_side.h)
 //   --segments LEN[:STEP]   also write <prefix>_segments.txt: every read with a hit called in segments of LEN window
-//                    positions, STEP apart (default LEN; LEN <= 1024 * STEP), under the rule of --min-hits / --confidence (kid_driver.h)
+//                    positions, STEP apart (default LEN; LEN <= 1024 * STEP), under the rule of --min-hits / --confidence (kid_side.h)
 //   --segment-votes LEN[:STEP]   also write <prefix>_segment_votes.txt: the same segments (of this option's own LEN[:STEP]) called
 //                    by root-path votes, which do not depend on the order of a segment's hits nor on the strand a record was
 //                    assembled on, under the rule of --min-hits / --confidence; needs no --segments and changes nothing it
-//                    writes (kid_driver.h)
+//                    writes (kid_side.h)
 //   --loci W             also write <prefix>_loci.txt: every read with a hit placed on a genome by its colinear hits, the diagonal
-//                    bin W wide (digits only, 1..2147483647); the probes are loaded with their sites (kid_driver.h)
+//                    bin W wide (digits only, 1..2147483647); the probes are loaded with their sites (kid_side.h)
 //   --pileup W[:MIN_CHAIN[:MIN_MARGIN]]   also write <prefix>_pileup.txt: the placed reads piled up per genome bin of W bases
 //                    and summed up per organism, a read placed when its chain has MIN_CHAIN (2) hits and MIN_MARGIN (1) more
-//                    than the best chain on another organism; the loci pass is --loci's when given (kid_driver.h)
+//                    than the best chain on another organism; the loci pass is --loci's when given (kid_side.h)
 //   --depth              also write <prefix>_depth.txt: per target, the hits on its database k-mers by the reads called (under the
 //                    rule of --min-hits / --confidence when given), how many of them were hit, the quartiles of their depth and
-//                    the largest (kid_driver.h)
+//                    the largest (kid_side.h)
 //   --seen               also write <prefix>_seen.bin: the sample's seen-bitmap, one bit per database k-mer (of the reads called
-//                    under the rule of --min-hits / --confidence when given), for kmer_shared to compare samples by (kid_driver.h)
+//                    under the rule of --min-hits / --confidence when given), for kmer_shared to compare samples by (kid_side.h)
 //   --fragments          also write <prefix>_fragments.txt: the result file of the mate pairs called as one fragment each -- record j
 //                    of the R1 file with record j of the R2 file, under the rule of --min-hits / --confidence when given
-//                    (kid_driver.h).  Not with --fasta
+//                    (kid_side.h).  Not with --fasta
 //   --votes              also write <prefix>_votes.txt: the result file of the reads called by root-path votes, which do not
-//                    depend on the order of a read's hits, under the rule of --min-hits / --confidence when given (kid_driver.h)
+//                    depend on the order of a read's hits, under the rule of --min-hits / --confidence when given (kid_side.h)
 //   --fragment-votes     also write <prefix>_fragment_votes.txt: the result file of the mate pairs called by root-path votes over
 //                    the hits of both mates -- the fragments of --fragments, a call that does not depend on the order of the
-//                    mates or of their hits -- under the rule of --min-hits / --confidence when given (kid_driver.h).  Not with
+//                    mates or of their hits -- under the rule of --min-hits / --confidence when given (kid_side.h).  Not with
 //                    --fasta; needs neither --fragments nor --votes
 //   --block-bytes N      the size of the FASTQ text blocks the files are cut into (8 MiB; at least 32 KiB are taken): no output
 //                    depends on it
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
 //                    what they would be on FASTQ files with those bases replaced by N; <prefix>_reads.txt prints the
-//                    sequences as they are (kid_driver.h)
+//                    sequences as they are (kid_side.h)
 //   --low-complexity T   bases in a low-complexity window at threshold T (0..1000; 0 = off, 20 = DUST's usual level) are
-//                    read as N in the same way, behind --min-base-quality; with --fasta too (kid_driver.h)
+//                    read as N in the same way, behind --min-base-quality; with --fasta too (kid_side.h)
 //   --timing         one JSON line on stderr when the run ends: seconds of the start-up phases (probes inflate / parse,
 //                    cache read / write, upload + table build on the GPU, first batch classified) and of the read files
 //   --dry-run FILE   host stages only (no GPU): parse the DB text files and the files a run would read (FASTQ, or

@@ -8,7 +8,7 @@
 // Differences to nk10 that reach the kernel: U/u count as T (:496-500,521-525) and the number of
 // targets comes from the data file (:1073-1084).
 // Extra options: --k K (30) --log2-slots L (30) --device D (0) --batch-reads N
-// and the side options (SideOptions, kid_driver.h), whose files stand beside ./JOBS/<job>_result.txt (SampleOutputs):
+// and the side options (SideOptions, kid_side.h), whose files stand beside ./JOBS/<job>_result.txt (SampleOutputs):
 //   --hits   every read's k-mer hits
 //   --min-hits N  --confidence F   the reads called by k-mer support
 //   --segments LEN[:STEP]   long records called in segments

@@ -3,7 +3,8 @@
 synthetic bact10 DB at a small scale (the text DB load is not what is measured), S samples of P
 pairs, reader-thread counts 1/2/4/8.  Prints reads/s per configuration (wall clock of the whole
 process minus the DB load measured on an empty directory).
-   python tools/cli_e2e_bench.py [nk10 binaries to compare on the same inputs, alternated, REPEATS (1) times each]"""
+   python tools/cli_e2e_bench.py [nk10 binaries to compare on the same inputs, alternated, REPEATS (1) times each]
+NK10_ARGS in the environment: further words for every nk10 command line (side options, say)."""
 import os
 import subprocess
 import sys
@@ -41,7 +42,7 @@ print("inputs generated in %.0f s: %d samples x %d pairs, %.0f MB gz" % (time.ti
 cache = os.path.join(cwd, "db.kidx")
 def run(nk10, d, threads):
     t = time.time()
-    subprocess.run([nk10, d, "--log2-slots", "24", "--db-cache", cache, "--threads", str(threads)], cwd=cwd, check=True, stdout=subprocess.DEVNULL)
+    subprocess.run([nk10, d, "--log2-slots", "24", "--db-cache", cache, "--threads", str(threads)] + os.environ.get("NK10_ARGS", "").split(), cwd=cwd, check=True, stdout=subprocess.DEVNULL)
     return time.time() - t
 run(binaries[0], empty, 1)  # writes the cache
 base = min(run(nk10, empty, 1) for nk10 in binaries for _ in range(2))
