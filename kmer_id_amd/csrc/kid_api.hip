@@ -78,7 +78,7 @@ struct kid_sample {
     KidDevBuf rare_fixed; // KidRareArgs
     struct { uint32_t *out_final = nullptr; uint64_t read0 = 0; uint32_t fixed_len = 0; int32_t fixed_nk = 0; bool valid = false; } fixed_held;
     uint64_t dev_clock_batches = 0; // batches since kid_sample_kernel_time_device was last asked
-    // the hit log (kid_seenlog_* in kid_kernels.hip.h): where the resolver leaves the entry ordinals of its hits, and the
+    // the hit log (kid_seenlog.hip.h): where the resolver leaves the entry ordinals of its hits, and the
     // scratch of the pass that turns them into bits of `seen` (all uint32; none of it without a log)
     KidDevBuf seen_log, seen_log_tail, seen_sorted, log_counts, log_bin_total;
     uint32_t seen_log_cap = 0, log_nbins = 0;
@@ -427,9 +427,9 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
     const int grid = kid_grid_for(b.n, wpb, db->num_cu * 16);
     const uint32_t hist_words32 = (ntar + 3u) & ~3u, hist_words16 = ((ntar + 1u) / 2u + 3u) & ~3u;
     const uint32_t hist_words = ml ? hist_words16 : hist_words32;
-    const uint32_t wave_words = ml ? KID_GEN_ML_LDS_WORDS : KID_WAVE_LDS_WORDS;
+    const uint32_t wave_words = ml ? KidWaveLds<true, 0>::total : KidWaveLds<false, 0>::total, pair_words = KidWaveLds<true, 1>::total; // (the duo loop's are the pair loop's)
     const bool hist = (hist_words + wpb * wave_words) * 4u + 32u <= 40u * 1024u;
-    const bool hist_pair = (hist_words16 + wpb * KID_PAIR_LDS_WORDS) * 4u + 32u <= 40u * 1024u;
+    const bool hist_pair = (hist_words16 + wpb * pair_words) * 4u + 32u <= 40u * 1024u;
     uint64_t span = b.n;
     if (ml && (hist || hist_pair)) {
         // reads per launch: < 65536 per workgroup -- and with the tapered shares (KID_TAPER) the workgroups dispatched
@@ -483,7 +483,7 @@ static int kid_launch_classify(kid_sample *s, const KidBatch &b, uint64_t bases_
                     s->kernel_variants |= dg ? 1ull << (48 + (PK - 1) * 8 + (r << 2 | hh << 1 | (KF == 30)))
                                              : 1ull << (PK * 16 | r << 3 | hh << 2 | m << 1 | (KF == 30));
                     hipLaunchKernelGGL((kid_classify_kernel<2, r, hh, m, KF, PK, dg>), dim3(grid), dim3(block),
-                                       (hw + (size_t)wpb * (PK ? KID_PAIR_LDS_WORDS : wave_words)) * 4 + 32, stream, db->d, pk, sd, hw,
+                                       (hw + (size_t)wpb * KidWaveLds<m, PK>::total) * 4 + 32, stream, db->d, pk, sd, hw,
                                        pk.desc, rare);
                 }
                 });

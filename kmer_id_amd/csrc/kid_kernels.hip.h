@@ -1,4 +1,11 @@
-// kid_kernels.hip.h -- gfx950 (MI355X, CDNA4) kernels of the k-mer read classifier.
+// kid_kernels.hip.h -- gfx950 (MI355X, CDNA4) kernels of the k-mer read classifier: kid_classify_kernel, and through
+// the headers it includes everything else a classify launch of the benchmark's workload executes --
+//   kid_table.hip.h    device structs, cell loads, lookup in both geometries, DPP row scans, msca, ancestor rows between lanes
+//   kid_prepare.hip.h  base packing; read descriptors from [start, stop] or FASTQ quality lines; the launch's argument block
+//   kid_seenlog.hip.h  hit log -> seen-bitmap, bitmap -> ucount, or
+//   kid_probes.hip.h   one lookup / hash / msca per thread (parity tests)
+//   kid_insert.hip.h   keys and targets -> table cells
+// DESIGN.md section 4 has a map of the classify kernel: which lambda exists for which instantiation, which loop calls what.
 //
 // All work here is integer / indexing work bounded by random reads of the hash
 // table in HBM; there is no MFMA-shaped computation on this path.
@@ -14,20 +21,33 @@
 //   ord_target u32[n_entries]       target of entry o (what the builder was handed)
 //   gcount  u64[ntar], stats u64[8] per sample
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <type_traits>
-#include "kid_common.h"
+#include "kid_table.hip.h"
+#include "kid_prepare.hip.h"
+#include "kid_seenlog.hip.h"
 
-#define KID_WAVE 64
-#define KID_TOMBSTONE_HI 0xFFFFFFFFu // high key word of a duplicate entry that lost to an earlier insert (keys are < 2^62)
 #define KID_SEG_KMERS 960  // k-mers per read segment: 960 + 30 bases + 15 alignment slack <= 64 chunks of 16 B
-#define KID_WAVE_LDS_WORDS 104 // per wave, general loops: 66 packed-base words + 34 invalid-mask words + 4 counters
-// pair kernel (no strips): 4 counters, the queue of unresolved lookups (3 words + 1 tag byte per entry) and the
-// results of 64 reads
-#define KID_CQ_CAP 192   // a read appends at most 128 entries to fewer than KID_CQ_FLUSH queued ones
+#define KID_CQ_CAP 192   // the queue of unresolved lookups: a read appends at most 128 entries to fewer than KID_CQ_FLUSH queued ones
 #define KID_CQ_FLUSH 64
-#define KID_PAIR_LDS_WORDS (4 + 3 * KID_CQ_CAP + KID_CQ_CAP / 4 + 64 + 128) // ... + the batch read numbers of 128 result slots
+// The LDS area of one wave, as word offsets from its start.  Three kinds of area: KidWaveLds<true, 1 or 2> of the pair
+// and duo loops (no strip: their words travel by ds_bpermute; one area and one dispatch limit for both, the duo loop
+// leaves the read numbers unused), <true, 0> of the general loops on the minimizer-localised table and <false, 0> of
+// those on the reference table (no queue: a hit is followed up on the spot).  The members behind `total` of a kind are
+// not part of it.  kid_launch_classify sizes the launch and sets its dispatch limits by `total`: 820, 792 and 104 words.
+template <bool MINLOC, int PAIRK>
+struct KidWaveLds {
+    static constexpr uint32_t strip = 0;                           // 64 packed-base words of the staged segment + 2 of zeros
+    static constexpr uint32_t mask = strip + (PAIRK ? 0 : 66);     // its invalid-base bits, 16 per word: 32 words + 2 of zeros
+    static constexpr uint32_t counters = mask + (PAIRK ? 0 : 34);  // [0..1] lookups (64 bits), [2] hits, [3] probes beyond the first of a lookup
+    // the queue of unresolved lookups, three columns of KID_CQ_CAP words -- key lo, key hi (or {target, ordinal} of a
+    // verified hit), table line -- and one tag byte per entry: read number mod 64 (+ 0x80: verified)
+    static constexpr uint32_t cq_klo = counters + 4, cq_khi = cq_klo + KID_CQ_CAP, cq_lw = cq_khi + KID_CQ_CAP;
+    static constexpr uint32_t cq_tag = cq_lw + KID_CQ_CAP;
+    static constexpr uint32_t results = cq_tag + KID_CQ_CAP / 4;   // result slots of a block of 64 reads
+    static constexpr uint32_t read_nums = results + 64;            // pair loop: the batch read numbers of 128 result slots
+    static constexpr uint32_t total = !MINLOC ? cq_klo : PAIRK ? read_nums + 128 : read_nums;
+};
+static_assert(KidWaveLds<true, 1>::total == 820 && KidWaveLds<true, 2>::total == 820 && KidWaveLds<true, 0>::total == 792 &&
+              KidWaveLds<false, 0>::total == 104, "tests/test_gpu_kernel_variants.py derives the dispatch limits from these");
 #define KID_TAPER 6u // the workgroups dispatched first take this many times the reads of those dispatched last
                      // (profiles/r02/ab_taper.txt: a launch ends when the slowest of its last workgroups does)
 // A lookup whose header shows a fingerprint match fetches its candidate cell on the spot -- the cell sits in the
@@ -43,424 +63,11 @@
 // (profiles/digest/ab_early_vs_deferred.txt).  The resolver then settles a flagged lookup from its table line alone:
 // the header (cell 0, the one HBM request) and the candidate cell behind it in the same 128 bytes -- the digest is not
 // read a second time (profiles/resolver_header/).
-#define KID_GEN_ML_LDS_WORDS (104 + 3 * KID_CQ_CAP + KID_CQ_CAP / 4 + 64) // general loops on the minimizer-localised table: strip, counters, queue, results
 #define KID_CLASSIFY_OCC 8 // waves per SIMD the register allocator must leave room for
 // ... except the duo loop with ancestor rows: at 64 VGPRs it spills, and a spill or copy of a register that an
 // asynchronous inline-assembly load (below) has not filled yet carries a stale value past the explicit s_waitcnt --
 // wrong hits, found by tests/test_gpu_kernel_variants.py.  Allowed 128 VGPRs it takes 80 (6 waves per SIMD), no spill.
 #define KID_CLASSIFY_OCC_DUO_ROWS 4
-
-typedef uint32_t kid_u4 __attribute__((ext_vector_type(4)));
-typedef uint32_t kid_u2 __attribute__((ext_vector_type(2)));
-
-// One table cell.  Reference placement: non-temporal -- a probe touches a random 16 bytes of a 16 GiB
-// table once, so the line is not worth keeping in L2 / Infinity Cache (tools/gather_policy.hip: 49 ->
-// 54 G random cells/s on a 16 GiB region).  Minimizer-localised placement: plain loads -- the header
-// of a line is read again by the resolver and the matching entry sits in the same 128 bytes, so the
-// line should stay cached (measured: 1.29 -> 1.23 ms per launch).
-// Fire-and-forget global writes of the classify kernel (per-read result, seen-bitmap bits).  Issued
-// from inline assembly so that the compiler's waitcnt insertion does not know them: on gfx9 a pending
-// store or no-return atomic shares vmcnt with the loads and makes the next wait a full vmcnt(0) drain,
-// i.e. every read would sit out the write acknowledgement of the one before.  Nothing in the kernel
-// reads these locations back; they complete before the kernel does.
-__device__ __forceinline__ void kid_store_u32_nowait(uint32_t *p, uint32_t v)
-{
-    asm volatile("global_store_dword %0, %1, off" : : "v"(p), "v"(v) : "memory");
-}
-__device__ __forceinline__ void kid_atomic_or_nowait(uint32_t *p, uint32_t v)
-{
-    asm volatile("global_atomic_or %0, %1, off" : : "v"(p), "v"(v) : "memory");
-}
-
-__device__ __forceinline__ uint4 kid_load_cell(const uint4 *table, uint32_t idx) { return table[idx]; }
-__device__ __forceinline__ uint4 kid_load_cell_nt(const uint4 *table, uint32_t idx)
-{
-    const kid_u4 v = __builtin_nontemporal_load(reinterpret_cast<const kid_u4 *>(table) + idx);
-    return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-struct KidDevDb {
-    const uint4 *table;
-    uint64_t nslots;
-    uint32_t slot_mask;
-    uint32_t max_probes;
-    int k;
-    uint32_t u_is_t;
-    uint32_t minloc; // 1: minimizer-localised geometry (kid_common.h), 0: the reference's fmix64 + triangular probing
-    uint32_t line_shift; // minloc: 32 - log2(lines)
-    uint32_t line_mask;  // minloc: lines - 1
-    const uint4 *rows; // null when the tree does not fit the row encoding
-    const int32_t *parent;
-    const int32_t *depth;
-    int32_t ntar;
-    const uint2 *digest; // minloc, GPU-built: the digest plane, 8 bytes per line (kid_common.h); null: the table has none
-};
-
-struct KidBatch { // what the caller handed over
-    const uint8_t *bases;
-    const uint64_t *offsets; // null: fixed_len layout
-    const int32_t *start;    // nullable
-    const int32_t *stop;     // nullable
-    uint32_t *out_final;     // nullable
-    uint64_t n;
-    uint32_t fixed_len;
-};
-
-// per-read descriptor written by kid_prepare_kernel: absolute index of the first base of the
-// classified range and the number of k-mer windows in it (<= 0: none)
-struct KidReadDesc {
-    uint64_t first_base;
-    int32_t n_kmers;
-    uint32_t pad;
-};
-
-// Very long records (FASTA contigs classified whole, kmer_read_vf6.cpp:803-861).  The classify kernels give a read to ONE
-// wave; a record of more than `long_cut` k-mers goes to the long-record kernels instead (kid_long_*): kid_prepare_kernel
-// hides it from the classify kernels (n_kmers = 0) and puts it on this list, kid_long_plan_kernel turns the list into
-// the records' places in the hit array.  All on the device: the batch may be one whose offsets the host never saw.
-#define KID_LONG_MAX 1024u
-struct KidLongList {
-    uint32_t n;       // records flagged so far (beyond KID_LONG_MAX: left to the classify kernels)
-    uint32_t pad[3];
-    struct Item { uint64_t first_base; uint32_t n_kmers; uint32_t read; } e[KID_LONG_MAX];
-};
-struct KidLongRec {
-    uint64_t first_base; // absolute index of the record's first classified base in the batch text
-    uint64_t hits_off;   // where its hits start in the hits array
-    uint32_t n_kmers;
-    uint32_t read;       // its number in the batch
-    uint64_t tile0;      // number of 256-position tiles of the records before it
-};
-struct KidLongPlan {
-    uint32_t n_recs;
-    uint32_t pad;
-    uint64_t n_tiles;
-    uint64_t total_kmers;
-    KidLongRec recs[KID_LONG_MAX];
-};
-
-// What a launch of the classify kernels reads: the ASCII read text as the caller handed it over -- the kernels turn it
-// into 2-bit codes in registers (kid_pack4 / kid_pack16), there is no packed image of the batch in memory -- and the
-// reads' descriptors.  Fixed layout (kid_classify_fixed_*): no descriptors either, read r of the launch is
-// bases[(read0 + r) * fixed_len ...) with fixed_nk k-mers (KidRareArgs).
-struct KidInput {
-    const uint8_t *bases;    // 16-byte aligned; readable up to 16 bytes past the last read
-    const KidReadDesc *desc; // of this launch's reads; null: fixed layout
-    uint32_t *out_final;     // of this launch's reads; nullable
-    uint64_t n;              // reads of this launch
-};
-
-struct KidSampleDev {
-    unsigned long long *gcount;
-    uint32_t *seen;
-    unsigned long long *stats; // [0] reads [1] lookups [2] probes [3] hits [4] argument errors [5] FASTQ records dropped by process_qual
-                               // [6] device-clock ticks [7] launches banked [8] quality lines shorter than their sequence
-                               // [29] workgroups through [30] first start [31] last end of the running launch
-};
-
-// What only rare paths of the classify kernel need (hit cells, the flush at the end): kept in device
-// memory and loaded where used, so it does not occupy scalar registers across the hot loop.
-struct KidRareArgs {
-    unsigned long long *gcount;
-    unsigned long long *stats;
-    uint32_t line_mask;
-    uint32_t fixed_len;           // fixed layout: bases per read (0: the launch has descriptors)
-    unsigned long long batch_max; // (batch sequence number << 32) | largest n_kmers of the batch: kid_prepare_kernel
-    unsigned long long read0;     // fixed layout: number of the launch's first read within the batch text
-    int32_t fixed_nk;             // fixed layout: k-mers per read
-    uint32_t pad;
-    // what the resolver / the 64-read flush of the pair kernels need (rare paths by now, bulk work: a scalar
-    // load there is cheaper than four scalar registers held across the hot loop)
-    const uint4 *rows;
-    uint32_t *seen;
-    uint32_t *out_final;   // of the current launch: written by kid_prepare_kernel / kid_rebase_kernel
-    const void *desc;      // of the current launch (KidReadDesc *; null: fixed layout)
-    // the hit log (see kid_seenlog_*): the resolver appends the entry ordinals of its hits instead of setting their bits
-    // in `seen` with one memory-side atomic each; null: atomics
-    uint32_t *seen_log;      // KID_LOG_SHARDS regions of seen_log_cap entries
-    uint32_t *seen_log_tail; // their fill counters, 64 bytes apart
-    uint32_t seen_log_cap;
-    uint32_t pad2;
-    const uint4 *table;      // the DIGEST instantiations keep the plane's pointer in scalar registers, not the table's
-};
-#define KID_LOG_SHARDS 64u      // regions (blockIdx & 63), each with its own fill counter: a resolver chunk costs one fetch-and-add on
-                                // its region's counter, and with 16 hits per read (reads from genomes the database holds) there are
-                                // 600 k chunks per 1 M pairs -- on 8 counters they queued for 3 ms (profiles/r03/clumped_db_log_shards.txt)
-#define KID_LOG_NONE 0xFFFFFFFFu // a log place whose lookup turned out not to be a hit
-#define KID_LOG_BIN_BITS 18     // the apply pass owns the bitmap in pieces of 2^18 bits = 32 KiB of LDS
-#define KID_LOG_WGS 1024u       // workgroups of the counting / scattering kernels: 16 per region
-
-// ------------------------------------------------------------------ hash lookup
-// Hashtable::getHash, newkmer_10nx.cpp:204-233 (+ probe cap kmer_read_m3.cpp:232)
-// Candidate entries of a line header for fingerprint fp, as a bit set: bit (15 - d) = entry 2d,
-// bit (31 - d) = entry 2d + 1 (d = header dword 0..3).  A superset of the true matches (the classic
-// zero-halfword test can also flag the upper half of a dword whose lower half matched); every
-// candidate is verified against the full key, so a false one only costs a load.
-__device__ __forceinline__ uint32_t kid_hdr_cand(const uint4 &h, uint32_t fp)
-{
-    const uint32_t rep = fp * 0x00010001u, one = 0x00010001u, top = 0x80008000u;
-    const uint32_t a = h.x ^ rep, b = h.y ^ rep, c = h.z ^ rep, d = (h.w ^ rep) | 0xFFFF0000u; // upper half of .w = count
-    return (((a - one) & ~a) & top) | ((((b - one) & ~b) & top) >> 1) | ((((c - one) & ~c) & top) >> 2) |
-           ((((d - one) & ~d) & top) >> 3);
-}
-// the same question as a yes/no, written as seven 16-bit compares: hipcc turns them into
-// v_cmp_eq_u16 with sub-dword operand selects, whose lane masks combine on the scalar unit
-__device__ __forceinline__ bool kid_hdr_any(const uint4 &h, uint32_t fp)
-{
-    const uint16_t f = (uint16_t)fp;
-    return ((uint16_t)h.x == f) | ((uint16_t)(h.x >> 16) == f) | ((uint16_t)h.y == f) | ((uint16_t)(h.y >> 16) == f) |
-           ((uint16_t)h.z == f) | ((uint16_t)(h.z >> 16) == f) | ((uint16_t)h.w == f);
-}
-__device__ __forceinline__ uint32_t kid_cand_entry(uint32_t bit) // bit index from kid_hdr_cand -> entry 0..6
-{
-    return 2u * (15u - (bit & 15u)) + (bit >> 4);
-}
-
-// Lookup in the minimizer-localised table: header, then the candidate entries, then the next line
-// while the chain continues.  Returns the target (0 = absent); ncell = cells read.
-__device__ __forceinline__ uint32_t kid_bucket_lookup(const KidDevDb &db, uint64_t key, uint32_t g, uint32_t &slot, uint32_t &ncell)
-{
-    uint32_t line = kid_minloc_line(g, db.line_shift);
-    const uint32_t fp = kid_key_fp(key);
-    ncell = 0;
-    slot = 0;
-    for (;;) {
-        const uint32_t base = line * KID_LINE_CELLS;
-        const uint4 h = db.table[base];
-        ncell++;
-        uint32_t m = kid_hdr_cand(h, fp);
-        while (m) {
-            const uint32_t j = kid_cand_entry((uint32_t)__builtin_ctz(m));
-            m &= m - 1;
-            const uint4 c = db.table[base + 1u + j];
-            ncell++;
-            if (c.z != 0 && c.x == (uint32_t)key && c.y == (uint32_t)(key >> 32)) { slot = c.w - 1u; return c.z; }
-        }
-        if (!kid_hdr_continues(h.w, fp)) return 0;
-        line = (line + 1u) & db.line_mask;
-    }
-}
-
-__device__ __forceinline__ uint32_t kid_dev_lookup(const KidDevDb &db, uint64_t key, uint32_t &slot, uint32_t &nprobe)
-{
-    uint32_t i = 0, res = 0;
-    slot = 0;
-    if (db.minloc) return kid_bucket_lookup(db, key, kid_minimizer_of_key(key, db.k), slot, nprobe);
-    const uint64_t hash = kid_fmix64(key);
-    uint64_t reprobe = 0;
-    do {
-        const uint32_t idx = ((uint32_t)hash + (uint32_t)reprobe) & db.slot_mask;
-        reprobe += ++i;
-        const uint4 c = db.table[idx];
-        if (c.z == 0) break;
-        if (c.x == (uint32_t)key && c.y == (uint32_t)(key >> 32)) { res = c.z; slot = c.w - 1u; break; }
-    } while (reprobe < db.nslots && (db.max_probes == 0 || i < db.max_probes));
-    nprobe = i;
-    return res;
-}
-
-// ------------------------------------------------------------------ sliding-window minimum over a wavefront
-// 16-lane DPP rows double as the blocks of the van Herk / Gil-Werman scheme: with P = prefix
-// minimum and S = suffix minimum inside each row, min(a[p..p+15]) = min(S[p], P[p+15]).
-// (a lane whose DPP source lies outside its row is disabled for that instruction: it keeps its own value.  A VGPR written
-//  by a VALU instruction may be read through DPP two wait states later: s_nop 1 between dependent steps of ONE scan;
-//  kid_row_scans interleaves four scans instead)
-__device__ __forceinline__ uint32_t kid_row_prefix_min(uint32_t x)
-{
-    uint32_t t;
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x111, 0xF, 0xF, false); x = x < t ? x : t; // row_shr:1
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x112, 0xF, 0xF, false); x = x < t ? x : t;
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x114, 0xF, 0xF, false); x = x < t ? x : t;
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x118, 0xF, 0xF, false); x = x < t ? x : t;
-    return x;
-}
-__device__ __forceinline__ uint32_t kid_row_suffix_min(uint32_t x)
-{
-    uint32_t t;
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x101, 0xF, 0xF, false); x = x < t ? x : t; // row_shl:1
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x102, 0xF, 0xF, false); x = x < t ? x : t;
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x104, 0xF, 0xF, false); x = x < t ? x : t;
-    t = (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)x, 0x108, 0xF, 0xF, false); x = x < t ? x : t;
-    return x;
-}
-// prefix and suffix minima of two tiles at once: p0 = s0 = hashes of the first tile, p1 = s1 = those of the second
-__device__ __forceinline__ void kid_row_scans(uint32_t &p0, uint32_t &s0, uint32_t &p1, uint32_t &s1)
-{
-    p0 = kid_row_prefix_min(p0); s0 = kid_row_suffix_min(s0);
-    p1 = kid_row_prefix_min(p1); s1 = kid_row_suffix_min(s1);
-}
-
-// ------------------------------------------------------------------ taxonomy
-// Tree1::msca, newkmer_10nx.cpp:118-144, on the ancestor-row encoding.
-// Let L = deepest common node of the two root paths.  The reference returns x
-// when y lies on x's root path (L == y), y when x lies on y's (L == x), else L.
-__device__ __forceinline__ uint32_t kid_row_entry(const uint4 &r, uint32_t d)
-{
-    const uint32_t w = d < 2 ? r.x : d < 4 ? r.y : d < 6 ? r.z : r.w;
-    return (d & 1) ? (w >> 16) : (w & 0xFFFFu);
-}
-
-__device__ __forceinline__ uint32_t kid_msca_rows(uint32_t x, const uint4 &rx, uint32_t y, const uint4 &ry, uint4 &rout)
-{
-    const uint32_t dx = rx.x & 0xFFFFu, dy = ry.x & 0xFFFFu;
-    const uint64_t lo = ((uint64_t)(rx.y ^ ry.y) << 32) | ((rx.x ^ ry.x) & 0xFFFF0000u);
-    const uint64_t hi = ((uint64_t)(rx.w ^ ry.w) << 32) | (rx.z ^ ry.z);
-    uint32_t f = lo ? (uint32_t)(__builtin_ctzll(lo) >> 4) : hi ? 4u + (uint32_t)(__builtin_ctzll(hi) >> 4) : 8u;
-    uint32_t c = f - 1; // entries 1..f-1 agree
-    c = c < dx ? c : dx;
-    c = c < dy ? c : dy;
-    if (c == 7 && dx == 8 && dy == 8 && x == y) c = 8; // depth-8 nodes are not stored in their own row
-    if (c == dy) { rout = rx; return x; }
-    if (c == dx) { rout = ry; return y; }
-    rout = rx;
-    rout.x = (rx.x & 0xFFFF0000u) | c;
-    return c == 0 ? 1u : kid_row_entry(rx, c);
-}
-
-// same function by climbing parent[]/depth[] (any tree shape)
-__device__ __forceinline__ uint32_t kid_msca_climb(const KidDevDb &db, uint32_t x, uint32_t y)
-{
-    uint32_t a = x, b = y;
-    int32_t da = db.depth[a], dd = db.depth[b];
-    while (da > dd) { a = (uint32_t)db.parent[a]; da--; }
-    while (dd > da) { b = (uint32_t)db.parent[b]; dd--; }
-    while (a != b) { a = (uint32_t)db.parent[a]; b = (uint32_t)db.parent[b]; }
-    if (a == y) return x;
-    if (a == x) return y;
-    return a;
-}
-
-// ------------------------------------------------------------------ base packing
-// ASCII bases -> 2-bit codes plus a mask of the bytes that are not ACGTacgt (those reset the reference's
-// rolling window, newkmer_10nx.cpp:520-524).  4 bytes at a time, no per-byte branches.
-// kid_pack4: the 4 bases of one dword (byte 0 = first base) -> codes in bits 7:0 (first base in bits 7:6),
-// invalid flags in bits 3:0 of inv (bit j = byte j).
-__device__ __forceinline__ void kid_pack4(const uint32_t x, const uint32_t u_is_t, uint32_t &codes, uint32_t &inv)
-{
-    const uint32_t c = ((x >> 1) ^ (x >> 2)) & 0x03030303u; // A,C,G,T -> 0,1,2,3 in every byte
-    codes = (c * 0x40100401u) >> 24;                        // byte0 -> bits 7:6 ... byte3 -> bits 1:0
-    // rebuild the upper-case letter each code stands for and compare
-    const uint32_t c0 = c & 0x01010101u, c1 = (c >> 1) & 0x01010101u, t = c0 & c1;
-    const uint32_t expect = 0x40404040u | (0x01010101u ^ t) | ((c0 ^ c1) << 1) | (c1 << 2) | (t << 4);
-    uint32_t diff = (x & 0xDFDFDFDFu) ^ expect;
-    if (u_is_t) diff &= ~t; // 'U' = 'T' ^ 1 and decodes to code 3
-    const uint32_t nz = (((diff & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | diff) & 0x80808080u;
-    inv = (((nz >> 7) * 0x00204081u) >> 21) & 0xFu;
-}
-// The same split in two for the pair loops, where almost no read has a base that is not ACGT: the codes and a word
-// `diff` that is non-zero in every byte that is not ACGTacgt(Uu) -- seven instructions (v_perm_b32 looks up the
-// letter a code stands for, v_dot4_u32_u8 gathers the four codes) --, and the 4-bit mask from `diff` when somebody
-// needs it.
-__device__ __forceinline__ uint32_t kid_codes4(const uint32_t x, const uint32_t u_is_t, uint32_t &diff)
-{
-    const uint32_t c = ((x >> 1) ^ (x >> 2)) & 0x03030303u;            // A,C,G,T -> 0,1,2,3 in every byte
-    const uint32_t expect = __builtin_amdgcn_perm(0u, 0x54474341u, c); // byte j = "ACGT"[code of byte j]
-    diff = (x & 0xDFDFDFDFu) ^ expect;
-    if (u_is_t) diff &= ~(c & (c >> 1) & 0x01010101u);                 // 'U' = 'T' ^ 1 and decodes to code 3
-    return __builtin_amdgcn_udot4(c, 0x01041040u, 0u, false);          // byte0 -> bits 7:6 ... byte3 -> bits 1:0
-}
-__device__ __forceinline__ uint32_t kid_inv4(const uint32_t diff)
-{
-    const uint32_t nz = (((diff & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | diff) & 0x80808080u;
-    return (((nz >> 7) * 0x00204081u) >> 21) & 0xFu;
-}
-// 16 bases -> one packed word (first base in the top bits) + 16-bit mask
-__device__ __forceinline__ void kid_pack16(const uint4 v, const uint32_t u_is_t, uint32_t &codes, uint32_t &inv)
-{
-    const uint32_t in[4] = {v.x, v.y, v.z, v.w};
-    codes = 0;
-    inv = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        uint32_t c8, i4;
-        kid_pack4(in[q], u_is_t, c8, i4);
-        codes = (codes << 8) | c8;
-        inv |= i4 << (4 * q);
-    }
-}
-
-// ------------------------------------------------------------------ batch preparation
-// What a launch of the classify kernels finds in its device argument block: its share of the descriptors (or the fixed
-// layout) and of the result array.  Set in classify-stream order.
-__device__ __forceinline__ void kid_rebase(KidRareArgs *rare, const KidReadDesc *desc, uint32_t *out_final, unsigned long long read0,
-                                           uint32_t fixed_len, int32_t fixed_nk)
-{
-    if (threadIdx.x == 0) {
-        rare->desc = desc;
-        rare->out_final = out_final;
-        rare->read0 = read0;
-        rare->fixed_len = fixed_len;
-        rare->fixed_nk = fixed_nk;
-    }
-}
-
-// [start, stop] -> descriptor; the range checks the reference leaves to string::at() happen here
-__global__ void kid_prepare_kernel(const KidBatch b, int k, KidReadDesc *desc, unsigned long long *stats, KidRareArgs *rare, uint32_t seq,
-                                   uint32_t long_cut, KidLongList *long_list, int rebase)
-{
-    // (the launch's descriptor / result pointers are set in classify-stream order: by kid_rebase_kernel when this kernel
-    //  may run while the batch before is being classified, else -- `rebase`, same stream -- right here for the batch's
-    //  first launch: one launch and its gap less per batch)
-    if (rebase && blockIdx.x == 0) kid_rebase(rare, desc, b.out_final, 0ull, 0u, 0);
-    uint32_t bad = 0, mx = 0;
-    for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < b.n; r += (uint64_t)gridDim.x * blockDim.x) {
-        uint64_t off;
-        int64_t rl;
-        if (b.offsets) { off = b.offsets[r]; rl = (int64_t)(b.offsets[r + 1] - off); }
-        else { off = r * (uint64_t)b.fixed_len; rl = b.fixed_len; }
-        int64_t s0 = b.start ? (int64_t)b.start[r] : 0;
-        int64_t e0 = b.stop ? (int64_t)b.stop[r] : rl - 1;
-        if (s0 <= e0 && (s0 < 0 || e0 >= rl)) { // never read outside the read; reported as KID_ERR_ARG
-            bad++;
-            if (s0 < 0) s0 = 0;
-            if (e0 >= rl) e0 = rl - 1;
-        }
-        KidReadDesc d;
-        int64_t nk = e0 - s0 + 1 - (k - 1);
-        if (s0 > e0) nk = 0;
-        d.first_base = off + (uint64_t)(s0 > 0 ? s0 : 0);
-        d.n_kmers = (int32_t)(nk > 0x7FFFFFFF ? 0x7FFFFFFF : nk);
-        d.pad = 0;
-        // a record that goes to the long-record kernels (kid_long_hits_kernel / kid_long_fold_kernel): the classify
-        // kernels see a read without k-mers (counted under target 0 until the fold corrects that)
-        if (long_cut && nk > (int64_t)long_cut) {
-            const uint32_t at = atomicAdd(&long_list->n, 1u);
-            if (at < KID_LONG_MAX) {
-                KidLongList::Item it;
-                it.first_base = d.first_base; it.n_kmers = (uint32_t)d.n_kmers; it.read = (uint32_t)r;
-                long_list->e[at] = it;
-                d.n_kmers = 0;
-            }
-        }
-        desc[r] = d;
-        if (d.n_kmers > 0 && (uint32_t)d.n_kmers > mx) mx = (uint32_t)d.n_kmers;
-    }
-    // largest read of the batch, tagged with the batch number so that the word never needs a reset: one
-    // atomic per workgroup at most (none once a workgroup sees a value as large as its own; a batch of
-    // equal reads is announced by workgroup 0 alone)
-    __shared__ uint32_t s_mx;
-    if (threadIdx.x == 0) s_mx = 0;
-    __syncthreads();
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const uint32_t y = (uint32_t)__shfl_xor((int)mx, o); mx = y > mx ? y : mx; }
-    if ((threadIdx.x & 63u) == 0 && mx) atomicMax(&s_mx, mx);
-    __syncthreads();
-    const bool uniform_batch = !b.offsets && !b.start && !b.stop;
-    if (threadIdx.x == 0 && (!uniform_batch || blockIdx.x == 0)) {
-        const unsigned long long v = ((unsigned long long)seq << 32) | s_mx;
-        if (v > *reinterpret_cast<volatile unsigned long long *>(&rare->batch_max)) atomicMax(&rare->batch_max, v);
-    }
-    if (bad) atomicAdd(&stats[4], (unsigned long long)bad);
-}
-
-// Sets a launch's argument block without kid_prepare_kernel: the later launches of a batch classified in several, and
-// every launch of a fixed-layout batch (no descriptors: the host knows the one read length; batch_max = (seq << 32) | k-mers)
-__global__ void kid_rebase_kernel(KidRareArgs *rare, const KidReadDesc *desc, uint32_t *out_final, unsigned long long read0,
-                                  uint32_t fixed_len, int32_t fixed_nk, unsigned long long batch_max)
-{
-    kid_rebase(rare, desc, out_final, read0, fixed_len, fixed_nk);
-    if (threadIdx.x == 0 && batch_max) rare->batch_max = batch_max;
-}
 
 // ------------------------------------------------------------------ classify
 // One wavefront per read (DESIGN.md section 4 has the long version).  What a read needs:
@@ -521,12 +128,13 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
     const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); // wave-uniform
     const uint32_t wpb = blockDim.x >> 6;
     uint32_t *hist = kid_smem;
-    uint32_t *WA = kid_smem + hist_words + wib * (PAIRK ? KID_PAIR_LDS_WORDS : MINLOC ? KID_GEN_ML_LDS_WORDS : KID_WAVE_LDS_WORDS); // strip: 66 packed words + 34 mask words
+    typedef KidWaveLds<MINLOC, PAIRK> LDS;
+    uint32_t *WA = kid_smem + hist_words + wib * LDS::total; // this wave's area
 
     // the workgroup's totals for kid_sample_stats (behind the waves' areas): one set of global atomics per workgroup --
     // four per WAVE, all on one line, were 32 768 atomics per launch queueing up on one L2 atomic unit (~0.1 ms)
     unsigned long long *const WGS = reinterpret_cast<unsigned long long *>(
-        kid_smem + hist_words + wpb * (PAIRK ? KID_PAIR_LDS_WORDS : MINLOC ? KID_GEN_ML_LDS_WORDS : KID_WAVE_LDS_WORDS));
+        kid_smem + hist_words + wpb * LDS::total);
     if (threadIdx.x < 4) WGS[threadIdx.x] = 0;
     if (HIST) {
         for (uint32_t i = threadIdx.x; i < hist_words; i += blockDim.x) hist[i] = 0;
@@ -548,14 +156,14 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
     // scalar registers (80 per wave at this occupancy, and the hot loop wants them all): lookups and
     // hits accumulate in the wave's LDS words, the msca row of the running result in lanes 0-3 of a
     // vector register, the probes beyond the first in a per-lane counter.
-    uint32_t *const WC = WA + (PAIRK ? 0 : 100); // [0..1] lookups (64 bits), [2] hits, [3] probes beyond the first of a lookup
+    uint32_t *const WC = WA + LDS::counters; // [0..1] lookups (64 bits), [2] hits, [3] probes beyond the first of a lookup
     unsigned long long *const WL = reinterpret_cast<unsigned long long *>(WC);
     if (lane < 4) WC[lane] = 0;
     uint32_t pend_t = 0, pend_n = 0;       // !HIST: run-length buffer in front of the global gcount atomics
 
     // ---- 1. stage one packed segment in a strip; returns "no base of it resets a window" (wave-uniform)
     auto stage = [&](uint32_t *W, const uint32_t codes, const uint32_t inv) -> bool {
-        uint32_t *IM = W + 66;
+        uint32_t *IM = W + (LDS::mask - LDS::strip);
         W[lane] = codes;
         reinterpret_cast<uint16_t *>(IM)[lane] = (uint16_t)inv;
         if (lane < 2) { W[64 + lane] = 0; IM[32 + lane] = 0; }
@@ -580,7 +188,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             return direct ? (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << (2u + LWS)), (int)wcodes) : W[idx];
         };
         auto mask32 = [&](const uint32_t idx) -> uint32_t { // invalid-mask bits of bases 32 idx .. 32 idx + 31
-            if (!direct) return (W + 66)[idx];
+            if (!direct) return (W + (LDS::mask - LDS::strip))[idx];
             const uint32_t lo = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(idx << (3u + LWS)), (int)winv);
             const uint32_t hi = (uint32_t)__builtin_amdgcn_ds_bpermute((int)((idx << (3u + LWS)) + (4u << LWS)), (int)winv);
             return (lo & 0xFFFFu) | (hi << 16);
@@ -666,71 +274,12 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
 
     // ---- 3b, 4, 5. the rest of the probe sequences, seen-bitmap, ordered fold into final_t (vfrow:
     // the ancestor row of final_t, in lanes 0-3)
-    auto group_back = [&](Group &g, uint32_t &final_t, uint32_t &vfrow) {
+    auto group_back = [&](auto &g, uint32_t &final_t, uint32_t &vfrow) {
+        static_assert(!MINLOC && sizeof(g) != 0, "the minimizer-localised table has no back half on the spot");
         uint32_t tgt[U], slot[U];
 #pragma unroll
         for (int u = 0; u < U; u++) { tgt[u] = 0; slot[u] = 0; }
-        if constexpr (DIGEST) {
-            // (the general loops' back half: never reached from the pair and duo loops)
-        } else if (MINLOC) {
-            uint32_t mm[U], fp[U];
-            bool more = false;
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                fp[u] = (g.fpp >> (16 * u)) & 0xFFFFu;
-                mm[u] = (g.act[u] && (kid_hdr_any(g.hd[u], fp[u]) || kid_hdr_continues(g.hd[u].w, fp[u]))) ? 1u : 0u;
-                more |= mm[u] != 0;
-            }
-            if (__ballot(more) == 0) return; // (wave-uniform) ~99 % of the lanes are settled by their header
-            // fingerprint matches (almost always the key itself): the first candidate cell of every
-            // pending lookup is requested at once -- one round trip for the whole group.  From here on a
-            // header is only its candidate set and its "line continues" flag.
-            uint32_t m[U], idx[U];
-            bool full[U];
-            uint4 c[U];
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                m[u] = mm[u] ? kid_hdr_cand(g.hd[u], fp[u]) : 0u;
-                full[u] = mm[u] && kid_hdr_continues(g.hd[u].w, fp[u]);
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                idx[u] = 0;
-                c[u] = make_uint4(0, 0, 0, 0);
-                if (m[u]) {
-                    idx[u] = g.hlo[u] * KID_LINE_CELLS + 1u + kid_cand_entry((uint32_t)__builtin_ctz(m[u]));
-                    m[u] &= m[u] - 1;
-                    c[u] = kid_load_cell(db.table, idx[u]);
-                    atomicAdd(&WC[3], 1u);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; u++) {
-                bool go = mm[u] != 0;
-                if (idx[u] && c[u].z != 0 && c[u].x == (uint32_t)g.key[u] && c[u].y == (uint32_t)(g.key[u] >> 32)) {
-                    tgt[u] = c[u].z; slot[u] = c[u].w - 1u; go = false;
-                }
-                // leftovers (a second candidate: 1e-4 of the lookups; a chained line: 1e-5)
-                uint32_t ln = g.hlo[u], mu = m[u];
-                bool fu = full[u];
-                while (go) {
-                    if (mu) {
-                        const uint32_t j = kid_cand_entry((uint32_t)__builtin_ctz(mu));
-                        mu &= mu - 1;
-                        const uint32_t ix = ln * KID_LINE_CELLS + 1u + j;
-                        const uint4 cc = kid_load_cell(db.table, ix);
-                        atomicAdd(&WC[3], 1u);
-                        if (cc.z != 0 && cc.x == (uint32_t)g.key[u] && cc.y == (uint32_t)(g.key[u] >> 32)) { tgt[u] = cc.z; slot[u] = cc.w - 1u; go = false; }
-                    } else if (fu) {
-                        ln = (ln + 1u) & rare->line_mask;
-                        const uint4 h = kid_load_cell(db.table, ln * KID_LINE_CELLS);
-                        atomicAdd(&WC[3], 1u);
-                        mu = kid_hdr_cand(h, fp[u]);
-                        fu = kid_hdr_continues(h.w, fp[u]);
-                    } else go = false;
-                }
-            }
-        } else {
+        {
             uint64_t rp[U];
             uint32_t step[U];
 #pragma unroll
@@ -787,20 +336,11 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                 const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)tgt[u], j);
                 if (x == final_t) continue; // msca(x,x) = x
                 uint4 rx = make_uint4(0, 0, 0, 0);
-                if (ROWS) {
-                    rx.x = (uint32_t)__builtin_amdgcn_readlane((int)row[u].x, j);
-                    rx.y = (uint32_t)__builtin_amdgcn_readlane((int)row[u].y, j);
-                    rx.z = (uint32_t)__builtin_amdgcn_readlane((int)row[u].z, j);
-                    rx.w = (uint32_t)__builtin_amdgcn_readlane((int)row[u].w, j);
-                }
+                if (ROWS) rx = kid_row_of_lane(row[u], j);
                 if (final_t != 0) { // :588-591
                     if (ROWS) {
-                        uint4 fr, ro;
-                        fr.x = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 0);
-                        fr.y = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 1);
-                        fr.z = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 2);
-                        fr.w = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 3);
-                        final_t = kid_msca_rows(x, rx, final_t, fr, ro);
+                        uint4 ro;
+                        final_t = kid_msca_rows(x, rx, final_t, kid_row_unpack(vfrow), ro);
                         rx = ro;
                     } else {
                         final_t = kid_msca_climb(db, x, final_t);
@@ -836,17 +376,17 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
     // is not followed up on the spot -- that would put two more dependent round trips (hit cell,
     // ancestor row) on every second read -- but queued in LDS; queued lookups are resolved 64 at a
     // time, one per lane, and folded read by read (entries are in read order, then window order).
-    uint32_t *const CQ_klo = WA + (PAIRK ? 4 : 104), *const CQ_khi = CQ_klo + KID_CQ_CAP, *const CQ_lw = CQ_khi + KID_CQ_CAP;
-    uint8_t *const CQ_tag = reinterpret_cast<uint8_t *>(CQ_lw + KID_CQ_CAP); // read number mod 64
+    uint32_t *const CQ_klo = WA + LDS::cq_klo, *const CQ_khi = WA + LDS::cq_khi, *const CQ_lw = WA + LDS::cq_lw;
+    uint8_t *const CQ_tag = reinterpret_cast<uint8_t *>(WA + LDS::cq_tag); // read number mod 64
     // per-read results wait in LDS for one scattered store per 64 reads: a pending store shares vmcnt
     // with the loads, and the explicit counts of the loop would have to sit out its acknowledgement
-    uint32_t *const RB = CQ_lw + KID_CQ_CAP + KID_CQ_CAP / 4;
+    uint32_t *const RB = WA + LDS::results;
     const uint32_t gw32 = (uint32_t)gw, nw32 = (uint32_t)nw; // 32-bit read indices (n < 2^31): read number i of this wave is gw + i nw
     uint32_t rd_first = gw32, rd_stride = nw32; // ... except where a wave takes a contiguous range (set below): rd_first + i
     uint32_t gen_cnt = 0;                         // general loops: reads of this wave
     uint64_t rb_skip = 0;   // result slots of the current block of 64 reads that are not this pass's to store
     bool rb_direct = false; // second pass of the general loops (reads of more than one segment): results stored at once
-    uint32_t *const RG = RB + 64; // pair kernel: which read of the batch a result slot belongs to (128 slots: the next block's are known early)
+    uint32_t *const RG = WA + LDS::read_nums; // pair kernel: which read of the batch a result slot belongs to (128 slots: the next block's are known early)
     auto flush_results = [&](const uint32_t i0, const uint32_t n) { // this wave's reads i0 .. i0+n-1 (n <= 64)
         uint32_t *const outp = rare->out_final;
         if (outp && lane < n && !((rb_skip >> ((i0 + lane) & 63u)) & 1ull))
@@ -860,9 +400,16 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
     uint32_t n_lookups = 0; // wave-uniform; per wave and launch: stays below 2^32 for batches of < 2^31 reads x 128 k-mers (longer reads: mod 2^32 is accepted for this counter)
     // the read the resolver left open (its run ended a chunk, or it is still being classified), and its fold so far
     uint32_t cur_tag = 0xFFFFFFFFu, final_c = 0, vfrow_c = 0;
-    auto commit = [&](const uint32_t i, const uint32_t final_t) { // gcount[final]++ (:605), per-read output
+    // what a finished read leaves, by the lane that knows its result f: gcount[f]++ (:605) in the workgroup's histogram
+    // (without one: the caller's own way to gcount), and the result stored at once or slotted for the flush
+    auto count_hist = [&](const uint32_t f) { atomicAdd(&hist[f >> 1], 1u << (16u * (f & 1u))); };
+    auto put_result = [&](const uint32_t i, const uint32_t f) { // i: the read's number in this wave
+        if (rb_direct) { if (b.out_final) kid_store_u32_nowait(&b.out_final[rd_first + i * rd_stride], f); }
+        else RB[i & 63u] = f;
+    };
+    auto commit = [&](const uint32_t i, const uint32_t final_t) {
         if (HIST) {
-            if (lane == 0) atomicAdd(&hist[final_t >> 1], 1u << (16u * (final_t & 1u)));
+            if (lane == 0) count_hist(final_t);
         } else if (final_t == pend_t) {
             pend_n++;
         } else {
@@ -870,8 +417,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             pend_t = final_t;
             pend_n = 1;
         }
-        if (rb_direct) { if (lane == 0 && b.out_final) kid_store_u32_nowait(&b.out_final[rd_first + i * rd_stride], final_t); }
-        else if (lane == 0) RB[i & 63u] = final_t;
+        if (lane == 0) put_result(i, final_t);
     };
     // the common case, a read without a single candidate: counted in a scalar register, its result slot is
     // zero already
@@ -1004,10 +550,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             if (lane == 0 && ctag != 0xFFFFFFFFu) {
                 if (valid && tag == ctag) { // the run continues the read left open by the chunk before
                     f = final_t;
-                    fr.x = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 0);
-                    fr.y = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 1);
-                    fr.z = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 2);
-                    fr.w = (uint32_t)__builtin_amdgcn_readlane((int)vfrow, 3);
+                    fr = kid_row_unpack(vfrow);
                 }
             }
             if (ctag != 0xFFFFFFFFu && (uint32_t)__builtin_amdgcn_readfirstlane((int)tag) != ctag) commit_tag(ctag, final_t);
@@ -1023,11 +566,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                     runs &= runs - 1;
                     const uint32_t e = runs ? (uint32_t)__builtin_ctzll(runs) : n; // the run is [h, e)
                     uint32_t uf = (uint32_t)__builtin_amdgcn_readlane((int)f, h);
-                    uint4 ufr;
-                    ufr.x = (uint32_t)__builtin_amdgcn_readlane((int)fr.x, h);
-                    ufr.y = (uint32_t)__builtin_amdgcn_readlane((int)fr.y, h);
-                    ufr.z = (uint32_t)__builtin_amdgcn_readlane((int)fr.z, h);
-                    ufr.w = (uint32_t)__builtin_amdgcn_readlane((int)fr.w, h);
+                    uint4 ufr = kid_row_of_lane(fr, h);
                     uint64_t rem = hitm & (e >= 64u ? ~0ull : ((1ull << e) - 1ull)) & ~((1ull << h) - 1ull);
                     while (rem) { // (kid_jump_fold of kid_tile.hip.h, written out on this loop's registers)
                         uint32_t rj = tgt;
@@ -1040,10 +579,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
                         if (!ch) break;
                         const int j = __builtin_ctzll(ch);
                         uf = (uint32_t)__builtin_amdgcn_readlane((int)rj, j);
-                        ufr.x = (uint32_t)__builtin_amdgcn_readlane((int)roj.x, j);
-                        ufr.y = (uint32_t)__builtin_amdgcn_readlane((int)roj.y, j);
-                        ufr.z = (uint32_t)__builtin_amdgcn_readlane((int)roj.z, j);
-                        ufr.w = (uint32_t)__builtin_amdgcn_readlane((int)roj.w, j);
+                        ufr = kid_row_of_lane(roj, j);
                         rem &= j >= 63 ? 0ull : ~((2ull << j) - 1ull);
                     }
                     if (lane == (uint32_t)h) { f = uf; fr = ufr; }
@@ -1052,11 +588,7 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             for (uint32_t t = 0; __ballot(head && t < len) != 0; t++) {
                 const int src = (int)(((lane + t) & 63u) << 2);
                 const uint32_t x = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)tgt);
-                uint4 rx;
-                rx.x = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)row.x);
-                rx.y = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)row.y);
-                rx.z = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)row.z);
-                rx.w = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)row.w);
+                const uint4 rx = kid_row_bpermute(src, row);
                 if (head && t < len && x != 0 && x != f) { // msca(x,x) = x
                     if (f != 0) {
                         if (ROWS) {
@@ -1076,10 +608,9 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
             const uint32_t last = 63u - (uint32_t)__builtin_clzll(hm); // hm != 0: n >= 1
             const bool more_chunks = base + 64u < qn || (uint32_t)__builtin_amdgcn_readlane((int)tag, (int)last) == open_tag; // "keep the last run open"
             if (head && (lane != last || !more_chunks)) {
-                if (HIST) atomicAdd(&hist[f >> 1], 1u << (16u * (f & 1u)));
+                if (HIST) count_hist(f);
                 else atomicAdd(&rare->gcount[f], 1ull);
-                if (rb_direct) { if (b.out_final) kid_store_u32_nowait(&b.out_final[rd_first + (i_now - ((i_now - tag) & 63u)) * rd_stride], f); }
-                else RB[tag] = f; // tag = read number mod 64
+                put_result(i_now - ((i_now - tag) & 63u), f); // (tag = read number mod 64)
             }
             if (more_chunks) {
                 ctag = (uint32_t)__builtin_amdgcn_readlane((int)tag, (int)last);
@@ -1144,47 +675,57 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
         return true;
     };
 
-    // ---- a whole read of any length on its own, given its descriptor and its first packed segment.
-    // `prefetch` issues the loads for the reads behind this one; it is called right after this read's
-    // first header loads went out (not before the loops: the compiler drains vmcnt in front of a loop)
+    // ---- the read driver of the general loops.  A read between its segments:
+    struct Read {
+        bool prefetched = false, had = false; // `prefetch` has been called; some lookup of the read was queued
+        uint32_t final_t = 0, vfrow = 0;      // reference geometry: the fold so far, and its ancestor row in lanes 0-3
+        uint32_t n_bad = 0;                   // windows without a k-mer
+    };
+    // one segment (<= KID_SEG_KMERS k-mers behind a shift of sh bases, its text in `raw`): staged, then group by group.
+    // `prefetch` issues the loads for the reads behind this one; it is called right after this read's first header
+    // loads went out (not before the loops: the compiler drains vmcnt in front of a loop)
+    auto run_segment = [&](Read &rd, const uint32_t i, const uint32_t sh, const uint32_t segk, const kid_u4 raw, auto &&prefetch) {
+        const uint32_t nb = segk + (uint32_t)k - 1;
+        uint32_t codes, inv;
+        kid_pack16(make_uint4(raw.x, raw.y, raw.z, raw.w), db.u_is_t, codes, inv);
+        const bool seg_clean = stage(WA + LDS::strip, codes, inv);
+        for (uint32_t t0 = 0; t0 < segk; t0 += U * 64u) {
+            Group g;
+            group_front(WA + LDS::strip, sh, nb, segk, t0, seg_clean, g, rd.n_bad);
+            if (!rd.prefetched) { prefetch(); rd.prefetched = true; }
+            if constexpr (MINLOC) {
+                rd.had |= back_deferred(g, i);
+                if (qn >= KID_CQ_FLUSH) resolve_all(i, i & 63u); // the read stays open: more groups may follow
+            } else {
+                group_back(g, rd.final_t, rd.vfrow);
+            }
+        }
+        __builtin_amdgcn_wave_barrier(); // strip is rewritten by the next segment / read
+    };
+    auto close_read = [&](Read &rd, const uint64_t r, const uint32_t i, const uint32_t n_kmers, auto &&prefetch) {
+        if constexpr (MINLOC) {
+            n_lookups += n_kmers - rd.n_bad;
+            if (!rd.had) commit_zero(i); // (else the resolver commits it, now that it is closed)
+        } else {
+            finish_read(r, rd.final_t, n_kmers - rd.n_bad);
+        }
+        if (!rd.prefetched) prefetch();
+    };
+    // a whole read of any length on its own, given its descriptor and the text of its first segment
     auto process_read = [&](const uint64_t r, const uint32_t i, const uint64_t first, const int64_t nk, const kid_u4 st_raw,
                             auto &&prefetch) {
-        bool prefetched = false, had = false;
-        uint32_t final_t = 0;
-        uint32_t vfrow = 0, n_bad = 0;
+        Read rd;
         for (int64_t seg = 0; seg < nk; seg += KID_SEG_KMERS) {
             const uint32_t segk = (uint32_t)((nk - seg) < KID_SEG_KMERS ? (nk - seg) : KID_SEG_KMERS);
             const uint64_t b0 = first + (uint64_t)seg; // first base of the segment
-            const uint32_t nb = segk + (uint32_t)k - 1;
-            const uint64_t c0 = b0 >> 4;
             const uint32_t sh = (uint32_t)(b0 & 15ull);
-            const uint32_t nchunks = (sh + nb + 15u) >> 4; // <= 64
+            const uint32_t nchunks = (sh + segk + (uint32_t)k - 1 + 15u) >> 4; // <= 64
             kid_u4 raw = st_raw;
             if (seg != 0) // long reads: later segments are fetched on the spot (lanes past the segment: its first chunk again)
-                raw = *reinterpret_cast<const kid_u4 *>(b.bases + 16ull * (c0 + (lane < nchunks ? lane : 0u)));
-            uint32_t codes, inv;
-            kid_pack16(make_uint4(raw.x, raw.y, raw.z, raw.w), db.u_is_t, codes, inv);
-            const bool seg_clean = stage(WA, codes, inv);
-            for (uint32_t t0 = 0; t0 < segk; t0 += U * 64u) {
-                Group g;
-                group_front(WA, sh, nb, segk, t0, seg_clean, g, n_bad);
-                if (!prefetched) { prefetch(); prefetched = true; }
-                if constexpr (MINLOC) {
-                    had |= back_deferred(g, i);
-                    if (qn >= KID_CQ_FLUSH) resolve_all(i, i & 63u); // the read stays open: more groups may follow
-                } else {
-                    group_back(g, final_t, vfrow);
-                }
-            }
-            __builtin_amdgcn_wave_barrier(); // strip is rewritten by the next segment / read
+                raw = *reinterpret_cast<const kid_u4 *>(b.bases + 16ull * ((b0 >> 4) + (lane < nchunks ? lane : 0u)));
+            run_segment(rd, i, sh, segk, raw, prefetch);
         }
-        if constexpr (MINLOC) {
-            n_lookups += (nk > 0 ? (uint32_t)nk : 0u) - n_bad;
-            if (!had) commit_zero(i); // (else the resolver commits it, now that it is closed)
-        } else {
-            finish_read(r, final_t, (nk > 0 ? (uint32_t)nk : 0u) - n_bad);
-        }
-        if (!prefetched) prefetch();
+        close_read(rd, r, i, nk > 0 ? (uint32_t)nk : 0u, prefetch);
     };
 
     auto fetch_desc = [&](uint32_t r, KidReadDesc &d) {
@@ -1212,34 +753,9 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
     auto short_read = [&](const uint32_t r, const uint32_t i, const uint64_t first, const int32_t nk, const kid_u4 st_raw,
                           auto &&prefetch) {
         if (nk > KID_SEG_KMERS) { any_long = true; rb_skip |= 1ull << (i & 63u); prefetch(); return; }
-        bool prefetched = false, had = false;
-        uint32_t final_t = 0;
-        uint32_t vfrow = 0, n_bad = 0;
-        if (nk > 0) {
-            const uint32_t sh = (uint32_t)first & 15u, segk = (uint32_t)nk, nb = segk + (uint32_t)k - 1;
-            uint32_t st_codes, st_inv;
-            kid_pack16(make_uint4(st_raw.x, st_raw.y, st_raw.z, st_raw.w), db.u_is_t, st_codes, st_inv);
-            const bool seg_clean = stage(WA, st_codes, st_inv);
-            for (uint32_t t0 = 0; t0 < segk; t0 += U * 64u) {
-                Group g;
-                group_front(WA, sh, nb, segk, t0, seg_clean, g, n_bad);
-                if (!prefetched) { prefetch(); prefetched = true; }
-                if constexpr (MINLOC) {
-                    had |= back_deferred(g, i);
-                    if (qn >= KID_CQ_FLUSH) resolve_all(i, i & 63u); // the read stays open: more groups may follow
-                } else {
-                    group_back(g, final_t, vfrow);
-                }
-            }
-            __builtin_amdgcn_wave_barrier(); // strip is rewritten by the next read
-        }
-        if constexpr (MINLOC) {
-            n_lookups += (nk > 0 ? (uint32_t)nk : 0u) - n_bad;
-            if (!had) commit_zero(i); // (else the resolver commits it, now that it is closed)
-        } else {
-            finish_read(r, final_t, (nk > 0 ? (uint32_t)nk : 0u) - n_bad);
-        }
-        if (!prefetched) prefetch();
+        Read rd;
+        if (nk > 0) run_segment(rd, i, (uint32_t)first & 15u, (uint32_t)nk, st_raw, prefetch);
+        close_read(rd, r, i, nk > 0 ? (uint32_t)nk : 0u, prefetch);
     };
     uint32_t reads_done = gw < b.n ? (uint32_t)((b.n - gw + nw - 1) / nw) : 0u; // the wave's strided share (the pair kernel counts its own)
     // ---- batches whose reads all fit one group (<= U*64 k-mers: Illumina reads): hand-pipelined pairs.
@@ -1632,516 +1148,5 @@ __global__ __launch_bounds__(512, (PAIRK == 2 && ROWS) ? KID_CLASSIFY_OCC_DUO_RO
     }
 }
 
-// ------------------------------------------------------------------ unit probes (parity tests)
-__global__ void kid_lookup_kernel(const KidDevDb db, const uint64_t *keys, uint64_t n, uint32_t *targets, uint32_t *probes)
-{
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        uint32_t slot, np;
-        targets[i] = kid_dev_lookup(db, keys[i], slot, np);
-        if (probes) probes[i] = np;
-    }
-}
-
-// Hashtable::integerHash (newkmer_10nx.cpp:189-197) as the device computes it
-__global__ void kid_fmix_kernel(const uint64_t *keys, uint64_t n, uint64_t *out)
-{
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-        out[i] = kid_fmix64(keys[i]);
-}
-
-__global__ void kid_msca_kernel(const KidDevDb db, const int32_t *x, const int32_t *y, uint64_t n, int32_t *out)
-{
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t a = (uint32_t)x[i], c = (uint32_t)y[i];
-        uint32_t r;
-        if (db.rows) {
-            uint4 ro;
-            r = kid_msca_rows(a, db.rows[a], c, db.rows[c], ro);
-        } else {
-            r = kid_msca_climb(db, a, c);
-        }
-        out[i] = (int32_t)r;
-    }
-}
-
-// process_qual, newkmer_10nx.cpp:714-760: the quality string of one read (len = length of its SEQUENCE, :716) ->
-// [start, stop].  A sequential scan by nature: one read per thread.
-__device__ __forceinline__ void kid_process_qual(const signed char *q, const int len, int &start, int &stop)
-{
-    start = 0;
-    stop = len - 1;
-    if (len <= 0) return;
-    while (q[start] < 49 && start < stop) start++;
-    while (q[stop] < 49 && stop > start) stop--;
-    if (start < stop - 4) {
-        int w = 0;
-        for (int i = 0; i < 4; i++) w += q[start + i] - 32;
-        while (w < 68 && start < stop - 4) { w += q[start + 4] - q[start]; start++; }
-    }
-    if (start < stop - 4) {
-        int w = 0;
-        for (int i = 0; i < 4; i++) w += q[stop - i] - 32;
-        while (w < 68 && start < stop - 4) { w += q[stop - 4] - q[stop]; stop--; }
-    }
-}
-
-__global__ void kid_trim_kernel(const uint8_t *quals, const uint64_t *offsets, uint64_t n, int k,
-                                int32_t *start_out, int32_t *stop_out, uint8_t *keep)
-{
-    for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
-        const int len = (int)(offsets[r + 1] - offsets[r]);
-        int start, stop;
-        kid_process_qual(reinterpret_cast<const signed char *>(quals + offsets[r]), len, start, stop);
-        start_out[r] = start;
-        stop_out[r] = stop;
-        keep[r] = (len > 0 && stop - start >= k) ? 1 : 0;
-    }
-}
-
-// A block of FASTQ text whose lines the host has found (kid_classify_fastq_async): process_qual + the ">= k" test
-// of :757 + the read descriptor, per record.  A record process_qual drops is not handed to process_read in the
-// reference, i.e. it is counted nowhere: the classify kernels see it as a read without k-mers (gcount[0]++), which
-// this kernel takes back (stats[5] counts them).  stats[8]: records whose quality line is shorter than the sequence
-// (qual.at() throws, :727).
-struct KidFastqRec {
-    uint32_t seq_off, seq_len, qual_off, qual_len; // byte offsets into the block's text
-};
-__global__ void kid_prepare_fastq_kernel(const uint8_t *text, const KidFastqRec *recs, uint64_t n, int k, KidReadDesc *desc,
-                                         int32_t *start_out, int32_t *stop_out, uint32_t *out_final, unsigned long long *stats,
-                                         unsigned long long *gcount, KidRareArgs *rare, uint32_t seq, int rebase)
-{
-    if (rebase && blockIdx.x == 0) kid_rebase(rare, desc, out_final, 0ull, 0u, 0);
-    uint32_t mx = 0, dropped = 0, bad = 0;
-    for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < n; r += (uint64_t)gridDim.x * blockDim.x) {
-        const KidFastqRec rc = recs[r];
-        int start = 0, stop = -1;
-        if (rc.qual_len < rc.seq_len) bad++;
-        else kid_process_qual(reinterpret_cast<const signed char *>(text + rc.qual_off), (int)rc.seq_len, start, stop);
-        const bool keep = rc.seq_len > 0 && rc.qual_len >= rc.seq_len && stop - start >= k;
-        KidReadDesc d;
-        d.first_base = (uint64_t)rc.seq_off + (uint64_t)(start > 0 ? start : 0);
-        d.n_kmers = keep ? stop - start + 1 - (k - 1) : 0;
-        d.pad = 0;
-        desc[r] = d;
-        start_out[r] = start;
-        stop_out[r] = stop;
-        if (!keep) dropped++;
-        if (d.n_kmers > 0 && (uint32_t)d.n_kmers > mx) mx = (uint32_t)d.n_kmers;
-    }
-    __shared__ uint32_t s_mx, s_dropped, s_bad;
-    if (threadIdx.x == 0) { s_mx = 0; s_dropped = 0; s_bad = 0; }
-    __syncthreads();
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t y = (uint32_t)__shfl_xor((int)mx, o);
-        mx = y > mx ? y : mx;
-        dropped += (uint32_t)__shfl_xor((int)dropped, o);
-        bad += (uint32_t)__shfl_xor((int)bad, o);
-    }
-    if ((threadIdx.x & 63u) == 0) {
-        if (mx) atomicMax(&s_mx, mx);
-        if (dropped) atomicAdd(&s_dropped, dropped);
-        if (bad) atomicAdd(&s_bad, bad);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long v = ((unsigned long long)seq << 32) | s_mx;
-        if (v > *reinterpret_cast<volatile unsigned long long *>(&rare->batch_max)) atomicMax(&rare->batch_max, v);
-        if (s_dropped) { atomicAdd(&gcount[0], 0ull - (unsigned long long)s_dropped); atomicAdd(&stats[5], (unsigned long long)s_dropped); }
-        if (s_bad) atomicAdd(&stats[8], (unsigned long long)s_bad);
-    }
-}
-
-// ------------------------------------------------------------------ table build on the GPU
-// Pass 1: every entry claims the first free cell on its probe path (same path
-// as Hashtable::add_kmer, newkmer_10nx.cpp:235-263) with a CAS on the ordinal
-// word.  Like the reference there is no key comparison: duplicates take
-// separate cells.  Entries with target 0 are skipped: in the reference they
-// leave their cell "empty" (value == 0), i.e. invisible to every lookup.
-// Pass 1: every entry claims a cell.  Reference geometry: the first free cell on the reference's
-// probe path (Hashtable::add_kmer, newkmer_10nx.cpp:235-263), claimed with a CAS on the ordinal
-// word; like the reference there is no key comparison, duplicates take separate cells.
-// Minimizer-localised geometry: the next free entry of the key's line (count in the header,
-// CAS), chaining into the following line when 7 entries are taken; the key's 16-bit fingerprint
-// goes into the header.  Entries with target 0 are skipped: in the reference they leave their
-// cell "empty" (value == 0), i.e. invisible to every lookup.
-__global__ void kid_build_insert_kernel(uint4 *table, uint32_t slot_mask, const uint64_t *keys, const uint32_t *targets,
-                                        uint64_t n, uint32_t ntar, unsigned long long *n_occupied, int k, uint32_t minloc,
-                                        uint32_t line_shift, uint32_t line_mask)
-{
-    for (uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; e < n; e += (uint64_t)gridDim.x * blockDim.x) {
-        const uint32_t t = targets[e];
-        if (t == 0) continue;
-        if (t >= ntar) { atomicAdd(n_occupied + 1, 1ull); continue; } // reported as KID_ERR_TARGET
-        const uint64_t key = keys[e];
-        if (minloc) {
-            uint32_t line = kid_minloc_line(kid_minimizer_of_key(key, k), line_shift);
-            const uint32_t fp = kid_key_fp(key);
-            for (;;) {
-                uint32_t *hdr = reinterpret_cast<uint32_t *>(table + (uint64_t)line * KID_LINE_CELLS);
-                uint32_t old = __hip_atomic_load(hdr + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                uint32_t cnt;
-                for (;;) {
-                    cnt = kid_hdr_count(old);
-                    if (cnt >= KID_HDR_FULL) break;
-                    const uint32_t seen = atomicCAS(hdr + 3, old, old + 0x10000u);
-                    if (seen == old) break;
-                    old = seen;
-                }
-                if (cnt < KID_LINE_ENTRIES) { // entry number cnt of this line is mine
-                    uint32_t *c = reinterpret_cast<uint32_t *>(table + (uint64_t)line * KID_LINE_CELLS + 1u + cnt);
-                    c[0] = (uint32_t)key;
-                    c[1] = (uint32_t)(key >> 32);
-                    c[2] = t;
-                    c[3] = (uint32_t)e + 1u;
-                    atomicOr(hdr + (cnt >> 1), fp << (16u * (cnt & 1u)));
-                    atomicAdd(n_occupied, 1ull);
-                    break;
-                }
-                atomicOr(hdr + 3, 1u << kid_ovf_bit(fp)); // pushed past this line: leave a trace for the lookups
-                line = (line + 1u) & line_mask; // cnt == 7 just became 8 (chain marker) or was 8 already
-            }
-            continue;
-        }
-        const uint32_t h = (uint32_t)kid_fmix64(key) & slot_mask;
-        uint32_t rp = 0, i = 0;
-        for (;;) {
-            const uint32_t idx = (h + rp) & slot_mask;
-            rp += ++i;
-            uint32_t *ordp = reinterpret_cast<uint32_t *>(table + idx) + 3;
-            if (atomicCAS(ordp, 0u, (uint32_t)e + 1u) == 0u) {
-                uint32_t *c = reinterpret_cast<uint32_t *>(table + idx);
-                c[0] = (uint32_t)key;
-                c[1] = (uint32_t)(key >> 32);
-                c[2] = t;
-                atomicAdd(n_occupied, 1ull);
-                break;
-            }
-        }
-    }
-}
-
-// Pass 2: the reference's lookup returns the FIRST-inserted copy of a key (earlier inserts sit
-// earlier on the path).  Pass 1 placed duplicate copies in arbitrary order, so every entry walks
-// its whole chain, finds the smallest ordinal among the cells holding its key and, unless that is
-// its own, turns ITS OWN cell into a tombstone (a key no lookup can ask for: keys are below 2^62).
-// Afterwards the first insert is the only copy a lookup can match, wherever it sits -- and the
-// ordinal it carries (cell word 3) names the key independently of the placement, which is what
-// the per-sample seen-bitmap is indexed by.  A tombstone keeps its cell occupied and its
-// fingerprint in the header, like the reference's unreachable duplicates keep theirs.  The first
-// insert is never touched, so concurrent walkers always see it; each thread writes one word of
-// its own cell only.
-__global__ void kid_build_firstwins_kernel(uint4 *table, uint32_t slot_mask, const uint64_t *keys, const uint32_t *targets,
-                                           uint64_t n, int k, uint32_t minloc, uint32_t line_shift, uint32_t line_mask)
-{
-    for (uint64_t e = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; e < n; e += (uint64_t)gridDim.x * blockDim.x) {
-        if (targets[e] == 0 || table == nullptr) continue;
-        const uint64_t key = keys[e];
-        uint32_t my_idx = 0, min_ord = 0xFFFFFFFFu, copies = 0;
-        if (minloc) {
-            uint32_t line = kid_minloc_line(kid_minimizer_of_key(key, k), line_shift);
-            for (;;) {
-                const uint32_t base = line * KID_LINE_CELLS;
-                const uint32_t w3 = reinterpret_cast<const uint32_t *>(table + base)[3];
-                const uint32_t cnt = kid_hdr_count(w3);
-                const uint32_t ne = cnt < KID_LINE_ENTRIES ? cnt : KID_LINE_ENTRIES;
-                for (uint32_t j = 0; j < ne; j++) {
-                    const uint32_t *c = reinterpret_cast<const uint32_t *>(table + base + 1u + j);
-                    if (c[0] == (uint32_t)key && c[1] == (uint32_t)(key >> 32)) {
-                        const uint32_t ord = c[3];
-                        if (ord == (uint32_t)e + 1u) my_idx = base + 1u + j;
-                        min_ord = ord < min_ord ? ord : min_ord;
-                        copies++;
-                    }
-                }
-                if (!kid_hdr_continues(w3, kid_key_fp(key))) break; // (every copy of this key left its trace on the way)
-                line = (line + 1u) & line_mask;
-            }
-        } else {
-            const uint32_t h = (uint32_t)kid_fmix64(key) & slot_mask;
-            uint32_t rp = 0, i = 0;
-            for (;;) {
-                const uint32_t idx = (h + rp) & slot_mask;
-                rp += ++i;
-                const uint32_t *c = reinterpret_cast<const uint32_t *>(table + idx);
-                const uint32_t ord = c[3];
-                if (ord == 0) break;
-                if (c[0] == (uint32_t)key && c[1] == (uint32_t)(key >> 32)) {
-                    if (ord == (uint32_t)e + 1u) my_idx = idx;
-                    min_ord = ord < min_ord ? ord : min_ord;
-                    copies++;
-                }
-            }
-        }
-        if (copies > 1 && min_ord != (uint32_t)e + 1u) reinterpret_cast<uint32_t *>(table + my_idx)[1] = KID_TOMBSTONE_HI;
-    }
-}
-
-// ------------------------------------------------------------------ the hit log -> seen-bitmap
-// The classify kernels append the entry ordinals of their hits to KID_LOG_SHARDS log regions.  Setting 2.5 M random
-// bits of a 13.6 MB bitmap costs one memory-side atomic each however it is done from the classify kernel; here the
-// entries are first sorted by bitmap piece (a counting sort: count, scan, scatter), then ONE workgroup per piece sets
-// its bits in LDS and ORs the piece into the bitmap as its only writer.  Run every few dozen launches (and before
-// anybody reads the bitmap), over everything logged since: ~16 bytes of traffic per logged hit + one pass over the bitmap.
-struct KidLogArgs {
-    const uint32_t *log;
-    const uint32_t *tail;
-    uint32_t cap;
-    uint32_t nbins;        // pieces of 2^KID_LOG_BIN_BITS bits
-    uint32_t *counts;      // [bin][workgroup]: entries of the bin in the workgroup's share of the log
-    uint32_t *bin_total;   // [bin]
-    uint32_t *sorted;
-    uint32_t *seen;
-    uint64_t seen_words;
-    unsigned long long *host_total; // mapped host memory: log places asked for per 1024 reads, as of this pass (the host paces the passes by it)
-    // Many hits per read (reads from genomes the database holds): neighbouring lookups name neighbouring bits, the
-    // resolver merges them over DPP and one atomic sets up to 16 -- cheaper than logging every hit and sorting the log
-    // (profiles/r03/dense_hits.txt: 15 hits per read 1-2 %, 60 hits 4.5 %, the builder-shaped database 6 %).  The
-    // pass decides: more than 8 log places per read of the `reads` it covers, and it takes the log out of the sample's
-    // argument blocks -- in stream order, in front of the next launch, without a trip to the host.
-    unsigned long long reads;
-    KidRareArgs *blocks[4];
-    unsigned int *off_flag;         // mapped host memory: set when the pass has switched the log off
-};
-// the share of the log a counting / scattering workgroup owns: region blockIdx / 16, 1/16 of its entries (whole
-// groups of 64 entries: a share starts on a 16-byte boundary)
-__device__ __forceinline__ void kid_log_share(const KidLogArgs &a, uint32_t &begin, uint32_t &end)
-{
-    const uint32_t per = KID_LOG_WGS / KID_LOG_SHARDS, sh = blockIdx.x / per, c = blockIdx.x % per;
-    const uint32_t t = a.tail[sh * 16u], filled = t < a.cap ? t : a.cap;
-    const uint32_t len = ((filled + per - 1u) / per + 63u) & ~63u;
-    begin = sh * a.cap + (c * len < filled ? c * len : filled);
-    end = sh * a.cap + ((c + 1u) * len < filled ? (c + 1u) * len : filled);
-}
-// every entry of [b0, b1) to f, four at a time (16-byte loads: these kernels are a stream over the log)
-template <class F>
-__device__ __forceinline__ void kid_log_for_each(const uint32_t *log, uint32_t b0, uint32_t b1, F &&f)
-{
-    const uint32_t n4 = (b1 - b0) >> 2;
-    const uint4 *p = reinterpret_cast<const uint4 *>(log + b0);
-    for (uint32_t i = threadIdx.x; i < n4; i += blockDim.x) {
-        const uint4 v = p[i];
-        if (v.x != KID_LOG_NONE) f(v.x);
-        if (v.y != KID_LOG_NONE) f(v.y);
-        if (v.z != KID_LOG_NONE) f(v.z);
-        if (v.w != KID_LOG_NONE) f(v.w);
-    }
-    for (uint32_t i = b0 + (n4 << 2) + threadIdx.x; i < b1; i += blockDim.x) {
-        const uint32_t e = log[i];
-        if (e != KID_LOG_NONE) f(e);
-    }
-}
-__global__ __launch_bounds__(256) void kid_seenlog_count_kernel(const KidLogArgs a)
-{
-    extern __shared__ uint32_t kid_lh[];
-    for (uint32_t i = threadIdx.x; i < a.nbins; i += blockDim.x) kid_lh[i] = 0;
-    __syncthreads();
-    uint32_t b0, b1;
-    kid_log_share(a, b0, b1);
-    kid_log_for_each(a.log, b0, b1, [&](const uint32_t e) { atomicAdd(&kid_lh[e >> KID_LOG_BIN_BITS], 1u); });
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < a.nbins; i += blockDim.x) a.counts[i * KID_LOG_WGS + blockIdx.x] = kid_lh[i];
-}
-// per bin: exclusive scan of the workgroups' counts (in place) and the bin's total
-__global__ __launch_bounds__(1024) void kid_seenlog_scan_kernel(const KidLogArgs a)
-{
-    __shared__ uint32_t part[KID_LOG_WGS];
-    uint32_t *c = a.counts + (size_t)blockIdx.x * KID_LOG_WGS;
-    const uint32_t v = c[threadIdx.x];
-    part[threadIdx.x] = v;
-    __syncthreads();
-    for (uint32_t o = 1; o < KID_LOG_WGS; o <<= 1) {
-        const uint32_t add = threadIdx.x >= o ? part[threadIdx.x - o] : 0u;
-        __syncthreads();
-        part[threadIdx.x] += add;
-        __syncthreads();
-    }
-    c[threadIdx.x] = part[threadIdx.x] - v;
-    if (threadIdx.x == KID_LOG_WGS - 1u) a.bin_total[blockIdx.x] = part[threadIdx.x];
-}
-// inclusive scan over the 64 lanes of a wave
-template <class T>
-__device__ __forceinline__ T kid_wave_incscan(T x)
-{
-    using S = typename std::conditional<sizeof(T) == 8, unsigned long long, int>::type; // (what __shfl_up moves)
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T y = (T)__shfl_up((S)x, (unsigned)o);
-        if ((int)(threadIdx.x & 63u) >= o) x += y;
-    }
-    return x;
-}
-// Exclusive scan over the 4 x 256 values of a workgroup of 256 threads, thread t holding values 4t .. 4t + 3 in x[]:
-// x[j] becomes the sum of everything before it; returns the sum up to and including the thread's own (thread 255: the
-// total).  wave_tot: LDS [4], the waves' totals afterwards; the caller's barrier comes before it is written again.
-template <class T>
-__device__ __forceinline__ T kid_block_exscan4(T (&x)[4], T *wave_tot)
-{
-    const uint32_t wv = threadIdx.x >> 6;
-    const T sum = x[0] + x[1] + x[2] + x[3], inc = kid_wave_incscan(sum);
-    if ((threadIdx.x & 63u) == 63u) wave_tot[wv] = inc;
-    __syncthreads();
-    T run = inc - sum;
-    for (uint32_t w = 0; w < wv; w++) run += wave_tot[w];
-#pragma unroll
-    for (int j = 0; j < 4; j++) { const T v = x[j]; x[j] = run; run += v; }
-    return run;
-}
-// where the bins start in `sorted`: exclusive scan of bin_total (<= 1024 bins) into LDS; returns the grand total
-__device__ __forceinline__ uint32_t kid_log_bin_bases(const KidLogArgs &a, uint32_t *bases /* nbins + 1 */)
-{
-    // (one wave does it: the totals are few)
-    if (threadIdx.x < 64u) {
-        uint32_t run = 0;
-        for (uint32_t i0 = 0; i0 < a.nbins; i0 += 64u) {
-            const uint32_t i = i0 + threadIdx.x;
-            const uint32_t v = i < a.nbins ? a.bin_total[i] : 0u, x = kid_wave_incscan(v);
-            if (i < a.nbins) bases[i] = run + x - v;
-            run += (uint32_t)__shfl((int)x, 63);
-        }
-        if (threadIdx.x == 0) bases[a.nbins] = run;
-    }
-    __syncthreads();
-    return bases[a.nbins];
-}
-// exclusive scan of v[0 .. n) (n <= 4 x blockDim) into out[0 .. n), by a workgroup of 256 threads; returns the total
-__device__ __forceinline__ uint32_t kid_block_exscan(const uint32_t *v, uint32_t *out, const uint32_t n, uint32_t *wave_tot /* [5] */)
-{
-    const uint32_t i0 = 4u * threadIdx.x;
-    uint32_t x[4];
-#pragma unroll
-    for (int j = 0; j < 4; j++) x[j] = i0 + j < n ? v[i0 + j] : 0u;
-    kid_block_exscan4(x, wave_tot);
-#pragma unroll
-    for (int j = 0; j < 4; j++) if (i0 + j < n) out[i0 + j] = x[j];
-    const uint32_t total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    __syncthreads();
-    return total;
-}
-// The log -> `sorted`, bin by bin.  A workgroup takes its share in tiles of KID_LOG_TILE entries and sorts a tile in LDS
-// first (count, scan, place), so that what goes out to memory are runs of neighbouring entries of one bin -- scattering
-// the entries one by one took 7 ps each (47 M partial-line writes per pass, profiles/r03/seen_log_first_kernel_stats.csv).
-#define KID_LOG_TILE 4096u
-__global__ __launch_bounds__(256) void kid_seenlog_scatter_kernel(const KidLogArgs a)
-{
-    extern __shared__ uint32_t kid_lh[]; // bin bases [nbins + 1], next place of this workgroup per bin [nbins], the tile's counts and offsets [2 nbins], the tile
-    const uint32_t nb = a.nbins;
-    uint32_t *bases = kid_lh, *next = bases + nb + 1u, *hist = next + nb, *toff = hist + nb, *stage = toff + nb;
-    __shared__ uint32_t wave_tot[5];
-    kid_log_bin_bases(a, bases);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        // (by the places ASKED for -- hits, header matches that were none, and what no longer fitted: a log that
-        // overflows holds fewer entries than there were hits.  Reported as ONE word, a rate: the host runs far ahead of
-        // the device, and a count would meet the wrong number of reads there)
-        unsigned long long asked = 0;
-        for (uint32_t i = 0; i < KID_LOG_SHARDS; i++) asked += a.tail[i * 16u];
-        if (a.host_total && a.reads) *a.host_total = ((asked << 10) / a.reads) | (1ull << 63);
-        if (a.reads && asked > 8ull * a.reads) {
-            for (int i = 0; i < 4; i++)
-                if (a.blocks[i]) a.blocks[i]->seen_log = nullptr;
-            if (a.off_flag) *a.off_flag = 1u;
-        }
-    }
-    for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) next[i] = bases[i] + a.counts[i * KID_LOG_WGS + blockIdx.x];
-    uint32_t b0, b1;
-    kid_log_share(a, b0, b1);
-    for (uint32_t t0 = b0; t0 < b1; t0 += KID_LOG_TILE) { // (workgroup-uniform)
-        const uint32_t n = b1 - t0 < KID_LOG_TILE ? b1 - t0 : KID_LOG_TILE;
-        for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) hist[i] = 0;
-        __syncthreads();
-        uint32_t e[KID_LOG_TILE / 256u], r[KID_LOG_TILE / 256u];
-#pragma unroll
-        for (uint32_t j = 0; j < KID_LOG_TILE / 256u; j++) {
-            const uint32_t i = j * 256u + threadIdx.x;
-            e[j] = i < n ? a.log[t0 + i] : KID_LOG_NONE;
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < KID_LOG_TILE / 256u; j++)
-            r[j] = e[j] != KID_LOG_NONE ? atomicAdd(&hist[e[j] >> KID_LOG_BIN_BITS], 1u) : 0u; // its rank among the tile's entries of its bin
-        __syncthreads();
-        const uint32_t tile_n = kid_block_exscan(hist, toff, nb, wave_tot);
-#pragma unroll
-        for (uint32_t j = 0; j < KID_LOG_TILE / 256u; j++)
-            if (e[j] != KID_LOG_NONE) stage[toff[e[j] >> KID_LOG_BIN_BITS] + r[j]] = e[j];
-        __syncthreads();
-        for (uint32_t p = threadIdx.x; p < tile_n; p += blockDim.x) { // neighbours in `stage` are neighbours in `sorted`
-            const uint32_t v = stage[p], bin = v >> KID_LOG_BIN_BITS;
-            a.sorted[next[bin] + (p - toff[bin])] = v;
-        }
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < nb; i += blockDim.x) next[i] += hist[i];
-        __syncthreads();
-    }
-}
-__global__ __launch_bounds__(1024) void kid_seenlog_apply_kernel(const KidLogArgs a)
-{
-    extern __shared__ uint32_t kid_lh[]; // 2^KID_LOG_BIN_BITS bits of the bitmap, then the bin bases
-    const uint32_t piece_words = 1u << (KID_LOG_BIN_BITS - 5);
-    uint32_t *piece = kid_lh, *bases = kid_lh + piece_words;
-    kid_log_bin_bases(a, bases);
-    const uint32_t e0 = bases[blockIdx.x], e1 = bases[blockIdx.x + 1u];
-    if (e0 == e1) return; // (workgroup-uniform)
-    for (uint32_t i = threadIdx.x; i < piece_words; i += blockDim.x) piece[i] = 0;
-    __syncthreads();
-    auto set = [&](const uint32_t v) { const uint32_t e = v & ((1u << KID_LOG_BIN_BITS) - 1u); atomicOr(&piece[e >> 5], 1u << (e & 31u)); };
-    // the bin's entries, 16 bytes per load between the first and the last 16-byte boundary
-    const uint32_t up = (e0 + 3u) & ~3u, a0 = up < e1 ? up : e1, a1 = a0 + ((e1 - a0) & ~3u);
-    for (uint32_t i = e0 + threadIdx.x; i < a0; i += blockDim.x) set(a.sorted[i]);
-    const uint4 *p4 = reinterpret_cast<const uint4 *>(a.sorted + a0);
-    for (uint32_t i = threadIdx.x; i < (a1 - a0) >> 2; i += blockDim.x) { const uint4 v = p4[i]; set(v.x); set(v.y); set(v.z); set(v.w); }
-    for (uint32_t i = a1 + threadIdx.x; i < e1; i += blockDim.x) set(a.sorted[i]);
-    __syncthreads();
-    const uint64_t w0 = (uint64_t)blockIdx.x * piece_words;
-    for (uint32_t i = threadIdx.x; i < piece_words; i += blockDim.x) {
-        const uint32_t v = piece[i];
-        if (v && w0 + i < a.seen_words) a.seen[w0 + i] |= v; // the only writer of this piece while the pass runs
-    }
-}
-
-// ------------------------------------------------------------------ ucount from the seen-bitmap
-// ucount[t] = number of distinct DB k-mers of target t seen in the sample
-// (newkmer_10nx.cpp:596-603), counted over the entry ordinals [w_begin*32, w_end*32): bit o of the
-// bitmap = "the key first inserted as entry o was hit", ord_target[o] = that entry's target
-template <bool HIST>
-__global__ void kid_ucount_kernel(const uint32_t *seen, uint64_t w_begin, uint64_t w_end, const uint32_t *ord_target,
-                                  unsigned long long *ucount, uint32_t ntar)
-{
-    // the bitmap is almost empty: stream it 16 bytes per lane and only look inside non-zero words;
-    // counts go to a per-workgroup LDS histogram first (millions of hits land on a few thousand targets)
-    extern __shared__ uint32_t kid_uhist[];
-    if (HIST) {
-        for (uint32_t i = threadIdx.x; i < ntar; i += blockDim.x) kid_uhist[i] = 0;
-        __syncthreads();
-    }
-    const uint64_t q_begin = w_begin >> 2, q_end = w_end >> 2; // callers pass 128-cell aligned ranges
-    const uint4 *seen4 = reinterpret_cast<const uint4 *>(seen);
-    for (uint64_t q = q_begin + blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; q < q_end; q += (uint64_t)gridDim.x * blockDim.x) {
-        const uint4 v = seen4[q];
-        if ((v.x | v.y | v.z | v.w) == 0) continue;
-        const uint32_t words[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            uint32_t bits = words[i];
-            while (bits) {
-                const uint32_t bpos = (uint32_t)__builtin_ctz(bits);
-                bits &= bits - 1;
-                const uint32_t t = ord_target[(q * 4ull + (uint64_t)i) * 32ull + bpos];
-                if (HIST) atomicAdd(&kid_uhist[t], 1u);
-                else atomicAdd(&ucount[t], 1ull);
-            }
-        }
-    }
-    if (HIST) {
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < ntar; i += blockDim.x) {
-            const uint32_t c = kid_uhist[i];
-            if (c) atomicAdd(&ucount[i], (unsigned long long)c);
-        }
-    }
-}
-
-__global__ void kid_or_kernel(uint32_t *dst, const uint32_t *src, uint64_t nwords)
-{
-    for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < nwords; i += (uint64_t)gridDim.x * blockDim.x)
-        dst[i] |= src[i];
-}
+#include "kid_probes.hip.h"
+#include "kid_insert.hip.h"

@@ -1,4 +1,4 @@
-// kid_long.hip.h -- very long records (FASTA contigs classified whole; KidLong* of kid_kernels.hip.h).
+// kid_long.hip.h -- very long records (FASTA contigs classified whole; KidLong* of kid_table.hip.h).
 // A record is one left fold over its hits (newkmer_10nx.cpp:588-595; msca is not associative), which the classify
 // kernels run inside ONE wave: 9.7 ms per megabase when the batch holds few records.  When the host sees few long
 // records in a batch it hands them to two kernels instead:

@@ -109,12 +109,7 @@ __device__ __forceinline__ void kid_jump_fold(const KidDevDb &db, uint32_t tgt, 
         if (!ch) break;
         const int jj = __builtin_ctzll(ch);
         uf = (uint32_t)__builtin_amdgcn_readlane((int)rj, jj);
-        if (ROWS) {
-            ufr.x = (uint32_t)__builtin_amdgcn_readlane((int)roj.x, jj);
-            ufr.y = (uint32_t)__builtin_amdgcn_readlane((int)roj.y, jj);
-            ufr.z = (uint32_t)__builtin_amdgcn_readlane((int)roj.z, jj);
-            ufr.w = (uint32_t)__builtin_amdgcn_readlane((int)roj.w, jj);
-        }
+        if (ROWS) ufr = kid_row_of_lane(roj, jj);
         rem &= jj >= 63 ? 0ull : ~((2ull << jj) - 1ull);
     }
 }

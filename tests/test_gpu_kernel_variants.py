@@ -26,8 +26,8 @@ ALL_VARIANTS = ML_VARIANTS + REF_VARIANTS
 assert len(set(ALL_VARIANTS)) == 32
 # k-mers per read for each loop (a host batch goes to the loop of its longest read)
 NKS = {1: [1, 64, 65, 128], 2: [129, 256, 200], 0: [257, 961, 400], "ref": [1, 64, 128, 129, 256, 257, 961]}
-# dispatch limits, derived from the LDS layout (kid_kernels.hip.h): (hist words + 8 waves * per-wave words) * 4 + 32
-# <= 40 KiB, hist words = ceil(ntar / 2) rounded up to 4 (two 16-bit counters) on the minimizer-localised table, ntar
+# dispatch limits, derived from the LDS layout (KidWaveLds<>::total in kid_kernels.hip.h): (hist words + 8 waves *
+# per-wave words) * 4 + 32 <= 40 KiB, hist words = ceil(ntar / 2) rounded up to 4 (two 16-bit counters) on the minimizer-localised table, ntar
 # rounded up to 4 on the reference placement
 PAIR_LDS_WORDS, GEN_ML_LDS_WORDS, WAVE_LDS_WORDS = 820, 792, 104
 LIM_PAIR_HIST, LIM_GEN_ML_HIST, LIM_GEN_REF_HIST = 7344, 7792, 9400
@@ -278,6 +278,33 @@ def test_fixed_layout_on_device_per_loop(dbs, pk):
     assert np.array_equal(d_out.cpu().numpy().view(np.uint32), exp)
     assert_counters(s, os_)
     assert (exp > 1).sum() > n // 4
+    s.close()
+
+
+# ------------------------------------------------------------------ 1b. the tapered shares at their edges
+@pytest.mark.parametrize("n", [1, 7, 9, 17, 24, 65, 129, 1000])
+@pytest.mark.parametrize("pk", [1, 2, 0], ids=lambda v: LOOPS[v])
+def test_tapered_shares_at_their_edges(dbs, pk, n):
+    """Batches of exactly n reads (no spacer reads) of one length per loop.  The grid has ceil(n / 8) workgroups, at most
+    16 per CU: n = 1 .. 24 gives one, two and three of them, so the first half of the grid (the KID_TAPER shares) is
+    empty or one workgroup and the grid is odd; an odd n ends a share of the pair loop on a phantom read; an n that is
+    no multiple of 64 ends a wave on a partial block of results; 1000 reads leave waves at the end without any."""
+    variant = (1, 1, 1, 30, pk)
+    d = dbs(*shape_of(1, 1, 1, 30))
+    nk = {1: 64, 2: 200, 0: 400}[pk]
+    assert nk in NKS[pk]
+    reads = d.reads([nk], n)
+    data = np.concatenate(reads)                       # reads of nk + 29 bases: starts on every byte offset mod 16
+    off = np.arange(n + 1, dtype=np.uint64) * np.uint64(nk + d.k - 1)
+    os_, exp = oracle_run(d, data, off)
+    s = d.db.sample()
+    got = s.classify(data, off)
+    assert s.kernel_variants() == {variant}
+    assert got.size == n and np.array_equal(got, exp), "final targets differ from the oracle in %d reads" % int((got != exp).sum())
+    assert_counters(s, os_)
+    assert s.stats()["reads"] == n
+    if n >= 17:
+        assert os_.stats()["hits"] > n                 # real hits and LCA folds
     s.close()
 
 

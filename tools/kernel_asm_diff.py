@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Which kernels of two device-only assembly listings (hipcc -S --cuda-device-only of kid_api.hip) have textually
 identical bodies.  A body = the lines between a kernel's label and its .Lfunc_end; the function ordinal in local labels
-(.LBB<n>_) is dropped, since it moves with a kernel's place in the file.
+(.LBB<n>_, and BB<n>_ in the comments behind them, whose column moves with the ordinal's width) is dropped, since it moves
+with a kernel's place in the file.
 
   python3 tools/kernel_asm_diff.py parent.s branch.s"""
 import hashlib
@@ -18,7 +19,7 @@ def bodies(path):
             cur, buf = m.group(1), []
         elif cur is not None:
             if line.startswith(".Lfunc_end"):
-                out[cur] = re.sub(r"\.LBB\d+_", ".LBB_", "".join(buf))
+                out[cur] = re.sub(r"[ \t]+;", " ;", re.sub(r"BB\d+_", "BB_", "".join(buf)))
                 cur = None
             else:
                 buf.append(line)
