@@ -9,16 +9,12 @@
 // Everything is a function of the two multisets: a permutation inside a mate changes nothing, an exchange of the mates
 // exchanges call_1 and call_2.
 //
-// Work split: that of kid_vote_kernel by the fragment's total m; a wave takes 64 consecutive fragments.
-//   m <= KID_VOTE_LANE_HITS   a lane; m <= KID_VOTE_WAVE_HITS the whole wave.  A fragment with p = 0 or q = 0 is a read: its
-//                             per-mate calls are 0 and call (the wave takes it with kid_vote_wave; the lanes of a wave
-//                             stay on one path whatever their p).  Otherwise ONE pairwise pass feeds three best sets.
-//                             While candidate i is tested against all m hits, "t_j is t_i or an ancestor" is counted
-//                             twice: over the span (P in the fragment) and over the j of i's own mate (P in that mate);
-//                             and two duplicate flags are kept: an earlier copy in the span, an earlier copy in the own
-//                             mate.  The candidate then enters the span's set with the first pair and its mate's set
-//                             with the second (kid_vote_merge); the wave merges each of the three sets once.  The
-//                             per-mate sets need no climb: call_1 and call_2 are their LCAs.
+// Work split: that of kid_vote_kernel by the fragment's total m (the loop of kid_calls_run, over the fragments of the CSR).
+//   m <= KID_VOTE_LANE_HITS   a lane; m <= KID_VOTE_WAVE_HITS the whole wave.  ONE pairwise pass feeds three best sets: the
+//                             MATES form of kid_vote_lane / kid_vote_wave (kid_votes.hip.h).  A fragment with p = 0 or
+//                             q = 0 is a read: its per-mate calls are 0 and call.  A lane gets that from the MATES pass
+//                             itself (the other mate's set is the span's, the empty mate's stays empty); the wave takes
+//                             the pass without MATES for such a fragment and copies call (kid_fragment_vote_one_mate)
 //   more                      the fragment's index goes to the list; kid_fragment_vote_big_kernel, queued behind, takes
 //                             it with one workgroup over its row: stages 1-3 and 5 of kid_vote_big_kernel
 //                             (kid_vote_big_best, kid_vote_big_clear) once per mate span when both hold hits, then
@@ -32,89 +28,6 @@ struct KidFragmentVote { // = kid_fragment_vote (include/kmer_id_amd.h)
     uint32_t call, confident, n_kmers, n_hits, p_best, n_best, s_call, s_confident, call_1, call_2;
 };
 
-// ---- one lane, one fragment of at most KID_VOTE_LANE_HITS hits (any p <= m: an empty mate's set stays empty)
-template <bool ROWS>
-__device__ __forceinline__ void kid_fragment_vote_lane(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t p, const KidSupportRule &rule,
-                                                       KidVote &res, uint32_t &call_1, uint32_t &call_2)
-{
-    const uint4 none = make_uint4(0, 0, 0, 0);
-    uint32_t best = 0, nb = 0, call = 0, best1 = 0, nb1 = 0, best2 = 0, nb2 = 0;
-    uint4 cr = none, cr1 = none, cr2 = none;
-    call_1 = call_2 = 0;
-    for (uint32_t i = 0; i < m; i++) {
-        const uint32_t ti = kid_support_target(db, h[i].target);
-        const uint4 ri = ROWS ? db.rows[ti] : none;
-        const bool first = i < p; // candidate i is of mate 1: its own mate is [0, p), else [p, m)
-        uint32_t ps = 0, pm = 0;
-        bool dup = false, dupm = false;
-        for (uint32_t j = 0; j < m; j++) {
-            const uint32_t tj = kid_support_target(db, h[j].target);
-            const bool own = (j < p) == first;
-            const bool same = tj == ti && j < i;
-            const uint32_t under = kid_vote_under<ROWS>(db, ti, ri, tj, ROWS ? db.rows[tj] : none) ? 1u : 0u;
-            dup = dup || same;
-            dupm = dupm || (same && own);
-            ps += under;
-            pm += own ? under : 0u;
-        }
-        kid_vote_merge<ROWS>(db, best, nb, call, cr, ps, dup ? 0u : 1u, ti, ri);
-        kid_vote_merge<ROWS>(db, best1, nb1, call_1, cr1, pm, first && !dupm ? 1u : 0u, ti, ri);
-        kid_vote_merge<ROWS>(db, best2, nb2, call_2, cr2, pm, !first && !dupm ? 1u : 0u, ti, ri);
-    }
-    res.p_best = best;
-    res.n_best = nb;
-    kid_vote_climb_lane<ROWS>(db, h, m, call, cr, rule, res);
-}
-
-// ---- the whole wave, one fragment of at most KID_VOTE_WAVE_HITS hits with 0 < p < m (every argument wave-uniform; so
-// is the result)
-template <bool ROWS>
-__device__ __forceinline__ void kid_fragment_vote_wave(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t p, const KidSupportRule &rule,
-                                                       uint32_t lane, KidVote &res, uint32_t &call_1, uint32_t &call_2)
-{
-    const uint4 none = make_uint4(0, 0, 0, 0);
-    uint32_t best = 0, nb = 0, call = 0, best1 = 0, nb1 = 0, best2 = 0, nb2 = 0;
-    uint4 cr = none, cr1 = none, cr2 = none;
-    call_1 = call_2 = 0;
-    for (uint32_t c0 = 0; c0 < m; c0 += 64u) { // a tile of 64 candidates, one per lane
-        const bool valid = lane < m - c0;
-        const uint32_t i = c0 + lane;
-        const uint32_t ti = valid ? kid_support_target(db, h[i].target) : 1u;
-        const uint4 ri = ROWS ? db.rows[ti] : none;
-        const bool first = i < p;
-        uint32_t ps = 0, pm = 0;
-        bool dup = false, dupm = false;
-        for (uint32_t j0 = 0; j0 < m; j0 += 64u) { // against all m hits, 64 at a time
-            const uint32_t nj = m - j0 < 64u ? m - j0 : 64u;
-            const uint32_t tj = lane < nj ? kid_support_target(db, h[j0 + lane].target) : 1u;
-            const uint4 rj = ROWS ? db.rows[tj] : none;
-            for (uint32_t q = 0; q < nj; q++) {
-                const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tj, (int)q);
-                const uint4 r = ROWS ? kid_vote_readlane(rj, (int)q) : none;
-                if (valid) {
-                    const uint32_t j = j0 + q;
-                    const bool own = (j < p) == first;
-                    const bool same = t == ti && j < i;
-                    const uint32_t under = kid_vote_under<ROWS>(db, ti, ri, t, r) ? 1u : 0u;
-                    dup = dup || same;
-                    dupm = dupm || (same && own);
-                    ps += under;
-                    pm += own ? under : 0u;
-                }
-            }
-        }
-        kid_vote_merge<ROWS>(db, best, nb, call, cr, ps, valid && !dup ? 1u : 0u, ti, ri);
-        kid_vote_merge<ROWS>(db, best1, nb1, call_1, cr1, pm, valid && first && !dupm ? 1u : 0u, ti, ri);
-        kid_vote_merge<ROWS>(db, best2, nb2, call_2, cr2, pm, valid && !first && !dupm ? 1u : 0u, ti, ri);
-    }
-    kid_vote_wave_merge<ROWS>(db, best, nb, call, cr);
-    kid_vote_wave_merge<ROWS>(db, best1, nb1, call_1, cr1);
-    kid_vote_wave_merge<ROWS>(db, best2, nb2, call_2, cr2);
-    res.p_best = best;
-    res.n_best = nb;
-    kid_vote_climb_wave<ROWS>(db, h, m, call, cr, rule, lane, res);
-}
-
 // a fragment with one mate's hits alone: its per-mate calls from the span's
 __device__ __forceinline__ void kid_fragment_vote_one_mate(uint32_t p, uint32_t call, uint32_t &call_1, uint32_t &call_2)
 {
@@ -123,7 +36,9 @@ __device__ __forceinline__ void kid_fragment_vote_one_mate(uint32_t p, uint32_t 
 }
 
 // tally.fastq_desc: the descriptors of the 2 F reads; a fragment is counted when at least one of its mates was kept.
-// big.list holds fragment indexes (uint32[n_fragments]).
+// big.list holds fragment indexes (uint32[n_fragments]).  The loop is that of kid_calls_run (kid_calls.hip.h) over the
+// fragments of the CSR, written out: on the driver the <true, true, true> form went from 79 to 83 VGPRs and from 6 to 5
+// waves per SIMD (-Rpass-analysis=kernel-resource-usage), so this kernel stays off it.
 template <bool ROWS, bool TALLY, bool DEPTH>
 __global__ __launch_bounds__(256) void kid_fragment_vote_kernel(const KidDevDb db, const uint64_t *hit_offsets, const KidHit *hits,
                                                                  const uint32_t *n_kmers, uint64_t n_fragments, const KidSupportRule rule,
@@ -136,8 +51,8 @@ __global__ __launch_bounds__(256) void kid_fragment_vote_kernel(const KidDevDb d
         const uint64_t f = f0 + lane;
         const bool have = f < n_fragments;
         uint64_t h0 = 0;
-        uint32_t p = 0, call_1 = 0, call_2 = 0;
-        KidVote res = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+        uint32_t p = 0;
+        KidFragmentVote res = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
         if (have) {
             h0 = hit_offsets[2u * f];
             p = (uint32_t)(hit_offsets[2u * f + 1] - h0);
@@ -152,8 +67,7 @@ __global__ __launch_bounds__(256) void kid_fragment_vote_kernel(const KidDevDb d
         if (TALLY)
             counted = have && !later && (!tally.fastq_desc || tally.fastq_desc[2u * f].n_kmers > 0 || tally.fastq_desc[2u * f + 1].n_kmers > 0);
         if (m > 0 && m <= KID_VOTE_LANE_HITS) { // (one path for the 64 lanes, whatever their p: a branch on it would run both)
-            kid_fragment_vote_lane<ROWS>(db, hits + h0, m, p, rule, res, call_1, call_2);
-            if (p == 0 || p == m) kid_fragment_vote_one_mate(p, res.call, call_1, call_2);
+            kid_vote_lane<ROWS, true>(db, hits + h0, m, p, rule, res);
             if (TALLY && counted && res.confident > 0)
                 for (uint32_t i = 0; i < m; i++) kid_support_tally_hit<DEPTH>(tally, hits[h0 + i]);
         }
@@ -164,21 +78,19 @@ __global__ __launch_bounds__(256) void kid_fragment_vote_kernel(const KidDevDb d
             const KidHit *wh = hits + (uint64_t)__shfl((unsigned long long)h0, j);
             const uint32_t wm = (uint32_t)__builtin_amdgcn_readlane((int)m, j);
             const uint32_t wp = (uint32_t)__builtin_amdgcn_readlane((int)p, j);
-            KidVote w = {0u, 0u, (uint32_t)__builtin_amdgcn_readlane((int)res.n_kmers, j), wm, 0u, 0u, 0u, 0u};
-            uint32_t w1 = 0, w2 = 0;
+            KidFragmentVote w = {0u, 0u, (uint32_t)__builtin_amdgcn_readlane((int)res.n_kmers, j), wm, 0u, 0u, 0u, 0u, 0u, 0u};
             if (wp == 0 || wp == wm) {
-                kid_vote_wave<ROWS>(db, wh, wm, rule, lane, w);
-                kid_fragment_vote_one_mate(wp, w.call, w1, w2);
+                kid_vote_wave<ROWS, false>(db, wh, wm, 0u, rule, lane, w);
+                kid_fragment_vote_one_mate(wp, w.call, w.call_1, w.call_2);
             } else {
-                kid_fragment_vote_wave<ROWS>(db, wh, wm, wp, rule, lane, w, w1, w2);
+                kid_vote_wave<ROWS, true>(db, wh, wm, wp, rule, lane, w);
             }
             if (TALLY && w.confident > 0 && ((__ballot(counted) >> j) & 1ull))
                 for (uint32_t c0 = 0; c0 < wm; c0 += 64u)
                     if (lane < wm - c0) kid_support_tally_hit<DEPTH>(tally, wh[c0 + lane]);
-            if (lane == (uint32_t)j) { res = w; call_1 = w1; call_2 = w2; }
+            if (lane == (uint32_t)j) res = w;
         }
-        if (have && !later && out)
-            out[f] = KidFragmentVote{res.call, res.confident, res.n_kmers, res.n_hits, res.p_best, res.n_best, res.s_call, res.s_confident, call_1, call_2};
+        if (have && !later && out) out[f] = res;
         if (TALLY) {
             const uint64_t zeros = __ballot(counted && res.confident == 0);
             if (lane == 0 && zeros) atomicAdd(&tally.gcount[0], (unsigned long long)__popcll(zeros));

@@ -10,15 +10,13 @@
 // msca is not associative, so final is not msca(final_1, final_2) in general: it is one left fold over the m hits that
 // continues from final_1 into mate 2's hits.
 //
-// Work split: that of kid_support_kernel.  A wave takes 64 consecutive fragments; a lane takes a fragment of at most
-// KID_SUPPORT_LANE_HITS hits in total; larger fragments are taken by the whole wave one after the other.  The six fields
-// come from kid_support_lane / kid_support_wave over the whole span.  At the mate boundary the kernel takes the route of
-// three folds: the span's (inside kid_support_*), mate 1's and mate 2's, the last two with kid_jump_fold in chunks of 64
-// counted from each mate's own first hit, so the boundary never falls inside a chunk.  A fragment with p = 0 or q = 0 has
-// its per-mate folds from the span's (0 and final) and folds once.
-// Pure and without atomics: byte-identical across runs.  The TALLY variant counts the batch into a sample:
-// gcount[confident]++ once per counted fragment, and for fragments with confident > 0 kid_support_tally_hit on every hit
-// of both mates (seen bit, and depth[entry]++ in the DEPTH form: a k-mer present in both mates adds 2).
+// Work split: that of kid_support_kernel by the fragment's hits in total.  The
+// six fields come from kid_support_lane / kid_support_wave over the whole span.  At the mate boundary the kernel takes the
+// route of three folds: the span's (inside kid_support_*), mate 1's and mate 2's, the last two (kid_fold_wave) in chunks of
+// 64 counted from each mate's own first hit, so the boundary never falls inside a chunk.  A fragment with p = 0 or q = 0
+// has its per-mate folds from the span's (0 and final) and folds once.
+// Pure and without atomics: byte-identical across runs.  The TALLY variant counts every hit of both mates (in the DEPTH
+// form a k-mer present in both mates adds 2).
 #pragma once
 #include "kid_support.hip.h"
 
@@ -26,41 +24,9 @@ struct KidFragment { // = kid_fragment (include/kmer_id_amd.h)
     uint32_t final_t, confident, n_kmers, n_hits, s_final, s_confident, final_1, final_2;
 };
 
-// one lane: the left fold of m hits (m <= KID_SUPPORT_LANE_HITS)
-template <bool ROWS>
-__device__ __forceinline__ uint32_t kid_fragment_fold_lane(const KidDevDb &db, const KidHit *h, uint32_t m)
-{
-    uint32_t f = 0;
-    uint4 fr = make_uint4(0, 0, 0, 0);
-    for (uint32_t i = 0; i < m; i++) {
-        const uint32_t t = kid_support_target(db, h[i].target);
-        if (ROWS) {
-            const uint4 row = db.rows[t];
-            if (f == 0) { f = t; fr = row; }
-            else { uint4 ro; f = kid_msca_rows(t, row, f, fr, ro); fr = ro; }
-        } else {
-            f = f == 0 ? t : kid_msca_climb(db, t, f);
-        }
-    }
-    return f;
-}
-
-// the whole wave: the left fold of m hits (every argument wave-uniform; so is the result)
-template <bool ROWS>
-__device__ __forceinline__ uint32_t kid_fragment_fold_wave(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t lane)
-{
-    uint32_t uf = 0;
-    uint4 ufr = make_uint4(0, 0, 0, 0);
-    for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
-        const uint32_t n = m - c0 < 64u ? m - c0 : 64u;
-        const uint32_t tgt = lane < n ? kid_support_target(db, h[(uint64_t)c0 + lane].target) : 0u;
-        uint4 row = make_uint4(0, 0, 0, 0);
-        if (ROWS && tgt) row = db.rows[tgt];
-        kid_jump_fold<ROWS>(db, tgt, row, n >= 64u ? ~0ull : ((1ull << n) - 1ull), uf, ufr);
-    }
-    return uf;
-}
-
+// The loop is that of kid_calls_run (kid_calls.hip.h) over the fragments of an interleaved CSR, written out as it was: on the
+// driver the kernel lay up to 0.6 % above the timing rule on the hit-dense workload in both samples
+// (profiles/call_kernels/ab_parent_vs_branch.txt).  The per-mate folds are the shared kid_fold_lane / kid_fold_wave.
 // tally.fastq_desc: the descriptors of the 2 F reads; a fragment is counted when at least one of its mates was kept
 template <bool ROWS, bool TALLY, bool DEPTH>
 __global__ __launch_bounds__(256) void kid_fragment_kernel(const KidDevDb db, const uint64_t *hit_offsets, const KidHit *hits,
@@ -75,6 +41,7 @@ __global__ __launch_bounds__(256) void kid_fragment_kernel(const KidDevDb db, co
         uint64_t h0 = 0;
         uint32_t p = 0, final_1 = 0, final_2 = 0;
         KidSupport res = {0u, 0u, 0u, 0u, 0u, 0u};
+        uint4 fr; // (the per-mate folds' rows: unused)
         if (have) {
             h0 = hit_offsets[2u * f];
             p = (uint32_t)(hit_offsets[2u * f + 1] - h0);
@@ -90,8 +57,8 @@ __global__ __launch_bounds__(256) void kid_fragment_kernel(const KidDevDb db, co
             if (p == 0) final_2 = res.final_t;
             else if (p == m) final_1 = res.final_t;
             else {
-                final_1 = kid_fragment_fold_lane<ROWS>(db, hits + h0, p);
-                final_2 = kid_fragment_fold_lane<ROWS>(db, hits + h0 + p, m - p);
+                final_1 = kid_fold_lane<ROWS>(db, hits + h0, p, fr);
+                final_2 = kid_fold_lane<ROWS>(db, hits + h0 + p, m - p, fr);
             }
             if (TALLY && counted && res.confident > 0)
                 for (uint32_t i = 0; i < m; i++) kid_support_tally_hit<DEPTH>(tally, hits[h0 + i]);
@@ -109,8 +76,8 @@ __global__ __launch_bounds__(256) void kid_fragment_kernel(const KidDevDb db, co
             if (wp == 0) w2 = w.final_t;
             else if (wp == wm) w1 = w.final_t;
             else {
-                w1 = kid_fragment_fold_wave<ROWS>(db, wh, wp, lane);
-                w2 = kid_fragment_fold_wave<ROWS>(db, wh + wp, wm - wp, lane);
+                w1 = kid_fold_wave<ROWS>(db, wh, wp, lane, fr);
+                w2 = kid_fold_wave<ROWS>(db, wh + wp, wm - wp, lane, fr);
             }
             if (TALLY && w.confident > 0 && ((__ballot(counted) >> j) & 1ull))
                 for (uint32_t c0 = 0; c0 < wm; c0 += 64u)

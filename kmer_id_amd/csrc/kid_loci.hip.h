@@ -32,7 +32,7 @@
 // Behind the best key every regime passes over the participants once more for n_org and the chain's ends.
 // No atomics but the list's counter; nothing is written outside `out`, the list and its counter.
 #pragma once
-#include "kid_hits.hip.h"
+#include "kid_calls.hip.h"
 
 #define KID_LOCI_LANE_HITS 8u    // a read with more hits than this is taken by the whole wave
 #define KID_LOCI_WAVE_HITS 256u  // ... and one with more than this by a workgroup of kid_loci_big_kernel
@@ -241,37 +241,28 @@ __device__ __forceinline__ void kid_loci_wave(const KidLociSites &s, const KidHi
     kid_loci_settle(top, e, res);
 }
 
+struct KidLociMethod {
+    typedef KidLocus Result;
+    static constexpr uint32_t lane_hits = KID_LOCI_LANE_HITS, wave_hits = KID_LOCI_WAVE_HITS;
+    const KidLociSites &sites;
+    static __device__ __forceinline__ Result empty(uint32_t n_kmers, uint32_t m) { return Result{0u, 0u, 0u, 0u, 0u, m, n_kmers, 0u, 0u, 0u}; }
+    template <class Unit>
+    __device__ __forceinline__ void lane(const KidHit *h, const Unit &un, Result &res) const
+    {
+        kid_loci_lane(sites, h, un.m, res);
+    }
+    template <class Unit>
+    __device__ __forceinline__ void wave(const KidHit *h, uint32_t m, const Unit &, int, uint32_t lane, Result &res) const
+    {
+        kid_loci_wave(sites, h, m, lane, res);
+    }
+};
+
 __global__ __launch_bounds__(256) void kid_loci_kernel(const uint64_t *hit_offsets, const KidHit *hits, const uint32_t *n_kmers,
                                                         uint64_t n_reads, const KidLociSites sites, KidLocus *out, const KidLociBig big)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
-    for (uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; r0 < n_reads; r0 += n_waves * 64u) {
-        const uint64_t r = r0 + lane;
-        const bool have = r < n_reads;
-        uint64_t h0 = 0;
-        KidLocus res = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-        if (have) {
-            h0 = hit_offsets[r];
-            res.n_hits = (uint32_t)(hit_offsets[r + 1] - h0);
-            res.n_kmers = n_kmers[r];
-        }
-        const uint32_t m = res.n_hits;
-        const bool later = m > KID_LOCI_WAVE_HITS; // kid_loci_big_kernel's: nothing is written for it here
-        if (later) big.list[atomicAdd(big.n_list, 1u)] = (uint32_t)r;
-        if (m > 0 && m <= KID_LOCI_LANE_HITS) kid_loci_lane(sites, hits + h0, m, res);
-        uint64_t wide = __ballot(m > KID_LOCI_LANE_HITS && !later);
-        while (wide) { // the reads of the 64 with more hits: the whole wave, one after the other
-            const int j = __builtin_ctzll(wide);
-            wide &= wide - 1ull;
-            const KidHit *wh = hits + (uint64_t)__shfl((unsigned long long)h0, j);
-            const uint32_t wm = (uint32_t)__builtin_amdgcn_readlane((int)m, j);
-            KidLocus w = {0u, 0u, 0u, 0u, 0u, wm, (uint32_t)__builtin_amdgcn_readlane((int)res.n_kmers, j), 0u, 0u, 0u};
-            kid_loci_wave(sites, wh, wm, lane, w);
-            if (lane == (uint32_t)j) res = w;
-        }
-        if (have && !later) out[r] = res;
-    }
+    kid_calls_run<false, false>(KidCsrUnits<KidLocus>{hit_offsets, hits, n_kmers, n_reads, out, big.list, big.n_list},
+                                KidLociMethod{sites}, KidSupportTally());
 }
 
 // ------------------------------------------------------------------ reads of more than KID_LOCI_WAVE_HITS hits

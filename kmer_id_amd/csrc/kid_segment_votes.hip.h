@@ -44,69 +44,12 @@ struct KidSegmentVoteBig {
     uint64_t list_cap;
 };
 
-// pos and n_pos of segment s of read r
-__device__ __forceinline__ void kid_segment_votes_place(const KidSegmentsIn &a, const KidSegGeom &g, uint64_t r, uint64_t s, const KidReadDesc &d,
-                                                        uint64_t &q_lo, uint64_t &q_hi, uint32_t &pos, uint32_t &n_pos)
-{
-    const uint64_t P = (uint64_t)(uint32_t)d.n_kmers;
-    q_lo = (s - a.seg_offsets[r]) * g.seg_step;
-    q_hi = P - q_lo > g.seg_len ? q_lo + g.seg_len : P;
-    const uint64_t origin = a.offsets ? a.offsets[r] : (uint64_t)a.recs[r].seq_off;
-    pos = (uint32_t)(d.first_base - origin + q_lo);
-    n_pos = (uint32_t)(q_hi - q_lo);
-}
-
-__device__ __forceinline__ bool kid_segment_votes_fits(const KidSegmentsIn &a, uint64_t n_seg)
-{
-    return n_seg <= a.seg_cap && a.tile_hit_off[a.tile_off[a.n_reads]] <= a.hits_cap;
-}
-
 template <bool ROWS>
 __global__ __launch_bounds__(256) void kid_segment_votes_kernel(const KidDevDb db, const KidSegmentsIn a, const KidSegGeom g,
                                                                  const KidSupportRule rule, KidSegmentVote *out, const KidSegmentVoteBig big)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_seg = a.seg_offsets[a.n_reads];
-    if (!kid_segment_votes_fits(a, n_seg)) return;
-    const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
-    for (uint64_t s0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; s0 < n_seg; s0 += n_waves * 64u) {
-        const uint64_t s_last = n_seg - s0 > 64u ? s0 + 63u : n_seg - 1u;
-        const uint64_t r_first = kid_segments_read_of(a.seg_offsets, 0, a.n_reads, s0);
-        const uint64_t r_last = kid_segments_read_of(a.seg_offsets, r_first, a.n_reads, s_last);
-        const uint64_t s = s0 + lane;
-        const bool have = s < n_seg;
-        uint64_t h0 = 0;
-        KidSegmentVote res = {0u, 0u, {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u}};
-        if (have) {
-            const uint64_t r = kid_segments_read_of(a.seg_offsets, r_first, r_last + 1u, s);
-            const KidReadDesc d = a.desc[r];
-            const uint64_t t0 = a.tile_off[r];
-            uint64_t q_lo, q_hi;
-            kid_segment_votes_place(a, g, r, s, d, q_lo, q_hi, res.pos, res.n_pos);
-            h0 = kid_segments_before(a.tile_hit_off, a.tile_mask, t0, q_lo);
-            res.v.n_hits = (uint32_t)(kid_segments_before(a.tile_hit_off, a.tile_mask, t0, q_hi) - h0);
-            res.v.n_kmers = (uint32_t)(kid_segments_before(a.tile_valid_off, a.tile_valid, t0, q_hi) -
-                                       kid_segments_before(a.tile_valid_off, a.tile_valid, t0, q_lo));
-        }
-        const uint32_t m = res.v.n_hits;
-        const bool later = m > KID_VOTE_WAVE_HITS; // kid_segment_votes_big_kernel's: nothing is written for it here
-        if (later) {
-            const uint32_t e = atomicAdd(big.n_list, 1u);
-            if (e < big.list_cap) big.list[e] = KidSegmentVoteEntry{s, h0, m, res.v.n_kmers};
-        }
-        if (m > 0 && m <= KID_VOTE_LANE_HITS) kid_vote_lane<ROWS>(db, a.hits + h0, m, rule, res.v);
-        uint64_t wide = __ballot(m > KID_VOTE_LANE_HITS && !later);
-        while (wide) { // the segments of the 64 with more hits: the whole wave, one after the other
-            const int j = __builtin_ctzll(wide);
-            wide &= wide - 1ull;
-            const KidHit *wh = a.hits + (uint64_t)__shfl((unsigned long long)h0, j);
-            const uint32_t wm = (uint32_t)__builtin_amdgcn_readlane((int)m, j);
-            KidVote w = {0u, 0u, (uint32_t)__builtin_amdgcn_readlane((int)res.v.n_kmers, j), wm, 0u, 0u, 0u, 0u};
-            kid_vote_wave<ROWS>(db, wh, wm, rule, lane, w);
-            if (lane == (uint32_t)j) res.v = w;
-        }
-        if (have && !later) out[s] = res;
-    }
+    kid_calls_run<false, false>(KidSegmentUnits<KidSegmentVote, KidSegmentVoteBig>{a, g, a.hits, out, big}, KidVoteMethod<ROWS>{db, rule},
+                                KidSupportTally());
 }
 
 // ------------------------------------------------------------------ segments of more than KID_VOTE_WAVE_HITS hits
@@ -116,7 +59,7 @@ __global__ __launch_bounds__(256) void kid_segment_votes_big_kernel(const KidDev
 {
     __shared__ uint32_t sh[4 * 9]; // as in kid_vote_big_kernel
     const uint64_t n_seg = a.seg_offsets[a.n_reads];
-    if (!kid_segment_votes_fits(a, n_seg)) return;
+    if (!kid_segments_fits(a, n_seg)) return;
     uint32_t *row = big.rows + (uint64_t)blockIdx.x * (uint64_t)db.ntar;
     const uint32_t n_list = *big.n_list;
     for (uint32_t e = blockIdx.x; e < n_list && e < big.list_cap; e += gridDim.x) {
@@ -132,7 +75,7 @@ __global__ __launch_bounds__(256) void kid_segment_votes_big_kernel(const KidDev
         if (threadIdx.x == 0) {
             const uint64_t r = kid_segments_read_of(a.seg_offsets, 0, a.n_reads, en.seg);
             uint64_t q_lo, q_hi;
-            kid_segment_votes_place(a, g, r, en.seg, a.desc[r], q_lo, q_hi, res.pos, res.n_pos);
+            kid_segments_place(a, g, r, en.seg, a.desc[r], q_lo, q_hi, res.pos, res.n_pos);
             out[en.seg] = res;
         }
         kid_vote_big_clear(db, row, h, en.m);

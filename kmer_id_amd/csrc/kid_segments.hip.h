@@ -16,9 +16,7 @@
 //   kid_segments_count_kernel   segments per read, from its descriptor
 //   kid_hits_scan_*<2>          -> seg_offsets[n_reads + 1] (in place)
 //   kid_hits_scan_*<1>          popcount(valid mask) per tile -> valid windows in front of every tile
-//   kid_segments_kernel         64 consecutive segments per wave: a lane takes a segment of at most
-//                               KID_SUPPORT_LANE_HITS hits (kid_support_lane), the whole wave then the others one after
-//                               the other (kid_support_wave)
+//   kid_segments_kernel         kid_calls_run (kid_calls.hip.h) over KidSegmentUnits with the support kernel's method
 // Pure, integer, no atomics, every output place a function of the batch: byte-identical across runs, across splits of
 // the reads into calls and across table kinds.
 #pragma once
@@ -87,50 +85,80 @@ __device__ __forceinline__ uint64_t kid_segments_read_of(const uint64_t *seg_off
     return lo;
 }
 
+// pos and n_pos of segment s of read r (descriptor d), and the positions [q_lo, q_hi) of the read it covers
+__device__ __forceinline__ void kid_segments_place(const KidSegmentsIn &a, const KidSegGeom &g, uint64_t r, uint64_t s, const KidReadDesc &d,
+                                                   uint64_t &q_lo, uint64_t &q_hi, uint32_t &pos, uint32_t &n_pos)
+{
+    const uint64_t P = (uint64_t)(uint32_t)d.n_kmers;
+    q_lo = (s - a.seg_offsets[r]) * g.seg_step;
+    q_hi = P - q_lo > g.seg_len ? q_lo + g.seg_len : P;
+    const uint64_t origin = a.offsets ? a.offsets[r] : (uint64_t)a.recs[r].seq_off;
+    pos = (uint32_t)(d.first_base - origin + q_lo);
+    n_pos = (uint32_t)(q_hi - q_lo);
+}
+
+__device__ __forceinline__ bool kid_segments_fits(const KidSegmentsIn &a, uint64_t n_seg)
+{
+    return n_seg <= a.seg_cap && a.tile_hit_off[a.tile_off[a.n_reads]] <= a.hits_cap;
+}
+
+// the segments of a batch as the units of kid_calls_run: Out is {pos, n_pos, the method's record}.  Big: the list of the
+// family's second kernel ({list, n_list, list_cap}: entries of {segment, h0, m, n_kmers}), or nothing
+struct KidNoList {};
+template <class Out, class Big>
+struct KidSegmentUnits {
+    const KidSegmentsIn &a;
+    const KidSegGeom &g;
+    const KidHit *hits;
+    Out *out;
+    Big big;
+    struct Unit {
+        uint64_t h0;
+        uint32_t m, n_kmers, pos, n_pos;
+    };
+    struct Span {
+        uint64_t r_first, r_last;
+    };
+    __device__ __forceinline__ uint64_t count() const
+    {
+        const uint64_t n_seg = a.seg_offsets[a.n_reads];
+        return kid_segments_fits(a, n_seg) ? n_seg : 0ull;
+    }
+    // the reads of the wave's first and last segment (wave-uniform searches), then every lane's own between them:
+    // 64 segments of a metagenomic batch are 64 reads, six steps; reads without a window in between cost nothing
+    __device__ __forceinline__ Span span(uint64_t s0, uint64_t n_seg) const
+    {
+        const uint64_t s_last = n_seg - s0 > 64u ? s0 + 63u : n_seg - 1u;
+        const uint64_t r_first = kid_segments_read_of(a.seg_offsets, 0, a.n_reads, s0);
+        return Span{r_first, kid_segments_read_of(a.seg_offsets, r_first, a.n_reads, s_last)};
+    }
+    __device__ __forceinline__ void find(const Span &sp, uint64_t s, Unit &un) const
+    {
+        const uint64_t r = kid_segments_read_of(a.seg_offsets, sp.r_first, sp.r_last + 1u, s);
+        const uint64_t t0 = a.tile_off[r];
+        uint64_t q_lo, q_hi;
+        kid_segments_place(a, g, r, s, a.desc[r], q_lo, q_hi, un.pos, un.n_pos);
+        un.h0 = kid_segments_before(a.tile_hit_off, a.tile_mask, t0, q_lo);
+        un.m = (uint32_t)(kid_segments_before(a.tile_hit_off, a.tile_mask, t0, q_hi) - un.h0);
+        un.n_kmers = (uint32_t)(kid_segments_before(a.tile_valid_off, a.tile_valid, t0, q_hi) -
+                                kid_segments_before(a.tile_valid_off, a.tile_valid, t0, q_lo));
+    }
+    __device__ __forceinline__ void append(uint64_t s, const Unit &un) const
+    {
+        const uint32_t e = atomicAdd(big.n_list, 1u);
+        if (e < big.list_cap) big.list[e] = {s, un.h0, un.m, un.n_kmers};
+    }
+    template <class R>
+    __device__ __forceinline__ void store(uint64_t s, const Unit &un, const R &res) const
+    {
+        out[s] = Out{un.pos, un.n_pos, res};
+    }
+};
+
 template <bool ROWS>
 __global__ __launch_bounds__(256) void kid_segments_kernel(const KidDevDb db, const KidSegmentsIn a, const KidSegGeom g, const KidSupportRule rule,
                                                             KidSegment *out)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_seg = a.seg_offsets[a.n_reads];
-    if (n_seg > a.seg_cap || a.tile_hit_off[a.tile_off[a.n_reads]] > a.hits_cap) return;
-    const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
-    for (uint64_t s0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; s0 < n_seg; s0 += n_waves * 64u) {
-        // the reads of the wave's first and last segment (wave-uniform searches), then every lane's own between them:
-        // 64 segments of a metagenomic batch are 64 reads, six steps; reads without a window in between cost nothing
-        const uint64_t s_last = n_seg - s0 > 64u ? s0 + 63u : n_seg - 1u;
-        const uint64_t r_first = kid_segments_read_of(a.seg_offsets, 0, a.n_reads, s0);
-        const uint64_t r_last = kid_segments_read_of(a.seg_offsets, r_first, a.n_reads, s_last);
-        const uint64_t s = s0 + lane;
-        const bool have = s < n_seg;
-        uint64_t h0 = 0;
-        KidSegment res = {0u, 0u, {0u, 0u, 0u, 0u, 0u, 0u}};
-        if (have) {
-            const uint64_t r = kid_segments_read_of(a.seg_offsets, r_first, r_last + 1u, s);
-            const KidReadDesc d = a.desc[r];
-            const uint64_t P = (uint64_t)(uint32_t)d.n_kmers, t0 = a.tile_off[r];
-            const uint64_t q_lo = (s - a.seg_offsets[r]) * g.seg_step;
-            const uint64_t q_hi = P - q_lo > g.seg_len ? q_lo + g.seg_len : P;
-            const uint64_t origin = a.offsets ? a.offsets[r] : (uint64_t)a.recs[r].seq_off;
-            res.pos = (uint32_t)(d.first_base - origin + q_lo);
-            res.n_pos = (uint32_t)(q_hi - q_lo);
-            h0 = kid_segments_before(a.tile_hit_off, a.tile_mask, t0, q_lo);
-            res.s.n_hits = (uint32_t)(kid_segments_before(a.tile_hit_off, a.tile_mask, t0, q_hi) - h0);
-            res.s.n_kmers = (uint32_t)(kid_segments_before(a.tile_valid_off, a.tile_valid, t0, q_hi) -
-                                       kid_segments_before(a.tile_valid_off, a.tile_valid, t0, q_lo));
-        }
-        const uint32_t m = res.s.n_hits;
-        if (m > 0 && m <= KID_SUPPORT_LANE_HITS) kid_support_lane<ROWS>(db, a.hits + h0, m, rule, res.s);
-        uint64_t big = __ballot(m > KID_SUPPORT_LANE_HITS);
-        while (big) { // the segments of the 64 with more hits: the whole wave, one after the other
-            const int j = __builtin_ctzll(big);
-            big &= big - 1ull;
-            const KidHit *wh = a.hits + (uint64_t)__shfl((unsigned long long)h0, j);
-            const uint32_t wm = (uint32_t)__builtin_amdgcn_readlane((int)m, j);
-            KidSupport w = {0u, 0u, (uint32_t)__builtin_amdgcn_readlane((int)res.s.n_kmers, j), wm, 0u, 0u};
-            kid_support_wave<ROWS>(db, wh, wm, rule, lane, w);
-            if (lane == (uint32_t)j) res.s = w;
-        }
-        if (have) out[s] = res;
-    }
+    kid_calls_run<false, false>(KidSegmentUnits<KidSegment, KidNoList>{a, g, a.hits, out, KidNoList()}, KidSupportMethod<ROWS>{db, rule},
+                                KidSupportTally());
 }

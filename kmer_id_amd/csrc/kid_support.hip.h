@@ -13,17 +13,17 @@
 // the common-prefix length of kid_msca_rows (its depth-8 case included) and the nine counts live in registers.  Trees
 // that do not fit the rows (db.rows == nullptr) climb parent[] and recount per candidate.
 //
-// Work split: a wave takes 64 consecutive reads.  A lane takes one read of at most KID_SUPPORT_LANE_HITS hits (0 - 4 in a
-// metagenomic sample); reads with more are then taken by the whole wave one after the other: the lanes stride over the
-// hits to count, and the ordered fold jumps from change to change of the running result (kid_jump_fold of
-// kid_tile.hip.h) -- a left fold in hit order either way.  Pure and without atomics: byte-identical across runs.
-// The TALLY variant also counts the batch into a sample as if it had been classified under the rule: gcount[confident]++
-// per counted read, and for reads with confident > 0 the seen bit of every hit with target > 1 (plain global atomics).
-// Its DEPTH form (KID_OPT_ENTRY_DEPTH) also adds 1 to depth[entry] beside every seen bit it sets (kid_depth.hip.h).
+// This file also holds the two pieces the other families over the tree call: the left fold (kid_fold_lane, kid_fold_wave:
+// the fragments' per-mate folds, the segments' lane) and the climb (kid_climb, a lane or a wave over the hits: the votes, the
+// segments' lane; the workgroup's is kid_vote_big_climb of kid_votes.hip.h).  kid_support_lane and kid_support_wave are fold
+// plus climb written out once more, as they were: each is kept by a timing (profiles/call_kernels/ab_parent_vs_branch.txt).
+//
+// Work split: the loop of kid_calls_run (kid_calls.hip.h) over the reads of the CSR; a read of at most KID_SUPPORT_LANE_HITS
+// hits (0 - 4 in a metagenomic sample) is a lane's, and the wave takes every other: the lanes stride over the hits to
+// count, and the ordered fold jumps from change to change of the running result (kid_jump_fold of kid_tile.hip.h) -- a
+// left fold in hit order either way.  Pure and without atomics: byte-identical across runs.
 #pragma once
-#include "kid_tile.hip.h"
-#include "kid_hits.hip.h"
-#include "kid_depth.hip.h"
+#include "kid_calls.hip.h"
 
 #define KID_SUPPORT_LANE_HITS 8u // a read with more hits than this is taken by the whole wave
 
@@ -33,25 +33,6 @@ struct KidSupport { // = kid_support (include/kmer_id_amd.h)
 struct KidSupportRule {
     uint32_t min_hits, min_permille;
 };
-struct KidSupportTally {
-    unsigned long long *gcount;
-    uint32_t *seen;
-    // the descriptors of a FASTQ block's hit pass: a record process_qual dropped has n_kmers == 0 there and is counted
-    // nowhere (a kept one has stop - start >= k, i.e. at least two windows).  null: every read of the batch is counted,
-    // one shorter than k under target 0.
-    const KidReadDesc *fastq_desc;
-    uint32_t *depth; // the DEPTH form alone: one saturating counter per entry
-};
-
-// what a tally does with one hit of a read it counted with confident > 0
-template <bool DEPTH>
-__device__ __forceinline__ void kid_support_tally_hit(const KidSupportTally &tally, const KidHit &h)
-{
-    if (h.target > 1) {
-        atomicOr(&tally.seen[h.entry >> 5], 1u << (h.entry & 31u));
-        if (DEPTH) kid_depth_count(tally.depth, h.entry);
-    }
-}
 
 __device__ __forceinline__ bool kid_support_passes(uint32_t s, uint32_t n, const KidSupportRule &rule)
 {
@@ -79,7 +60,21 @@ __device__ __forceinline__ uint32_t kid_support_common_depth(uint32_t x, const u
     return c;
 }
 
-// the climb on the rows: ge[d] = hits with d_i >= d = S(node at depth d of final's root path)
+// is c the node t or one of its ancestors (any tree shape)
+__device__ __forceinline__ bool kid_support_under(const KidDevDb &db, uint32_t t, uint32_t c, int32_t dc)
+{
+    int32_t dt = db.depth[t];
+    while (dt > dc) { t = (uint32_t)db.parent[t]; dt--; }
+    return t == c;
+}
+
+// ---- the climb from a node (a fold's final, a vote's call; never 0) over the m > 0 hits at h
+struct KidClimb {
+    uint32_t s_node;                // S(node)
+    uint32_t confident, s_confident; // the first node on node's root path that passes, and its S; 0, 0: none does
+};
+
+// the climb on the rows into a kid_support record: ge[d] = hits with d_i >= d = S(node at depth d of final's root path)
 __device__ __forceinline__ void kid_support_settle_rows(uint32_t f, const uint4 &fr, const uint32_t (&ge)[9], const KidSupportRule &rule,
                                                         KidSupport &res)
 {
@@ -97,15 +92,87 @@ __device__ __forceinline__ void kid_support_settle_rows(uint32_t f, const uint4 
     if (conf_d != 9u) res.confident = conf_d == df ? f : conf_d == 0u ? 1u : kid_row_entry(fr, conf_d);
 }
 
-// is c the node t or one of its ancestors (any tree shape)
-__device__ __forceinline__ bool kid_support_under(const KidDevDb &db, uint32_t t, uint32_t c, int32_t dc)
+// WIDTH threads share the hits: 1, a lane on its own; 64, the lanes of a wave stride over them (every argument
+// wave-uniform; so is the result).  (The workgroup's form, with its sums through LDS, is kid_vote_big_climb.)
+template <bool ROWS, uint32_t WIDTH>
+__device__ __forceinline__ KidClimb kid_climb(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t node, const uint4 &nr, uint32_t n_kmers,
+                                              const KidSupportRule &rule)
 {
-    int32_t dt = db.depth[t];
-    while (dt > dc) { t = (uint32_t)db.parent[t]; dt--; }
-    return t == c;
+    const uint32_t lane = WIDTH == 1u ? 0u : threadIdx.x & 63u;
+    if (ROWS) {
+        uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t c0 = 0; c0 < m; c0 += WIDTH) {
+            const bool valid = WIDTH == 1u || lane < m - c0;
+            uint32_t di = 0;
+            if (valid) {
+                const uint32_t t = kid_support_target(db, h[(uint64_t)c0 + lane].target);
+                di = kid_support_common_depth(t, db.rows[t], node, nr);
+            }
+#pragma unroll
+            for (int d = 0; d < 9; d++)
+                ge[d] += WIDTH == 1u ? (di >= (uint32_t)d ? 1u : 0u) : (uint32_t)__popcll(__ballot(valid && di >= (uint32_t)d));
+        }
+        KidSupport s = {0u, 0u, n_kmers, 0u, 0u, 0u};
+        kid_support_settle_rows(node, nr, ge, rule, s);
+        return KidClimb{s.s_final, s.confident, s.s_confident};
+    }
+    KidClimb r = {0u, 0u, 0u};
+    for (uint32_t c = node;;) { // candidates node, parent(node), .., 1: recount under each
+        const int32_t dc = db.depth[c];
+        uint32_t s = 0;
+        for (uint32_t c0 = 0; c0 < m; c0 += WIDTH) {
+            const bool valid = WIDTH == 1u || lane < m - c0;
+            const bool under = valid && kid_support_under(db, kid_support_target(db, h[(uint64_t)c0 + lane].target), c, dc);
+            s += WIDTH == 1u ? (under ? 1u : 0u) : (uint32_t)__popcll(__ballot(under));
+        }
+        if (c == node) r.s_node = s;
+        if (kid_support_passes(s, n_kmers, rule)) { r.confident = c; r.s_confident = s; break; }
+        if (c == 1u) break;
+        c = (uint32_t)db.parent[c];
+    }
+    return r;
 }
 
-// ---- one lane, one read of at most KID_SUPPORT_LANE_HITS hits
+// ---- the left fold of the m hits at h -> the result (0: m = 0), fr its row when ROWS
+// one lane (m <= KID_SUPPORT_LANE_HITS)
+template <bool ROWS>
+__device__ __forceinline__ uint32_t kid_fold_lane(const KidDevDb &db, const KidHit *h, uint32_t m, uint4 &fr)
+{
+    uint32_t f = 0;
+    fr = make_uint4(0, 0, 0, 0);
+    for (uint32_t i = 0; i < m; i++) {
+        const uint32_t t = kid_support_target(db, h[i].target);
+        if (ROWS) {
+            const uint4 row = db.rows[t];
+            if (f == 0) { f = t; fr = row; }
+            else { uint4 ro; f = kid_msca_rows(t, row, f, fr, ro); fr = ro; }
+        } else {
+            f = f == 0 ? t : kid_msca_climb(db, t, f);
+        }
+    }
+    return f;
+}
+
+// the whole wave (every argument wave-uniform; so is the result)
+template <bool ROWS>
+__device__ __forceinline__ uint32_t kid_fold_wave(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t lane, uint4 &ufr)
+{
+    uint32_t uf = 0; // the running result
+    ufr = make_uint4(0, 0, 0, 0);
+    for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
+        const uint32_t n = m - c0 < 64u ? m - c0 : 64u;
+        const uint32_t tgt = lane < n ? kid_support_target(db, h[(uint64_t)c0 + lane].target) : 0u;
+        uint4 row = make_uint4(0, 0, 0, 0);
+        if (ROWS && tgt) row = db.rows[tgt];
+        kid_jump_fold<ROWS>(db, tgt, row, n >= 64u ? ~0ull : ((1ull << n) - 1ull), uf, ufr);
+    }
+    return uf;
+}
+
+// ---- a read's record: fold plus climb.  One lane, one read of at most KID_SUPPORT_LANE_HITS hits: kid_fold_lane plus
+// kid_climb<ROWS, 1>, written out.  As a call of those two, the support kernel lay 0.3 to 0.5 % above the timing rule on the
+// hit-dense workload, which never runs this code, whether it was on the driver or not; with this text its six bodies are
+// the parent's to the byte.
 template <bool ROWS>
 __device__ __forceinline__ void kid_support_lane(const KidDevDb &db, const KidHit *h, uint32_t m, const KidSupportRule &rule, KidSupport &res)
 {
@@ -144,7 +211,9 @@ __device__ __forceinline__ void kid_support_lane(const KidDevDb &db, const KidHi
     }
 }
 
-// ---- the whole wave, one read of any number of hits (every argument wave-uniform; so is the result)
+// The whole wave (every argument wave-uniform; so is the result): kid_fold_wave plus kid_climb<ROWS, 64>, written out.  As
+// a call of those two it lay 0.8 % above the parent on support / dense and on fragments / dense and 1.2 to 2.0 % on
+// segments / megabase, outside the timing rule in both samples.  A change to either copy belongs in both.
 template <bool ROWS>
 __device__ __forceinline__ void kid_support_wave(const KidDevDb &db, const KidHit *h, uint32_t m, const KidSupportRule &rule, uint32_t lane,
                                                  KidSupport &res)
@@ -189,6 +258,35 @@ __device__ __forceinline__ void kid_support_wave(const KidDevDb &db, const KidHi
     }
 }
 
+// the method of kid_segments_kernel (the methods of kid_calls_run hold references to their kernel's arguments).  Its lane
+// calls the shared fold and climb: with kid_support_lane there, segments / megabase 1000:500 lay 0.65 % above in both samples.
+template <bool ROWS>
+struct KidSupportMethod {
+    typedef KidSupport Result;
+    static constexpr uint32_t lane_hits = KID_SUPPORT_LANE_HITS, wave_hits = 0u;
+    const KidDevDb &db;
+    const KidSupportRule &rule;
+    static __device__ __forceinline__ Result empty(uint32_t n_kmers, uint32_t m) { return Result{0u, 0u, n_kmers, m, 0u, 0u}; }
+    template <class Unit>
+    __device__ __forceinline__ void lane(const KidHit *h, const Unit &un, Result &res) const
+    {
+        uint4 fr;
+        const uint32_t f = kid_fold_lane<ROWS>(db, h, un.m, fr);
+        const KidClimb c = kid_climb<ROWS, 1u>(db, h, un.m, f, fr, res.n_kmers, rule);
+        res.final_t = f;
+        res.s_final = c.s_node;
+        res.confident = c.confident;
+        res.s_confident = c.s_confident;
+    }
+    template <class Unit>
+    __device__ __forceinline__ void wave(const KidHit *h, uint32_t m, const Unit &, int, uint32_t lane, Result &res) const
+    {
+        kid_support_wave<ROWS>(db, h, m, rule, lane, res);
+    }
+};
+
+// The loop is that of kid_calls_run (kid_calls.hip.h) over the reads of a CSR, written out as it was: on the driver the kernel
+// lay 0.5 % above the timing rule on the hit-dense workload in both samples.
 template <bool ROWS, bool TALLY, bool DEPTH>
 __global__ __launch_bounds__(256) void kid_support_kernel(const KidDevDb db, const uint64_t *hit_offsets, const KidHit *hits,
                                                            const uint32_t *n_kmers, uint64_t n_reads, const KidSupportRule rule,

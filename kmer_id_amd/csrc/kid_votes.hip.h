@@ -17,10 +17,9 @@
 //                             kid_support_common_depth(t_i, t_j) == depth(t_j)), a later copy of a target skipped, the
 //                             best set kept as (best, |L|, running LCA) -- a larger P starts it afresh
 //   m <= KID_VOTE_WAVE_HITS   the whole wave: 64 candidates per tile, every lane against all m hits (read 64 at a time
-//                             and handed round by readlane); the lanes' best sets are merged by a butterfly.  The merge
-//                             is associative and commutative (max, +, LCA), so any order gives the same record
-//   more                      pairwise costs too much: kid_vote_kernel appends the read's index to a device list, writes
-//                             nothing and tallies nothing for it; kid_vote_big_kernel, queued behind it, takes the list
+//                             and handed round by readlane); the lanes' best sets are merged by a butterfly
+//   more                      pairwise costs too much: the read goes to the list of kid_calls_run (kid_calls.hip.h);
+//                             kid_vote_big_kernel, queued behind kid_vote_kernel, takes the list
 //                             with one workgroup per read over a row uint32[ntar] of scratch (zero between reads):
 //                             1 w into the row, 2 P(t_i) from the row along t_i's root path and its maximum, 3 every
 //                             distinct member of L claimed once by a marker bit, counted and LCA-reduced, 4 the ge[d]
@@ -29,8 +28,8 @@
 //                             The order of the list is not deterministic; nothing read from it depends on that.
 // The row is read and written through agent-scope atomics alone (they bypass the CU's L1, which RMW atomics do not
 // refresh).  The TALLY variants count as kid_support_kernel does, in whichever kernel settles the read.
-// kid_fragment_votes.hip.h calls a mate pair with the same pieces: the climb behind a best set (kid_vote_climb_*) and the
-// stages of the second kernel (kid_vote_big_best / _climb / _clear) are functions of their own for it.
+// kid_fragment_votes.hip.h and kid_segment_votes.hip.h call their units with the same pieces: the pairwise pass
+// (kid_vote_lane, kid_vote_wave) and the stages of the second kernel (kid_vote_big_best / _climb / _clear).
 #pragma once
 #include "kid_support.hip.h"
 
@@ -111,122 +110,75 @@ __device__ __forceinline__ void kid_vote_wave_merge(const KidDevDb &db, uint32_t
     cr = kid_vote_readlane(cr, 0);
 }
 
-// call and the ge[d] counts against it -> the record's last fields (the rows' climb: kid_support_settle_rows)
-__device__ __forceinline__ void kid_vote_settle_rows(uint32_t call, const uint4 &cr, const uint32_t (&ge)[9], const KidSupportRule &rule,
-                                                     KidVote &res)
+// call and the climb from it (kid_climb of kid_support.hip.h) -> the record's call, s_call, confident, s_confident
+template <class R>
+__device__ __forceinline__ void kid_vote_climbed(R &res, uint32_t call, const KidClimb &c)
 {
-    KidSupport s = {0u, 0u, res.n_kmers, res.n_hits, 0u, 0u};
-    kid_support_settle_rows(call, cr, ge, rule, s);
     res.call = call;
-    res.s_call = s.s_final;
-    res.confident = s.confident;
-    res.s_confident = s.s_confident;
+    res.s_call = c.s_node;
+    res.confident = c.confident;
+    res.s_confident = c.s_confident;
 }
 
-// one lane: S along call's root path over the m hits and the climb -> call, s_call, confident, s_confident (m > 0)
-template <bool ROWS>
-__device__ __forceinline__ void kid_vote_climb_lane(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t call, const uint4 &cr,
-                                                    const KidSupportRule &rule, KidVote &res)
-{
-    if (ROWS) {
-        uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t i = 0; i < m; i++) {
-            const uint32_t t = kid_support_target(db, h[i].target);
-            const uint32_t di = kid_support_common_depth(t, db.rows[t], call, cr);
-#pragma unroll
-            for (int d = 0; d < 9; d++) ge[d] += di >= (uint32_t)d ? 1u : 0u;
-        }
-        kid_vote_settle_rows(call, cr, ge, rule, res);
-    } else {
-        res.call = call;
-        for (uint32_t c = call;;) { // candidates call, parent(call), .., 1: recount under each
-            const int32_t dc = db.depth[c];
-            uint32_t s = 0;
-            for (uint32_t i = 0; i < m; i++) s += kid_support_under(db, kid_support_target(db, h[i].target), c, dc) ? 1u : 0u;
-            if (c == call) res.s_call = s;
-            if (kid_support_passes(s, res.n_kmers, rule)) { res.confident = c; res.s_confident = s; break; }
-            if (c == 1u) break;
-            c = (uint32_t)db.parent[c];
-        }
-    }
-}
-
-// ---- one lane, one read of at most KID_VOTE_LANE_HITS hits
-template <bool ROWS>
-__device__ __forceinline__ void kid_vote_lane(const KidDevDb &db, const KidHit *h, uint32_t m, const KidSupportRule &rule, KidVote &res)
+// The pairwise pass over the m > 0 hits at h, by one lane (kid_vote_lane, m <= KID_VOTE_LANE_HITS) or by the whole wave
+// (kid_vote_wave, m <= KID_VOTE_WAVE_HITS; every argument wave-uniform, so is the result) -> the fields of R that kid_vote
+// names.  MATES (R = KidFragmentVote, the first p hits are mate 1's): the one pass feeds three best sets.  While candidate i
+// is tested against all m hits, "t_j is t_i or an ancestor" is counted twice, over the span (ps) and over the j of i's own
+// mate (pm), and two duplicate flags are kept: an earlier copy in the span, an earlier copy in the own mate.  The candidate
+// then enters the span's set with the first pair and its mate's set with the second; the per-mate sets need no climb,
+// call_1 and call_2 are their LCAs (an empty mate's set stays empty).
+template <bool ROWS, bool MATES, class R>
+__device__ __forceinline__ void kid_vote_lane(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t p, const KidSupportRule &rule, R &res)
 {
     const uint4 none = make_uint4(0, 0, 0, 0);
-    uint32_t best = 0, nb = 0, call = 0;
-    uint4 cr = none;
+    uint32_t best = 0, nb = 0, call = 0, best1 = 0, nb1 = 0, call1 = 0, best2 = 0, nb2 = 0, call2 = 0;
+    uint4 cr = none, cr1 = make_uint4(0, 0, 0, 0), cr2 = make_uint4(0, 0, 0, 0); // (copies of `none` that go unused without MATES keep cr in memory)
     for (uint32_t i = 0; i < m; i++) {
         const uint32_t ti = kid_support_target(db, h[i].target);
         const uint4 ri = ROWS ? db.rows[ti] : none;
-        uint32_t p = 0;
-        bool dup = false;
+        const bool first = i < p; // candidate i is of mate 1: its own mate is [0, p), else [p, m)
+        uint32_t ps = 0, pm = 0;
+        bool dup = false, dupm = false;
         for (uint32_t j = 0; j < m; j++) {
             const uint32_t tj = kid_support_target(db, h[j].target);
-            dup = dup || (tj == ti && j < i);
-            p += kid_vote_under<ROWS>(db, ti, ri, tj, ROWS ? db.rows[tj] : none) ? 1u : 0u;
+            const bool same = tj == ti && j < i; // a later copy of a target is skipped
+            const uint32_t under = kid_vote_under<ROWS>(db, ti, ri, tj, ROWS ? db.rows[tj] : none) ? 1u : 0u;
+            dup = dup || same;
+            ps += under;
+            if constexpr (MATES) {
+                const bool own = (j < p) == first;
+                dupm = dupm || (same && own);
+                pm += own ? under : 0u;
+            }
         }
-        if (!dup) kid_vote_merge<ROWS>(db, best, nb, call, cr, p, 1u, ti, ri);
+        kid_vote_merge<ROWS>(db, best, nb, call, cr, ps, dup ? 0u : 1u, ti, ri);
+        if constexpr (MATES) {
+            kid_vote_merge<ROWS>(db, best1, nb1, call1, cr1, pm, first && !dupm ? 1u : 0u, ti, ri);
+            kid_vote_merge<ROWS>(db, best2, nb2, call2, cr2, pm, !first && !dupm ? 1u : 0u, ti, ri);
+        }
     }
     res.p_best = best;
     res.n_best = nb;
-    kid_vote_climb_lane<ROWS>(db, h, m, call, cr, rule, res);
+    kid_vote_climbed(res, call, kid_climb<ROWS, 1u>(db, h, m, call, cr, res.n_kmers, rule));
+    if constexpr (MATES) { res.call_1 = call1; res.call_2 = call2; }
 }
 
-// the whole wave: the same over m hits (every argument wave-uniform; so is the result)
-template <bool ROWS>
-__device__ __forceinline__ void kid_vote_climb_wave(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t call, const uint4 &cr,
-                                                    const KidSupportRule &rule, uint32_t lane, KidVote &res)
-{
-    if (ROWS) {
-        uint32_t ge[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
-            const bool valid = lane < m - c0;
-            uint32_t di = 0;
-            if (valid) {
-                const uint32_t t = kid_support_target(db, h[c0 + lane].target);
-                di = kid_support_common_depth(t, db.rows[t], call, cr);
-            }
-#pragma unroll
-            for (int d = 0; d < 9; d++) ge[d] += (uint32_t)__popcll(__ballot(valid && di >= (uint32_t)d));
-        }
-        kid_vote_settle_rows(call, cr, ge, rule, res);
-    } else {
-        res.call = call;
-        for (uint32_t c = call;;) {
-            const int32_t dc = db.depth[c];
-            uint32_t s = 0;
-            for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
-                const bool valid = lane < m - c0;
-                const bool under = valid && kid_support_under(db, kid_support_target(db, h[c0 + lane].target), c, dc);
-                s += (uint32_t)__popcll(__ballot(under));
-            }
-            if (c == call) res.s_call = s;
-            if (kid_support_passes(s, res.n_kmers, rule)) { res.confident = c; res.s_confident = s; break; }
-            if (c == 1u) break;
-            c = (uint32_t)db.parent[c];
-        }
-    }
-}
-
-// ---- the whole wave, one read of at most KID_VOTE_WAVE_HITS hits (every argument wave-uniform; so is the result)
-template <bool ROWS>
-__device__ __forceinline__ void kid_vote_wave(const KidDevDb &db, const KidHit *h, uint32_t m, const KidSupportRule &rule, uint32_t lane,
-                                              KidVote &res)
+template <bool ROWS, bool MATES, class R>
+__device__ __forceinline__ void kid_vote_wave(const KidDevDb &db, const KidHit *h, uint32_t m, uint32_t p, const KidSupportRule &rule,
+                                              uint32_t lane, R &res)
 {
     const uint4 none = make_uint4(0, 0, 0, 0);
-    uint32_t best = 0, nb = 0, call = 0;
-    uint4 cr = none;
+    uint32_t best = 0, nb = 0, call = 0, best1 = 0, nb1 = 0, call1 = 0, best2 = 0, nb2 = 0, call2 = 0;
+    uint4 cr = none, cr1 = make_uint4(0, 0, 0, 0), cr2 = make_uint4(0, 0, 0, 0); // (copies of `none` that go unused without MATES keep cr in memory)
     for (uint32_t c0 = 0; c0 < m; c0 += 64u) { // a tile of 64 candidates, one per lane
         const bool valid = lane < m - c0;
         const uint32_t i = c0 + lane;
         const uint32_t ti = valid ? kid_support_target(db, h[i].target) : 1u;
         const uint4 ri = ROWS ? db.rows[ti] : none;
-        uint32_t p = 0;
-        bool dup = false;
-        for (uint32_t j0 = 0; j0 < m; j0 += 64u) { // against all m hits, 64 at a time
+        const bool first = i < p;
+        uint32_t ps = 0, pm = 0;
+        bool dup = false, dupm = false;
+        for (uint32_t j0 = 0; j0 < m; j0 += 64u) { // against all m hits, 64 at a time, handed round by readlane
             const uint32_t nj = m - j0 < 64u ? m - j0 : 64u;
             const uint32_t tj = lane < nj ? kid_support_target(db, h[j0 + lane].target) : 1u;
             const uint4 rj = ROWS ? db.rows[tj] : none;
@@ -234,66 +186,63 @@ __device__ __forceinline__ void kid_vote_wave(const KidDevDb &db, const KidHit *
                 const uint32_t t = (uint32_t)__builtin_amdgcn_readlane((int)tj, (int)q);
                 const uint4 r = ROWS ? kid_vote_readlane(rj, (int)q) : none;
                 if (valid) {
-                    dup = dup || (t == ti && j0 + q < i);
-                    p += kid_vote_under<ROWS>(db, ti, ri, t, r) ? 1u : 0u;
+                    const uint32_t j = j0 + q;
+                    const bool same = t == ti && j < i;
+                    const uint32_t under = kid_vote_under<ROWS>(db, ti, ri, t, r) ? 1u : 0u;
+                    dup = dup || same;
+                    ps += under;
+                    if constexpr (MATES) {
+                        const bool own = (j < p) == first;
+                        dupm = dupm || (same && own);
+                        pm += own ? under : 0u;
+                    }
                 }
             }
         }
-        if (valid && !dup) kid_vote_merge<ROWS>(db, best, nb, call, cr, p, 1u, ti, ri);
+        kid_vote_merge<ROWS>(db, best, nb, call, cr, ps, valid && !dup ? 1u : 0u, ti, ri);
+        if constexpr (MATES) {
+            kid_vote_merge<ROWS>(db, best1, nb1, call1, cr1, pm, valid && first && !dupm ? 1u : 0u, ti, ri);
+            kid_vote_merge<ROWS>(db, best2, nb2, call2, cr2, pm, valid && !first && !dupm ? 1u : 0u, ti, ri);
+        }
     }
-    kid_vote_wave_merge<ROWS>(db, best, nb, call, cr);
+    kid_vote_wave_merge<ROWS>(db, best, nb, call, cr); // (associative and commutative -- max, +, LCA: any order, one record)
     res.p_best = best;
     res.n_best = nb;
-    kid_vote_climb_wave<ROWS>(db, h, m, call, cr, rule, lane, res);
+    kid_vote_climbed(res, call, kid_climb<ROWS, 64u>(db, h, m, call, cr, res.n_kmers, rule));
+    if constexpr (MATES) {
+        kid_vote_wave_merge<ROWS>(db, best1, nb1, call1, cr1);
+        kid_vote_wave_merge<ROWS>(db, best2, nb2, call2, cr2);
+        res.call_1 = call1;
+        res.call_2 = call2;
+    }
 }
+
+template <bool ROWS>
+struct KidVoteMethod {
+    typedef KidVote Result;
+    static constexpr uint32_t lane_hits = KID_VOTE_LANE_HITS, wave_hits = KID_VOTE_WAVE_HITS;
+    const KidDevDb &db;
+    const KidSupportRule &rule;
+    static __device__ __forceinline__ Result empty(uint32_t n_kmers, uint32_t m) { return Result{0u, 0u, n_kmers, m, 0u, 0u, 0u, 0u}; }
+    template <class Unit>
+    __device__ __forceinline__ void lane(const KidHit *h, const Unit &un, Result &res) const
+    {
+        kid_vote_lane<ROWS, false>(db, h, un.m, 0u, rule, res);
+    }
+    template <class Unit>
+    __device__ __forceinline__ void wave(const KidHit *h, uint32_t m, const Unit &, int, uint32_t lane, Result &res) const
+    {
+        kid_vote_wave<ROWS, false>(db, h, m, 0u, rule, lane, res);
+    }
+};
 
 template <bool ROWS, bool TALLY, bool DEPTH>
 __global__ __launch_bounds__(256) void kid_vote_kernel(const KidDevDb db, const uint64_t *hit_offsets, const KidHit *hits,
                                                         const uint32_t *n_kmers, uint64_t n_reads, const KidSupportRule rule,
                                                         KidVote *out /* nullable */, const KidSupportTally tally, const KidVoteBig big)
 {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t n_waves = (uint64_t)gridDim.x * 4u;
-    for (uint64_t r0 = ((uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6)) * 64u; r0 < n_reads; r0 += n_waves * 64u) {
-        const uint64_t r = r0 + lane;
-        const bool have = r < n_reads;
-        uint64_t h0 = 0;
-        KidVote res = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-        if (have) {
-            h0 = hit_offsets[r];
-            res.n_hits = (uint32_t)(hit_offsets[r + 1] - h0);
-            res.n_kmers = n_kmers[r];
-        }
-        const uint32_t m = res.n_hits;
-        const bool later = m > KID_VOTE_WAVE_HITS; // kid_vote_big_kernel's: nothing is written or counted for it here
-        if (later) big.list[atomicAdd(big.n_list, 1u)] = (uint32_t)r;
-        bool counted = false;
-        if (TALLY) counted = have && !later && (!tally.fastq_desc || tally.fastq_desc[r].n_kmers > 0);
-        if (m > 0 && m <= KID_VOTE_LANE_HITS) {
-            kid_vote_lane<ROWS>(db, hits + h0, m, rule, res);
-            if (TALLY && counted && res.confident > 0)
-                for (uint32_t i = 0; i < m; i++) kid_support_tally_hit<DEPTH>(tally, hits[h0 + i]);
-        }
-        uint64_t wide = __ballot(m > KID_VOTE_LANE_HITS && !later);
-        while (wide) { // the reads of the 64 with more hits: the whole wave, one after the other
-            const int j = __builtin_ctzll(wide);
-            wide &= wide - 1ull;
-            const KidHit *wh = hits + (uint64_t)__shfl((unsigned long long)h0, j);
-            const uint32_t wm = (uint32_t)__builtin_amdgcn_readlane((int)m, j);
-            KidVote w = {0u, 0u, (uint32_t)__builtin_amdgcn_readlane((int)res.n_kmers, j), wm, 0u, 0u, 0u, 0u};
-            kid_vote_wave<ROWS>(db, wh, wm, rule, lane, w);
-            if (TALLY && w.confident > 0 && ((__ballot(counted) >> j) & 1ull))
-                for (uint32_t c0 = 0; c0 < wm; c0 += 64u)
-                    if (lane < wm - c0) kid_support_tally_hit<DEPTH>(tally, wh[c0 + lane]);
-            if (lane == (uint32_t)j) res = w;
-        }
-        if (have && !later && out) out[r] = res;
-        if (TALLY) {
-            const uint64_t zeros = __ballot(counted && res.confident == 0);
-            if (lane == 0 && zeros) atomicAdd(&tally.gcount[0], (unsigned long long)__popcll(zeros));
-            if (counted && res.confident != 0) atomicAdd(&tally.gcount[res.confident], 1ull);
-        }
-    }
+    kid_calls_run<TALLY, DEPTH>(KidCsrUnits<KidVote>{hit_offsets, hits, n_kmers, n_reads, out, big.list, big.n_list},
+                                KidVoteMethod<ROWS>{db, rule}, tally);
 }
 
 // ------------------------------------------------------------------ reads of more than KID_VOTE_WAVE_HITS hits
@@ -386,6 +335,20 @@ __device__ __forceinline__ void kid_vote_big_best(const KidDevDb &db, uint32_t *
         kid_vote_merge<ROWS>(db, pb, nb, call, cr, best, s6[0], s6[1], make_uint4(s6[2], s6[3], s6[4], s6[5]));
     }
     __syncthreads();
+}
+
+// call and the ge[d] counts against it -> the record's last fields (the rows' climb: kid_support_settle_rows, which fills
+// the support field names; with a KidClimb returned from it instead, and this function gone, kid_vote_big_kernel<true, true,
+// true> and kid_segment_votes_kernel<true> went from 8 to 7 waves per SIMD: profiles/call_kernels/resource_usage.txt)
+__device__ __forceinline__ void kid_vote_settle_rows(uint32_t call, const uint4 &cr, const uint32_t (&ge)[9], const KidSupportRule &rule,
+                                                     KidVote &res)
+{
+    KidSupport s = {0u, 0u, res.n_kmers, res.n_hits, 0u, 0u};
+    kid_support_settle_rows(call, cr, ge, rule, s);
+    res.call = call;
+    res.s_call = s.s_final;
+    res.confident = s.confident;
+    res.s_confident = s.s_confident;
 }
 
 // 4: S along call's root path, and the climb
