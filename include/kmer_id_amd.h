@@ -679,6 +679,75 @@ int kid_db_loci_from_hits_device(kid_db *db, const void *d_hit_offsets, const vo
                                  uint32_t diag_bin, void *d_out, void *stream);
 int kid_db_read_loci_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *reads);
 
+/* ---- placing mate pairs as one fragment by colinear hits ------------------------------------
+ * The two mates of a pair are the two ends of one fragment: on the same genome, on opposite strands, a few hundred bases
+ * apart.  One hit in each mate that agree on this is a chain of two, with a strand, an insert size and a genome interval
+ * that includes the unsequenced middle -- where kid_db_read_loci gives each mate n_chain = 1 and a strand that says nothing.
+ * The choice is joint: it cannot be made from the two mates' kid_locus records.  Integers only; targets play no role; no
+ * rule, no tally, no sample.
+ * The batch holds 2 F reads interleaved as for kid_db_read_fragments; an absent or empty mate contributes nothing.  W =
+ * diag_bin >= 1, max_span >= 0 in bases, k the database's k-mer length.
+ *   participants  per mate s, exactly those of kid_db_read_loci for that read: the first min(m_s, KID_LOCI_MAX_HITS) hits
+ *                 in list order whose entry < n_entries
+ *   keys          per mate, exactly kid_db_read_loci's: forward (g, floor((x - r) / W)), reverse (g, (x + r) / W).  F_s(g, D)
+ *                 is the number of participants of mate s with the forward key (g, D), R_s(g, E) with the reverse key (g, E)
+ *   paired placement (o, g, D, E)  o = 0 takes F_1(g, D) >= 1 and R_2(g, E) >= 1 (mate 1 forward, mate 2 reverse), o = 1
+ *                 takes F_2(g, D) >= 1 and R_1(g, E) >= 1.  Allowed when D <= E and (E - D) * W <= max_span (64-bit).  Its
+ *                 score is the sum of the two counts.  With W = 1, E - D is the insert length minus k
+ *   solo placement (s, t, g, d)    one key of one mate, t = 0 forward or 1 reverse, its count the score; its orient is t for
+ *                 s = 1 and 1 - t for s = 2: orient = 0 always means "mate 1 reads forward"
+ *   best          the highest score; ties: a paired placement before a solo one; paired ones by (o, g, D, E) ascending;
+ *                 solo ones by (t, g, d, s) ascending (with one mate absent: kid_db_read_loci's tie order)
+ *   org, orient   those of the best placement;  mates  3 for a paired best, s for a solo best, 0 without a participant
+ *   n_chain       the best score;  n_chain_s  the count of the chosen key within mate s, 0 for a mate that is not in the
+ *                 placement: n_chain = n_chain_1 + n_chain_2
+ *   n_org         the participants of both mates with org[entry] = org
+ *   n_other       the largest score of any placement, paired or solo, with g != org; 0 when there is none
+ *   n_hits        m_1 + m_2, all hits;  n_kmers = n_1 + n_2 in uint32, as kid_fragment.n_kmers
+ *   pos_first_s, pos_last_s  the smallest and largest read position in mate s's chain (the participants of mate s that
+ *                 have the chosen key); 0 for a mate that is not in the placement
+ *   lo, hi        for each mate in the placement: a = pos[entry] of its chain hit at pos_first_s (the lowest entry if several
+ *                 share that position), d = pos_last_s - pos_first_s; a forward key covers [a, a + d + k - 1], a reverse key
+ *                 [max(0, a - d), a + k - 1] (the pileup's formula for a read).  lo is the smallest low end and hi the
+ *                 largest high end over the mates in the placement; hi saturates at 2^32 - 1.  With W = 1 and a paired best
+ *                 [lo, hi] is the fragment's genome interval as far as its k-mers show it
+ * Without a participant every field but n_hits and n_kmers is 0.
+ * Worked case.  k = 30, W = 1, max_span = 1000; entries 0..4 with the sites (org, pos) = (3,100) (3,130) (3,400) (9,40)
+ *   (3,5000); mate 1 has the hits (pos, entry) = (10,0) (40,1) (5,3), mate 2 (60,2) (20,4).  Mate 1's forward keys on org 3
+ *   are 90, 90; mate 2's reverse keys on org 3 are 460 and 5020.  (o = 0, g = 3, D = 90, E = 460) is allowed (370 <= 1000)
+ *   and scores 3; no other pair is allowed.  The record: org 3, orient 0, mates 3, n_chain 3, n_chain_1 2, n_chain_2 1,
+ *   n_org 4, n_other 1, n_hits 5, n_kmers 242, lo 100, hi 429, pos_first_1 10, pos_last_1 40, pos_first_2 60, pos_last_2 60.
+ *   (The fragment starts at 90; mate 2 of 150 bases ends at 489: the insert is 400 = E - D + k.)  With the mates exchanged
+ *   orient is 1 and the _1 / _2 fields swap.  Under max_span = 369 the pair is refused and the best is mate 1 alone: mates
+ *   1, n_chain 2, lo 100, hi 159.  With one hit each, (10,0) and (60,2): mates 3, n_chain 2, orient 0, lo 100, hi 429.
+ * While each mate has at most KID_LOCI_MAX_HITS hits the record is a pure function of the two multisets of (pos, entry) and
+ * of n_1 + n_2: the same under any permutation of the hits inside a mate, byte-identical across runs, splits of a batch
+ * into calls at even read indexes and table kinds.  With mate 2 without a participant, org, orient (= strand), n_chain,
+ * n_org, n_other, pos_first_1 and pos_last_1 are mate 1's kid_locus and [lo, hi] is the interval the pileup gives it; the
+ * mirror holds for mate 2 with strand = 1 - orient.  No atomics on outputs; a fragment with more than a few hits in either
+ * mate is settled by a second kernel queued behind the first, whose worst case is one test per allowed pair of keys.     */
+typedef struct kid_fragment_locus {
+    uint32_t org, orient, mates, n_chain, n_chain_1, n_chain_2, n_org, n_other, n_hits /* m_1 + m_2 */, n_kmers, lo, hi, pos_first_1, pos_last_1,
+        pos_first_2, pos_last_2;
+} kid_fragment_locus;
+/* The forms of kid_db_read_fragments* argument for argument, with (diag_bin, max_span) in the place of the rule and without
+ * a tally: host buffers (64 bytes per fragment come back; out[n_reads / 2]), two FASTQ blocks (KID_DB_OPT_MIN_BASE_QUALITY
+ * and KID_DB_OPT_LOW_COMPLEXITY apply as in kid_db_read_fragments_fastq), the kernels alone on an interleaved CSR in HBM
+ * (d_out: kid_fragment_locus[n_reads / 2]; asynchronous on `stream`), and the device time of the fragment-loci kernels
+ * ALONE since the last query.  Refused, in this order: what kid_db_read_fragments* refuses -- too many reads, n_reads odd,
+ * out = NULL with reads: KID_ERR_ARG --, then diag_bin = 0 KID_ERR_ARG, then a database without sites KID_ERR_STATE
+ * (nothing is allocated or launched); then n_reads = 0 returns KID_OK and launches nothing; then the batch's own null
+ * pointers, KID_ERR_ARG.  The one-call-at-a-time rule of every call on a kid_db holds.  Scratch beside the hit pass's: 4
+ * bytes per fragment of the largest batch.                                                                            */
+int kid_db_read_fragment_loci(kid_db *db, const uint8_t *bases, const uint64_t *offsets, const int32_t *start, const int32_t *stop,
+                              uint64_t n_reads, uint32_t diag_bin, uint32_t max_span, kid_fragment_locus *out);
+int kid_db_read_fragment_loci_fastq(kid_db *db, const uint8_t *text1, uint64_t nbytes1, const kid_fastq_rec *recs1, const uint8_t *text2,
+                                    uint64_t nbytes2, const kid_fastq_rec *recs2, uint64_t n_fragments, uint32_t diag_bin, uint32_t max_span,
+                                    kid_fragment_locus *out);
+int kid_db_fragment_loci_from_hits_device(kid_db *db, const void *d_hit_offsets, const void *d_hits, const void *d_n_kmers, uint64_t n_reads,
+                                          uint32_t diag_bin, uint32_t max_span, void *d_out, void *stream);
+int kid_db_read_fragment_loci_time(kid_db *db, double *device_ms, uint64_t *calls, uint64_t *fragments);
+
 /* ---- placed reads piled up per genome bin ---------------------------------------------------
  * kid_locus records added up: how many placed reads cover each stretch of each genome.  Integers only.
  * Geometry.  A pileup belongs to one kid_db that has sites and to a bin width W >= 1; its geometry is that of
@@ -749,6 +818,21 @@ int kid_pileup_bins(kid_pileup *p, uint64_t *bin_base /* [n_orgs + 1] */, uint32
 int kid_pileup_export(kid_pileup *p, uint32_t *starts /* [B] */, uint32_t *steps /* [B + n_orgs] */);
 int kid_pileup_merge(kid_pileup *p, const uint32_t *starts, const uint32_t *steps, uint64_t n_records, uint64_t n_placed);
 int kid_pileup_time(kid_pileup *p, double *device_ms, uint64_t *calls, uint64_t *records);
+/* Fragments into the same pileup: kid_fragment_locus records carry their org and interval themselves.  A record L is
+ * placed when L.mates is in 1..3, paired_only = 0 or L.mates = 3, L.n_chain >= min_chain, (L.n_chain >= L.n_other ?
+ * L.n_chain - L.n_other : 0) >= min_margin, L.org < n_orgs and span_bins[L.org] >= 1, and L.lo <= L.hi; otherwise it changes
+ * nothing.  A placed record adds 1 to starts[g][b_lo] and 1 to depth[g][b] for b_lo..b_hi with g = L.org, b_lo = min(L.lo /
+ * W, span_bins[g] - 1) and b_hi = min(L.hi / W, span_bins[g] - 1): the same step array and three atomics as a read.
+ * n_records and n_placed count as for kid_pileup_add; the statuses are those of kid_pileup_add*; fragment records and read
+ * records may be added to one pileup, whose counters are then the sums.
+ * Worked case, on the pileup's own above (W = 100, organism 3 with span_bins = 10), under (min_chain, min_margin) = (2, 1):
+ *   mates 3, n_chain 3, n_other 1, [lo, hi] = [100, 429]: bins 1..4;  mates 1, n_chain 2, n_other 0, [100, 159]: bin 1;
+ *   mates 3, n_chain 2, n_other 2: the margin is 0, not placed;  mates 0: not placed.  Then starts = [0,2,0,0,0,0,0,0,0,0],
+ *   depth = [0,2,1,1,1,0,0,0,0,0], n_records 4, n_placed 2.  With paired_only = 1 the second is not placed either.     */
+int kid_pileup_add_fragments(kid_pileup *p, const kid_fragment_locus *recs, uint64_t n, uint32_t min_chain, uint32_t min_margin,
+                             int paired_only);
+int kid_pileup_add_fragments_device(kid_pileup *p, const void *d_recs, uint64_t n, uint32_t min_chain, uint32_t min_margin, int paired_only,
+                                    void *stream);
 
 /* ---- results -----------------------------------------------------------------
  * gcount[ntar], ucount[ntar] as written to <prefix>_result.txt (:1040-1043).

@@ -64,6 +64,11 @@ def _loci_family():
         "kid_db_read_loci_fastq": (C.c_int, [_p, _p, _u64, _p, _u64, _u32, _p]),
         "kid_db_loci_from_hits_device": (C.c_int, [_p, _p, _p, _p, _u64, _u32, _p, _p]),
         "kid_db_read_loci_time": _TIME,
+        # the quartet of kid_db_read_fragments* with (diag_bin, max_span) in the place of the rule, no tally
+        "kid_db_read_fragment_loci": (C.c_int, [_p, _p, _p, _p, _p, _u64, _u32, _u32, _p]),
+        "kid_db_read_fragment_loci_fastq": (C.c_int, [_p, _p, _u64, _p, _p, _u64, _p, _u64, _u32, _u32, _p]),
+        "kid_db_fragment_loci_from_hits_device": (C.c_int, [_p, _p, _p, _p, _u64, _u32, _u32, _p, _p]),
+        "kid_db_read_fragment_loci_time": _TIME,
     }
 
 
@@ -77,6 +82,8 @@ def _pileup_family():
         "kid_pileup_reset": (C.c_int, [_p]),
         "kid_pileup_add": (C.c_int, [_p, _p, _u64, _u32, _u32]),
         "kid_pileup_add_device": (C.c_int, [_p, _p, _u64, _u32, _u32, _p]),
+        "kid_pileup_add_fragments": (C.c_int, [_p, _p, _u64, _u32, _u32, C.c_int]),
+        "kid_pileup_add_fragments_device": (C.c_int, [_p, _p, _u64, _u32, _u32, C.c_int, _p]),
         "kid_pileup_counts": (C.c_int, [_p, c_u64p, c_u64p]),
         "kid_pileup_summary": (C.c_int, [_p, _p]),
         "kid_pileup_bins": (C.c_int, [_p, _p, _p, _p, _u64]),

@@ -113,6 +113,10 @@ SEGMENT_VOTE_DTYPE = np.dtype([("pos", np.uint32), ("n_pos", np.uint32)] + [(nam
 # kid_locus: one record per read (kid_db_read_loci*)
 LOCUS_DTYPE = np.dtype([(name, np.uint32) for name in ("org", "strand", "n_chain", "n_org", "n_other", "n_hits", "n_kmers", "pos_first",
                                                        "pos_last", "entry_first")])
+# kid_fragment_locus: one record per fragment (kid_db_read_fragment_loci*): sixteen uint32
+FRAGMENT_LOCUS_DTYPE = np.dtype([(name, np.uint32) for name in ("org", "orient", "mates", "n_chain", "n_chain_1", "n_chain_2", "n_org", "n_other",
+                                                                "n_hits", "n_kmers", "lo", "hi", "pos_first_1", "pos_last_1", "pos_first_2",
+                                                                "pos_last_2")])
 # kid_pileup_rec: one record per organism (kid_pileup_summary): nine uint32, four bytes of padding, depth_sum at offset 40
 PILEUP_FIELDS = ("n_placed", "span_bins", "bins_covered", "max_gap", "max_depth", "max_depth_bin", "max_starts", "max_starts_bin", "reserved")
 PILEUP_DTYPE = np.dtype({"names": PILEUP_FIELDS + ("depth_sum",), "formats": [np.uint32] * 9 + [np.uint64],
@@ -551,6 +555,45 @@ class KmerDB:
         """-> (device ms, calls, reads) of the loci kernels alone since the last query"""
         return self._time(self._lib.kid_db_read_loci_time)
 
+    def read_fragment_loci(self, bases, offsets, start=None, stop=None, diag_bin=1, max_span=1000):
+        """Place mate pairs as one fragment by colinear hits (kid_db_read_fragment_loci): -> a structured array
+        (FRAGMENT_LOCUS_DTYPE: org, orient, mates, n_chain, n_chain_1, n_chain_2, n_org, n_other, n_hits, n_kmers, lo, hi,
+        pos_first_1, pos_last_1, pos_first_2, pos_last_2), one record per fragment.  The batch holds 2 F reads in interleaved
+        order, as for read_fragments.  A paired placement takes a forward key (g, D) of one mate and a reverse key (g, E) of
+        the other with D <= E and (E - D) * diag_bin <= max_span, and scores the sum of their counts; a solo placement is one
+        key of one mate.  The best placement has the highest score (ties: paired first, then the keys' order); mates is 3
+        for a paired best, 1 or 2 for a solo best, 0 without a hit; orient = 0 means mate 1 reads forward; [lo, hi] is the
+        genome interval the chosen chains cover, the unsequenced middle of a paired best included."""
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        out = np.zeros(n // 2, FRAGMENT_LOCUS_DTYPE)
+        check(self._lib.kid_db_read_fragment_loci(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, diag_bin, max_span, _ptr(out)))
+        return out
+
+    def read_fragment_loci_fastq(self, text1, recs1, text2, recs2, diag_bin=1, max_span=1000):
+        """The same for two blocks of FASTQ text with their line indexes, as read_fragments_fastq: record i of recs1 is mate
+        1 and record i of recs2 is mate 2; a record with seq_len = 0 and qual_len = 0 is an absent mate.
+        KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply as in read_fragments_fastq."""
+        text1, recs1, n = _fastq_block(text1, recs1)
+        text2, recs2, n2 = _fastq_block(text2, recs2)
+        if n != n2:
+            raise ValueError("recs1 and recs2 must hold one record per fragment each")
+        out = np.zeros(n, FRAGMENT_LOCUS_DTYPE)
+        check(self._lib.kid_db_read_fragment_loci_fastq(self._h, _ptr(text1), text1.size, _ptr(recs1), _ptr(text2), text2.size, _ptr(recs2), n,
+                                                        diag_bin, max_span, _ptr(out)))
+        return out
+
+    def fragment_loci_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, diag_bin=1, max_span=1000, stream=0):
+        """The fragment-loci kernels alone on an interleaved CSR of n_reads = 2 F reads resident in HBM (raw pointers);
+        asynchronous on `stream`: kid_db_fragment_loci_from_hits_device.  d_out: kid_fragment_locus[n_reads / 2]
+        (FRAGMENT_LOCUS_DTYPE)."""
+        check(self._lib.kid_db_fragment_loci_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
+                                                              C.c_void_p(d_n_kmers), n_reads, diag_bin, max_span, C.c_void_p(d_out),
+                                                              C.c_void_p(stream or None)))
+
+    def read_fragment_loci_time(self):
+        """-> (device ms, calls, fragments) of the fragment-loci kernels alone since the last query"""
+        return self._time(self._lib.kid_db_read_fragment_loci_time)
+
     def pileup(self, bin_width=1000):
         """A pileup of placed reads per genome bin over this database's sites (kid_pileup_create): -> Pileup.  The
         database must outlive it."""
@@ -640,6 +683,20 @@ class Pileup:
     def add_device(self, ptr, n, min_chain=2, min_margin=1, stream=0):
         """Add n kid_locus records resident in HBM (a raw pointer); asynchronous on `stream`: kid_pileup_add_device."""
         check(self._lib.kid_pileup_add_device(self._h, C.c_void_p(ptr or None), n, min_chain, min_margin, C.c_void_p(stream or None)))
+
+    def add_fragments(self, recs, min_chain=2, min_margin=1, paired_only=False):
+        """Add FRAGMENT_LOCUS_DTYPE records held in host memory (kid_pileup_add_fragments): a record is placed over the
+        bins of its own [lo, hi] on its org when mates is in 1..3 (3 alone under paired_only), n_chain >= min_chain, n_chain
+        - n_other (0 when negative) >= min_margin, the org has a bin and lo <= hi.  Fragment and read records may share a
+        pileup."""
+        recs = np.ascontiguousarray(recs, FRAGMENT_LOCUS_DTYPE)
+        check(self._lib.kid_pileup_add_fragments(self._h, _ptr(recs), recs.size, min_chain, min_margin, int(bool(paired_only))))
+
+    def add_fragments_device(self, ptr, n, min_chain=2, min_margin=1, paired_only=False, stream=0):
+        """Add n kid_fragment_locus records resident in HBM (a raw pointer); asynchronous on `stream`:
+        kid_pileup_add_fragments_device."""
+        check(self._lib.kid_pileup_add_fragments_device(self._h, C.c_void_p(ptr or None), n, min_chain, min_margin, int(bool(paired_only)),
+                                                        C.c_void_p(stream or None)))
 
     def counts(self):
         """-> (records handed in, records placed)"""

@@ -1066,6 +1066,7 @@ extern "C" int kid_sample_seen_or(kid_sample *s, uint64_t byte_off, uint64_t nby
 #include "kid_api_segments.h"
 #include "kid_api_segment_votes.h"
 #include "kid_api_loci.h"
+#include "kid_api_fragment_loci.h"
 #include "kid_api_pileup.h"
 #include "kid_api_depth.h"
 #include "kid_api_shared.h"

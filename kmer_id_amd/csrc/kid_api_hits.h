@@ -74,6 +74,7 @@ enum KidFamily : int {
     KID_FAM_VOTES,
     KID_FAM_FRAGMENT_VOTES,
     KID_FAM_LOCI,
+    KID_FAM_FRAGMENT_LOCI,
     KID_FAM_COUNT
 };
 constexpr unsigned kid_settle(KidFamily f) { return 1u << f; }
@@ -116,6 +117,7 @@ struct KidHitsState {
     // family's rows)
     KidVoteScratch vote_big, fragment_vote_big, segment_vote_big;
     KidDevBuf loci_list, loci_n_list; // kid_db_read_loci* (kid_api_loci.h): the reads of the second kernel (uint32 per read), their number
+    KidDevBuf fragment_loci_list, fragment_loci_n_list; // kid_db_read_fragment_loci* (kid_api_fragment_loci.h): the same, of its own, in fragments
     KidDevBuf lowc_plane; // KID_DB_OPT_LOW_COMPLEXITY: the flag plane of a staged block with a line that is split (kid_lowc.hip.h)
     KidHitsState() { segment_vote_big.rows = &vote_big.own_rows; }
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }

@@ -176,7 +176,8 @@ static int kid_pileup_check_add(kid_pileup *p, const void *loci, uint64_t n, uin
 }
 
 // the add kernel over n records in HBM on `stream` between two events (under mu)
-static int kid_pileup_launch_add(kid_pileup *p, const KidLocus *d_loci, uint64_t n, uint32_t min_chain, uint32_t min_margin, hipStream_t stream)
+template <class Rec>
+static int kid_pileup_launch_add(kid_pileup *p, const Rec *d_recs, uint64_t n, KidPileupRule rule, hipStream_t stream)
 {
     if (p->queued.size() >= 64) { // (a caller that never reads: the events do not pile up)
         int rc = kid_pileup_settle(p);
@@ -191,8 +192,8 @@ static int kid_pileup_launch_add(kid_pileup *p, const KidLocus *d_loci, uint64_t
         KID_HIP(s.ev1.create());
     }
     KID_HIP(hipEventRecord(s.ev0.e, stream));
-    hipLaunchKernelGGL(kid_pileup_add_kernel, dim3(kid_grid_for(n, 256, p->num_cu * 8)), dim3(256), 0, stream, d_loci, n, kid_pileup_geo(p), min_chain,
-                       min_margin, p->starts.as<uint32_t>(), p->steps.as<uint32_t>(), p->counts.as<unsigned long long>());
+    hipLaunchKernelGGL(kid_pileup_add_kernel<Rec>, dim3(kid_grid_for(n, 256, p->num_cu * 8)), dim3(256), 0, stream, d_recs, n, kid_pileup_geo(p), rule,
+                       p->starts.as<uint32_t>(), p->steps.as<uint32_t>(), p->counts.as<unsigned long long>());
     KID_HIP(hipGetLastError());
     KID_HIP(hipEventRecord(s.ev1.e, stream));
     p->queued.push_back(std::move(s));
@@ -201,25 +202,50 @@ static int kid_pileup_launch_add(kid_pileup *p, const KidLocus *d_loci, uint64_t
     return KID_OK;
 }
 
-extern "C" int kid_pileup_add_device(kid_pileup *p, const void *d_loci, uint64_t n, uint32_t min_chain, uint32_t min_margin, void *stream)
+// the two forms of an add, for either record type: the records in HBM on the caller's stream, or staged from the host
+template <class Rec>
+static int kid_pileup_add_on_device(kid_pileup *p, const void *d_recs, uint64_t n, KidPileupRule rule, void *stream)
 {
     bool go;
-    int rc = kid_pileup_check_add(p, d_loci, n, min_chain, &go);
+    int rc = kid_pileup_check_add(p, d_recs, n, rule.min_chain, &go);
     if (rc != KID_OK || !go) return rc;
     std::lock_guard<std::mutex> lock(p->mu);
-    return kid_pileup_launch_add(p, (const KidLocus *)d_loci, n, min_chain, min_margin, (hipStream_t)stream);
+    return kid_pileup_launch_add(p, (const Rec *)d_recs, n, rule, (hipStream_t)stream);
+}
+
+template <class Rec>
+static int kid_pileup_add_from_host(kid_pileup *p, const void *recs, uint64_t n, KidPileupRule rule)
+{
+    bool go;
+    int rc = kid_pileup_check_add(p, recs, n, rule.min_chain, &go);
+    if (rc != KID_OK || !go) return rc;
+    std::lock_guard<std::mutex> lock(p->mu);
+    if ((rc = kid_pileup_settle(p)) != KID_OK) return rc; // (the add before may still read the staged records)
+    KID_HIP(kid_hits_ensure(p->staged, n * sizeof(Rec)));
+    KID_HIP(hipMemcpy(p->staged.p, recs, n * sizeof(Rec), hipMemcpyHostToDevice));
+    return kid_pileup_launch_add(p, p->staged.as<Rec>(), n, rule, 0);
+}
+
+extern "C" int kid_pileup_add_device(kid_pileup *p, const void *d_loci, uint64_t n, uint32_t min_chain, uint32_t min_margin, void *stream)
+{
+    return kid_pileup_add_on_device<KidLocus>(p, d_loci, n, KidPileupRule{min_chain, min_margin, 0u}, stream);
 }
 
 extern "C" int kid_pileup_add(kid_pileup *p, const kid_locus *loci, uint64_t n, uint32_t min_chain, uint32_t min_margin)
 {
-    bool go;
-    int rc = kid_pileup_check_add(p, loci, n, min_chain, &go);
-    if (rc != KID_OK || !go) return rc;
-    std::lock_guard<std::mutex> lock(p->mu);
-    if ((rc = kid_pileup_settle(p)) != KID_OK) return rc; // (the add before may still read the staged records)
-    KID_HIP(kid_hits_ensure(p->staged, n * sizeof(KidLocus)));
-    KID_HIP(hipMemcpy(p->staged.p, loci, n * sizeof(KidLocus), hipMemcpyHostToDevice));
-    return kid_pileup_launch_add(p, p->staged.as<KidLocus>(), n, min_chain, min_margin, 0);
+    return kid_pileup_add_from_host<KidLocus>(p, loci, n, KidPileupRule{min_chain, min_margin, 0u});
+}
+
+extern "C" int kid_pileup_add_fragments_device(kid_pileup *p, const void *d_recs, uint64_t n, uint32_t min_chain, uint32_t min_margin,
+                                               int paired_only, void *stream)
+{
+    return kid_pileup_add_on_device<KidFragmentLocus>(p, d_recs, n, KidPileupRule{min_chain, min_margin, paired_only ? 1u : 0u}, stream);
+}
+
+extern "C" int kid_pileup_add_fragments(kid_pileup *p, const kid_fragment_locus *recs, uint64_t n, uint32_t min_chain, uint32_t min_margin,
+                                        int paired_only)
+{
+    return kid_pileup_add_from_host<KidFragmentLocus>(p, recs, n, KidPileupRule{min_chain, min_margin, paired_only ? 1u : 0u});
 }
 
 extern "C" int kid_pileup_counts(kid_pileup *p, uint64_t *n_records, uint64_t *n_placed)

@@ -266,7 +266,7 @@ __global__ __launch_bounds__(256) void kid_loci_kernel(const uint64_t *hit_offse
 }
 
 // ------------------------------------------------------------------ reads of more than KID_LOCI_WAVE_HITS hits
-// keys[0, n2) of LDS ascending: n2 a power of two, at least 512; entered and left by all 256 threads
+// keys[0, n2) of LDS ascending: n2 a power of two (512 and more keep every thread busy); entered and left by all 256 threads
 __device__ __forceinline__ void kid_loci_sort(uint64_t *keys, uint32_t n2)
 {
     for (uint32_t k = 2; k <= n2; k <<= 1)

@@ -6,7 +6,8 @@
 // the sentinel when b_hi is the organism's last bin and never a slot of the next organism.  The steps of an organism sum
 // to zero, so ONE unsegmented inclusive scan over all B + n_orgs slots is every organism's depth, and a record costs
 // three atomics whatever its chain spans.
-//   add     kid_pileup_add_kernel: one lane per record; the lanes of a wave whose slot is that of the lane before them
+//   add     kid_pileup_add_kernel, once per record type (kid_locus, or the kid_fragment_locus of kid_fragment_loci.hip.h,
+//           which carries its interval: kid_pileup_interval): one lane per record; the lanes of a wave whose slot is that of the lane before them
 //           form a run, and the head of a run issues one atomicAdd of the run's length (every read on one locus, or a
 //           sorted input: one atomic per wave and array instead of 64 on one address).  Runs are an optimisation only.
 //   scan    kid_pileup_tile_sum_kernel, kid_pileup_tile_scan_kernel (one workgroup), kid_pileup_apply_kernel: ordered by
@@ -19,6 +20,7 @@
 #include <stdint.h>
 
 #include "kid_coverage.hip.h"
+#include "kid_fragment_loci.hip.h"
 #include "kid_loci.hip.h"
 
 #define KID_PILEUP_SCAN_TILE 2048u // slots per tile of the scan: 256 threads, 8 slots each
@@ -46,10 +48,50 @@ __device__ __forceinline__ void kid_pileup_add_runs(uint32_t *a, uint64_t key, u
     }
 }
 
+struct KidPileupRule {
+    uint32_t min_chain, min_margin;
+    uint32_t paired_only; // fragment records alone: 1 places none but those with both mates
+};
+
+// Is the record placed, and where: its organism and the two ends of its genome interval.  One overload per record type.
+__device__ __forceinline__ bool kid_pileup_interval(const KidLocus &L, const KidPileupGeo &geo, const KidPileupRule &rule, uint32_t &org, int64_t &lo,
+                                                    int64_t &hi)
+{
+    const uint32_t margin = L.n_chain >= L.n_other ? L.n_chain - L.n_other : 0u;
+    if (!(L.n_chain >= rule.min_chain && margin >= rule.min_margin && L.strand <= 1u && L.entry_first < geo.n_entries &&
+          L.org == geo.org[L.entry_first] && L.org < geo.n_orgs))
+        return false;
+    const int64_t a = (int64_t)geo.pos[L.entry_first];
+    const int64_t d = L.pos_last >= L.pos_first ? (int64_t)(L.pos_last - L.pos_first) : 0;
+    if (L.strand == 0u) {
+        lo = a;
+        hi = a + d + (int64_t)geo.k - 1;
+    } else {
+        lo = a - d > 0 ? a - d : 0;
+        hi = a + (int64_t)geo.k - 1;
+    }
+    org = L.org;
+    return true;
+}
+
+// (a fragment record carries its interval: the sites are not looked at)
+__device__ __forceinline__ bool kid_pileup_interval(const KidFragmentLocus &L, const KidPileupGeo &geo, const KidPileupRule &rule, uint32_t &org,
+                                                    int64_t &lo, int64_t &hi)
+{
+    const uint32_t margin = L.n_chain >= L.n_other ? L.n_chain - L.n_other : 0u;
+    if (!(L.mates >= 1u && L.mates <= 3u && (!rule.paired_only || L.mates == 3u) && L.n_chain >= rule.min_chain && margin >= rule.min_margin &&
+          L.org < geo.n_orgs && L.lo <= L.hi))
+        return false;
+    lo = (int64_t)L.lo;
+    hi = (int64_t)L.hi;
+    org = L.org;
+    return true;
+}
+
 // counts: [0] records handed in, [1] records placed (one atomic per wave and counter)
-__global__ __launch_bounds__(256) void kid_pileup_add_kernel(const KidLocus *loci, uint64_t n, KidPileupGeo geo, uint32_t min_chain,
-                                                             uint32_t min_margin, uint32_t *starts, uint32_t *steps,
-                                                             unsigned long long *counts)
+template <class Rec>
+__global__ __launch_bounds__(256) void kid_pileup_add_kernel(const Rec *loci, uint64_t n, KidPileupGeo geo, KidPileupRule rule, uint32_t *starts,
+                                                             uint32_t *steps, unsigned long long *counts)
 {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
@@ -59,26 +101,16 @@ __global__ __launch_bounds__(256) void kid_pileup_add_kernel(const KidLocus *loc
         const uint64_t i = r * stride + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
         uint64_t slot_lo = ~0ull, slot_hi1 = ~0ull, g = 0;
         if (i < n) {
-            const KidLocus L = loci[i];
-            const uint32_t margin = L.n_chain >= L.n_other ? L.n_chain - L.n_other : 0u;
-            if (L.n_chain >= min_chain && margin >= min_margin && L.strand <= 1u && L.entry_first < geo.n_entries &&
-                L.org == geo.org[L.entry_first] && L.org < geo.n_orgs) {
-                const uint32_t nb = geo.span[L.org];
+            const Rec L = loci[i];
+            uint32_t org;
+            int64_t lo, hi;
+            if (kid_pileup_interval(L, geo, rule, org, lo, hi)) {
+                const uint32_t nb = geo.span[org];
                 if (nb >= 1u) { // (an organism with an entry has a bin)
-                    const int64_t a = (int64_t)geo.pos[L.entry_first];
-                    const int64_t d = L.pos_last >= L.pos_first ? (int64_t)(L.pos_last - L.pos_first) : 0;
-                    int64_t lo, hi;
-                    if (L.strand == 0u) {
-                        lo = a;
-                        hi = a + d + (int64_t)geo.k - 1;
-                    } else {
-                        lo = a - d > 0 ? a - d : 0;
-                        hi = a + (int64_t)geo.k - 1;
-                    }
                     uint64_t b_lo = (uint64_t)lo / geo.bin_width, b_hi = (uint64_t)hi / geo.bin_width;
                     b_lo = b_lo < nb - 1u ? b_lo : nb - 1u;
                     b_hi = b_hi < nb - 1u ? b_hi : nb - 1u;
-                    g = L.org;
+                    g = org;
                     const uint64_t base = geo.bin_base[g] + g; // the organism's first slot
                     slot_lo = base + b_lo;
                     slot_hi1 = base + b_hi + 1u; // at most the sentinel, base + nb

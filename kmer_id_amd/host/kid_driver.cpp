@@ -464,6 +464,19 @@ static void loci_lines_of(const Classified &c, std::string &out)
     }
 }
 
+// The lines of a run of fragments under --fragment-loci: those with a hit; j0 is the index of the first record in its files
+static void fragment_loci_lines(const std::vector<kid_fragment_locus> &recs, unsigned long long j0, std::string &out)
+{
+    char num[256];
+    for (size_t i = 0; i < recs.size(); i++) {
+        const kid_fragment_locus &l = recs[i];
+        if (l.n_hits == 0) continue;
+        const int n = snprintf(num, sizeof(num), "%llu\t%u\t%u\t%u:%u:%u:%u:%u:%u:%u:%u:%u:%u\n", j0 + i, l.n_kmers, l.n_hits, l.org, l.orient, l.mates,
+                               l.n_chain, l.n_chain_1, l.n_chain_2, l.n_org, l.n_other, l.lo, l.hi);
+        out.append(num, (size_t)n);
+    }
+}
+
 // (the support pass: nothing comes back, the batch is tallied into the device's confident sample under the rule -- (0, 0)
 // when --depth runs it without one)
 static void support_into(const Classified &c, kid_sample *tally)
@@ -516,14 +529,17 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
     std::deque<InFlight> q;
     std::vector<long long> handed(count, 0);
     const size_t max_in_flight = 2 * e.samples.size();
-    // --fragments and --fragment-votes: the blocks of each mate file that are through, in file order, until their records have been paired
+    // --fragments, --fragment-votes and --fragment-loci: the blocks of each mate file that are through, in file order, until their records have been paired
     struct HeldBlock {
         std::unique_ptr<ReadBatch> batch;
         size_t paired = 0; // records of the block that have been handed on
     };
     const bool by_fold = out.on(SF_FRAGMENTS) && count == 2 && !e.tallied[TALLY_FRAGMENTS].empty();
     const bool by_votes = out.on(SF_FRAGMENT_VOTES) && count == 2 && !e.tallied[TALLY_FRAGMENT_VOTES].empty();
-    const bool fragments = by_fold || by_votes; // (either pairs the records; both are handed the same run of the same blocks)
+    const bool by_loci = out.on(SF_FRAGMENT_LOCI) && count == 2 && e.site_pos; // (the databases have their sites: engine_open)
+    const bool fragments = by_fold || by_votes || by_loci; // (each pairs the records; all are handed the same run of the same blocks)
+    std::vector<kid_fragment_locus> fragment_loci;
+    unsigned long long fragments_done = 0; // the index j of the next fragment: the records are paired in file order
     std::deque<HeldBlock> held[2];
     unsigned long long mate_records[2] = {0, 0};
     std::vector<kid_fastq_rec> absent;
@@ -559,7 +575,18 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
                 rc = kid_db_read_fragment_votes_fastq(e.dbs[dev], text[0], nbytes[0], recs[0], text[1], nbytes[1], recs[1], n,
                                                       e.side.support.min_hits, e.side.support.min_permille, (kid_fragment_vote *)nullptr,
                                                       e.tallied[TALLY_FRAGMENT_VOTES][dev]);
+            if (rc == KID_OK && by_loci) {
+                fragment_loci.resize(n);
+                rc = kid_db_read_fragment_loci_fastq(e.dbs[dev], text[0], nbytes[0], recs[0], text[1], nbytes[1], recs[1], n, e.side.fragment_loci_bin,
+                                                     e.side.fragment_loci_span, fragment_loci.data());
+                if (rc == KID_OK) {
+                    lines.clear();
+                    fragment_loci_lines(fragment_loci, fragments_done, lines);
+                    out.add(SF_FRAGMENT_LOCI, saver_file, lines);
+                }
+            }
             if (rc != KID_OK) die_kid(rc);
+            fragments_done += n;
             for (int m = 0; m < 2; m++)
                 if (have[m]) held[m].front().paired += n;
         }
@@ -653,7 +680,7 @@ long long run_files(Engine &e, Prefetcher &pf, size_t first, size_t count, ReadS
         if (mate_records[0] != mate_records[1]) {
             const unsigned long long a = mate_records[0], b = mate_records[1];
             fprintf(stderr, "kmer_id_amd: %s: %s: the mate files hold %llu and %llu records: %llu fragments have an absent mate\n",
-                    by_fold ? "--fragments" : "--fragment-votes", out.result_path().c_str(), a, b, a > b ? a - b : b - a);
+                    by_fold ? "--fragments" : by_votes ? "--fragment-votes" : "--fragment-loci", out.result_path().c_str(), a, b, a > b ? a - b : b - a);
         }
     }
     long long n = 0;

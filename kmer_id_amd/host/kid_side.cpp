@@ -112,8 +112,21 @@ static void read_pileup(SideOptions &o, const char *prog, const char *opt, const
     o.pileup = PileupOption{true, (uint32_t)w, (uint32_t)chain, (uint32_t)margin};
 }
 
+static void read_fragment_loci(SideOptions &o, const char *prog, const char *opt, const char *v)
+{
+    const char *const what = "takes W[:MAX_SPAN], digits only: W in 1..2147483647, MAX_SPAN in 0..2147483647";
+    unsigned long long w = 0, span = 1000;
+    size_t at = 0;
+    if (digits_up_to(0x7FFFFFFFull, v, at, w) <= 0) usage_error(prog, opt, what); // (an empty part too)
+    if (v[at] == ':' && digits_up_to(0x7FFFFFFFull, v, ++at, span) <= 0) usage_error(prog, opt, what);
+    if (v[at] != 0 || w < 1) usage_error(prog, opt, what); // (a third part too)
+    o.fragment_loci = true;
+    o.fragment_loci_bin = (uint32_t)w;
+    o.fragment_loci_span = (uint32_t)span;
+}
+
 // The side options: their words and what reads the value of each -- or, for a switch, which takes none, the flag it sets
-// and whether it is an option of nk10 alone.  The rows stand in the order in which malformed values are diagnosed; an
+// -- and whether it is an option of nk10 alone (such an option names the flag that says it is on, a valued one too).  The rows stand in the order in which malformed values are diagnosed; an
 // option whose row has new_group set is diagnosed behind every option of the rows above it, the options of one group in
 // their order on the command line.  (A switch cannot be malformed: the switches stand where they disturb no group.)
 static const struct {
@@ -135,7 +148,8 @@ static const struct {
                     {"--segments", true, read_segments, nullptr, false},
                     {"--segment-votes", true, read_segment_votes, nullptr, false},
                     {"--loci", true, read_loci, nullptr, false},
-                    {"--pileup", true, read_pileup, nullptr, false}};
+                    {"--pileup", true, read_pileup, nullptr, false},
+                    {"--fragment-loci", true, read_fragment_loci, &SideOptions::fragment_loci, true}};
 
 int side_option_values(const char *word)
 {
@@ -261,7 +275,13 @@ static const struct {
     // line for every organism with n_placed >= 1, in ascending order:
     //   #<n_records>,<n_placed>,<W>,<MIN_CHAIN>,<MIN_MARGIN>
     //   <org>,<n_placed>,<span_bins>,<bins_covered>,<max_gap>,<max_depth>,<max_depth_bin>,<max_starts>,<max_starts_bin>,<depth_sum>
-    {"result", "pileup", "", [](const SideOptions &o) { return o.pileup.on; }, FILL_PILEUP, TALLY_COUNT}};
+    {"result", "pileup", "", [](const SideOptions &o) { return o.pileup.on; }, FILL_PILEUP, TALLY_COUNT},
+    // --fragment-loci W[:MAX_SPAN] (nk10): the fragments of --fragments (the same pairing of records, the same blocks, absent
+    // mates and stderr line -- printed once whatever combination of the three fragment options is given), each placed by
+    // kid_db_read_fragment_loci_fastq with diag_bin = W and max_span = MAX_SPAN.  One line per fragment with n_hits >= 1, in
+    // ascending j, the 0-based index of the 4-line record in its files, tab-separated:
+    //   <j> <n_kmers> <n_hits> <org>:<orient>:<mates>:<n_chain>:<n_chain_1>:<n_chain_2>:<n_org>:<n_other>:<lo>:<hi>
+    {"result", "fragment_loci", "", [](const SideOptions &o) { return o.fragment_loci; }, FILL_LINES, TALLY_COUNT}};
 
 static std::string side_path(const std::string &result_path, int which)
 {

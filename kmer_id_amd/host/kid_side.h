@@ -70,12 +70,18 @@ struct SideOptions {
     // --pileup W[:MIN_CHAIN[:MIN_MARGIN]].  It loads the sites as --loci does and runs the loci pass where --loci runs it, with
     // --loci's diagonal bin when that is given, else 1: with both options one loci pass per batch feeds both files.
     PileupOption pileup;
+    // --fragment-loci W[:MAX_SPAN] (nk10 alone, like --fragments): place the mate pairs as one fragment by colinear hits
+    // (kid_db_read_fragment_loci_fastq).  Digits only; W, the diagonal bin width, in 1..2147483647; MAX_SPAN, the largest
+    // (E - D) * W of a paired placement in bases, in 0..2147483647, default 1000.  It loads the sites as --loci does and pairs
+    // the records exactly as --fragments does.
+    bool fragment_loci = false;
+    uint32_t fragment_loci_bin = 0, fragment_loci_span = 1000;
 };
 // The one place that reads them.  Every word of argv that is an option's name is an occurrence and the word behind it
 // its value; a later occurrence overrides an earlier one.  A missing or malformed value (an empty part or a second colon
-// of --segments or --segment-votes, a fourth part of --pileup too) is a usage error: "<prog>: <option> <what>" on stderr
+// of --segments or --segment-votes, a fourth part of --pileup or a third of --fragment-loci too) is a usage error: "<prog>: <option> <what>" on stderr
 // and exit code 2 -- of several, the first in the order of the option table's groups (--min-hits / --confidence,
-// --min-base-quality / --low-complexity, --segments, --segment-votes, --loci, --pileup); within a group, the first in argv.
+// --min-base-quality / --low-complexity, --segments, --segment-votes, --loci, --pileup, --fragment-loci); within a group, the first in argv.
 SideOptions side_options(int argc, char **argv, const char *prog);
 // For a front-end that rejects the words it does not know: the number of value words behind `word` (0 or 1) if it
 // is a side option, else -1
@@ -95,7 +101,7 @@ ReaderOptions parse_reader_options(int argc, char **argv, int default_threads);
 
 // The files a sample / job may have beside its result file, in the order they are written.  kid_side.cpp has a row for
 // each: its name, the options it is on under, what fills it, and its format.
-enum SideFile { SF_CONFIDENT, SF_FRAGMENTS, SF_VOTES, SF_FRAGMENT_VOTES, SF_DEPTH, SF_SEEN, SF_HITS, SF_SEGMENTS, SF_SEGMENT_VOTES, SF_LOCI, SF_PILEUP, SF_COUNT };
+enum SideFile { SF_CONFIDENT, SF_FRAGMENTS, SF_VOTES, SF_FRAGMENT_VOTES, SF_DEPTH, SF_SEEN, SF_HITS, SF_SEGMENTS, SF_SEGMENT_VOTES, SF_LOCI, SF_PILEUP, SF_FRAGMENT_LOCI, SF_COUNT };
 
 // The samples beside the classified one that an engine holds per device, each tallied into by a pass over every batch
 // (or fragment) and written as a result file of its own (the row of the side file names its tally)

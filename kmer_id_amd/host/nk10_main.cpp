@@ -44,6 +44,10 @@
 //                    the hits of both mates -- the fragments of --fragments, a call that does not depend on the order of the
 //                    mates or of their hits -- under the rule of --min-hits / --confidence when given (kid_side.h).  Not with
 //                    --fasta; needs neither --fragments nor --votes
+//   --fragment-loci W[:MAX_SPAN]   also write <prefix>_fragment_loci.txt: the mate pairs of --fragments placed on a genome as one
+//                    fragment each by colinear hits -- a forward diagonal of one mate with a reverse diagonal of the other at
+//                    most MAX_SPAN (1000) bases above it, diagonal bins of W bases -- one line per fragment with a hit
+//                    (kid_side.h).  Not with --fasta
 //   --block-bytes N      the size of the FASTQ text blocks the files are cut into (8 MiB; at least 32 KiB are taken): no output
 //                    depends on it
 //   --min-base-quality Q   bases of quality below Q (0..93; 0 = off) are read as N: the result, hits and confident files are
@@ -145,6 +149,10 @@ int main(int argc, char **argv)
         std::cerr << "nk10: --fragment-votes needs the two FASTQ files of a sample: not with --fasta\n";
         return 2;
     }
+    if (side.fragment_loci && fasta_mode) {
+        std::cerr << "nk10: --fragment-loci needs the two FASTQ files of a sample: not with --fasta\n";
+        return 2;
+    }
     if (!db_dir.empty() && db_dir.back() != '/') db_dir += "/";
     if (batch_reads < 1) batch_reads = 1;
     if (threads < 1) threads = 1;
@@ -182,7 +190,7 @@ int main(int argc, char **argv)
                 if (kid_host_alloc(warm_device, 4096, &p) == KID_OK) kid_host_free(p);
             });
         }
-        load_database(tpath, pname, db_cache, k, ntar, parent, ps, &from_cache, threads, &tm, &cache_writer, (side.loci.on || side.pileup.on) && dry_run.empty());
+        load_database(tpath, pname, db_cache, k, ntar, parent, ps, &from_cache, threads, &tm, &cache_writer, (side.loci.on || side.pileup.on || side.fragment_loci) && dry_run.empty());
         const double t_db_loaded = since_start();
         double t_gpu_ready = -1, t_first_file = -1;
         size_t n_entries = ps.keys.size(), n_devices = 0;
