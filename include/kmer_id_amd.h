@@ -854,6 +854,10 @@ int kid_sample_stats(kid_sample *s, uint64_t out[4]);
  * up the elapsed times since the last call and returns the number of batches they belong to.  */
 int kid_sample_set_timing(kid_sample *s, int enabled);
 int kid_sample_kernel_time(kid_sample *s, double *total_ms, uint64_t *launches);
+/* The same event pairs one by one: the milliseconds of every timed batch since the last call of THIS function, oldest
+ * first (the two queries do not take from each other; a sample that is never asked keeps the latest 65536).  *n = how
+ * many there are; the first min(cap, *n) are written to ms, and all of them count as reported.  Synchronises. */
+int kid_sample_kernel_times(kid_sample *s, double *ms, uint64_t cap, uint64_t *n);
 /* The same interval on the device's own clock, always on: the first workgroup of kid_classify_kernel to
  * start and the last one to finish stamp the 100 MHz realtime counter.  Sum over the batches since
  * the last call (or kid_sample_reset) and their number.  No event overhead, comparable with a

@@ -1056,6 +1056,16 @@ class Sample:
         check(self._lib.kid_sample_kernel_time(self._h, C.byref(ms), C.byref(n)))
         return ms.value, n.value
 
+    def kernel_times(self, cap=None):
+        """-> (ms float64[min(cap, n)], n): the HIP-event time of each timed batch since the last call of this method,
+        oldest first (kid_sample_kernel_times); cap=None asks for all of them"""
+        n = C.c_uint64(0)
+        if cap is None:
+            cap = 1 << 16  # (as many as a sample keeps)
+        ms = np.empty(cap, np.float64)
+        check(self._lib.kid_sample_kernel_times(self._h, ms.ctypes.data_as(C.POINTER(C.c_double)), cap, C.byref(n)))
+        return ms[:min(cap, n.value)], n.value
+
     def kernel_time_device(self):
         """-> (total ms, batches) of kid_classify_kernel since the last call, on the device's own 100 MHz clock"""
         ms, n = C.c_double(0), C.c_uint64(0)

@@ -48,6 +48,10 @@ struct kid_sample {
     bool timing = false;
     std::vector<std::pair<KidEvent, KidEvent>> timed; // around each classify launch, while timing is on
     uint64_t timed_batches = 0;
+    // ... read off by a query: ms per batch that kid_sample_kernel_times has not reported yet (the latest KID_TIMED_KEEP
+    // of them), and the sum of those kid_sample_kernel_time has not
+    std::vector<double> timed_ms;
+    double timed_ms_unsummed = 0;
     uint32_t batch_seq = 0;
     // Per-batch scratch of the device pipeline (prepare -> classify), grown on demand.  Three sets taken in turn, so
     // that the prepare kernel of batch b + 1 can run (on another stream) while the classify kernels of batch b still
@@ -593,22 +597,44 @@ extern "C" int kid_sample_set_timing(kid_sample *s, int enabled)
     return KID_OK;
 }
 
+// the event pairs recorded so far -> milliseconds, for both queries below (synchronises)
+static int kid_timed_read(kid_sample *s)
+{
+    static const size_t KID_TIMED_KEEP = 1u << 16;
+    KID_HIP(hipDeviceSynchronize());
+    for (auto &ev : s->timed) {
+        float ms = 0;
+        KID_HIP(hipEventElapsedTime(&ms, ev.first.e, ev.second.e));
+        s->timed_ms.push_back(ms);
+        s->timed_ms_unsummed += ms;
+    }
+    s->timed.clear();
+    if (s->timed_ms.size() > KID_TIMED_KEEP) s->timed_ms.erase(s->timed_ms.begin(), s->timed_ms.end() - KID_TIMED_KEEP);
+    return KID_OK;
+}
+
 extern "C" int kid_sample_kernel_time(kid_sample *s, double *total_ms, uint64_t *launches)
 {
     if (!s || !total_ms || !launches) return kid_fail(KID_ERR_ARG, "null argument");
     int rc = kid_use_device(s->db->device);
+    if (rc == KID_OK) rc = kid_timed_read(s);
     if (rc != KID_OK) return rc;
-    KID_HIP(hipDeviceSynchronize());
-    double sum = 0;
-    for (auto &ev : s->timed) {
-        float ms = 0;
-        KID_HIP(hipEventElapsedTime(&ms, ev.first.e, ev.second.e));
-        sum += ms;
-    }
-    *total_ms = sum;
+    *total_ms = s->timed_ms_unsummed;
     *launches = s->timed_batches; // batches: the kernels of one batch count as one launch
-    s->timed.clear();
+    s->timed_ms_unsummed = 0;
     s->timed_batches = 0;
+    return KID_OK;
+}
+
+extern "C" int kid_sample_kernel_times(kid_sample *s, double *ms, uint64_t cap, uint64_t *n)
+{
+    if (!s || !n || (cap && !ms)) return kid_fail(KID_ERR_ARG, "null argument");
+    int rc = kid_use_device(s->db->device);
+    if (rc == KID_OK) rc = kid_timed_read(s);
+    if (rc != KID_OK) return rc;
+    *n = s->timed_ms.size();
+    for (uint64_t i = 0; i < cap && i < *n; i++) ms[i] = s->timed_ms[i];
+    s->timed_ms.clear();
     return KID_OK;
 }
 
