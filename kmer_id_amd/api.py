@@ -128,6 +128,8 @@ PILEUP_DTYPE = np.dtype({"names": PILEUP_FIELDS + ("depth_sum",), "formats": [np
 _UNIT_FAMILIES = {"support": (SUPPORT_DTYPE, 1), "votes": (VOTE_DTYPE, 1), "fragments": (FRAGMENT_DTYPE, 2),
                   "fragment_votes": (FRAGMENT_VOTE_DTYPE, 2)}
 _SEGMENT_FAMILIES = {"segments": SEGMENT_DTYPE, "segment_votes": SEGMENT_VOTE_DTYPE}
+# the families that place by the database's sites: their parameters are (diag_bin,) and (diag_bin, max_span)
+_LOCI_FAMILIES = {"loci": (LOCUS_DTYPE, 1), "fragment_loci": (FRAGMENT_LOCUS_DTYPE, 2)}
 
 
 class ReadSegments:
@@ -524,6 +526,31 @@ class KmerDB:
         """Free the sites: every read_loci call is KID_ERR_STATE until set_sites."""
         check(self._lib.kid_db_set_sites(self._h, None, None, 0))
 
+    def _loci_offsets(self, family, bases, offsets, start, stop, params):
+        """kid_db_read_<family> over a batch held in host memory -> its records, one per unit"""
+        dtype, unit = _LOCI_FAMILIES[family]
+        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
+        out = np.zeros(n // unit, dtype)
+        check(getattr(self._lib, "kid_db_read_" + family)(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, *params, _ptr(out)))
+        return out
+
+    def _loci_fastq(self, family, blocks, params):
+        """kid_db_read_<family>_fastq over one block (text, recs) of FASTQ text, or two: the mates -> one record per unit"""
+        blocks = [_fastq_block(text, recs) for text, recs in blocks]
+        n = blocks[0][2]
+        if any(b[2] != n for b in blocks):
+            raise ValueError("recs1 and recs2 must hold one record per fragment each")
+        out = np.zeros(n, _LOCI_FAMILIES[family][0])
+        texts = [a for text, recs, _ in blocks for a in (_ptr(text), text.size, _ptr(recs))]
+        check(getattr(self._lib, "kid_db_read_%s_fastq" % family)(self._h, *texts, n, *params, _ptr(out)))
+        return out
+
+    def _loci_from_hits_device(self, family, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, params, stream):
+        """kid_db_<family>_from_hits_device: a family's kernels alone on a CSR resident in HBM"""
+        check(getattr(self._lib, "kid_db_%s_from_hits_device" % family)(
+            self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None), C.c_void_p(d_n_kmers), n_reads, *params, C.c_void_p(d_out),
+            C.c_void_p(stream or None)))
+
     def read_loci(self, bases, offsets, start=None, stop=None, diag_bin=1):
         """Place the reads of a batch held in host memory by colinear hits (kid_db_read_loci): -> a structured array
         (LOCUS_DTYPE: org, strand, n_chain, n_org, n_other, n_hits, n_kmers, pos_first, pos_last, entry_first), one record
@@ -531,25 +558,18 @@ class KmerDB:
         the reverse key (org[e], 1, (pos[e] + r) / diag_bin); the chain is the set of hits with the most common key
         (ties: strand 0, then the lowest org, then the lowest diagonal), n_other the most common key's count on another
         org.  The chain lies at genome coordinate pos[entry_first] at read position pos_first."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        out = np.zeros(n, LOCUS_DTYPE)
-        check(self._lib.kid_db_read_loci(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, diag_bin, _ptr(out)))
-        return out
+        return self._loci_offsets("loci", bases, offsets, start, stop, (diag_bin,))
 
     def read_loci_fastq(self, text, recs, diag_bin=1):
         """The same for a block of FASTQ text with its line index (uint32[n, 4], as Sample.classify_fastq): a record that
         fails stop - start >= k has no window and no hit; KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply
         as in read_hits_fastq."""
-        text, recs, n = _fastq_block(text, recs)
-        out = np.zeros(n, LOCUS_DTYPE)
-        check(self._lib.kid_db_read_loci_fastq(self._h, _ptr(text), text.size, _ptr(recs), n, diag_bin, _ptr(out)))
-        return out
+        return self._loci_fastq("loci", [(text, recs)], (diag_bin,))
 
     def loci_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, diag_bin=1, stream=0):
         """The loci kernels alone on a CSR resident in HBM (raw pointers, as kid_db_read_hits_device left it); asynchronous
         on `stream`: kid_db_loci_from_hits_device.  d_out: kid_locus[n_reads] (LOCUS_DTYPE)."""
-        check(self._lib.kid_db_loci_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None), C.c_void_p(d_n_kmers),
-                                                     n_reads, diag_bin, C.c_void_p(d_out), C.c_void_p(stream or None)))
+        self._loci_from_hits_device("loci", d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, (diag_bin,), stream)
 
     def read_loci_time(self):
         """-> (device ms, calls, reads) of the loci kernels alone since the last query"""
@@ -564,31 +584,19 @@ class KmerDB:
         key of one mate.  The best placement has the highest score (ties: paired first, then the keys' order); mates is 3
         for a paired best, 1 or 2 for a solo best, 0 without a hit; orient = 0 means mate 1 reads forward; [lo, hi] is the
         genome interval the chosen chains cover, the unsequenced middle of a paired best included."""
-        bases, offsets, start, stop, n = _offsets_batch(bases, offsets, start, stop)
-        out = np.zeros(n // 2, FRAGMENT_LOCUS_DTYPE)
-        check(self._lib.kid_db_read_fragment_loci(self._h, _ptr(bases), _ptr(offsets), _ptr(start), _ptr(stop), n, diag_bin, max_span, _ptr(out)))
-        return out
+        return self._loci_offsets("fragment_loci", bases, offsets, start, stop, (diag_bin, max_span))
 
     def read_fragment_loci_fastq(self, text1, recs1, text2, recs2, diag_bin=1, max_span=1000):
         """The same for two blocks of FASTQ text with their line indexes, as read_fragments_fastq: record i of recs1 is mate
         1 and record i of recs2 is mate 2; a record with seq_len = 0 and qual_len = 0 is an absent mate.
         KID_DB_OPT_MIN_BASE_QUALITY and KID_DB_OPT_LOW_COMPLEXITY apply as in read_fragments_fastq."""
-        text1, recs1, n = _fastq_block(text1, recs1)
-        text2, recs2, n2 = _fastq_block(text2, recs2)
-        if n != n2:
-            raise ValueError("recs1 and recs2 must hold one record per fragment each")
-        out = np.zeros(n, FRAGMENT_LOCUS_DTYPE)
-        check(self._lib.kid_db_read_fragment_loci_fastq(self._h, _ptr(text1), text1.size, _ptr(recs1), _ptr(text2), text2.size, _ptr(recs2), n,
-                                                        diag_bin, max_span, _ptr(out)))
-        return out
+        return self._loci_fastq("fragment_loci", [(text1, recs1), (text2, recs2)], (diag_bin, max_span))
 
     def fragment_loci_from_hits_device(self, d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, diag_bin=1, max_span=1000, stream=0):
         """The fragment-loci kernels alone on an interleaved CSR of n_reads = 2 F reads resident in HBM (raw pointers);
         asynchronous on `stream`: kid_db_fragment_loci_from_hits_device.  d_out: kid_fragment_locus[n_reads / 2]
         (FRAGMENT_LOCUS_DTYPE)."""
-        check(self._lib.kid_db_fragment_loci_from_hits_device(self._h, C.c_void_p(d_hit_offsets), C.c_void_p(d_hits or None),
-                                                              C.c_void_p(d_n_kmers), n_reads, diag_bin, max_span, C.c_void_p(d_out),
-                                                              C.c_void_p(stream or None)))
+        self._loci_from_hits_device("fragment_loci", d_hit_offsets, d_hits, d_n_kmers, n_reads, d_out, (diag_bin, max_span), stream)
 
     def read_fragment_loci_time(self):
         """-> (device ms, calls, fragments) of the fragment-loci kernels alone since the last query"""

@@ -8,6 +8,7 @@
 #include <memory>
 #include <stdint.h>
 #include <string.h>
+#include <tuple>
 #include <type_traits>
 #include <utility>
 #include <vector>

@@ -95,6 +95,12 @@ struct KidVoteScratch {
     KidDevBuf *rows = &own_rows; // (the segment-vote family's: the vote family's, KidHitsState())
 };
 
+// What the second kernel of a loci family works on: the units its first kernel leaves to it (uint32 per unit of the
+// largest batch) and their number (one word).  One set per family and kid_db.
+struct KidLociScratch {
+    KidDevBuf list, n_list;
+};
+
 struct KidHitsState {
     KidDevBuf desc, tile_off, rsum, tile_mask, tile_hit_off, tsum, trim_start, trim_stop;          // every form
     KidDevBuf in_bases, in_offsets, in_start, in_stop, in_recs, out_offsets, out_nk, out_hits;      // host-buffer forms
@@ -116,8 +122,9 @@ struct KidHitsState {
     // holds fragment indexes), kid_db_read_segment_votes* (a list of 24 B per segment the call can write, and the vote
     // family's rows)
     KidVoteScratch vote_big, fragment_vote_big, segment_vote_big;
-    KidDevBuf loci_list, loci_n_list; // kid_db_read_loci* (kid_api_loci.h): the reads of the second kernel (uint32 per read), their number
-    KidDevBuf fragment_loci_list, fragment_loci_n_list; // kid_db_read_fragment_loci* (kid_api_fragment_loci.h): the same, of its own, in fragments
+    // kid_db_read_loci* (kid_api_loci.h, which binds them), kid_db_read_fragment_loci* (the same set once more, of its own; the
+    // list holds fragment indexes)
+    KidLociScratch loci_big, fragment_loci_big;
     KidDevBuf lowc_plane; // KID_DB_OPT_LOW_COMPLEXITY: the flag plane of a staged block with a line that is split (kid_lowc.hip.h)
     KidHitsState() { segment_vote_big.rows = &vote_big.own_rows; }
     unsigned long long *ctl() const { return ctl_buf.as<unsigned long long>(); }

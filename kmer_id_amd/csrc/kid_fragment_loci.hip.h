@@ -16,10 +16,11 @@
 // The forward diagonal is biased by 2^32 inside the key word and the reverse one is not: kid_floci_pair takes the bias off
 // before it compares D with E.
 //
-// What a set of placements comes to is a KidFlociTop: the best (c, k1, k2) and the largest score among placements of another
-// org, with that org.  Two of them merge (kid_floci_top_merge); the merge is associative, commutative and idempotent in
-// what the record takes from it, so lanes, waves and the two orientations fold in any order, and a placement may be offered
-// more than once.
+// What a set of placements comes to is a KidFlociTop, the KidLociTop of kid_loci.hip.h over keys of two words: the best
+// (c, k1, k2) and the largest score among placements of another org, with that org (k1 has the org where a key word has
+// it).  The algebra of its merge is stated there: lanes, waves and the two orientations fold in any order, and a placement
+// may be offered more than once.  The ends of a mate's chain, the fold over the workgroup and the stages of the second
+// kernel are that file's too.
 //
 // Two regimes by the mates' hits (m_1, m_2), both giving the same record:
 //   both <= KID_FLOCI_LANE_HITS   a lane takes the fragment: the keys of both mates in registers, counts and pairs by
@@ -55,128 +56,52 @@ struct KidFlociRule {
     uint32_t reach; // max_span / diag_bin: the largest E - D of an allowed pair
     uint32_t k;     // the database's k-mer length
 };
-struct KidFlociTop {
-    uint64_t k1, k2; // the best placement so far (c > 0)
-    uint32_t c;      // its score; 0: no placement yet
-    uint32_t c2, g2; // the largest score among placements of another org than the best one's, and that org (c2 > 0)
-};
-struct KidFlociEnds { // of one mate's chain
-    unsigned long long first; // min of pos << 32 | entry over the chain
-    uint32_t last, n;
-};
-
-__device__ __forceinline__ uint32_t kid_floci_org(uint64_t k1) { return (uint32_t)(k1 >> 34) & 0xFFFFFFu; }
-
-__device__ __forceinline__ KidFlociTop kid_floci_top_empty()
-{
-    KidFlociTop t = {~0ull, ~0ull, 0u, 0u, 0u};
-    return t;
-}
-
-// a := what the placements behind a and those behind b come to together
-__device__ __forceinline__ void kid_floci_top_merge(KidFlociTop &a, const KidFlociTop &b)
-{
-    const uint32_t cc[4] = {a.c, a.c2, b.c, b.c2};
-    const uint32_t gg[4] = {kid_floci_org(a.k1), a.g2, kid_floci_org(b.k1), b.g2};
-    if (b.c > a.c || (b.c == a.c && (b.k1 < a.k1 || (b.k1 == a.k1 && b.k2 < a.k2)))) { a.k1 = b.k1; a.k2 = b.k2; a.c = b.c; }
-    const uint32_t g = kid_floci_org(a.k1);
-    a.c2 = a.g2 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        if (gg[i] != g && cc[i] > a.c2) { a.c2 = cc[i]; a.g2 = gg[i]; }
-}
-
-__device__ __forceinline__ void kid_floci_top_add(KidFlociTop &a, uint64_t k1, uint64_t k2, uint32_t c)
-{
-    const KidFlociTop b = {k1, k2, c, 0u, 0u};
-    kid_floci_top_merge(a, b);
-}
+typedef KidLociTop<2> KidFlociTop; // k[0] = k1, k[1] = k2 of the best placement; c its score
 
 // the solo placement of mate s (0 or 1) on `key` (a key word of either strand) with count c
 __device__ __forceinline__ void kid_floci_solo(KidFlociTop &a, uint64_t key, uint32_t c, uint32_t s)
 {
-    kid_floci_top_add(a, KID_FLOCI_SOLO | key, (uint64_t)s, c);
+    a.add(KID_FLOCI_SOLO | key, (uint64_t)s, c);
 }
 
 // the paired placement of orientation o on the forward key fk (count cf) and the reverse key rk (count cr), if it is allowed
 __device__ __forceinline__ void kid_floci_pair(KidFlociTop &a, const KidFlociRule &rule, uint32_t o, uint64_t fk, uint32_t cf, uint64_t rk, uint32_t cr)
 {
-    if (kid_floci_org(fk) != kid_floci_org(rk)) return;
+    if (kid_loci_key_org(fk) != kid_loci_key_org(rk)) return;
     const int64_t D = (int64_t)(fk & KID_FLOCI_DIAG_MASK) - (1ll << 32), E = (int64_t)(rk & KID_FLOCI_DIAG_MASK);
     if (D > E || E - D > (int64_t)rule.reach) return;
-    kid_floci_top_add(a, fk | (uint64_t)o << 58, rk, cf + cr);
-}
-
-// the tops of a wave's lanes -> one, the same in every lane
-__device__ __forceinline__ void kid_floci_top_wave(KidFlociTop &t)
-{
-    for (int s = 32; s >= 1; s >>= 1) {
-        KidFlociTop o;
-        o.k1 = (uint64_t)__shfl_xor((unsigned long long)t.k1, s);
-        o.k2 = (uint64_t)__shfl_xor((unsigned long long)t.k2, s);
-        o.c = (uint32_t)__shfl_xor((int)t.c, s);
-        o.c2 = (uint32_t)__shfl_xor((int)t.c2, s);
-        o.g2 = (uint32_t)__shfl_xor((int)t.g2, s);
-        kid_floci_top_merge(t, o);
-    }
-    // (lanes may differ in g2 where two orgs tie for c2, which nobody reads behind this: one copy for all)
-    t.k1 = (uint64_t)__shfl((unsigned long long)t.k1, 0);
-    t.k2 = (uint64_t)__shfl((unsigned long long)t.k2, 0);
-    t.c = (uint32_t)__builtin_amdgcn_readlane((int)t.c, 0);
-    t.c2 = (uint32_t)__builtin_amdgcn_readlane((int)t.c2, 0);
-    t.g2 = (uint32_t)__builtin_amdgcn_readlane((int)t.g2, 0);
+    a.add(fk | (uint64_t)o << 58, rk, cf + cr);
 }
 
 // What the best placement chooses: the key word of each mate's chain (KID_LOCI_NO_KEY: the mate is not in the placement).
 __device__ __forceinline__ void kid_floci_chosen(const KidFlociTop &t, uint64_t ck[2])
 {
     ck[0] = ck[1] = KID_LOCI_NO_KEY;
-    if (t.k1 & KID_FLOCI_SOLO)
-        ck[t.k2 & 1ull] = t.k1 & ~KID_FLOCI_SOLO;
+    if (t.k[0] & KID_FLOCI_SOLO)
+        ck[t.k[1] & 1ull] = t.k[0] & ~KID_FLOCI_SOLO;
     else {
-        const uint32_t o = (uint32_t)(t.k1 >> 58) & 1u; // the forward mate is mate 1 + o
-        ck[o] = t.k1 & ~(1ull << 58);
-        ck[1u - o] = t.k2;
+        const uint32_t o = (uint32_t)(t.k[0] >> 58) & 1u; // the forward mate is mate 1 + o
+        ck[o] = t.k[0] & ~(1ull << 58);
+        ck[1u - o] = t.k[1];
     }
 }
 
-__device__ __forceinline__ KidFlociEnds kid_floci_ends_empty()
+// one participant of a mate (fk != KID_LOCI_NO_KEY) into n_org and, if it has the mate's chosen key ck, the chain's ends and length
+__device__ __forceinline__ void kid_floci_chain_add(KidLociEnds &e, uint32_t &n_org, uint32_t org, uint64_t ck, uint64_t fk, uint64_t rk,
+                                                    const KidHit &h)
 {
-    KidFlociEnds e = {~0ull, 0u, 0u};
-    return e;
-}
-
-// one participant of a mate (fk != KID_LOCI_NO_KEY) into n_org and, if it has the mate's chosen key ck, the chain's ends
-__device__ __forceinline__ void kid_floci_ends_add(KidFlociEnds &e, uint32_t &n_org, uint32_t org, uint64_t ck, uint64_t fk, uint64_t rk,
-                                                   const KidHit &h)
-{
-    n_org += kid_floci_org(fk) == org ? 1u : 0u;
-    if (ck != KID_LOCI_NO_KEY && ((ck >> 58) & 1ull ? rk : fk) == ck) {
-        const unsigned long long p = (unsigned long long)h.pos << 32 | h.entry;
-        e.first = p < e.first ? p : e.first;
-        e.last = h.pos > e.last ? h.pos : e.last;
+    n_org += kid_loci_key_org(fk) == org ? 1u : 0u;
+    if (ck != KID_LOCI_NO_KEY && kid_loci_has_key(ck, fk, rk)) {
+        e.add(h);
         e.n++;
     }
 }
 
-__device__ __forceinline__ void kid_floci_ends_merge(KidFlociEnds &e, unsigned long long first, uint32_t last, uint32_t n)
-{
-    e.first = first < e.first ? first : e.first;
-    e.last = last > e.last ? last : e.last;
-    e.n += n;
-}
-
-__device__ __forceinline__ void kid_floci_ends_wave(KidFlociEnds &e)
-{
-    for (int s = 32; s >= 1; s >>= 1)
-        kid_floci_ends_merge(e, __shfl_xor(e.first, s), (uint32_t)__shfl_xor((int)e.last, s), (uint32_t)__shfl_xor((int)e.n, s));
-}
-
 // top (c > 0), its chosen keys and the ends of the two chains -> every field of the record but n_hits and n_kmers
 __device__ __forceinline__ void kid_floci_settle(const KidLociSites &s, const KidFlociRule &rule, const KidFlociTop &t, const uint64_t ck[2],
-                                                 const KidFlociEnds e[2], uint32_t n_org, KidFragmentLocus &res)
+                                                 const KidLociEnds e[2], uint32_t n_org, KidFragmentLocus &res)
 {
-    res.org = kid_floci_org(t.k1);
+    res.org = t.org();
     res.mates = (ck[0] != KID_LOCI_NO_KEY ? 1u : 0u) | (ck[1] != KID_LOCI_NO_KEY ? 2u : 0u);
     // 0: mate 1 reads forward -- its own key is forward, or mate 2's is reverse
     res.orient = ck[0] != KID_LOCI_NO_KEY ? (uint32_t)(ck[0] >> 58) & 1u : 1u - ((uint32_t)(ck[1] >> 58) & 1u);
@@ -227,7 +152,7 @@ __device__ __forceinline__ void kid_floci_lane(const KidLociSites &s, const KidF
         if (i < m1) kid_loci_keys(s, h1[i], fk[0][i], rk[0][i]);
         if (i < m2) kid_loci_keys(s, h2[i], fk[1][i], rk[1][i]);
     }
-    KidFlociTop top = kid_floci_top_empty();
+    KidFlociTop top = KidFlociTop::empty();
 #pragma unroll
     for (uint32_t m = 0; m < 2u; m++)
 #pragma unroll
@@ -255,13 +180,13 @@ __device__ __forceinline__ void kid_floci_lane(const KidLociSites &s, const KidF
     if (top.c == 0) return;
     uint64_t ck[2];
     kid_floci_chosen(top, ck);
-    KidFlociEnds e[2] = {kid_floci_ends_empty(), kid_floci_ends_empty()};
+    KidLociEnds e[2] = {KidLociEnds::empty(), KidLociEnds::empty()};
     uint32_t n_org = 0;
-    const uint32_t org = kid_floci_org(top.k1);
+    const uint32_t org = top.org();
 #pragma unroll
     for (uint32_t i = 0; i < L; i++) {
-        if (fk[0][i] != KID_LOCI_NO_KEY) kid_floci_ends_add(e[0], n_org, org, ck[0], fk[0][i], rk[0][i], h1[i]);
-        if (fk[1][i] != KID_LOCI_NO_KEY) kid_floci_ends_add(e[1], n_org, org, ck[1], fk[1][i], rk[1][i], h2[i]);
+        if (fk[0][i] != KID_LOCI_NO_KEY) kid_floci_chain_add(e[0], n_org, org, ck[0], fk[0][i], rk[0][i], h1[i]);
+        if (fk[1][i] != KID_LOCI_NO_KEY) kid_floci_chain_add(e[1], n_org, org, ck[1], fk[1][i], rk[1][i], h2[i]);
     }
     kid_floci_settle(s, rule, top, ck, e, n_org, res);
 }
@@ -286,32 +211,6 @@ __global__ __launch_bounds__(256) void kid_fragment_loci_kernel(const uint64_t *
 }
 
 // ------------------------------------------------------------------ fragments with a mate of more than KID_FLOCI_LANE_HITS hits
-// the end of the run of `k` that starts at keys[i] of the ascending keys[0, n): the first index behind i whose key is larger
-__device__ __forceinline__ uint32_t kid_floci_run_end(const uint64_t *keys, uint32_t i, uint32_t n, uint64_t k)
-{
-    uint32_t lo = i + 1u, hi = n;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (keys[mid] <= k) lo = mid + 1u;
-        else hi = mid;
-    }
-    return lo;
-}
-
-// keys[0, n2) <- the forward (reverse: the reverse) keys of the first p hits at h, KID_LOCI_NO_KEY behind them; sorted.
-// Entered and left by all 256 threads; n2 a power of two.
-__device__ __forceinline__ void kid_floci_fill_sort(uint64_t *keys, uint32_t n2, const KidLociSites &sites, const KidHit *h, uint32_t p,
-                                                    bool reverse)
-{
-    for (uint32_t i = threadIdx.x; i < n2; i += 256u) {
-        uint64_t fk = KID_LOCI_NO_KEY, rk = KID_LOCI_NO_KEY;
-        if (i < p) kid_loci_keys(sites, h[i], fk, rk);
-        keys[i] = reverse ? rk : fk;
-    }
-    __syncthreads();
-    if (p > 1u) kid_loci_sort(keys, n2); // (uniform)
-}
-
 // (the arguments of kid_fragment_loci_kernel; the list is at most n_fragments long by construction)
 __global__ __launch_bounds__(256) void kid_fragment_loci_big_kernel(const uint64_t *hit_offsets, const KidHit *hits, const uint32_t *n_kmers,
                                                                      uint64_t /* n_fragments */, const KidLociSites sites,
@@ -319,97 +218,75 @@ __global__ __launch_bounds__(256) void kid_fragment_loci_big_kernel(const uint64
 {
     __shared__ uint64_t ka[KID_LOCI_MAX_HITS], kb[KID_LOCI_MAX_HITS]; // the forward keys of one mate, the reverse keys of the other
     __shared__ KidFlociTop sh_top[4];
-    __shared__ KidFlociEnds sh_ends[4][2];
-    __shared__ uint32_t sh_n_org[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    __shared__ KidLociEnds sh_ends[2][4];
+    __shared__ KidLociCount sh_n_org[4];
     const uint32_t n_list = *big.n_list;
     for (uint32_t e = blockIdx.x; e < n_list; e += gridDim.x) {
         const uint64_t f = big.list[e];
         const uint64_t o0 = hit_offsets[2u * f], o1 = hit_offsets[2u * f + 1u], o2 = hit_offsets[2u * f + 2u];
         const KidHit *h[2] = {hits + o0, hits + o1};
         const uint32_t m[2] = {(uint32_t)(o1 - o0), (uint32_t)(o2 - o1)};
-        uint32_t p[2], n2[2];
-        for (int s = 0; s < 2; s++) {
-            p[s] = m[s] < KID_LOCI_MAX_HITS ? m[s] : KID_LOCI_MAX_HITS;
-            n2[s] = KID_FLOCI_MIN_SORT;
-            while (n2[s] < p[s]) n2[s] <<= 1; // (at most KID_LOCI_MAX_HITS)
-        }
-        KidFlociTop top = kid_floci_top_empty();
+        const uint32_t p[2] = {m[0] < KID_LOCI_MAX_HITS ? m[0] : KID_LOCI_MAX_HITS, m[1] < KID_LOCI_MAX_HITS ? m[1] : KID_LOCI_MAX_HITS};
+        KidFlociTop top = KidFlociTop::empty();
         for (uint32_t o = 0; o < 2u; o++) { // mate A = o reads forward, mate B = 1 - o reverse
             const uint32_t A = o, B = 1u - o;
-            kid_floci_fill_sort(ka, n2[A], sites, h[A], p[A], false);
-            kid_floci_fill_sort(kb, n2[B], sites, h[B], p[B], true);
+            const uint32_t na = kid_loci_fill_sort(ka, KID_FLOCI_MIN_SORT, sites, h[A], p[A], false);
+            const uint32_t nb = kid_loci_fill_sort(kb, KID_FLOCI_MIN_SORT, sites, h[B], p[B], true);
             __syncthreads();
             for (uint32_t i = threadIdx.x; i < p[A]; i += 256u) { // the first element of a forward run
+                if (!kid_loci_run_starts(ka, i)) continue;
                 const uint64_t k = ka[i];
-                if (k == KID_LOCI_NO_KEY || (i > 0 && ka[i - 1] == k)) continue;
-                const uint32_t cf = kid_floci_run_end(ka, i, n2[A], k) - i;
+                const uint32_t cf = kid_loci_run_end(ka, i, na, k) - i;
                 kid_floci_solo(top, k, cf, A);
                 // its partners: the reverse keys of the same org with E in [max(D, 0), D + reach]
                 const int64_t D = (int64_t)(k & KID_FLOCI_DIAG_MASK) - (1ll << 32);
                 int64_t e_hi = D + (int64_t)rule.reach;
                 if (e_hi < 0) continue;
                 e_hi = e_hi > (int64_t)KID_FLOCI_DIAG_MASK ? (int64_t)KID_FLOCI_DIAG_MASK : e_hi;
-                const uint64_t base = 1ull << 58 | (uint64_t)kid_floci_org(k) << 34;
+                const uint64_t base = 1ull << 58 | (uint64_t)kid_loci_key_org(k) << 34;
                 const uint64_t r_lo = base | (uint64_t)(D > 0 ? D : 0), r_hi = base | (uint64_t)e_hi;
-                uint32_t lo = 0, hi = n2[B];
+                uint32_t lo = 0, hi = nb;
                 while (lo < hi) { // the first key that is at least r_lo
                     const uint32_t mid = (lo + hi) >> 1;
                     if (kb[mid] < r_lo) lo = mid + 1u;
                     else hi = mid;
                 }
-                while (lo < n2[B]) {
+                while (lo < nb) {
                     const uint64_t r = kb[lo];
                     if (r > r_hi) break; // (KID_LOCI_NO_KEY is larger than every r_hi)
-                    const uint32_t next = kid_floci_run_end(kb, lo, n2[B], r);
+                    const uint32_t next = kid_loci_run_end(kb, lo, nb, r);
                     kid_floci_pair(top, rule, o, k, cf, r, next - lo);
                     lo = next;
                 }
             }
-            for (uint32_t i = threadIdx.x; i < p[B]; i += 256u) { // the first element of a reverse run
-                const uint64_t k = kb[i];
-                if (k == KID_LOCI_NO_KEY || (i > 0 && kb[i - 1] == k)) continue;
-                kid_floci_solo(top, k, kid_floci_run_end(kb, i, n2[B], k) - i, B);
-            }
+            for (uint32_t i = threadIdx.x; i < p[B]; i += 256u) // the first element of a reverse run
+                if (kid_loci_run_starts(kb, i)) kid_floci_solo(top, kb[i], kid_loci_run_end(kb, i, nb, kb[i]) - i, B);
             __syncthreads(); // (the keys are overwritten next)
         }
-        kid_floci_top_wave(top);
-        if (lane == 0) sh_top[wave] = top;
-        __syncthreads();
-        top = sh_top[0];
-        for (uint32_t w = 1; w < 4u; w++) kid_floci_top_merge(top, sh_top[w]);
+        kid_loci_fold(top, sh_top);
         KidFragmentLocus res = kid_floci_empty(m[0] + m[1], n_kmers[2u * f] + n_kmers[2u * f + 1u]);
         if (top.c != 0) { // (uniform)
             uint64_t ck[2];
             kid_floci_chosen(top, ck);
-            KidFlociEnds ends[2] = {kid_floci_ends_empty(), kid_floci_ends_empty()};
-            uint32_t n_org = 0;
-            const uint32_t org = kid_floci_org(top.k1);
+            KidLociEnds ends[2] = {KidLociEnds::empty(), KidLociEnds::empty()};
+            KidLociCount n_org = {0u};
+            const uint32_t org = top.org();
             for (int s = 0; s < 2; s++)
                 for (uint32_t i = threadIdx.x; i < p[s]; i += 256u) {
                     uint64_t fk, rk;
                     kid_loci_keys(sites, h[s][i], fk, rk);
-                    if (fk != KID_LOCI_NO_KEY) kid_floci_ends_add(ends[s], n_org, org, ck[s], fk, rk, h[s][i]);
+                    if (fk != KID_LOCI_NO_KEY) kid_floci_chain_add(ends[s], n_org.n, org, ck[s], fk, rk, h[s][i]);
                 }
-            kid_floci_ends_wave(ends[0]);
-            kid_floci_ends_wave(ends[1]);
-            for (int s = 32; s >= 1; s >>= 1) n_org += (uint32_t)__shfl_xor((int)n_org, s);
-            if (lane == 0) {
-                sh_ends[wave][0] = ends[0];
-                sh_ends[wave][1] = ends[1];
-                sh_n_org[wave] = n_org;
-            }
+            kid_loci_fold_put(ends[0], sh_ends[0]); // (the three at one barrier: a fold each costs vector registers)
+            kid_loci_fold_put(ends[1], sh_ends[1]);
+            kid_loci_fold_put(n_org, sh_n_org);
             __syncthreads();
-            ends[0] = sh_ends[0][0];
-            ends[1] = sh_ends[0][1];
-            n_org = sh_n_org[0];
-            for (uint32_t w = 1; w < 4u; w++) {
-                for (int s = 0; s < 2; s++) kid_floci_ends_merge(ends[s], sh_ends[w][s].first, sh_ends[w][s].last, sh_ends[w][s].n);
-                n_org += sh_n_org[w];
-            }
-            if (threadIdx.x == 0) kid_floci_settle(sites, rule, top, ck, ends, n_org, res);
+            kid_loci_fold_get(ends[0], sh_ends[0]);
+            kid_loci_fold_get(ends[1], sh_ends[1]);
+            kid_loci_fold_get(n_org, sh_n_org);
+            if (threadIdx.x == 0) kid_floci_settle(sites, rule, top, ck, ends, n_org.n, res);
         }
         if (threadIdx.x == 0) out[f] = res;
-        __syncthreads(); // (the shared tops and ends are written again for the next fragment)
+        __syncthreads(); // (the shared tops, ends and counts are written again for the next fragment)
     }
 }

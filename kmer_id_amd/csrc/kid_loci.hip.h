@@ -17,8 +17,14 @@
 // at least -(2^32 - 1), and both stay below 2^34), so the tie order is the order of the words.
 //
 // What a set of keys comes to is a KidLociTop: the best (c, key) and the largest c among keys of another g, with that g.
-// Two of them merge (kid_loci_top_merge); the merge is associative, commutative and idempotent in what the record takes
-// from it, so lanes, waves and strands may be folded in any order and a key may be offered more than once.
+// Two of them merge (KidLociTop::merge); the merge is associative, commutative and idempotent in what the record takes
+// from it (the best (c, key) is a maximum in a total order, c2 the maximum of c over the keys of another g than the best
+// one's, and a maximum is all three; g2 alone may depend on the order where two orgs tie for c2, and nobody reads it
+// behind the last merge), so lanes, waves and strands may be folded in any order and a key may be offered more than once.
+// The top is a template over the words of its key, compared first word first: one word here, two for the placements of
+// kid_fragment_loci.hip.h, which shares everything below that has no family in its name: the top, the ends of a chain
+// (KidLociEnds), a count (KidLociCount), the fold of either over a workgroup (kid_loci_fold) and the stages of the second
+// kernel (kid_loci_fill_sort, kid_loci_run_starts, kid_loci_run_end).
 //
 // Three regimes by the read's hits m, all giving the same record:
 //   m <= KID_LOCI_LANE_HITS   a lane takes the read: its keys in registers, c by pairwise tests
@@ -51,17 +57,131 @@ struct KidLociBig { // the reads left to kid_loci_big_kernel
     uint32_t *list;   // uint32[n_reads]
     uint32_t *n_list; // their number: zeroed in front of kid_loci_kernel
 };
-struct KidLociTop {
-    uint64_t key;    // the best key so far (c > 0)
-    uint32_t c;      // its count; 0: no key yet
-    uint32_t c2, g2; // the largest count among keys of another org than the best key's, and that org (c2 > 0)
-};
-struct KidLociEnds { // of the chain, and n_org
-    unsigned long long first; // min of pos << 32 | entry over the chain
-    uint32_t last, n_org;
-};
 
 __device__ __forceinline__ uint32_t kid_loci_key_org(uint64_t key) { return (uint32_t)(key >> 34) & 0xFFFFFFu; }
+
+// What a set of keys of NK words comes to (on top).  Every word of every key has its org where a key word has it.
+template <int NK> struct KidLociTop {
+    uint64_t k[NK];  // the best key so far (c > 0)
+    uint32_t c;      // its count; 0: no key yet
+    uint32_t c2, g2; // the largest count among keys of another org than the best key's, and that org (c2 > 0)
+
+    static __device__ __forceinline__ KidLociTop empty()
+    {
+        KidLociTop t;
+#pragma unroll
+        for (int i = 0; i < NK; i++) t.k[i] = KID_LOCI_NO_KEY;
+        t.c = t.c2 = t.g2 = 0u;
+        return t;
+    }
+    __device__ __forceinline__ uint32_t org() const { return kid_loci_key_org(k[0]); }
+    // whether this one's key is before o's in the tie order: word I decides, then the words behind it
+    template <int I = 0> __device__ __forceinline__ bool before(const KidLociTop &o) const
+    {
+        if constexpr (I == NK - 1) return k[I] < o.k[I];
+        else return k[I] < o.k[I] || (k[I] == o.k[I] && before<I + 1>(o));
+    }
+    // this := what the keys behind this and those behind b come to together
+    __device__ __forceinline__ void merge(const KidLociTop &b)
+    {
+        const uint32_t cc[4] = {c, c2, b.c, b.c2};
+        const uint32_t gg[4] = {org(), g2, b.org(), b.g2};
+        if (b.c > c || (b.c == c && b.before(*this))) {
+#pragma unroll
+            for (int i = 0; i < NK; i++) k[i] = b.k[i];
+            c = b.c;
+        }
+        const uint32_t g = org();
+        c2 = g2 = 0;
+#pragma unroll
+        for (int i = 0; i < 4; i++)
+            if (gg[i] != g && cc[i] > c2) { c2 = cc[i]; g2 = gg[i]; }
+    }
+    __device__ __forceinline__ void add(uint64_t k0, uint32_t n)
+    {
+        static_assert(NK == 1, "a key of one word");
+        const KidLociTop b = {{k0}, n, 0u, 0u};
+        merge(b);
+    }
+    __device__ __forceinline__ void add(uint64_t k0, uint64_t k1, uint32_t n)
+    {
+        static_assert(NK == 2, "a key of two words");
+        const KidLociTop b = {{k0, k1}, n, 0u, 0u};
+        merge(b);
+    }
+    // the tops of a wave's lanes -> one, the same in every lane
+    __device__ __forceinline__ void wave()
+    {
+        for (int s = 32; s >= 1; s >>= 1) {
+            KidLociTop o;
+#pragma unroll
+            for (int i = 0; i < NK; i++) o.k[i] = (uint64_t)__shfl_xor((unsigned long long)k[i], s);
+            o.c = (uint32_t)__shfl_xor((int)c, s);
+            o.c2 = (uint32_t)__shfl_xor((int)c2, s);
+            o.g2 = (uint32_t)__shfl_xor((int)g2, s);
+            merge(o);
+        }
+        // (lanes may differ in g2 where two orgs tie for c2, which nobody reads behind this: one copy for all)
+#pragma unroll
+        for (int i = 0; i < NK; i++) k[i] = (uint64_t)__shfl((unsigned long long)k[i], 0);
+        c = (uint32_t)__builtin_amdgcn_readlane((int)c, 0);
+        c2 = (uint32_t)__builtin_amdgcn_readlane((int)c2, 0);
+        g2 = (uint32_t)__builtin_amdgcn_readlane((int)g2, 0);
+    }
+};
+
+// The ends of a chain, and a count beside them that the family gives its meaning (kid_loci_chain_add: n_org;
+// kid_floci_chain_add: the chain's length).
+struct KidLociEnds {
+    unsigned long long first; // min of pos << 32 | entry over the chain
+    uint32_t last, n;
+
+    static __device__ __forceinline__ KidLociEnds empty() { return KidLociEnds{~0ull, 0u, 0u}; }
+    __device__ __forceinline__ void merge(const KidLociEnds &o)
+    {
+        first = o.first < first ? o.first : first;
+        last = o.last > last ? o.last : last;
+        n += o.n;
+    }
+    // a hit of the chain
+    __device__ __forceinline__ void add(const KidHit &h) { merge(KidLociEnds{(unsigned long long)h.pos << 32 | h.entry, h.pos, 0u}); }
+    __device__ __forceinline__ void wave()
+    {
+        for (int s = 32; s >= 1; s >>= 1)
+            merge(KidLociEnds{__shfl_xor(first, s), (uint32_t)__shfl_xor((int)last, s), (uint32_t)__shfl_xor((int)n, s)});
+    }
+};
+struct KidLociCount {
+    uint32_t n;
+    __device__ __forceinline__ void merge(const KidLociCount &o) { n += o.n; }
+    __device__ __forceinline__ void wave()
+    {
+        for (int s = 32; s >= 1; s >>= 1) n += (uint32_t)__shfl_xor((int)n, s);
+    }
+};
+
+// The values of a workgroup's 256 threads (a top, ends, a count) -> one, the same in every thread, through sh[4]: every
+// wave puts its own there, and behind a barrier every thread gets the four merged.  Entered and left by all 256 threads; sh
+// is free again behind the workgroup's next barrier.  (The two halves are for several values at one barrier.)
+template <class T> __device__ __forceinline__ void kid_loci_fold_put(T &v, T *sh)
+{
+    v.wave();
+    if ((threadIdx.x & 63u) == 0) sh[threadIdx.x >> 6] = v;
+}
+template <class T> __device__ __forceinline__ void kid_loci_fold_get(T &v, const T *sh)
+{
+    v = sh[0];
+    for (uint32_t w = 1; w < 4u; w++) v.merge(sh[w]);
+}
+template <class T> __device__ __forceinline__ void kid_loci_fold(T &v, T *sh)
+{
+    kid_loci_fold_put(v, sh);
+    __syncthreads();
+    kid_loci_fold_get(v, sh);
+}
+
+// whether a participant with the keys fk and rk has the key ck (of either strand)
+__device__ __forceinline__ bool kid_loci_has_key(uint64_t ck, uint64_t fk, uint64_t rk) { return ((ck >> 58) & 1ull ? rk : fk) == ck; }
 
 // the two keys of a hit; KID_LOCI_NO_KEY twice when its entry is none of the database's (the CSR may be the caller's)
 __device__ __forceinline__ void kid_loci_keys(const KidLociSites &s, const KidHit &h, uint64_t &fk, uint64_t &rk)
@@ -80,86 +200,20 @@ __device__ __forceinline__ void kid_loci_keys(const KidLociSites &s, const KidHi
     rk = 1ull << 58 | g << 34 | dr;
 }
 
-__device__ __forceinline__ KidLociTop kid_loci_top_empty()
+// one participant (fk != KID_LOCI_NO_KEY) into n_org and, if it has the key `best`, the ends of the chain
+__device__ __forceinline__ void kid_loci_chain_add(KidLociEnds &e, uint64_t best, uint64_t fk, uint64_t rk, const KidHit &h)
 {
-    KidLociTop t = {KID_LOCI_NO_KEY, 0u, 0u, 0u};
-    return t;
-}
-
-// a := what the keys behind a and those behind b come to together
-__device__ __forceinline__ void kid_loci_top_merge(KidLociTop &a, const KidLociTop &b)
-{
-    const uint32_t cc[4] = {a.c, a.c2, b.c, b.c2};
-    const uint32_t gg[4] = {kid_loci_key_org(a.key), a.g2, kid_loci_key_org(b.key), b.g2};
-    if (b.c > a.c || (b.c == a.c && b.key < a.key)) { a.key = b.key; a.c = b.c; }
-    const uint32_t g = kid_loci_key_org(a.key);
-    a.c2 = a.g2 = 0;
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-        if (gg[i] != g && cc[i] > a.c2) { a.c2 = cc[i]; a.g2 = gg[i]; }
-}
-
-__device__ __forceinline__ void kid_loci_top_add(KidLociTop &a, uint64_t key, uint32_t c)
-{
-    const KidLociTop b = {key, c, 0u, 0u};
-    kid_loci_top_merge(a, b);
-}
-
-// the tops of a wave's lanes -> one, the same in every lane
-__device__ __forceinline__ void kid_loci_top_wave(KidLociTop &t)
-{
-    for (int s = 32; s >= 1; s >>= 1) {
-        KidLociTop o;
-        o.key = (uint64_t)__shfl_xor((unsigned long long)t.key, s);
-        o.c = (uint32_t)__shfl_xor((int)t.c, s);
-        o.c2 = (uint32_t)__shfl_xor((int)t.c2, s);
-        o.g2 = (uint32_t)__shfl_xor((int)t.g2, s);
-        kid_loci_top_merge(t, o);
-    }
-    // (lanes may differ in g2 where two orgs tie for c2, which nobody reads behind this: one copy for all)
-    t.key = (uint64_t)__shfl((unsigned long long)t.key, 0);
-    t.c = (uint32_t)__builtin_amdgcn_readlane((int)t.c, 0);
-    t.c2 = (uint32_t)__builtin_amdgcn_readlane((int)t.c2, 0);
-    t.g2 = (uint32_t)__builtin_amdgcn_readlane((int)t.g2, 0);
-}
-
-__device__ __forceinline__ KidLociEnds kid_loci_ends_empty()
-{
-    KidLociEnds e = {~0ull, 0u, 0u};
-    return e;
-}
-
-// one participant (fk != KID_LOCI_NO_KEY) into the ends of the chain of `best`
-__device__ __forceinline__ void kid_loci_ends_add(KidLociEnds &e, uint64_t best, uint64_t fk, uint64_t rk, const KidHit &h)
-{
-    e.n_org += kid_loci_key_org(fk) == kid_loci_key_org(best) ? 1u : 0u;
-    if ((best >> 58 ? rk : fk) == best) {
-        const unsigned long long p = (unsigned long long)h.pos << 32 | h.entry;
-        e.first = p < e.first ? p : e.first;
-        e.last = h.pos > e.last ? h.pos : e.last;
-    }
-}
-
-__device__ __forceinline__ void kid_loci_ends_merge(KidLociEnds &e, unsigned long long first, uint32_t last, uint32_t n_org)
-{
-    e.first = first < e.first ? first : e.first;
-    e.last = last > e.last ? last : e.last;
-    e.n_org += n_org;
-}
-
-__device__ __forceinline__ void kid_loci_ends_wave(KidLociEnds &e)
-{
-    for (int s = 32; s >= 1; s >>= 1)
-        kid_loci_ends_merge(e, __shfl_xor(e.first, s), (uint32_t)__shfl_xor((int)e.last, s), (uint32_t)__shfl_xor((int)e.n_org, s));
+    e.n += kid_loci_key_org(fk) == kid_loci_key_org(best) ? 1u : 0u;
+    if (kid_loci_has_key(best, fk, rk)) e.add(h);
 }
 
 // top (c > 0) and the ends of its chain -> the record's first five fields and its last three
-__device__ __forceinline__ void kid_loci_settle(const KidLociTop &t, const KidLociEnds &e, KidLocus &res)
+__device__ __forceinline__ void kid_loci_settle(const KidLociTop<1> &t, const KidLociEnds &e, KidLocus &res)
 {
-    res.org = kid_loci_key_org(t.key);
-    res.strand = (uint32_t)(t.key >> 58) & 1u;
+    res.org = t.org();
+    res.strand = (uint32_t)(t.k[0] >> 58) & 1u;
     res.n_chain = t.c;
-    res.n_org = e.n_org;
+    res.n_org = e.n;
     res.n_other = t.c2;
     res.pos_first = (uint32_t)(e.first >> 32);
     res.pos_last = e.last;
@@ -175,7 +229,7 @@ __device__ __forceinline__ void kid_loci_lane(const KidLociSites &s, const KidHi
         fk[i] = rk[i] = KID_LOCI_NO_KEY;
         if (i < m) kid_loci_keys(s, h[i], fk[i], rk[i]);
     }
-    KidLociTop top = kid_loci_top_empty();
+    KidLociTop<1> top = KidLociTop<1>::empty();
 #pragma unroll
     for (uint32_t i = 0; i < KID_LOCI_LANE_HITS; i++) {
         if (fk[i] == KID_LOCI_NO_KEY) continue;
@@ -185,14 +239,14 @@ __device__ __forceinline__ void kid_loci_lane(const KidLociSites &s, const KidHi
             cf += fk[j] == fk[i] ? 1u : 0u;
             cr += rk[j] == rk[i] ? 1u : 0u;
         }
-        kid_loci_top_add(top, fk[i], cf);
-        kid_loci_top_add(top, rk[i], cr);
+        top.add(fk[i], cf);
+        top.add(rk[i], cr);
     }
     if (top.c == 0) return;
-    KidLociEnds e = kid_loci_ends_empty();
+    KidLociEnds e = KidLociEnds::empty();
 #pragma unroll
     for (uint32_t i = 0; i < KID_LOCI_LANE_HITS; i++)
-        if (fk[i] != KID_LOCI_NO_KEY) kid_loci_ends_add(e, top.key, fk[i], rk[i], h[i]);
+        if (fk[i] != KID_LOCI_NO_KEY) kid_loci_chain_add(e, top.k[0], fk[i], rk[i], h[i]);
     kid_loci_settle(top, e, res);
 }
 
@@ -205,7 +259,7 @@ __device__ __forceinline__ uint64_t kid_loci_readlane(uint64_t v, uint32_t j)
 // ---- the whole wave, one read of at most KID_LOCI_WAVE_HITS hits (every argument wave-uniform; so is the result)
 __device__ __forceinline__ void kid_loci_wave(const KidLociSites &s, const KidHit *h, uint32_t m, uint32_t lane, KidLocus &res)
 {
-    KidLociTop top = kid_loci_top_empty();
+    KidLociTop<1> top = KidLociTop<1>::empty();
     for (uint32_t c0 = 0; c0 < m; c0 += 64u) { // a tile of 64 candidate hits, one per lane
         uint64_t fk = KID_LOCI_NO_KEY, rk = KID_LOCI_NO_KEY;
         if (lane < m - c0) kid_loci_keys(s, h[c0 + lane], fk, rk);
@@ -223,21 +277,21 @@ __device__ __forceinline__ void kid_loci_wave(const KidLociSites &s, const KidHi
             }
         }
         if (fk != KID_LOCI_NO_KEY) {
-            kid_loci_top_add(top, fk, cf);
-            kid_loci_top_add(top, rk, cr);
+            top.add(fk, cf);
+            top.add(rk, cr);
         }
     }
-    kid_loci_top_wave(top);
+    top.wave();
     if (top.c == 0) return;
-    KidLociEnds e = kid_loci_ends_empty();
+    KidLociEnds e = KidLociEnds::empty();
     for (uint32_t c0 = 0; c0 < m; c0 += 64u) {
         if (lane < m - c0) {
             uint64_t fk, rk;
             kid_loci_keys(s, h[c0 + lane], fk, rk);
-            if (fk != KID_LOCI_NO_KEY) kid_loci_ends_add(e, top.key, fk, rk, h[c0 + lane]);
+            if (fk != KID_LOCI_NO_KEY) kid_loci_chain_add(e, top.k[0], fk, rk, h[c0 + lane]);
         }
     }
-    kid_loci_ends_wave(e);
+    e.wave();
     kid_loci_settle(top, e, res);
 }
 
@@ -266,7 +320,7 @@ __global__ __launch_bounds__(256) void kid_loci_kernel(const uint64_t *hit_offse
 }
 
 // ------------------------------------------------------------------ reads of more than KID_LOCI_WAVE_HITS hits
-// keys[0, n2) of LDS ascending: n2 a power of two (512 and more keep every thread busy); entered and left by all 256 threads
+// keys[0, n2) of LDS ascending: n2 a power of two; entered and left by all 256 threads
 __device__ __forceinline__ void kid_loci_sort(uint64_t *keys, uint32_t n2)
 {
     for (uint32_t k = 2; k <= n2; k <<= 1)
@@ -280,62 +334,72 @@ __device__ __forceinline__ void kid_loci_sort(uint64_t *keys, uint32_t n2)
         }
 }
 
+// keys[0, n2) of LDS <- the forward (reverse: the reverse) keys of the first p <= KID_LOCI_MAX_HITS hits at h, KID_LOCI_NO_KEY
+// behind them, ascending; -> n2, the first power of two that is at least p and min_sort (a power of two; 512 and more
+// keep every thread busy).  Entered and left by all 256 threads.
+__device__ __forceinline__ uint32_t kid_loci_fill_sort(uint64_t *keys, uint32_t min_sort, const KidLociSites &sites, const KidHit *h, uint32_t p,
+                                                       bool reverse)
+{
+    uint32_t n2 = min_sort;
+    while (n2 < p) n2 <<= 1;
+    for (uint32_t i = threadIdx.x; i < n2; i += 256u) {
+        uint64_t fk = KID_LOCI_NO_KEY, rk = KID_LOCI_NO_KEY;
+        if (i < p) kid_loci_keys(sites, h[i], fk, rk);
+        keys[i] = reverse ? rk : fk;
+    }
+    __syncthreads();
+    if (p > 1u) kid_loci_sort(keys, n2); // (uniform)
+    return n2;
+}
+
+// whether a run of a participant's key starts at keys[i] of the ascending keys
+__device__ __forceinline__ bool kid_loci_run_starts(const uint64_t *keys, uint32_t i)
+{
+    return keys[i] != KID_LOCI_NO_KEY && (i == 0 || keys[i - 1] != keys[i]);
+}
+
+// the end of the run of `k` that starts at keys[i] of the ascending keys[0, n): the first index behind i whose key is larger
+__device__ __forceinline__ uint32_t kid_loci_run_end(const uint64_t *keys, uint32_t i, uint32_t n, uint64_t k)
+{
+    uint32_t lo = i + 1u, hi = n;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (keys[mid] <= k) lo = mid + 1u;
+        else hi = mid;
+    }
+    return lo;
+}
+
 // (the arguments of kid_loci_kernel; the list is at most n_reads long by construction, so that number is not looked at)
 __global__ __launch_bounds__(256) void kid_loci_big_kernel(const uint64_t *hit_offsets, const KidHit *hits, const uint32_t *n_kmers,
                                                             uint64_t /* n_reads */, const KidLociSites sites, KidLocus *out, const KidLociBig big)
 {
     __shared__ uint64_t keys[KID_LOCI_MAX_HITS];
-    __shared__ KidLociTop sh_top[4];
+    __shared__ KidLociTop<1> sh_top[4];
     __shared__ KidLociEnds sh_ends[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t n_list = *big.n_list;
     for (uint32_t e = blockIdx.x; e < n_list; e += gridDim.x) {
         const uint32_t r = big.list[e];
         const KidHit *h = hits + hit_offsets[r];
         const uint32_t m = (uint32_t)(hit_offsets[r + 1] - hit_offsets[r]);
         const uint32_t p = m < KID_LOCI_MAX_HITS ? m : KID_LOCI_MAX_HITS;
-        uint32_t n2 = 512u;
-        while (n2 < p) n2 <<= 1; // (at most KID_LOCI_MAX_HITS)
-        KidLociTop top = kid_loci_top_empty();
+        KidLociTop<1> top = KidLociTop<1>::empty();
         for (uint32_t strand = 0; strand < 2u; strand++) {
-            for (uint32_t i = threadIdx.x; i < n2; i += 256u) {
-                uint64_t fk = KID_LOCI_NO_KEY, rk = KID_LOCI_NO_KEY;
-                if (i < p) kid_loci_keys(sites, h[i], fk, rk);
-                keys[i] = strand ? rk : fk;
-            }
-            __syncthreads();
-            kid_loci_sort(keys, n2);
-            for (uint32_t i = threadIdx.x; i < p; i += 256u) { // the first element of a run finds its end
-                const uint64_t k = keys[i];
-                if (k == KID_LOCI_NO_KEY || (i > 0 && keys[i - 1] == k)) continue;
-                uint32_t lo = i + 1u, hi = n2;
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) >> 1;
-                    if (keys[mid] <= k) lo = mid + 1u;
-                    else hi = mid;
-                }
-                kid_loci_top_add(top, k, lo - i);
-            }
+            const uint32_t n2 = kid_loci_fill_sort(keys, 512u, sites, h, p, strand != 0u);
+            for (uint32_t i = threadIdx.x; i < p; i += 256u) // the first element of a run finds its end
+                if (kid_loci_run_starts(keys, i)) top.add(keys[i], kid_loci_run_end(keys, i, n2, keys[i]) - i);
             __syncthreads(); // (the keys are overwritten next)
         }
-        kid_loci_top_wave(top);
-        if (lane == 0) sh_top[wave] = top;
-        __syncthreads();
-        top = sh_top[0];
-        for (uint32_t w = 1; w < 4u; w++) kid_loci_top_merge(top, sh_top[w]);
-        KidLocus res = {0u, 0u, 0u, 0u, 0u, m, n_kmers[r], 0u, 0u, 0u};
+        kid_loci_fold(top, sh_top);
+        KidLocus res = KidLociMethod::empty(n_kmers[r], m);
         if (top.c != 0) { // (uniform)
-            KidLociEnds ends = kid_loci_ends_empty();
+            KidLociEnds ends = KidLociEnds::empty();
             for (uint32_t i = threadIdx.x; i < p; i += 256u) {
                 uint64_t fk, rk;
                 kid_loci_keys(sites, h[i], fk, rk);
-                if (fk != KID_LOCI_NO_KEY) kid_loci_ends_add(ends, top.key, fk, rk, h[i]);
+                if (fk != KID_LOCI_NO_KEY) kid_loci_chain_add(ends, top.k[0], fk, rk, h[i]);
             }
-            kid_loci_ends_wave(ends);
-            if (lane == 0) sh_ends[wave] = ends;
-            __syncthreads();
-            ends = sh_ends[0];
-            for (uint32_t w = 1; w < 4u; w++) kid_loci_ends_merge(ends, sh_ends[w].first, sh_ends[w].last, sh_ends[w].n_org);
+            kid_loci_fold(ends, sh_ends);
             kid_loci_settle(top, ends, res);
         }
         if (threadIdx.x == 0) out[r] = res;
